@@ -16,11 +16,14 @@ Launch forms:
                                        one-shot all-reduce over peer pointers) -- the path a C / JVM host uses
   python bench.py --group --logical-shards N    N logical shards on device 0 (protocol test / timing on a one-GPU box)
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the kernels' own stream in extra
-iterations after the timed region; `parity_check` compares the affinity statistics and the sigma2 update of the state the
-timed region ended in with the strict C oracle (outside the timed region; folded into `valid`); `cpu_baseline` times the
-optimised C restatement (oracle/cpd_baseline.c, built here with -O3 -march=native -fopenmp) plus the numpy GP part on the
-host cores on a bounded sample of the same workload.  oracle/ is the checker and the reported baseline -- never the product.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes the state of the last timed step with
+--dump-outputs DIR, and prints the line; the fields below stay null unless --full asks for them.  With --full: `sustained`
+is a second, longer timed run; `roofline` / `kernels` are measured live with HIP events on the kernels' own stream in extra
+iterations after the timed region (and `exchange` for N > 1); `parity_check` compares the affinity statistics and the sigma2
+update of the state the timed region ended in with the strict C oracle (outside the timed region; folded into `valid`);
+`cpu_baseline` times the optimised C restatement (oracle/cpd_baseline.c, built here with -O3 -march=native -fopenmp) plus the
+numpy GP part on the host cores on a bounded sample of the same workload; for N > 1 `shard_consistency`, `group_mode` and
+`variants` follow.  oracle/ is the checker and the reported baseline -- never the product.
 """
 from __future__ import annotations
 
@@ -81,6 +84,27 @@ def synth_gpmm(ref: np.ndarray, rank: int, sigma: float = 70.0, scaling: float =
         U[d::3, d::3] = Us
         lam[d::3] = ev
     return U[:, :rank].copy(order="F"), lam[:rank].copy()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, alpha, sc, fit):
+    """--dump-outputs: what a caller of the timed path receives after its last timed step -- the model coefficients, the fit and the
+    pose / sigma2 scalars of the state (gingr_fitter_get_state) -- as DIR/<name>.npy in float64, so that two builds can be compared
+    output for output.  A fit larger than the budget is written as a fixed sample of its rows (seed 0), their indices as fit_rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"alpha": alpha, "sigma2": sc.sigma2, "scale": sc.scale, "euler": sc.euler[:], "center": sc.center[:],
+              "translation": sc.translation[:], "iteration": sc.iteration, "status": sc.status}
+    fit = np.asarray(fit, dtype=np.float64)
+    room = DUMP_LIMIT_BYTES - (1 << 20) - np.asarray(alpha).nbytes
+    if fit.nbytes > room:
+        rows = np.sort(np.random.default_rng(0).choice(fit.shape[0], room // (4 * 8), replace=False))
+        arrays["fit_rows"] = rows
+        fit = fit[rows]
+    arrays["fit"] = fit
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -287,7 +311,7 @@ def run_group_mode(args, world: int, shared_device: bool):
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--group", "--gpus", str(world), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--points", str(args.points), "--rank", str(args.rank), "--w", str(args.w), "--roofline-steps", str(args.roofline_steps),
-           "--sustained-steps", str(args.sustained_steps), "--no-cpu-baseline", "--no-parity-check"]
+           "--sustained-steps", str(args.sustained_steps), "--no-cpu-baseline", "--no-parity-check", "--full"]
     if shared_device:
         cmd += ["--logical-shards", str(world)]   # the one-GPU test mode: the shards share device 0
     env = _child_env()
@@ -311,7 +335,7 @@ def run_variants(args, world: int, shared_device: bool):
     env = _child_env()
     common = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--points", str(args.points), "--rank", str(args.rank), "--w", str(args.w),
               "--roofline-steps", str(args.roofline_steps), "--sustained-steps", "0", "--no-cpu-baseline", "--no-parity-check", "--no-group-mode",
-              "--no-variants"]
+              "--no-variants", "--full"]
     out = {}
 
     def digest(cmd, what):
@@ -412,11 +436,19 @@ def main():
     ap.add_argument("--rank", type=int, default=100)
     ap.add_argument("--w", type=float, default=0.1)
     ap.add_argument("--host-gpmm", action="store_true", help="synthesise the GPMM with numpy on the host and upload it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-check", action="store_true")
-    ap.add_argument("--roofline-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything next to the headline: the sustained run, the live roofline and per-kernel times, the exchange "
+                         "times, the oracle parity check, the shard consistency check, the CPU baseline and (N > 1) the child runs; "
+                         "without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed step produced (alpha, fit, pose, sigma2) to "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity-check", action="store_true", help="with --full: skip the oracle parity and shard consistency checks")
+    ap.add_argument("--roofline-steps", type=int, default=3, help="with --full: instrumented iterations of the live roofline")
     ap.add_argument("--sustained-steps", type=int, default=200,
-                    help="a second, longer timed run of the same workload reported as `sustained` next to the contract's K steps (0: skip)")
+                    help="with --full: a second, longer timed run of the same workload reported as `sustained` next to the contract's "
+                         "K steps (0: skip)")
     ap.add_argument("--sigma2", type=float, default=0.0,
                     help="experiment: start from this sigma2 instead of the CPD initial value (late-iteration regime)")
     ap.add_argument("--group", action="store_true",
@@ -438,10 +470,10 @@ def main():
                     help="N > 1 (one process per GPU): who runs the two all-reduces of an iteration -- the library itself (ncclAllReduce on "
                          "its own stream, gingr_fitter_update_cpd_rccl_async; default) or torch.distributed called back once per exchange")
     ap.add_argument("--no-group-mode", action="store_true",
-                    help="N > 1: skip the second measurement through the in-library device group (a child process started by rank 0 after "
+                    help="N > 1 with --full: skip the second measurement through the in-library device group (a child process started by rank 0 after "
                          "the headline measurement; its line is folded into the output as `group_mode`)")
     ap.add_argument("--no-variants", action="store_true",
-                    help="N > 1: skip the two child runs behind the headline (emulated shard without exchange, split column-sum exchange)")
+                    help="N > 1 with --full: skip the two child runs behind the headline (emulated shard without exchange, split column-sum exchange)")
     ap.add_argument("--ctx-option", action="append", default=[], metavar="NAME=VALUE",
                     help="same-box comparisons: gingr_ctx_set_option on the context, NAME in cull | fine_cull | nn_grid | tri_grid | "
                          "split_exchange | gram_downdate (all select between code paths with the same results)")
@@ -757,9 +789,11 @@ def main():
                   "a registration")
     ok = reason is None
     sigma2_timed = float(sc.sigma2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, alpha, sc, fit)
     # the driver's contract fixes K = 20 (46 ms at 50k): a longer run of the same workload next to it, same rules
     sustained = None
-    if elapsed is not None and args.sustained_steps > 0:
+    if args.full and elapsed is not None and args.sustained_steps > 0:
         s_el, _, s_info, s_state, s_bad = timed_updates(args.sustained_steps, args.warmup)
         sustained = {"steps": args.sustained_steps, "valid": s_bad is None and s_el is not None and ok, "timing": s_info, "reason": s_bad}
         if s_el is not None:
@@ -768,115 +802,114 @@ def main():
     if elapsed is None:                           # nothing could be timed: keep the line well-formed
         elapsed, enqueue_s = float("nan"), float("nan")
 
-    # ---- live roofline of the dominant kernels (HIP events on the kernels' stream, extra iterations)
-    roof = None
-    kernels = []
-    # (from a defined, live spot of the same trajectory: sigma2_0 + the warm-up of the timed blocks)
-    w_roof = int(timing_info.get("warmup_per_block", args.warmup))
-    runner.reset(sigma2_0)
-    runner.update(w_roof)
-    runner.sync()
-    timing(enable=True, reset=True)
-    runner.update(args.roofline_steps)
-    runner.sync()
-    pairs = float(m_loc) * float(N)
-    names = {0: ("cpd_colsum_kernel", 11.0), 1: ("cpd_rowstats_kernel", 18.0)}
-    for which, (name, flops_per_pair) in names.items():
-        ms, n = timing(which)
+    roof, kernels, upd_ms, exchange = None, [], None, None
+    if args.full:
+        # ---- live roofline of the dominant kernels (HIP events on the kernels' stream, extra iterations)
+        # (from a defined, live spot of the same trajectory: sigma2_0 + the warm-up of the timed blocks)
+        w_roof = int(timing_info.get("warmup_per_block", args.warmup))
+        runner.reset(sigma2_0)
+        runner.update(w_roof)
+        runner.sync()
+        timing(enable=True, reset=True)
+        runner.update(args.roofline_steps)
+        runner.sync()
+        pairs = float(m_loc) * float(N)
+        names = {0: ("cpd_colsum_kernel", 11.0), 1: ("cpd_rowstats_kernel", 18.0)}
+        for which, (name, flops_per_pair) in names.items():
+            ms, n = timing(which)
+            if n:
+                avg = ms / n
+                ach = flops_per_pair * pairs / (avg * 1e-3) / 1e12
+                kernels.append({"kernel": name, "avg_ms": avg, "launches": n, "bound": "valu_f64",
+                                "achieved": ach, "peak": F64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                "frac": ach / F64_VALU_PEAK_TFLOPS, "algorithmic_flops_per_pair": flops_per_pair})
+        # Secondary kernels, with SURVEY 8d's formulas at the MODEL rank r (not the padded rank rp the kernels stream and multiply):
+        #   Gram: 3 M r^2 flops SYRK-halved -- what a triangle-only kernel has to issue, and `frac`; 6 M r^2 (full symmetric) as a note;
+        #         its pass over the basis is 24 M r bytes, quoted against the HBM peak next to it (neither bound is near saturation
+        #         at r = 100; the matrix pipe is the binding one from r = 256 on);
+        #   sweeps: 24 M r bytes.
+        r_model = args.rank
+        rp = (args.rank + 15) // 16 * 16
+        wide = rp >= 128
+        ms, n = timing(2)
         if n:
             avg = ms / n
-            ach = flops_per_pair * pairs / (avg * 1e-3) / 1e12
-            kernels.append({"kernel": name, "avg_ms": avg, "launches": n, "bound": "valu_f64",
-                            "achieved": ach, "peak": F64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                            "frac": ach / F64_VALU_PEAK_TFLOPS, "algorithmic_flops_per_pair": flops_per_pair})
-    # Secondary kernels, with SURVEY 8d's formulas at the MODEL rank r (not the padded rank rp the kernels stream and multiply):
-    #   Gram: 3 M r^2 flops SYRK-halved -- what a triangle-only kernel has to issue, and `frac`; 6 M r^2 (full symmetric) as a note;
-    #         its pass over the basis is 24 M r bytes, quoted against the HBM peak next to it (neither bound is near saturation
-    #         at r = 100; the matrix pipe is the binding one from r = 256 on);
-    #   sweeps: 24 M r bytes.
-    r_model = args.rank
-    rp = (args.rank + 15) // 16 * 16
-    wide = rp >= 128
-    ms, n = timing(2)
-    if n:
-        avg = ms / n
-        gram_name = "gram_wide_kernel" if wide else "gram_tri_kernel"
-        ach_half = 3.0 * m_loc * r_model * r_model / (avg * 1e-3) / 1e12
-        hbm = 24.0 * m_loc * r_model / (avg * 1e-3) / 1e9
-        kernels.append({"kernel": gram_name, "avg_ms": avg, "launches": n, "bound": "mfma",
-                        "achieved": ach_half, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": ach_half / F64_MFMA_PEAK_TFLOPS,
-                        "algorithmic_flops": 3.0 * m_loc * r_model * r_model,
-                        "note": "SYRK-halved count 3 M r^2 at the model rank (the kernel multiplies the upper triangle only); "
-                                "full_symmetric_* is SURVEY 8d's 6 M r^2 count of the same launch",
-                        "full_symmetric_achieved": 2.0 * ach_half, "full_symmetric_frac": 2.0 * ach_half / F64_MFMA_PEAK_TFLOPS,
-                        "hbm_achieved_GBs": hbm, "hbm_frac": hbm / HBM_PEAK_GBS, "algorithmic_bytes": 24.0 * m_loc * r_model,
-                        "padded_rank": rp,
-                        "traffic": (load_pmc_traffic(gram_name, M, args.rank) if n_shards == 1 and not args.emulate_world else (None, None))[0],
-                        # busy cycles of the matrix pipe / (SIMDs x kernel cycles) from the SQ counters (tracked artefact), next to
-                        # the time-derived fractions above
-                        "mfma_counters": load_pmc_mfma(gram_name, M, args.rank) if n_shards == 1 and not args.emulate_world else None})
-    ms, n = timing(4)
-    if n:
-        avg = ms / n
-        gbs = 24.0 * m_loc * r_model / (avg * 1e-3) / 1e9
-        tr, src = load_pmc_traffic("sweep_fit_boxes_kernel", M, args.rank) if n_shards == 1 else (None, None)
-        kernels.append({"kernel": "sweep_fit_boxes_kernel", "avg_ms": avg, "launches": n, "bound": "hbm", "achieved": gbs,
-                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
-                        "algorithmic_bytes": 24.0 * m_loc * r_model, "padded_rank": rp, "traffic": tr, "traffic_source": src})
-    ms, n = timing(5)
-    if n:
-        if rp > 240:    # the multi-workgroup blocked solve (gp.hip: launch_posterior_solve): one event pair around all of its launches
-            kernels.append({"kernel": "posterior solve (solve_system + per 64-column panel chol_block64 / chol_panel / chol_trailing / "
-                                      "chol_backward + solve_finish)", "avg_ms": ms / n, "launches": n, "bound": "latency",
-                            "note": "r^3 / 3 flops on the critical path of the iteration; ~6 us per launch, the 64 x 64 diagonal block "
-                                    "(one workgroup, 17 us) per panel"})
-        else:
-            solve_name = ("posterior_solve_wide_kernel" if rp > 128 else "posterior_solve_lds_kernel")
-            kernels.append({"kernel": solve_name, "avg_ms": ms / n, "launches": n, "bound": "latency",
-                            "note": "one workgroup: r^3 / 3 flops on the critical path of the iteration"})
-    if n_shards == 1 and not args.emulate_world:
-        for k in kernels:   # the tracked rocprof summary of the same workload, where there is one
-            ms_r, src_r = load_rocprof_avg_ms(k["kernel"], M, args.rank)
-            if ms_r is not None:
-                k["rocprof_avg_ms"] = ms_r
-                k["rocprof_source"] = src_r
-                if "achieved" in k and k.get("avg_ms"):
-                    k["frac_from_rocprof"] = k["frac"] * k["avg_ms"] / ms_r
-    # (the whole update as HIP events see it DURING these instrumented iterations: the per-kernel event pairs serialise the
-    # launches, and the iterations sit at a later sigma2 than the timed ones -- so it is an upper bracket of ms_per_step, not a
-    # second measurement of it)
-    ms, n = timing(3)
-    upd_ms = ms / n if n else None
-    # ---- the two exchanges of an iteration as this rank / shard 0 sees them (HIP events on the kernels' stream around the collective
-    # resp. around the group's wait + peer-sum kernel: includes waiting for the slowest peer); N > 1: maximum over the ranks
-    exchange = None
-    if n_shards > 1 or use_dist:
-        ex = []
-        for seg in (0, 1):
-            ms, n = timing(6 + seg)
-            ex.append(ms / n if n else 0.0)
-        per_rank = None
-        if use_dist:
-            # every rank's own view first (events around each collective on ITS stream: its wait for the slowest peer included), with the
-            # two pair loops it ran next to them -- the first 8-GPU line has to be readable rank by rank
-            mine = {"rank": rank, "segment0_column_sums_ms": ex[0], "segment1_gram_bundle_ms": ex[1]}
-            for which, name in ((0, "cpd_colsum_kernel_ms"), (1, "cpd_rowstats_kernel_ms"), (3, "instrumented_update_ms")):
-                ms_k, n_k = timing(which)
-                mine[name] = ms_k / n_k if n_k else None
-            per_rank = [None] * dist.get_world_size()
-            dist.all_gather_object(per_rank, mine)
-            te = torch.tensor(ex, dtype=torch.float64, device="cpu" if shared_device else f"cuda:{local_rank}")
-            dist.all_reduce(te, op=dist.ReduceOp.MAX)
-            ex = [float(v) for v in te.tolist()]
-        exchange = {"path": exchange_path if use_dist else "in-library device group (peer pointers)",
-                    "per_rank": per_rank,
-                    "rccl": ctx.rccl_info() if (use_dist and native) else None,
-                    "segment0_column_sums_ms": ex[0], "segment1_gram_bundle_ms": ex[1],
-                    "bytes": {"segment0": 8 * N, "segment1": 8 * (((args.rank + 15) // 16 * 16) ** 2 + 2 * ((args.rank + 15) // 16 * 16) + 8)},
-                    "how": "HIP events around each all-reduce on the stream the kernels run on, averaged over the roofline "
-                           "iterations, max over ranks; includes the wait for the slowest peer"}
-    timing(enable=False)
+            gram_name = "gram_wide_kernel" if wide else "gram_tri_kernel"
+            ach_half = 3.0 * m_loc * r_model * r_model / (avg * 1e-3) / 1e12
+            hbm = 24.0 * m_loc * r_model / (avg * 1e-3) / 1e9
+            kernels.append({"kernel": gram_name, "avg_ms": avg, "launches": n, "bound": "mfma",
+                            "achieved": ach_half, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                            "frac": ach_half / F64_MFMA_PEAK_TFLOPS,
+                            "algorithmic_flops": 3.0 * m_loc * r_model * r_model,
+                            "note": "SYRK-halved count 3 M r^2 at the model rank (the kernel multiplies the upper triangle only); "
+                                    "full_symmetric_* is SURVEY 8d's 6 M r^2 count of the same launch",
+                            "full_symmetric_achieved": 2.0 * ach_half, "full_symmetric_frac": 2.0 * ach_half / F64_MFMA_PEAK_TFLOPS,
+                            "hbm_achieved_GBs": hbm, "hbm_frac": hbm / HBM_PEAK_GBS, "algorithmic_bytes": 24.0 * m_loc * r_model,
+                            "padded_rank": rp,
+                            "traffic": (load_pmc_traffic(gram_name, M, args.rank) if n_shards == 1 and not args.emulate_world else (None, None))[0],
+                            # busy cycles of the matrix pipe / (SIMDs x kernel cycles) from the SQ counters (tracked artefact), next to
+                            # the time-derived fractions above
+                            "mfma_counters": load_pmc_mfma(gram_name, M, args.rank) if n_shards == 1 and not args.emulate_world else None})
+        ms, n = timing(4)
+        if n:
+            avg = ms / n
+            gbs = 24.0 * m_loc * r_model / (avg * 1e-3) / 1e9
+            tr, src = load_pmc_traffic("sweep_fit_boxes_kernel", M, args.rank) if n_shards == 1 else (None, None)
+            kernels.append({"kernel": "sweep_fit_boxes_kernel", "avg_ms": avg, "launches": n, "bound": "hbm", "achieved": gbs,
+                            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
+                            "algorithmic_bytes": 24.0 * m_loc * r_model, "padded_rank": rp, "traffic": tr, "traffic_source": src})
+        ms, n = timing(5)
+        if n:
+            if rp > 240:    # the multi-workgroup blocked solve (gp.hip: launch_posterior_solve): one event pair around all of its launches
+                kernels.append({"kernel": "posterior solve (solve_system + per 64-column panel chol_block64 / chol_panel / chol_trailing / "
+                                          "chol_backward + solve_finish)", "avg_ms": ms / n, "launches": n, "bound": "latency",
+                                "note": "r^3 / 3 flops on the critical path of the iteration; ~6 us per launch, the 64 x 64 diagonal block "
+                                        "(one workgroup, 17 us) per panel"})
+            else:
+                solve_name = ("posterior_solve_wide_kernel" if rp > 128 else "posterior_solve_lds_kernel")
+                kernels.append({"kernel": solve_name, "avg_ms": ms / n, "launches": n, "bound": "latency",
+                                "note": "one workgroup: r^3 / 3 flops on the critical path of the iteration"})
+        if n_shards == 1 and not args.emulate_world:
+            for k in kernels:   # the tracked rocprof summary of the same workload, where there is one
+                ms_r, src_r = load_rocprof_avg_ms(k["kernel"], M, args.rank)
+                if ms_r is not None:
+                    k["rocprof_avg_ms"] = ms_r
+                    k["rocprof_source"] = src_r
+                    if "achieved" in k and k.get("avg_ms"):
+                        k["frac_from_rocprof"] = k["frac"] * k["avg_ms"] / ms_r
+        # (the whole update as HIP events see it DURING these instrumented iterations: the per-kernel event pairs serialise the
+        # launches, and the iterations sit at a later sigma2 than the timed ones -- so it is an upper bracket of ms_per_step, not a
+        # second measurement of it)
+        ms, n = timing(3)
+        upd_ms = ms / n if n else None
+        # ---- the two exchanges of an iteration as this rank / shard 0 sees them (HIP events on the kernels' stream around the collective
+        # resp. around the group's wait + peer-sum kernel: includes waiting for the slowest peer); N > 1: maximum over the ranks
+        if n_shards > 1 or use_dist:
+            ex = []
+            for seg in (0, 1):
+                ms, n = timing(6 + seg)
+                ex.append(ms / n if n else 0.0)
+            per_rank = None
+            if use_dist:
+                # every rank's own view first (events around each collective on ITS stream: its wait for the slowest peer included), with the
+                # two pair loops it ran next to them -- the first 8-GPU line has to be readable rank by rank
+                mine = {"rank": rank, "segment0_column_sums_ms": ex[0], "segment1_gram_bundle_ms": ex[1]}
+                for which, name in ((0, "cpd_colsum_kernel_ms"), (1, "cpd_rowstats_kernel_ms"), (3, "instrumented_update_ms")):
+                    ms_k, n_k = timing(which)
+                    mine[name] = ms_k / n_k if n_k else None
+                per_rank = [None] * dist.get_world_size()
+                dist.all_gather_object(per_rank, mine)
+                te = torch.tensor(ex, dtype=torch.float64, device="cpu" if shared_device else f"cuda:{local_rank}")
+                dist.all_reduce(te, op=dist.ReduceOp.MAX)
+                ex = [float(v) for v in te.tolist()]
+            exchange = {"path": exchange_path if use_dist else "in-library device group (peer pointers)",
+                        "per_rank": per_rank,
+                        "rccl": ctx.rccl_info() if (use_dist and native) else None,
+                        "segment0_column_sums_ms": ex[0], "segment1_gram_bundle_ms": ex[1],
+                        "bytes": {"segment0": 8 * N, "segment1": 8 * (((args.rank + 15) // 16 * 16) ** 2 + 2 * ((args.rank + 15) // 16 * 16) + 8)},
+                        "how": "HIP events around each all-reduce on the stream the kernels run on, averaged over the roofline "
+                               "iterations, max over ranks; includes the wait for the slowest peer"}
+        timing(enable=False)
     # ---- who took part: the world the collective library saw and the physical devices behind the ranks / shards
     ranks_info = None
     if use_dist:
@@ -913,7 +946,7 @@ def main():
     # affinity statistics of that evaluation (P1, PX of this rank's rows; den, Np) and the sigma2 it committed against the strict
     # C oracle evaluated at the pre-update state (full size: ~2.5e9 pair evaluations on the host cores)
     parity = None
-    if not args.no_parity_check and args.emulate_world <= 1 and rank == 0 and not args.group and world == 1:
+    if args.full and not args.no_parity_check and args.emulate_world <= 1 and rank == 0 and not args.group and world == 1:
         from oracle import c_oracle as co
         _, sc, fit = runner.state()                            # the state after the warm-up + roofline iterations
         runner.update(1)
@@ -937,7 +970,7 @@ def main():
     # rank 0 replays the warm-up + roofline iterations the sharded state went through on its own GPU: milliseconds).  Same arithmetic, different order of
     # the partial sums, so agreement is ~1e-12; a wrong exchange shows up as O(1)
     shard_check = None
-    if n_shards > 1 and rank == 0 and not args.emulate_world and not args.group and not args.no_parity_check:
+    if args.full and n_shards > 1 and rank == 0 and not args.emulate_world and not args.group and not args.no_parity_check:
         a_sh, sc_sh, _ = runner.state()
         with torch.cuda.stream(stream):
             single = ShardedFitter(ctx, model, x, rank=0, world=1, all_reduce=None,
@@ -958,7 +991,7 @@ def main():
         ok = ok and shard_check["ok"]
 
     cpu = None
-    if rank == 0 and n_shards == 1 and not args.no_cpu_baseline and not args.emulate_world:
+    if args.full and rank == 0 and n_shards == 1 and not args.no_cpu_baseline and not args.emulate_world:
         cpu = cpu_baseline(y, x, sigma2_0, args.w, model=model)
 
     if rank == 0:
@@ -1008,9 +1041,9 @@ def main():
     ctx.close()
     if use_dist:
         dist.destroy_process_group()
-    if rank == 0 and world > 1 and not args.group and not args.no_group_mode and not args.emulate_world:
+    if args.full and rank == 0 and world > 1 and not args.group and not args.no_group_mode and not args.emulate_world:
         out["group_mode"] = run_group_mode(args, world, shared_device)
-    if rank == 0 and world > 1 and not args.group and not args.no_variants and not args.emulate_world:
+    if args.full and rank == 0 and world > 1 and not args.group and not args.no_variants and not args.emulate_world:
         # next to the headline, from child processes on the same devices: what one rank's shard costs with the exchanges taken out
         # (an emulated shard on one GPU), and the same N-rank run with the column-sum exchange split in two halves
         # (GINGR_OPT_SPLIT_EXCHANGE = 1; off by default: 26-35 us slower in the single-GPU emulation, never seen on real links)

@@ -85,3 +85,28 @@ def test_a_hung_child_run_is_stopped_with_everything_it_started(monkeypatch, tmp
     with pytest.raises(TimeoutError):                                           # nothing left: refused at once
         b._run_child([sys.executable, "-c", "print(1)"], dict(os.environ), 60.0)
     b._CHILD_DEADLINE[0] = None
+
+
+def test_dump_outputs_writes_the_state_in_float64_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array of the state as DIR/<name>.npy in float64; a fit above the budget becomes the same seeded row
+    sample on every run, with its row indices next to it."""
+    import numpy as np
+    from gingr_amd import _native as nat
+    b = _bench()
+    sc = nat.StateScalars()
+    sc.sigma2, sc.scale, sc.iteration = 2.5, 1.0, 23
+    sc.translation[:] = [1.0, 2.0, 3.0]
+    alpha = np.linspace(-1.0, 1.0, 100)
+    fit = np.arange(3000.0).reshape(1000, 3)
+    b.dump_outputs(str(tmp_path / "a"), alpha, sc, fit)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"alpha", "fit", "sigma2", "scale", "euler", "center", "translation", "iteration", "status"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["fit"], fit) and np.array_equal(got["alpha"], alpha) and got["sigma2"] == 2.5
+    assert list(got["translation"]) == [1.0, 2.0, 3.0] and got["iteration"] == 23
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", (1 << 20) + 800 + 32 * 100)       # room for 100 of the 1000 rows
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), alpha, sc, fit)
+    rows_b, rows_c = np.load(tmp_path / "b" / "fit_rows.npy"), np.load(tmp_path / "c" / "fit_rows.npy")
+    assert rows_b.shape == (100,) and np.array_equal(rows_b, rows_c) and np.all(np.diff(rows_b) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "fit.npy"), fit[rows_b.astype(int)])

@@ -20,7 +20,7 @@ def test_bench_launch_line_with_ranks_sharing_the_device(world, points):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1",
-                        "--points", str(points), "--rank", "40", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True,
+                        "--points", str(points), "--rank", "40", "--no-cpu-baseline", "--full"], env=env, cwd=ROOT, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -67,7 +67,7 @@ def test_bench_native_rccl_exchange_with_a_one_rank_communicator():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GINGR_BENCH_SHARED_DEVICE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "4", "--warmup", "1", "--points", "6000",
-                        "--rank", "40", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--rank", "40", "--no-cpu-baseline", "--full"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     ex = out["exchange"]
@@ -83,7 +83,7 @@ def test_bench_group_mode_reports_the_exchange():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--group", "--logical-shards", "2", "--steps", "4", "--warmup", "1",
-                        "--points", "6000", "--rank", "40", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True,
+                        "--points", "6000", "--rank", "40", "--no-cpu-baseline", "--full"], env=env, cwd=ROOT, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])

@@ -106,7 +106,7 @@ def test_bench_launch_line_on_distinct_devices(world):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GINGR_BENCH_SHARED_DEVICE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--points", "6000",
-                        "--rank", "40", "--sustained-steps", "0", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1800)
+                        "--rank", "40", "--sustained-steps", "0", "--no-cpu-baseline", "--full"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     assert out["n_gpus"] == world and out["valid"] is True, out.get("reason")

@@ -206,14 +206,14 @@ def config2():
 
 
 def config3():
-    o = _bench("--points", "15000", "--steps", "100", "--warmup", "10")
+    o = _bench("--full", "--points", "15000", "--steps", "100", "--warmup", "10")
     o["config"] = 3
     o["metric"] = "GiNGR update iters/sec, 15k<->15k CPD"
     return o
 
 
 def config4():
-    o = _bench("--points", "100000", "--steps", "20", "--warmup", "3")
+    o = _bench("--full", "--points", "100000", "--steps", "20", "--warmup", "3")
     o["config"] = 4
     o["metric"] = "GiNGR update iters/sec, 100k<->100k CPD"
     e = _bench("--points", "100000", "--emulate-world", "8", "--no-cpu-baseline", "--no-parity-check", "--steps", "40", "--warmup", "5",
@@ -312,7 +312,7 @@ def metric_rank256():
     """The metric workload (50k <-> 50k CPD) at SURVEY 8d's second model rank, r = 256: bench.py's own line (child process: bench.py
     owns its context), with the kernels of the wide path (gram_wide_kernel, posterior_solve_wide_kernel, sweep_fit_boxes_kernel<16, 1>)."""
     import subprocess
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rank", "256", "--no-cpu-baseline"], capture_output=True, text=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--rank", "256", "--no-cpu-baseline"], capture_output=True, text=True,
                        timeout=1200, cwd=ROOT)
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     d["config"] = "metric workload at model rank 256 (SURVEY 8d: r in {100, 256})"

@@ -34,7 +34,7 @@ for r in (128, 200, 256, 512):
         if r == 256:
             shutil.copy(os.path.join(F, "bench_rank256.json"), os.path.join(P, f"r{rnd}_bench50k_r256.json"))
 if ranks:
-    json.dump({"what": "the metric workload (50k <-> 50k CPD) at model ranks above 112: python bench.py --rank R --no-cpu-baseline", "ranks": ranks},
+    json.dump({"what": "the metric workload (50k <-> 50k CPD) at model ranks above 112: python bench.py --full --rank R --no-cpu-baseline", "ranks": ranks},
               open(os.path.join(P, f"r{rnd}_bench50k_wide_ranks.json"), "w"), indent=1)
 
 e50 = {str(n): load(f"emu{n}.json")["ms_per_step"] for n in (1, 2, 4, 8)}
