@@ -84,6 +84,15 @@ class ScalarKernel(ctypes.Structure):
                 ("scaling", c_double), ("lookup", _dp)]
 
 
+GPMM_MAX_COLUMNS = 1536
+
+
+class GpmmInfo(ctypes.Structure):
+    """gingr_gpmm_info"""
+    _fields_ = [("columns", c_int32), ("rank", c_int32), ("tolerance_reached", c_int32), ("residual_fraction", c_double),
+                ("kept_variance_fraction", c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/gingr_hip.h declares
 SIGNATURES = {
     "gingr_device_count": (c_int, []),
@@ -136,6 +145,9 @@ SIGNATURES = {
     "gingr_model_new_reference": (c_int, [c_void_p, c_void_p, c_int64, _dp, _ip, _dp, c_int64, c_int64, POINTER(c_void_p)]),
     "gingr_gpmm_build_diagonal": (c_int, [c_void_p, c_int64, _dp, POINTER(ScalarKernel), POINTER(ScalarKernel), POINTER(ScalarKernel),
                                           c_double, c_int32, c_int64, c_int64, POINTER(c_void_p)]),
+    "gingr_gpmm_build_diagonal_ex": (c_int, [c_void_p, c_int64, _dp, POINTER(ScalarKernel), POINTER(ScalarKernel), POINTER(ScalarKernel),
+                                             c_double, c_int32, c_int32, c_int64, c_int64, POINTER(GpmmInfo), POINTER(c_void_p)]),
+    "gingr_model_truncate": (c_int, [c_void_p, c_void_p, c_int32, POINTER(c_void_p)]),
     "gingr_gpmm_build_gaussian": (c_int, [c_void_p, c_int64, _dp, c_int32, _dp, _dp, c_double, c_int32, c_int64, c_int64,
                                           POINTER(c_void_p)]),
     "gingr_pointset_distance_extrema": (c_int, [c_void_p, _dp, c_int64, _dp, _dp]),

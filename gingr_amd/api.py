@@ -225,6 +225,26 @@ class PointDistributionModel:
     def numberOfPoints(self) -> int:
         return int(self.reference.shape[0])
 
+    def truncate(self, k: int) -> "PointDistributionModel":
+        """PointDistributionModel.truncate(k): the first k basis functions, as an independent model (copies)."""
+        k = int(k)
+        if k < 1 or k > self.rank:
+            raise ValueError(f"truncate: k = {k} outside 1..{self.rank} (the model's rank)")
+        return PointDistributionModel(reference=np.array(self.reference, dtype=np.float64), mean=np.array(self.mean, dtype=np.float64),
+                                      basis=np.array(np.asarray(self.basis)[:, :k], dtype=np.float64, order="F"),
+                                      variance=np.array(np.asarray(self.variance)[:k], dtype=np.float64),
+                                      cells=None if self.cells is None else np.array(self.cells))
+
+
+@dataclasses.dataclass(frozen=True)
+class GpmmBuildInfo:
+    """gingr_gpmm_info: what the factorisation behind a device-built model did."""
+    columns: int                   # factor columns of the pivoted Cholesky (= the model's rank before truncation)
+    rank: int                      # rank of the model
+    tolerance_reached: bool        # the residual trace fell below relativeTolerance * trace
+    residual_fraction: float       # residual trace / trace at the stop
+    kept_variance_fraction: float  # kept eigenvalues / all eigenvalues (1 without truncation)
+
 
 @dataclasses.dataclass(frozen=True)
 class ScalarKernelSpec:
@@ -258,19 +278,74 @@ class DevicePointDistributionModel:
     (gingr_gpmm_build_gaussian / gingr_gpmm_build_diagonal).  Quacks like PointDistributionModel (reference / mean / basis /
     variance / rank / numberOfPoints); basis and variance are downloaded lazily, only if somebody asks for them."""
 
+    _to_tolerance, _keep, _info = False, 0, None   # (subclasses that are not built from kernels)
+
     def __init__(self, ctx: Context, reference, sigmas: Sequence[float], scalings: Sequence[float],
                  relativeTolerance: float, maxRank: int = 0, kernels: Optional[Sequence[ScalarKernelSpec]] = None,
-                 cells: Optional[np.ndarray] = None):
+                 cells: Optional[np.ndarray] = None, toTolerance: bool = False, keepRank: int = 0):
+        """toTolerance / keepRank: the build goes through gingr_gpmm_build_diagonal_ex -- maxRank is then the largest number of FACTOR
+        columns (0: run to relativeTolerance, an error if the library's ceiling comes first; nothing is shortened silently) and the
+        model keeps the keepRank leading eigenpairs (0: all).  Without them: today's call, maxRank silently clamped to 512."""
         self.ctx = ctx
         self.reference = f64(reference)
         self._sig, self._sc = f64(sigmas), f64(scalings)
         self._tol, self._maxrank = float(relativeTolerance), int(maxRank)
         self._kernels = None if kernels is None else tuple(kernels)          # (k_x, k_y, k_z) of a DiagonalKernel
         self.cells = cells
+        self._to_tolerance, self._keep = bool(toTolerance), int(keepRank)
+        self._info: Optional[GpmmBuildInfo] = None
         self._full: Optional["DeviceModel"] = None
         self._host: Optional[PointDistributionModel] = None
 
+    def _build_ex(self, ctx: Context, row_begin: int, row_end: int):
+        kernels = self._kernels
+        if kernels is None:
+            k = ScalarKernelSpec("gauss", tuple(float(v) for v in self._sig), tuple(float(v) for v in self._sc))
+            kernels = (k, k, k)
+        keep: list = []
+        uniq = {}
+        nk = []
+        for spec in kernels:
+            if id(spec) not in uniq:
+                uniq[id(spec)] = spec._native(keep)
+            nk.append(uniq[id(spec)])
+        if self._to_tolerance:
+            max_columns = self._maxrank
+        else:            # today's stop (maxRank clamped to the rank limit), with a truncation folded in
+            max_columns = self._maxrank if 0 < self._maxrank <= 512 else 512
+        h, info = c_void_p(), nat.GpmmInfo()
+        rc = ctx._lib.gingr_gpmm_build_diagonal_ex(ctx.handle, self.numberOfPoints, dptr(self.reference), ctypes.byref(nk[0]),
+                                                   ctypes.byref(nk[1]), ctypes.byref(nk[2]), self._tol, int(max_columns), self._keep,
+                                                   row_begin, row_end, ctypes.byref(info), ctypes.byref(h))
+        self._info = GpmmBuildInfo(int(info.columns), int(info.rank), bool(info.tolerance_reached), float(info.residual_fraction),
+                                   float(info.kept_variance_fraction))
+        _check(ctx.handle, rc, "gingr_gpmm_build_diagonal_ex")
+        return h
+
+    @property
+    def buildInfo(self) -> Optional[GpmmBuildInfo]:
+        """gingr_gpmm_info of the build (builds the model if that has not happened); None for a model that was not built through
+        gingr_gpmm_build_diagonal_ex (toTolerance / truncate)."""
+        if self._to_tolerance or self._keep > 0:
+            self.device()
+        return self._info
+
+    def truncate(self, k: int) -> "DevicePointDistributionModel":
+        """PointDistributionModel.truncate(k) on the device.  A kernel model that has not been built yet folds the truncation into its
+        build (keep_rank = k: the only way a factor of more than 512 columns becomes a model); a resident one is truncated in HBM
+        (gingr_model_truncate)."""
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"truncate: k = {k} < 1")
+        if self._full is None and type(self) is DevicePointDistributionModel:
+            keep = k if self._keep <= 0 else min(k, self._keep)
+            return DevicePointDistributionModel(self.ctx, self.reference, self._sig, self._sc, self._tol, self._maxrank, self._kernels,
+                                                self.cells, toTolerance=self._to_tolerance, keepRank=keep)
+        return TruncatedDevicePointDistributionModel(self.device(), k, cells=self.cells)
+
     def _build(self, ctx: Context, row_begin: int, row_end: int):
+        if self._to_tolerance or self._keep > 0:
+            return self._build_ex(ctx, row_begin, row_end)
         h = c_void_p()
         if self._kernels is not None:
             keep: list = []
@@ -355,6 +430,33 @@ class InterpolatedDevicePointDistributionModel(DevicePointDistributionModel):
         return self.to_host(basis=False).mean
 
 
+class TruncatedDevicePointDistributionModel(DevicePointDistributionModel):
+    """model.truncate(k) of a model resident in HBM (gingr_model_truncate): the k leading basis functions, an independent model."""
+
+    def __init__(self, source: "DeviceModel", k: int, cells=None):
+        if source.row_begin != 0 or source.M_local != source.host.numberOfPoints:
+            raise ValueError("truncate: the source is a row shard")
+        self.ctx = source.ctx
+        self.reference = f64(source.host.reference)
+        self._src_dev, self._k = source, int(k)
+        self.cells = cells
+        self._kernels, self._full, self._host, self._info = None, None, None, None
+        self._to_tolerance, self._keep = False, 0
+        if self._k < 1 or self._k > source.rank:
+            raise ValueError(f"truncate: k = {self._k} outside 1..{source.rank} (the model's rank)")
+
+    def _build(self, ctx: Context, row_begin: int, row_end: int):
+        if ctx is not self.ctx or int(row_begin) != 0 or int(row_end) != self.numberOfPoints:
+            raise ValueError("a truncated resident model lives whole on the context of its source; download it (to_host) for anything else")
+        h = c_void_p()
+        _check(ctx.handle, ctx._lib.gingr_model_truncate(ctx.handle, self._src_dev.handle, self._k, ctypes.byref(h)), "gingr_model_truncate")
+        return h
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self.to_host(basis=False).mean
+
+
 @dataclasses.dataclass
 class GaussianKernelParameters:
     """GPMMHelper.scala:94"""
@@ -389,8 +491,12 @@ class GPMMTriangleMesh3D:
     """GPMMTriangleMesh3D(reference, relativeTolerance) (GPMMHelper.scala:96-153): every kernel of the reference, the low-rank
     factorisation built in HBM.  `cells` (the triangulation) is only needed by the Laplacian kernels; it is handed on to the model."""
 
-    def __init__(self, ctx: Context, reference, relativeTolerance: float = 0.01, maxRank: int = 0, cells=None):
+    def __init__(self, ctx: Context, reference, relativeTolerance: float = 0.01, maxRank: int = 0, cells=None, toTolerance: bool = False):
+        """toTolerance=False: maxRank columns at most, silently clamped to 512 (the rank limit of a model).  toTolerance=True: the
+        reference's behaviour -- the factorisation runs until relativeTolerance is met (maxRank = 0) or to maxRank factor columns,
+        and a model above rank 512 is an error that asks for .truncate(k) (see DevicePointDistributionModel)."""
         self.ctx, self.reference, self.relativeTolerance, self.maxRank = ctx, f64(reference), relativeTolerance, maxRank
+        self.toTolerance = bool(toTolerance)
         self.cells = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32)
 
     def Gaussian(self, sigma: float, scaling: float) -> DevicePointDistributionModel:
@@ -398,7 +504,7 @@ class GPMMTriangleMesh3D:
 
     def GaussianMixture(self, pars: Sequence[GaussianKernelParameters]) -> DevicePointDistributionModel:
         return DevicePointDistributionModel(self.ctx, self.reference, [p.sigma for p in pars], [p.scaling for p in pars],
-                                            self.relativeTolerance, self.maxRank, cells=self.cells)
+                                            self.relativeTolerance, self.maxRank, cells=self.cells, toTolerance=self.toTolerance)
 
     def AutomaticGaussian(self) -> DevicePointDistributionModel:
         mx = PointSetHelper(self.ctx, self.reference).maximumPointDistance()
@@ -406,7 +512,7 @@ class GPMMTriangleMesh3D:
 
     def _diagonal(self, kx: ScalarKernelSpec, ky: ScalarKernelSpec, kz: ScalarKernelSpec) -> DevicePointDistributionModel:
         return DevicePointDistributionModel(self.ctx, self.reference, [], [], self.relativeTolerance, self.maxRank,
-                                            kernels=(kx, ky, kz), cells=self.cells)
+                                            kernels=(kx, ky, kz), cells=self.cells, toTolerance=self.toTolerance)
 
     def GaussianDot(self, sigma: float, scaling: float) -> DevicePointDistributionModel:
         """GPMMHelper.scala:103-106: DotProductKernel(GaussianKernel(sigma), 1.0) * scaling.  DotProductKernel.k returns
@@ -479,12 +585,13 @@ class LaplacianHelper:
         return (u * np.where(s > precision, 1.0 / np.where(s > precision, s, 1.0), 0.0)[None, :]) @ vt
 
 
-def automaticGPMMfromTemplate(ctx: Context, template, relativeTolerance: float = 0.1) -> DevicePointDistributionModel:
-    """registration/utils/GPMMHelper.scala:39-69 (on the model's own points the TriangleMeshInterpolator is the identity)."""
+def automaticGPMMfromTemplate(ctx: Context, template, relativeTolerance: float = 0.1, toTolerance: bool = False) -> DevicePointDistributionModel:
+    """registration/utils/GPMMHelper.scala:39-69 (on the model's own points the TriangleMeshInterpolator is the identity).
+    toTolerance: see GPMMTriangleMesh3D."""
     h = PointSetHelper(ctx, template)
     mx, mn = h.maximumPointDistance(), h.minimumPointDistance()
     sig = [mx / 4, mx / 8, mn * 5]
-    return DevicePointDistributionModel(ctx, template, sig, [v / 2 for v in sig], relativeTolerance)
+    return DevicePointDistributionModel(ctx, template, sig, [v / 2 for v in sig], relativeTolerance, toTolerance=toTolerance)
 
 
 class DeviceModel:
@@ -524,6 +631,15 @@ class DeviceModel:
         self.row_begin, self.row_end, self.M_local = 0, M, M
         self.rank = int(self._lib.gingr_model_rank(handle))
         return self
+
+    def truncate(self, k: int) -> "DeviceModel":
+        """The k leading basis functions as a new, independent resident model (gingr_model_truncate); complete models only."""
+        if isinstance(self.host, PointDistributionModel):
+            host = self.host.truncate(k)
+            h = c_void_p()
+            _check(self.ctx.handle, self._lib.gingr_model_truncate(self.ctx.handle, self.handle, int(k), ctypes.byref(h)), "gingr_model_truncate")
+            return DeviceModel._adopt(self.ctx, h, host, host.numberOfPoints)
+        return TruncatedDevicePointDistributionModel(self, k, cells=getattr(self.host, "cells", None)).device()
 
     def download(self, basis: bool = True) -> "PointDistributionModel":
         """Local rows back on the host in gingr_model_upload's layout (gingr_model_download)."""

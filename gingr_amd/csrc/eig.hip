@@ -392,7 +392,293 @@ __global__ __launch_bounds__(W * 64) void sym_eig_cols_kernel(EigBatch batch) {
     }
 }
 
+// ---- 193 .. 512 columns: the same decomposition (Cholesky, then one-sided Jacobi on the factor's columns) on many workgroups ----
+//
+// The register kernel ends at 192 columns (one workgroup's registers); the two-sided grid kernel of gpmm.hip that served everything
+// larger meets its 64 workgroups at a spin-wait barrier once a round.  Here every step is a launch of its own and the workgroups of
+// a launch never wait for each other:
+//   * the factor C (G = C C^T) is kept column-major, [columns padded to blocks of 16][rows padded to 64], zero padded;
+//   * Cholesky right-looking in panels of 16 columns: one workgroup factors the panel, a grid applies its rank-16 update;
+//   * a sweep is nblk - 1 launches (round-robin tournament of the nblk column blocks).  A workgroup owns one pair of blocks: it
+//     takes their 32 columns into LDS (at most 32 x 512 x 8 B = 128 KB), and its 16 waves rotate 16 disjoint column pairs at a
+//     time -- the 16 cross rounds (column i of one block against column i + s of the other), or, in the first launch of a sweep,
+//     the 31 rounds of a full tournament of the 32 columns, which also meets the pairs inside a block: every pair of columns
+//     once a sweep.  A pair's three dot products are summed by DPP (wave_allsum), the rotation is the register kernel's;
+//   * launches count the rotations of a sweep in a word of their own; the host stops after a sweep without one;
+//   * up to three problems side by side (blockIdx.y): the coordinate blocks of one model differ by at most one column.
+// Eigenvalue = squared column length, eigenvector = normalised column, as above.  A failed Cholesky pivot or a numerically singular
+// spectrum is reported in info[1]; the caller then takes the two-sided kernel, as it does for the register kernel.
+constexpr int kEbCols = 16;      // columns of a block
+constexpr int kEbThreads = 1024;  // 16 waves: one column pair each
+
+struct EigbBatch {
+    double *X[3];      // [nblk * 16][ldx]
+    int32_t n[3];
+};
+
+__global__ __launch_bounds__(256) void eigb_load_kernel(EigbBatch b, const double *G0, const double *G1, const double *G2, int32_t ld0,
+                                                        int32_t ld1, int32_t ld2, int32_t ldx, int32_t cols) {
+    const int q = blockIdx.y;
+    const double *G = q == 0 ? G0 : (q == 1 ? G1 : G2);
+    const int ldg = q == 0 ? ld0 : (q == 1 ? ld1 : ld2);
+    const int n = b.n[q];
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= cols * ldx) return;
+    const int c = idx / ldx, r = idx - c * ldx;
+    b.X[q][idx] = (c < n && r < n) ? G[(int64_t)c * ldg + r] : 0.0;  // (symmetric: column c is read as row c)
+}
+
+// columns k0 .. k0 + 15 of the factor, rows from the diagonal down; the rows above the diagonal are cleared at the end
+__global__ __launch_bounds__(kEbThreads) void eigb_chol_panel_kernel(EigbBatch b, int32_t ldx, int32_t k0, int32_t *__restrict__ failed) {
+    const int q = blockIdx.x;
+    const int n = b.n[q];
+    double *X = b.X[q];
+    const int t = threadIdx.x;
+    const int k1 = min(k0 + kEbCols, n);
+    for (int j = k0; j < k1; ++j) {
+        __syncthreads();
+        const double d = X[(int64_t)j * ldx + j];
+        const bool ok = d > 0.0 && d <= 1.79769313486231570815e308;
+        const double rs = ok ? 1.0 / sqrt(d) : 0.0;
+        __syncthreads();
+        if (!ok && t == 0) failed[q] = 1;
+        for (int r = j + t; r < n; r += kEbThreads) X[(int64_t)j * ldx + r] *= rs;
+        __syncthreads();
+        const int rows = n - j - 1;  // rows j + 1 .. n - 1 of the columns j + 1 .. k1 - 1
+        for (int idx = t; idx < (k1 - j - 1) * rows; idx += kEbThreads) {
+            const int c = j + 1 + idx / rows, r = j + 1 + idx % rows;
+            if (r >= c) X[(int64_t)c * ldx + r] = __builtin_fma(-X[(int64_t)j * ldx + r], X[(int64_t)j * ldx + c], X[(int64_t)c * ldx + r]);
+        }
+    }
+    __syncthreads();
+    for (int idx = t; idx < (k1 - k0) * n; idx += kEbThreads) {
+        const int c = k0 + idx / n, r = idx % n;
+        if (r < c) X[(int64_t)c * ldx + r] = 0.0;
+    }
+}
+
+// X[c][r] -= sum_{k0 <= k < k0 + 16} X[k][r] X[k][c]   for the columns c >= k0 + 16 (blockIdx.y), rows r >= c
+__global__ __launch_bounds__(256) void eigb_chol_update_kernel(EigbBatch b, int32_t ldx, int32_t k0) {
+    const int q = blockIdx.z;
+    const int n = b.n[q];
+    double *X = b.X[q];
+    const int c = k0 + kEbCols + blockIdx.y;
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n || r >= n || r < c) return;
+    double acc = X[(int64_t)c * ldx + r];
+#pragma unroll
+    for (int k = 0; k < kEbCols; ++k) acc = __builtin_fma(-X[(int64_t)(k0 + k) * ldx + r], X[(int64_t)(k0 + k) * ldx + c], acc);
+    X[(int64_t)c * ldx + r] = acc;
+}
+
+// One launch of the tournament of column blocks: workgroup (m, q) rotates the columns of its pair of blocks of problem q against
+// each other.  E = ldx / 64 values of a column per lane.  `full`: all pairs of the 32 columns, not only the cross pairs.
+template <int E>
+__global__ __launch_bounds__(kEbThreads) void eigb_round_kernel(EigbBatch b, int32_t nblk, int32_t rd, int32_t full,
+                                                                int32_t *__restrict__ rotations) {
+    extern __shared__ double eb_cols[];  // [32][E * 64]
+    constexpr int ldx = E * 64;
+    const int q = blockIdx.y;
+    const int n = b.n[q];
+    double *X = b.X[q];
+    const int m = blockIdx.x;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ba = m == 0 ? nblk - 1 : (rd + m) % (nblk - 1), bb = (rd + nblk - 1 - m) % (nblk - 1);
+    if ((full ? min(ba, bb) : max(ba, bb)) * kEbCols >= n) return;  // padding: no pair of columns to rotate
+    for (int idx = threadIdx.x; idx < 2 * kEbCols * ldx; idx += kEbThreads) {
+        const int j = idx / ldx, r = idx - j * ldx;
+        const int c = (j < kEbCols ? ba * kEbCols + j : bb * kEbCols + j - kEbCols);
+        eb_cols[idx] = X[(int64_t)c * ldx + r];
+    }
+    __syncthreads();
+    const double tol2 = (double)n * 2.220446049250313e-16 * 2.220446049250313e-16;
+    const int inner = full ? 2 * kEbCols - 1 : kEbCols;
+    int rotated = 0;
+    for (int s = 0; s < inner; ++s) {
+        int p, r;  // this wave's pair of local columns
+        if (full) {
+            constexpr int np = 2 * kEbCols;
+            p = w == 0 ? np - 1 : (s + w) % (np - 1);
+            r = (s + np - 1 - w) % (np - 1);
+        } else {
+            p = w;
+            r = kEbCols + ((w + s) & (kEbCols - 1));
+        }
+        const int cp = p < kEbCols ? ba * kEbCols + p : bb * kEbCols + p - kEbCols;
+        const int cr = r < kEbCols ? ba * kEbCols + r : bb * kEbCols + r - kEbCols;
+        if (cp < n && cr < n) {  // wave uniform
+            double x[E], y[E];
+            double vpp = 0.0, vqq = 0.0, vpq = 0.0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                x[e] = eb_cols[p * ldx + e * 64 + lane];
+                y[e] = eb_cols[r * ldx + e * 64 + lane];
+                vpp = __builtin_fma(x[e], x[e], vpp);
+                vqq = __builtin_fma(y[e], y[e], vqq);
+                vpq = __builtin_fma(x[e], y[e], vpq);
+            }
+            const double app = wave_allsum(vpp), aqq = wave_allsum(vqq), apq = wave_allsum(vpq);
+            // tan 2 theta = 2 apq / (aqq - app), |theta| <= pi / 4 (the register kernel's rotation)
+            const double alpha = aqq - app, beta = 2.0 * apq;
+            const double r2 = __builtin_fma(alpha, alpha, beta * beta);
+            if (apq * apq > tol2 * (app * aqq) && r2 > 0.0) {
+                const double ir = rsqrt_nr(r2);
+                const double c2 = __builtin_fma(0.5 * fabs(alpha), ir, 0.5);
+                const double ic = rsqrt_nr(c2);
+                const double c = c2 * ic;
+                const double sn = (alpha >= 0.0 ? 0.5 : -0.5) * beta * ir * ic;
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    eb_cols[p * ldx + e * 64 + lane] = __builtin_fma(c, x[e], -(sn * y[e]));
+                    eb_cols[r * ldx + e * 64 + lane] = __builtin_fma(sn, x[e], c * y[e]);
+                }
+                rotated = 1;
+            }
+        }
+        __syncthreads();
+    }
+    if (!__syncthreads_or(rotated)) return;  // nothing changed: nothing to write back
+    for (int idx = threadIdx.x; idx < 2 * kEbCols * ldx; idx += kEbThreads) {
+        const int j = idx / ldx, r = idx - j * ldx;
+        const int c = (j < kEbCols ? ba * kEbCols + j : bb * kEbCols + j - kEbCols);
+        X[(int64_t)c * ldx + r] = eb_cols[idx];
+    }
+    if (threadIdx.x == 0) atomicAdd(&rotations[q], 1);
+}
+
+// squared column lengths, their descending rank (ties in column order), the eigenvalues and the two words of info
+__global__ __launch_bounds__(kEbThreads) void eigb_rank_kernel(EigbBatch b, int32_t ldx, double *e0, double *e1, double *e2, int32_t *i0,
+                                                               int32_t *i1, int32_t *i2, int32_t *__restrict__ rank_of /* [3][512] */,
+                                                               double *__restrict__ norms /* [3][512] */, int32_t sweeps,
+                                                               const int32_t *__restrict__ failed) {
+    __shared__ double nr[512];
+    const int q = blockIdx.x;
+    const int n = b.n[q];
+    const double *X = b.X[q];
+    double *evals = q == 0 ? e0 : (q == 1 ? e1 : e2);
+    int32_t *info = q == 0 ? i0 : (q == 1 ? i1 : i2);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int c = w; c < n; c += kEbThreads / 64) {
+        double v = 0.0;
+        for (int r = lane; r < n; r += 64) v = __builtin_fma(X[(int64_t)c * ldx + r], X[(int64_t)c * ldx + r], v);
+        v = wave_allsum(v);
+        if (lane == 0) nr[c] = v;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += kEbThreads) {
+        const double li = nr[i];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) {
+            const double lj = nr[j];
+            rank += (lj > li || (lj == li && j < i)) ? 1 : 0;
+        }
+        rank_of[q * 512 + i] = rank;
+        norms[q * 512 + i] = li;
+        evals[rank] = li;
+    }
+    if (threadIdx.x == 0) {
+        double mx = 0.0, mn = __builtin_huge_val();
+        for (int i = 0; i < n; ++i) {
+            mx = fmax(mx, nr[i]);
+            mn = fmin(mn, nr[i]);
+        }
+        info[0] = sweeps;
+        info[1] = (failed[q] || !(mn > (double)n * 2.220446049250313e-16 * mx)) ? 1 : 0;
+    }
+}
+
+// Vs[row][rank of column i] = C V [row][i] / its length
+__global__ __launch_bounds__(256) void eigb_vectors_kernel(EigbBatch b, int32_t ldx, double *v0, double *v1, double *v2,
+                                                           const int32_t *__restrict__ rank_of, const double *__restrict__ norms) {
+    const int q = blockIdx.y;
+    const int n = b.n[q];
+    double *Vs = q == 0 ? v0 : (q == 1 ? v1 : v2);
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n * n) return;
+    const int i = idx / n, row = idx - i * n;
+    const double len = sqrt(norms[q * 512 + i]);
+    Vs[(int64_t)row * n + rank_of[q * 512 + i]] = len > 0.0 ? b.X[q][(int64_t)i * ldx + row] / len : 0.0;
+}
+
+template <int E>
+void launch_eigb_round(gingr_ctx *ctx, const EigbBatch &b, int count, int nblk, int rd, int32_t *rotations) {
+    const size_t lds = (size_t)2 * kEbCols * E * 64 * sizeof(double);
+    set_dynamic_lds(eigb_round_kernel<E>, lds);
+    hipLaunchKernelGGL((eigb_round_kernel<E>), dim3(nblk / 2, count), dim3(kEbThreads), lds, ctx->stream, b, nblk, rd, rd == 0 ? 1 : 0,
+                       rotations);
+}
+
 }  // namespace
+
+int64_t sym_eig_blocks_work_doubles(int32_t n) {
+    const int64_t nblk = (ceil_div(n, kEbCols) + 1) & ~(int64_t)1;
+    return nblk * kEbCols * round_up(n, 64);
+}
+
+// Up to three decompositions side by side, every n in kSymEigColsMaxN + 1 .. 512.  work[q]: sym_eig_blocks_work_doubles(largest n)
+// doubles; info[q]: two int32 on the device (sweeps, singular flag), valid when the call returns.  Synchronises the stream.
+int sym_eig_blocks(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ldg, const int32_t *n, double *const *work,
+                   double *const *evals, double *const *Vs, int32_t *const *info) {
+    int32_t nmax = 0;
+    EigbBatch b;
+    for (int q = 0; q < 3; ++q) {
+        const int s = q < count ? q : 0;
+        if (n[s] <= kSymEigColsMaxN || n[s] > 512) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sym_eig_blocks: n = %d outside %d..512", (int)n[s], kSymEigColsMaxN + 1);
+        b.X[q] = work[s], b.n[q] = n[s];
+        nmax = std::max(nmax, n[s]);
+    }
+    const int32_t ldx = (int32_t)round_up(nmax, 64);
+    const int nblk = (int)((ceil_div(nmax, kEbCols) + 1) & ~(int64_t)1);
+    const int cols = nblk * kEbCols;
+    constexpr int kMaxSweeps = 60;
+    DevBuf words, ranks, norms;  // [0..2] failed pivots, [3 + 3 sweep + q] rotations of a sweep
+    HIP_TRY(ctx, words.alloc((size_t)(3 + 3 * kMaxSweeps) * sizeof(int32_t)));
+    HIP_TRY(ctx, ranks.alloc((size_t)3 * 512 * sizeof(int32_t)));
+    HIP_TRY(ctx, norms.alloc((size_t)3 * 512 * sizeof(double)));
+    HIP_TRY(ctx, hipMemsetAsync(words.p, 0, words.bytes, ctx->stream));
+    int32_t *failed = words.as<int32_t>();
+    hipLaunchKernelGGL(eigb_load_kernel, dim3((unsigned)ceil_div((int64_t)cols * ldx, 256), count), dim3(256), 0, ctx->stream, b, G[0],
+                       G[count > 1 ? 1 : 0], G[count > 2 ? 2 : 0], ldg[0], ldg[count > 1 ? 1 : 0], ldg[count > 2 ? 2 : 0], ldx, cols);
+    for (int k0 = 0; k0 < nmax; k0 += kEbCols) {
+        hipLaunchKernelGGL(eigb_chol_panel_kernel, dim3(count), dim3(kEbThreads), 0, ctx->stream, b, ldx, k0, failed);
+        if (k0 + kEbCols < nmax)
+            hipLaunchKernelGGL(eigb_chol_update_kernel, dim3((unsigned)ceil_div(nmax, 256), nmax - k0 - kEbCols, count), dim3(256), 0,
+                               ctx->stream, b, ldx, k0);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    int32_t hfail[3] = {0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(hfail, failed, sizeof(hfail), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    int sweep = 0;
+    if (!(hfail[0] | hfail[1] | hfail[2])) {  // (a failed pivot: the caller's other kernel decomposes G itself)
+        for (; sweep < kMaxSweeps; ++sweep) {
+            int32_t *rot = words.as<int32_t>() + 3 + 3 * sweep;
+            for (int rd = 0; rd < nblk - 1; ++rd) switch (ldx / 64) {
+                    case 4: launch_eigb_round<4>(ctx, b, count, nblk, rd, rot); break;
+                    case 5: launch_eigb_round<5>(ctx, b, count, nblk, rd, rot); break;
+                    case 6: launch_eigb_round<6>(ctx, b, count, nblk, rd, rot); break;
+                    case 7: launch_eigb_round<7>(ctx, b, count, nblk, rd, rot); break;
+                    default: launch_eigb_round<8>(ctx, b, count, nblk, rd, rot); break;
+                }
+            HIP_TRY(ctx, hipGetLastError());
+            int32_t h[3] = {0, 0, 0};
+            HIP_TRY(ctx, hipMemcpyAsync(h, rot, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (!(h[0] | h[1] | h[2])) {
+                ++sweep;
+                break;
+            }
+        }
+    }
+    hipLaunchKernelGGL(eigb_rank_kernel, dim3(count), dim3(kEbThreads), 0, ctx->stream, b, ldx, evals[0], evals[count > 1 ? 1 : 0],
+                       evals[count > 2 ? 2 : 0], info[0], info[count > 1 ? 1 : 0], info[count > 2 ? 2 : 0], ranks.as<int32_t>(),
+                       norms.as<double>(), (int32_t)sweep, failed);
+    hipLaunchKernelGGL(eigb_vectors_kernel, dim3((unsigned)ceil_div((int64_t)nmax * nmax, 256), count), dim3(256), 0, ctx->stream, b, ldx,
+                       Vs[0], Vs[count > 1 ? 1 : 0], Vs[count > 2 ? 2 : 0], ranks.as<int32_t>(), norms.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the work buffers go out of scope
+    return GINGR_OK;
+}
 
 int64_t sym_eig_cols_work_doubles(int32_t n) {
     return (int64_t)kEigSlots * n + kEigSlots;

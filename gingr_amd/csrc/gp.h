@@ -337,6 +337,11 @@ int launch_jacobi_eig(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, d
 // eig.hip: one-sided register Jacobi on the Cholesky factor, n <= kSymEigColsMaxN, up to three problems per launch (see sym_eig, gpmm.hip)
 constexpr int kSymEigColsMaxN = 192;
 int64_t sym_eig_cols_work_doubles(int32_t n);
+// eig.hip: the same decomposition for kSymEigColsMaxN < n <= 512 on many workgroups, a launch per round (no grid barrier); work[q]:
+// sym_eig_blocks_work_doubles(largest n of the call) doubles.  Synchronises the stream.
+int64_t sym_eig_blocks_work_doubles(int32_t n);
+int sym_eig_blocks(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ldg, const int32_t *n, double *const *work,
+                   double *const *evals, double *const *Vs, int32_t *const *info);
 void launch_sym_eig_cols(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ldg, const int32_t *n, double *const *work,
                          double *const *evals, double *const *Vs, int32_t *const *info);
 // doubles of the `work` buffer launch_posterior_solve / launch_posterior_logpdf need (used when r > 128)

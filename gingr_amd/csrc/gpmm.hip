@@ -27,7 +27,9 @@
 #include "fastexp.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdio>
 
 namespace {
 
@@ -612,15 +614,17 @@ __global__ __launch_bounds__(kJacGridThreads) void jacobi_eig_grid_kernel(const 
 }
 
 // B[i][c] = sum_r L[r][c] V[r][i]   (c over ALL points, i < n): column i of  U sqrt(lambda) = L V
-constexpr int kLvCols = 8;  // columns of B per thread: L is read n / 8 times instead of n times (the same fma sequence per entry)
-__global__ __launch_bounds__(256) void lv_kernel(const double *__restrict__ L, int64_t M, int32_t n,
+// Only the leading `nout` columns are formed (a truncated model keeps the leading eigenvectors of a block); an entry's fma sequence
+// does not depend on nout.
+constexpr int kLvCols = 8;  // columns of B per thread: L is read nout / 8 times instead of nout times (the same fma sequence per entry)
+__global__ __launch_bounds__(256) void lv_kernel(const double *__restrict__ L, int64_t M, int32_t n, int32_t nout,
                                                  const double *__restrict__ V, double *__restrict__ B) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int i0 = blockIdx.y * kLvCols;
     if (c >= M) return;
-    int col[kLvCols];  // workgroup-uniform; columns past n repeat the last one and are not stored
+    int col[kLvCols];  // workgroup-uniform; columns past nout repeat the last one and are not stored
 #pragma unroll
-    for (int u = 0; u < kLvCols; ++u) col[u] = min(i0 + u, n - 1);
+    for (int u = 0; u < kLvCols; ++u) col[u] = min(i0 + u, nout - 1);
     double acc[kLvCols];
 #pragma unroll
     for (int u = 0; u < kLvCols; ++u) acc[u] = 0.0;
@@ -632,7 +636,7 @@ __global__ __launch_bounds__(256) void lv_kernel(const double *__restrict__ L, i
     }
 #pragma unroll
     for (int u = 0; u < kLvCols; ++u)
-        if (i0 + u < n) B[(int64_t)(i0 + u) * M + c] = acc[u];
+        if (i0 + u < nout) B[(int64_t)(i0 + u) * M + c] = acc[u];
 }
 
 // Q0[(3s+d)*rp + q] = B_set(q)[idx(q)][row_begin + perm[s]] when coordinate(q) == d, else 0
@@ -772,9 +776,12 @@ static int jacobi_two_sided(gingr_ctx *ctx, const double *G, int32_t ldg, int32_
 // Eigen-decompositions of up to three symmetric positive semi-definite matrices (leading n[q] x n[q] block of G[q], row stride ldg[q]):
 // evals[q] descending, Vs[q][:, k] the matching eigenvectors.  Up to kSymEigColsMaxN the register kernel of eig.hip, all problems in
 // one launch; a problem it reports as numerically singular or not converged -- and anything larger -- goes through the two-sided
-// kernel.  Synchronises the stream.  GINGR_ERR_NONFINITE when a decomposition does not converge.
+// kernel.  `blocks`: problems above kSymEigColsMaxN go through the block kernel of eig.hip first (sym_eig_blocks; the scalar route of
+// gingr_gpmm_build_diagonal_ex, whose blocks no earlier entry could reach) -- without it they take the two-sided kernel directly, as
+// every model with such a problem always has.  GINGR_EIG_TWO_SIDED=1 in the environment switches `blocks` off (same-box timing of the
+// two kernels).  Synchronises the stream.  GINGR_ERR_NONFINITE when a decomposition does not converge.
 static int sym_eig(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ldg, const int32_t *n, double *const *evals,
-            double *const *Vs) {
+            double *const *Vs, bool blocks = false) {
     if (count < 1 || count > 3) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sym_eig: 1..3 problems");
     bool redo[3] = {false, false, false};
     DevBuf work[3], info;
@@ -807,12 +814,56 @@ static int sym_eig(gingr_ctx *ctx, int count, const double *const *G, const int3
             if (h[2 * q] >= 60 || h[2 * q + 1]) redo[q] = true;
         }
     }
+    static const bool two_sided_only = getenv("GINGR_EIG_TWO_SIDED") != nullptr;
+    // GINGR_EIG_TIMING=1 (tools/bench_gpmm_to_tolerance.py): wall time of the problems above kSymEigColsMaxN, one line on stderr
+    static const bool timing_on = getenv("GINGR_EIG_TIMING") != nullptr;
+    bool timing = false;
+    for (int q = 0; q < count; ++q) timing = timing || (timing_on && n[q] > kSymEigColsMaxN);
+    std::chrono::steady_clock::time_point t0;
+    if (timing) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        t0 = std::chrono::steady_clock::now();
+    }
+    if (blocks && !two_sided_only) {  // the problems above the register kernel's size, side by side
+        DevBuf bwork[3];
+        const double *bG[3];
+        int32_t bld[3], bn[3], big_of[3], nmax = 0;
+        double *bw[3], *be[3], *bv[3];
+        int32_t *bi[3];
+        int big = 0;
+        for (int q = 0; q < count; ++q)
+            if (n[q] > kSymEigColsMaxN) nmax = std::max(nmax, n[q]);
+        for (int q = 0; q < count; ++q) {
+            if (n[q] <= kSymEigColsMaxN) continue;
+            HIP_TRY(ctx, bwork[q].alloc((size_t)sym_eig_blocks_work_doubles(nmax) * sizeof(double)));
+            bG[big] = G[q], bld[big] = ldg[q], bn[big] = n[q], bw[big] = bwork[q].as<double>(), be[big] = evals[q], bv[big] = Vs[q];
+            bi[big] = info.as<int32_t>() + 2 * q;
+            big_of[big++] = q;
+        }
+        if (big) {
+            GINGR_TRY(sym_eig_blocks(ctx, big, bG, bld, bn, bw, be, bv, bi));
+            int32_t h[6];
+            HIP_TRY(ctx, hipMemcpy(h, info.p, sizeof(h), hipMemcpyDeviceToHost));
+            for (int f = 0; f < big; ++f) {
+                const int q = big_of[f];
+                redo[q] = h[2 * q] >= 60 || h[2 * q + 1];
+            }
+        }
+    }
     for (int q = 0; q < count; ++q) {
         if (!redo[q]) continue;
         GINGR_TRY(jacobi_two_sided(ctx, G[q], ldg[q], n[q], evals[q], Vs[q], info.as<int32_t>() + 2 * q));
         int32_t sw = 0;
         HIP_TRY(ctx, hipMemcpy(&sw, info.as<int32_t>() + 2 * q, sizeof(sw), hipMemcpyDeviceToHost));
         if (sw >= 60) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "sym_eig: Jacobi did not converge (n = %d)", (int)n[q]);
+    }
+    if (timing) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        int fell_back = 0;
+        for (int q = 0; q < count; ++q) fell_back += redo[q] ? 1 : 0;
+        fprintf(stderr, "sym_eig_timing n=%d,%d,%d kernel=%s two_sided_runs=%d ms=%.3f\n", (int)n[0], count > 1 ? (int)n[1] : 0,
+                count > 2 ? (int)n[2] : 0, blocks && !two_sided_only ? "blocks" : "two_sided", fell_back, ms);
     }
     return GINGR_OK;
 }
@@ -965,13 +1016,34 @@ bool same_kernel(const gingr_scalar_kernel *a, const gingr_scalar_kernel *b) {
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref, const gingr_scalar_kernel *kx,
-                              const gingr_scalar_kernel *ky, const gingr_scalar_kernel *kz, double relative_tolerance,
-                              int32_t max_rank, int64_t row_begin, int64_t row_end, gingr_model **out) {
+// Q[(row) * rpn + q] = q < k ? Qs[row * rps + q] : 0 for the 3M basis rows (the slack rows behind them are cleared by model_create_impl)
+__global__ __launch_bounds__(256) void truncate_basis_kernel(const double *__restrict__ Qs, int32_t rps, int64_t rows, int32_t k, int32_t rpn,
+                                                             double *__restrict__ Q) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * rpn) return;
+    const int64_t row = idx / rpn;
+    const int32_t q = (int32_t)(idx - row * rpn);
+    Q[idx] = q < k ? Qs[row * rps + q] : 0.0;
+}
+
+}  // namespace
+
+// The construction behind gingr_gpmm_build_diagonal (`ex` false: max_columns is its max_rank, silently clamped to the model's rank
+// limit, no truncation) and gingr_gpmm_build_diagonal_ex (`ex` true: max_columns <= 0 runs to the tolerance under the library's
+// ceiling, nothing is ever shortened silently, keep_rank leading eigenpairs of the merged spectrum are kept).
+static int gpmm_build_impl(gingr_ctx *ctx, int64_t M_total, const double *ref, const gingr_scalar_kernel *kx,
+                           const gingr_scalar_kernel *ky, const gingr_scalar_kernel *kz, double relative_tolerance, bool ex,
+                           int32_t max_columns, int32_t keep_rank, int64_t row_begin, int64_t row_end, gingr_gpmm_info *info,
+                           gingr_model **out) {
     if (!ctx || !out) return GINGR_ERR_BAD_ARGUMENT;
     *out = nullptr;
+    if (info) memset(info, 0, sizeof(*info));
+    if (ex && max_columns > GINGR_GPMM_MAX_COLUMNS)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: max_columns = %d is above the ceiling of %d factor columns",
+                               (int)max_columns, GINGR_GPMM_MAX_COLUMNS);
+    const bool to_tolerance = ex && max_columns <= 0;
     if (M_total < 1 || !ref || !kx || !ky || !kz) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: need M >= 1, a reference and three kernels");
     if (!(relative_tolerance >= 0.0) || !(relative_tolerance < 1.0))
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: relative tolerance must be in [0, 1)");
@@ -1022,8 +1094,42 @@ int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref
             return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: unknown kernel kind %d", (int)k->kind);
         }
     }
-    if (max_rank <= 0 || max_rank > 512) max_rank = 512;  // the model's rank limit (gingr_model_upload)
+    int32_t max_rank = max_columns;  // factor columns at most
+    if (ex) {
+        if (to_tolerance) max_rank = GINGR_GPMM_MAX_COLUMNS;
+    } else if (max_rank <= 0 || max_rank > 512) {
+        max_rank = 512;  // the model's rank limit (gingr_model_upload)
+    }
     if ((int64_t)max_rank > 3 * M_total) max_rank = (int32_t)(3 * M_total);
+    // what the ex entry does with a finished factorisation of `columns` columns (residual trace / trace = `fraction`): fills info,
+    // refuses a ceiling that came before the tolerance and a model above the rank limit; `keep` = columns of the model
+    auto unfinished = [&](int32_t columns, double fraction) -> int {  // to tolerance, and the ceiling came first
+        if (info) info->columns = columns, info->residual_fraction = fraction, info->kept_variance_fraction = 1.0;
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT,
+                               "gpmm_build: the ceiling of %d factor columns (GINGR_GPMM_MAX_COLUMNS) was reached at a residual fraction of %.6g, "
+                               "above the relative tolerance %.6g",
+                               GINGR_GPMM_MAX_COLUMNS, fraction, relative_tolerance);
+    };
+    auto conclude = [&](int32_t columns, bool reached, double fraction, const std::vector<double> &lam_desc, int32_t *keep) -> int {
+        *keep = (ex && keep_rank > 0 && keep_rank < columns) ? keep_rank : columns;
+        double all = 0.0, kept = 0.0;
+        for (int32_t q = 0; q < columns; ++q) {
+            all += lam_desc[(size_t)q];
+            if (q + 1 == *keep) kept = all;
+        }
+        if (info) {
+            info->columns = columns;
+            info->rank = *keep;
+            info->tolerance_reached = reached ? 1 : 0;
+            info->residual_fraction = fraction;
+            info->kept_variance_fraction = all > 0.0 ? kept / all : 1.0;
+        }
+        if (ex && *keep > 512)
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT,
+                                   "gpmm_build: the factorisation has %d columns (columns = %d), a model holds at most 512: pass keep_rank <= 512",
+                                   (int)columns, (int)columns);
+        return GINGR_OK;
+    };
 
     DevBuf aos, soa;
     HIP_TRY(ctx, aos.alloc((size_t)3 * M * sizeof(double)));
@@ -1042,10 +1148,19 @@ int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref
         // argmax of the residual diagonal in the permuted entry order, stop at relTol * trace -- then the eigen-decomposition of
         // L^T L and U sqrt(lambda) = L V, exactly as for any matrix-valued kernel.
         Factor fg;
-        GINGR_TRY(fg.init(ctx, sp3, pts, true, (int32_t)std::min<int64_t>(3 * M, max_rank)));
+        const int32_t gcap = (int32_t)std::min<int64_t>(std::min<int64_t>(3 * M, max_rank), 512);  // (the pivot step's swap log: 512 entries)
+        GINGR_TRY(fg.init(ctx, sp3, pts, true, gcap));
         GINGR_TRY(fg.run_to_tolerance(relative_tolerance));
         const int32_t n = fg.ks;
         if (n < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: empty model (tolerance too large)");
+        const double gfraction = fg.htrace[(size_t)n] / fg.htrace[0];
+        const bool greached = !(fg.htrace[(size_t)n] >= relative_tolerance * fg.htrace[0]) || (int64_t)n == 3 * M;
+        if (ex && !greached && n == gcap && gcap < max_rank) {
+            if (info) info->columns = n, info->residual_fraction = gfraction, info->kept_variance_fraction = 1.0;
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT,
+                                   "gpmm_build: coordinate-wise different kernels: at most 512 factor columns (residual fraction %.6g after 512)", gfraction);
+        }
+        if (to_tolerance && !greached) return unfinished(n, gfraction);
         DevBuf G, ev, V, B;
         HIP_TRY(ctx, G.alloc((size_t)n * n * sizeof(double)));
         HIP_TRY(ctx, ev.alloc((size_t)(n + 1) * sizeof(double)));
@@ -1058,20 +1173,22 @@ int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref
             const int32_t ns[1] = {n};
             GINGR_TRY(sym_eig(ctx, 1, Gs, ns, ns, es, vs));
         }
-        hipLaunchKernelGGL(lv_kernel, dim3((unsigned)ceil_div(3 * M, 256), (unsigned)ceil_div(n, kLvCols)), dim3(256), 0, ctx->stream, fg.Lb.as<double>(), 3 * M, n,
-                           V.as<double>(), B.as<double>());
-        GINGR_TRY(check(ctx));
         std::vector<double> hev((size_t)n);
         HIP_TRY(ctx, hipMemcpyAsync(hev.data(), ev.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         for (auto &v : hev) v = v > 0.0 ? v : 0.0;
+        int32_t keep = n;
+        GINGR_TRY(conclude(n, greached, gfraction, hev, &keep));
+        hipLaunchKernelGGL(lv_kernel, dim3((unsigned)ceil_div(3 * M, 256), (unsigned)ceil_div(keep, kLvCols)), dim3(256), 0, ctx->stream, fg.Lb.as<double>(), 3 * M, n,
+                           keep, V.as<double>(), B.as<double>());
+        GINGR_TRY(check(ctx));
         auto fill = [&](gingr_model *m) -> int {
             const int64_t total = 3 * m->M * m->rp;
             hipLaunchKernelGGL(gpmm_pack_generic_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, B.as<double>(),
                                M_total, m->row_begin, m->M, m->r, m->rp, m->perm, m->Q0);
             return check(ctx);
         };
-        return model_create_impl(ctx, M_total, n, ref, zero_mean.data(), hev.data(), row_begin, row_end, fill, out);
+        return model_create_impl(ctx, M_total, keep, ref, zero_mean.data(), hev.data(), row_begin, row_end, fill, out);
     }
 
     // One kernel for all coordinates: the generic pivot sequence is (P0,x),(P0,y),(P0,z),(P1,x),... with P0,P1,.. the scalar
@@ -1079,7 +1196,9 @@ int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref
     // the scalar factorisation's own permuted order); after n = 3j + e pivots the residual trace is (3-e) tr_s(j) + e tr_s(j+1).
     Factor fac[1];
     int32_t cnt[3] = {0, 0, 0};  // columns per coordinate
-    int32_t n = 0;               // generic pivots = rank
+    int32_t n = 0;               // generic pivots = factor columns
+    bool reached = false;
+    double fraction = 0.0;
     {
         const int32_t kmax = (int32_t)std::min<int64_t>(M, (max_rank + 2) / 3);  // scalar columns that can ever be needed
         GINGR_TRY(fac[0].init(ctx, sp3, pts, false, kmax));
@@ -1096,7 +1215,14 @@ int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref
             ++n;
         }
         for (int d = 0; d < 3; ++d) cnt[d] = n / 3 + (d < n % 3 ? 1 : 0);
+        {  // the residual trace after the n pivots (the traces it needs exist: n <= 3 ks)
+            const int32_t j = n / 3, e = n % 3;
+            const double tr = e == 0 ? 3.0 * htr[(size_t)j] : (3 - e) * htr[(size_t)j] + e * htr[(size_t)j + 1];
+            reached = !(tr >= tol_g) || (int64_t)n == 3 * M;
+            fraction = tr / (3.0 * htr[0]);
+        }
     }
+    if (to_tolerance && !reached) return unfinished(n, fraction);
     if (n < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: empty model (tolerance too large)");
 
     // blocks = distinct column counts among the coordinates; eigen-decomposition of L_s[:, :count]^T L_s[:, :count]
@@ -1131,12 +1257,8 @@ int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref
             Gs[b] = G[q].as<double>(), lds[b] = set_kk[q], ns[b] = nb_, es[b] = ev[b].as<double>(), vs[b] = V[b].as<double>();
             hev[b].resize((size_t)nb_);
         }
-        GINGR_TRY(sym_eig(ctx, nblocks, Gs, lds, ns, es, vs));  // the blocks side by side, one workgroup each
+        GINGR_TRY(sym_eig(ctx, nblocks, Gs, lds, ns, es, vs, ex));  // the blocks side by side
     }
-    for (int b = 0; b < nblocks; ++b)
-        hipLaunchKernelGGL(lv_kernel, dim3((unsigned)ceil_div(M, 256), (unsigned)ceil_div(block_n[b], kLvCols)), dim3(256), 0, ctx->stream,
-                           fac[block_set[b]].Lb.as<double>(), M, block_n[b], V[b].as<double>(), B[b].as<double>());
-    GINGR_TRY(check(ctx));
     for (int b = 0; b < nblocks; ++b)
         HIP_TRY(ctx, hipMemcpyAsync(hev[b].data(), ev[b].p, hev[b].size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1154,7 +1276,20 @@ int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref
         if (x.idx != y.idx) return x.idx < y.idx;
         return x.dim < y.dim;
     });
-    const int32_t rank = (int32_t)cols.size();  // == n
+    int32_t rank = (int32_t)cols.size();  // == n
+    {
+        std::vector<double> lam((size_t)rank);
+        for (int32_t q = 0; q < rank; ++q) lam[(size_t)q] = cols[(size_t)q].lam > 0.0 ? cols[(size_t)q].lam : 0.0;
+        GINGR_TRY(conclude(n, reached, fraction, lam, &rank));
+    }
+    // U sqrt(lambda) = L V for the eigenvectors the model keeps: the leading ones of every block
+    int32_t block_out[3] = {0, 0, 0};
+    for (int32_t q = 0; q < rank; ++q) block_out[cols[(size_t)q].set] = std::max(block_out[cols[(size_t)q].set], cols[(size_t)q].idx + 1);
+    for (int b = 0; b < nblocks; ++b)
+        if (block_out[b] > 0)
+            hipLaunchKernelGGL(lv_kernel, dim3((unsigned)ceil_div(M, 256), (unsigned)ceil_div(block_out[b], kLvCols)), dim3(256), 0, ctx->stream,
+                               fac[block_set[b]].Lb.as<double>(), M, block_n[b], block_out[b], V[b].as<double>(), B[b].as<double>());
+    GINGR_TRY(check(ctx));
     std::vector<double> variance((size_t)rank);
     std::vector<int32_t> qmap((size_t)3 * rank);
     for (int32_t q = 0; q < rank; ++q) {
@@ -1175,6 +1310,46 @@ int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref
         return check(ctx);
     };
     return model_create_impl(ctx, M_total, rank, ref, zero_mean.data(), variance.data(), row_begin, row_end, fill, out);
+}
+
+extern "C" {
+
+int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref, const gingr_scalar_kernel *kx,
+                              const gingr_scalar_kernel *ky, const gingr_scalar_kernel *kz, double relative_tolerance,
+                              int32_t max_rank, int64_t row_begin, int64_t row_end, gingr_model **out) {
+    return gpmm_build_impl(ctx, M_total, ref, kx, ky, kz, relative_tolerance, false, max_rank, 0, row_begin, row_end, nullptr, out);
+}
+
+int gingr_gpmm_build_diagonal_ex(gingr_ctx *ctx, int64_t M_total, const double *ref, const gingr_scalar_kernel *kx,
+                                 const gingr_scalar_kernel *ky, const gingr_scalar_kernel *kz, double relative_tolerance,
+                                 int32_t max_columns, int32_t keep_rank, int64_t row_begin, int64_t row_end, gingr_gpmm_info *info,
+                                 gingr_model **out) {
+    return gpmm_build_impl(ctx, M_total, ref, kx, ky, kz, relative_tolerance, true, max_columns, keep_rank, row_begin, row_end, info, out);
+}
+
+int gingr_model_truncate(gingr_ctx *ctx, const gingr_model *src, int32_t k, gingr_model **out) {
+    if (!ctx || !out) return GINGR_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    if (!src) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: no model");
+    if (src->ctx != ctx || !src->finalized)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: the source must be a finalized model of this context");
+    if (src->row_begin != 0 || src->row_end != src->M_total)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: the source is a row shard; truncate the complete model (or build the shard with keep_rank)");
+    if (k < 1 || k > src->r)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: k = %d outside 1..%d (the model's rank)", (int)k, (int)src->r);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t M = src->M;
+    std::vector<double> href((size_t)3 * M), hmean((size_t)3 * M);
+    GINGR_TRY(gingr_model_download(ctx, src, href.data(), hmean.data(), nullptr, nullptr));
+    auto fill = [&](gingr_model *m) -> int {
+        // the same points and mean give the same row order (Morton order of ref + mean): rows are copied in place
+        if (m->M != M || m->hperm != src->hperm) return gingr_set_error(ctx, GINGR_ERR_STATE, "model_truncate: row order differs from the source's");
+        const int64_t total = 3 * M * m->rp;
+        hipLaunchKernelGGL(truncate_basis_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, src->Q0, src->rp, 3 * M, k, m->rp,
+                           m->Q0);
+        return check(ctx);
+    };
+    return model_create_impl(ctx, src->M_total, k, href.data(), hmean.data(), src->variance.data(), 0, src->M_total, fill, out);
 }
 
 int gingr_gpmm_build_gaussian(gingr_ctx *ctx, int64_t M_total, const double *ref, int32_t n_kernels, const double *sigmas,

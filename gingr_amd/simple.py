@@ -341,8 +341,10 @@ class SimpleTriangleModels3D:
     """G/simple/SimpleModels.scala:52-75: one call from a kernel choice to a model, built in HBM."""
 
     @staticmethod
-    def create(ctx: Context, reference: TriangleMesh3D, kernelSelect, relativeTolerance: float = 0.01, maxRank: int = 0):
-        g = GPMMTriangleMesh3D(ctx, reference.points, relativeTolerance=relativeTolerance, maxRank=maxRank, cells=reference.cells)
+    def create(ctx: Context, reference: TriangleMesh3D, kernelSelect, relativeTolerance: float = 0.01, maxRank: int = 0,
+               toTolerance: bool = False):
+        g = GPMMTriangleMesh3D(ctx, reference.points, relativeTolerance=relativeTolerance, maxRank=maxRank, cells=reference.cells,
+                               toTolerance=toTolerance)
         if isinstance(kernelSelect, InvLapKernel):
             return g.InverseLaplacian(scaling=kernelSelect.scaling)
         if isinstance(kernelSelect, InvLapDotKernel):

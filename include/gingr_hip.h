@@ -199,6 +199,38 @@ typedef struct gingr_scalar_kernel {
 int gingr_gpmm_build_diagonal(gingr_ctx *ctx, int64_t M_total, const double *ref, const gingr_scalar_kernel *kx,
                               const gingr_scalar_kernel *ky, const gingr_scalar_kernel *kz, double relative_tolerance,
                               int32_t max_rank, int64_t row_begin, int64_t row_end, gingr_model **out);
+/* NOTE on max_rank of the two entries above: it is clamped to 512 (the rank limit of a model) SILENTLY -- a factorisation that
+ * has not met relative_tolerance after 512 columns comes back as a 512-column model with GINGR_OK.  The entry below never does that.
+ *
+ * gingr_gpmm_build_diagonal_ex: the same construction with the factor allowed to be longer than the model, as the reference's
+ * pivoted Cholesky (no rank limit, G/api/gpmm/GPMMHelper.scala:39-52) followed by PointDistributionModel.truncate(k).
+ *   max_columns > 0   the caller's stop: at most that many factor columns; stopping there is no error (tolerance_reached = 0).
+ *                     Above GINGR_GPMM_MAX_COLUMNS: GINGR_ERR_BAD_ARGUMENT.
+ *   max_columns <= 0  to tolerance: the factorisation runs until relative_tolerance is met.  If the library's ceiling of
+ *                     GINGR_GPMM_MAX_COLUMNS columns (or 3 M_total) comes first: GINGR_ERR_BAD_ARGUMENT, the text names the
+ *                     ceiling and the residual fraction.
+ *   keep_rank > 0     the model keeps the keep_rank leading eigenpairs of the merged, descending spectrum (equal eigenvalues in
+ *                     the order of the untruncated model); keep_rank <= 0 or >= columns keeps everything.
+ * A model above rank 512 is GINGR_ERR_BAD_ARGUMENT (the text names `columns`; ask again with keep_rank <= 512), never a shorter
+ * model; *out stays NULL.  info (may be NULL) is filled whenever the factorisation itself finished, also on these errors.
+ * Coordinates with different kernels (GaussianSymmetry) stay within 512 factor columns: needing more is GINGR_ERR_BAD_ARGUMENT.
+ * With max_columns <= 512 and keep_rank <= 0 the model is bit-identical to gingr_gpmm_build_diagonal's with max_rank = max_columns. */
+#define GINGR_GPMM_MAX_COLUMNS 1536
+typedef struct gingr_gpmm_info {
+    int32_t columns;               /* factor columns the pivoted Cholesky produced (= the model's rank before truncation) */
+    int32_t rank;                  /* rank of the returned model */
+    int32_t tolerance_reached;     /* 1: residual trace < relative_tolerance * trace when the factorisation stopped */
+    double residual_fraction;      /* residual trace / trace at the stop */
+    double kept_variance_fraction; /* sum of kept eigenvalues / sum of all `columns` eigenvalues (1 without truncation) */
+} gingr_gpmm_info;
+int gingr_gpmm_build_diagonal_ex(gingr_ctx *ctx, int64_t M_total, const double *ref, const gingr_scalar_kernel *kx,
+                                 const gingr_scalar_kernel *ky, const gingr_scalar_kernel *kz, double relative_tolerance,
+                                 int32_t max_columns, int32_t keep_rank, int64_t row_begin, int64_t row_end, gingr_gpmm_info *info,
+                                 gingr_model **out);
+/* PointDistributionModel.truncate(k): a new, finalized, independent model of the k leading basis functions of a complete
+ * (single-shard, finalized) model of this context, built or uploaded; 1 <= k <= rank, else GINGR_ERR_BAD_ARGUMENT.  A row
+ * shard is refused: build the shards with keep_rank, or truncate the complete model. */
+int gingr_model_truncate(gingr_ctx *ctx, const gingr_model *src, int32_t k, gingr_model **out);
 /* PointSetHelper.maximumPointDistance / minimumPointDistance (GPMMHelper.scala:75-87; the O(n^2) scans behind
  * AutomaticGaussian and automaticGPMMfromTemplate): largest pairwise distance, smallest distance to the nearest OTHER point. */
 int gingr_pointset_distance_extrema(gingr_ctx *ctx, const double *xyz, int64_t n, double *max_distance, double *min_distance);
