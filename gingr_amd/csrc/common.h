@@ -48,10 +48,10 @@ struct gingr_ctx {
     void *rccl_comm = nullptr;
     int32_t rccl_world = 0, rccl_rank = 0;
     // GINGR_OPT_SPLIT_EXCHANGE: the column-sum exchange in two halves, the first on a second stream of the context behind the first
-    // half of pass 1 (fitter.hip: fitter_sharded_update).  side_stream / the events are created on first use; exchange_stream is
+    // half of pass 1 (fitter_phases.hip: fitter_sharded_update).  side_stream / the events are created on first use; exchange_stream is
     // where the native all-reduce is enqueued right now (nullptr = the context's stream).
     int split_exchange = 0;
-    int gram_downdate = -1;  // GINGR_OPT_GRAM_DOWNDATE: 0 / 1 weights of the surface ICP -> the model's moment minus the rejected rows (fitter.hip, phase 1); -1: by size
+    int gram_downdate = -1;  // GINGR_OPT_GRAM_DOWNDATE: 0 / 1 weights of the surface ICP -> the model's moment minus the rejected rows (fitter_phases.hip: phase1_gram); -1: by size
     hipStream_t side_stream = nullptr, exchange_stream = nullptr;
     hipEvent_t split_ev[2] = {nullptr, nullptr};
     // scratch kept across calls (grown on demand, never shrunk) so steady-state updates do not allocate
@@ -91,7 +91,7 @@ struct DevBuf {
         p = nullptr;
         bytes = n;
         const hipError_t e = hipMalloc(&p, n ? n : 8);
-        static const bool poison = getenv("GINGR_DEBUG_POISON") != nullptr;  // (diagnostic: see dev_alloc, fitter.hip)
+        static const bool poison = getenv("GINGR_DEBUG_POISON") != nullptr;  // (diagnostic: see dev_alloc, fitter.h)
         if (e == hipSuccess && poison) {
             (void)hipMemset(p, 0xFF, n ? n : 8);
             (void)hipDeviceSynchronize();

@@ -28,7 +28,7 @@ struct DevState {
 };
 
 // DevState from the scalars the host pushed (one thread; state_init_kernel, and the tail of the launch that brings a Metropolis-Hastings
-// step's random-walk parameters: fitter.hip, mh_begin_kernel)
+// step's random-walk parameters: fitter_mh.hip, mh_begin_kernel)
 __device__ inline void state_init_body(DevState *st, const gingr_state_scalars *h, double *zero_slot) {
     if (zero_slot) *zero_slot = 0.0;  // see SweepArgs::absmax_slot
     for (int q = 0; q < 3; ++q) {
@@ -116,7 +116,7 @@ struct gingr_model {
     double *Binv = nullptr;   // [rp*rp] (S_tot/eps + I)^-1, valid after finalize
     double *eigV = nullptr;   // [r*r] eigenvectors of S_tot = Q^T Q (column k, row stride r) and
     double *eigL = nullptr;   // [r] its eigenvalues (descending): uniform-weight posterior (launch_posterior_solve_eig); rank <= 192
-    bool eig_ready = false;  // decided once by model_finalize_impl (fitter.hip), identically on every shard
+    bool eig_ready = false;  // decided once by model_finalize_impl (model.hip), identically on every shard
     double *cmat = nullptr;   // [19][rp*rp], valid after finalize: [0] C = Binv S_tot / eps (alpha_1 = C a),
                               // [1 + 3d + e] Binv S[d][e], [10 + 3d + e] Binv S[d][e] C  (Binv S[d][e] alpha_1 = (Binv S[d][e] C) a)
     double *pvec = nullptr;   // PostVec: the r-vectors and scalars the post-solve kernel reads, valid after finalize
@@ -131,7 +131,7 @@ struct gingr_model {
 void launch_interp_pack(gingr_ctx *ctx, const double *Qs, int32_t rp, const int32_t *inv_src, const int32_t *ids, const double *w,
                         const int32_t *perm_new, int64_t row_begin, int64_t M, double *Q0);
 
-// fitter.hip: common part of model construction; fill_basis writes m->Q0 on ctx->stream (see gingr_model_upload)
+// model.hip: common part of model construction; fill_basis writes m->Q0 on ctx->stream (see gingr_model_upload)
 int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const double *ref, const double *mean,
                       const double *variance, int64_t row_begin, int64_t row_end,
                       const std::function<int(gingr_model *)> &fill_basis, gingr_model **out);
@@ -140,7 +140,7 @@ int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const doubl
 // the gather step of a sharded surface update writes the shard's contribution to the full fit (nullptr: in place)
 void fitter_set_partial_output(gingr_fitter *f, double *base);
 void fitter_set_partial_fullfit(gingr_fitter *f, double *base);
-// the sharded update (fitter.hip) for the other translation units: flavour 0 CPD, 1 ICP point cloud, 2 ICP surface; z nullable (sampled proposal)
+// the sharded update (fitter_phases.hip) for the other translation units: flavour 0 CPD, 1 ICP point cloud, 2 ICP surface; z nullable (sampled proposal)
 // gather (nullable): the host's own all-gather of the fit -- 0 done, > 0 not possible here (fall back to the zero-padded all-reduce), < 0 failed
 typedef int (*fitter_gather_fn)(void *user, gingr_fitter *f);
 // split_native: the caller's `reduce` is the library's own RCCL all-reduce (user = the context) and honours ctx->exchange_stream:
@@ -166,7 +166,7 @@ const gingr_model *fitter_model(gingr_fitter *f);
 // ---- the device-side choice between the Gram downdate and the pass over the basis (surface ICP) -----------
 // counts[b] = zero-weight vertices of block b of obs_points_kernel (256 vertices each; every launch rewrites all of them: nothing to
 // clear).  A kernel that carries a gate sums the counts in its prologue; "many" = more than one vertex in eight has weight 0 -- a
-// fixed rule, independent of timing: both forms of the Gram matrix round differently (fitter.hip: kGramDowndateMinRows).
+// fixed rule, independent of timing: both forms of the Gram matrix round differently (fitter.h: kGramDowndateMinRows).
 struct ZeroGate {          // (plain data: ZeroGate{} and memset-zeroed argument blocks mean "no gate")
     const int32_t *counts;  // nullptr: no gate (the kernel always runs)
     int32_t nblocks;

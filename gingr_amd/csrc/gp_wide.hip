@@ -335,7 +335,7 @@ int launch_gram_wide(gingr_ctx *ctx, const double *Q0, int64_t M, int32_t rp, co
 }
 
 // Z^T Z of `rows` plain rows of width rp (128 .. 512, a multiple of 16; 48 zero rows behind them), unweighted: slab partials of the
-// upper tiles in ws, the slab count returned.  One-off products (the model's moment blocks: fitter.hip): at most 96 workgroups, so
+// upper tiles in ws, the slab count returned.  One-off products (the model's moment blocks: model.hip): at most 96 workgroups, so
 // that the partials stay small.
 constexpr int kRowsWorkgroups = 96;
 int64_t gram_rows_ws_doubles(int64_t rows, int32_t rp) {

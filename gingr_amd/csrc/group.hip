@@ -4,7 +4,7 @@
 //
 // Partitioning (BASELINE.json north_star): contiguous row shards of the reference / fit points, one
 // gingr_ctx + gingr_model + gingr_fitter per device; target cloud and all r-sized state replicated.  Per iteration the two
-// exchange segments of fitter.hip (CPD column sums den[N]; Gram + right-hand side + sigma2 sums) are summed across shards
+// exchange segments of fitter_phases.hip (CPD column sums den[N]; Gram + right-hand side + sigma2 sums) are summed across shards
 // by a ONE-SHOT all-reduce over peer pointers: every shard writes its partial segment into its own send buffer, records an
 // event, waits for the events of all peers and then sums the n send buffers -- its own and, through the xGMI peer
 // mapping, the remote ones -- in rank order into its exchange buffer.  Both messages are small (400 KB and 100 KB at
@@ -655,7 +655,7 @@ int gingr_group_set_meshes(gingr_group *g, int64_t n_model_triangles, const int3
     if (!g) return GINGR_ERR_BAD_ARGUMENT;
     if (g->fit.empty() || !g->fit[0] || g->xch.empty()) return group_fail(g, GINGR_ERR_STATE, "group set_meshes: no model / target set");
     GINGR_TRY(gingr_group_synchronize(g));
-    // every shard's set_meshes drops its direction and frees its reversed-direction sums (fitter.hip: free_meshes): the group forgets
+    // every shard's set_meshes drops its direction and frees its reversed-direction sums (fitter_surface.hip: free_meshes): the group forgets
     // the direction with them, or the next update would hand a null total buffer to the peer-sum kernel
     g->reversed = false;
     GINGR_TRY(g->run([&](int r) {

@@ -79,7 +79,7 @@ int rccl_fail(gingr_ctx *ctx, const char *what, int rc) {
 // the gingr_allreduce_fn of the native path: user = the context
 int native_allreduce(void *user, int32_t, void *device_ptr, int64_t count) {
     gingr_ctx *ctx = static_cast<gingr_ctx *>(user);
-    // (exchange_stream: the first half of a split column-sum exchange runs on the context's second stream, fitter.hip)
+    // (exchange_stream: the first half of a split column-sum exchange runs on the context's second stream, fitter_phases.hip)
     const int rc = g_rccl.AllReduce(device_ptr, device_ptr, (size_t)count, /* ncclFloat64 */ 8, /* ncclSum */ 0, ctx->rccl_comm,
                                     ctx->exchange_stream ? ctx->exchange_stream : ctx->stream);
     if (rc != 0) {

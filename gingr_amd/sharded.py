@@ -1,7 +1,7 @@
 """Row-sharded GiNGR update: one process per GPU, reference-point rows split across ranks.
 
 The N x M affinity matrix is sharded by reference (fit) rows; the target cloud and all r-sized state are replicated
-(SURVEY.md section 8e).  One iteration is the three phases of gingr_amd/csrc/fitter.hip; after phases 0 and 1 the partial
+(SURVEY.md section 8e).  One iteration is the three phases of gingr_amd/csrc/fitter_phases.hip; after phases 0 and 1 the partial
 sums in exchange segment p are all-reduced (sum, float64) across ranks:
 
     segment 0  CPD column sums den_j (N doubles)          <- the column-sum exchange named in BASELINE.json north_star
@@ -47,7 +47,7 @@ SEGMENT_REVSUM = nat.SEGMENT_REVSUM
 
 def drive_update(run_phase: Callable[[int], None], all_reduce_segment: Callable[[int], None], world: int,
                  skip_segment0: bool = False, flavour: int = 0, reversed_direction: bool = False) -> None:
-    """One iteration in the order of fitter_sharded_update (gingr_amd/csrc/fitter.hip): for the surface correspondence (flavour 2)
+    """One iteration in the order of fitter_sharded_update (gingr_amd/csrc/fitter_phases.hip): for the surface correspondence (flavour 2)
     the gather of the fit first; then phase p followed (for p < 2) by the all-reduce of exchange segment p -- the ICP flavours
     exchange nothing after phase 0 (their closest-point search is local to the shard's rows)."""
     if (flavour == 2 or (flavour == 1 and reversed_direction)) and world > 1:   # (the reversed direction works on the gathered template)

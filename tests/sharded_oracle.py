@@ -1,6 +1,6 @@
 """Oracle-backed restatement of the three update phases for ONE row shard (test infrastructure).
 
-Mirrors gingr_amd/csrc/fitter.hip phase by phase with numpy so that the sharding algebra -- which partial sums are
+Mirrors gingr_amd/csrc/fitter_phases.hip phase by phase with numpy so that the sharding algebra -- which partial sums are
 exchanged, in which order, and what is replicated -- can be exercised across real processes (gloo) without a GPU.
 Segment layout = gingr_fitter_exchange: [den N] [G rp*rp | rhs rp | 8 scalars | Q0^T e rp] [full fit 3 M_total] [reversal sums 4 M_total], with rp = r
 here (no MFMA padding on the CPU).  Flavours as in gingr_fitter_update_sharded_async: 0 CPD, 1 ICP with the point-cloud closest
