@@ -172,6 +172,11 @@ SIGNATURES = {
     "gingr_fitter_update_icp_sample_async": (c_int, [c_void_p, POINTER(IcpParams), _dp]),
     "gingr_fitter_posterior_logpdf_cpd": (c_int, [c_void_p, POINTER(CpdParams), _dp, _dp]),
     "gingr_fitter_posterior_logpdf_icp": (c_int, [c_void_p, POINTER(IcpParams), _dp, _dp]),
+    "gingr_model_marginal_covariance": (c_int, [c_void_p, c_void_p, _dp, _dp, _dp]),
+    "gingr_model_cross_covariance": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int64, _dp]),
+    "gingr_fitter_posterior_covariance_cpd": (c_int, [c_void_p, POINTER(CpdParams), _dp]),
+    "gingr_fitter_posterior_covariance_icp": (c_int, [c_void_p, POINTER(IcpParams), _dp]),
+    "gingr_fitter_posterior_covariance_icp_surface": (c_int, [c_void_p, POINTER(IcpParams), _dp]),
     "gingr_fitter_retry_counter": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
     "gingr_fitter_exchange": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
     "gingr_fitter_cpd_phase_async": (c_int, [c_void_p, POINTER(CpdParams), c_int32]),

@@ -544,7 +544,13 @@ class GPMMTriangleMesh3D:
         return self.cells
 
     def computeDistanceAbsMesh(self, model, lmId: int) -> np.ndarray:
-        """GPMMHelper.scala:144-153: sum_i |cov(lmId, pid)_ii| per vertex, cov = U diag(variance) U^T (3 x 3 blocks)."""
+        """GPMMHelper.scala:144-153: sum_i |cov(lmId, pid)_ii| per vertex, cov = U diag(variance) U^T (3 x 3 blocks).
+        A device-resident model (DevicePointDistributionModel, DeviceModel) is read where it is: one cross-covariance pass
+        instead of a download of the basis."""
+        dm = model.device() if isinstance(model, DevicePointDistributionModel) else model
+        if isinstance(dm, DeviceModel):
+            c = dm.crossCovariance(int(lmId))
+            return np.abs(c[:, 0, 0]) + np.abs(c[:, 1, 1]) + np.abs(c[:, 2, 2])
         U = f64(model.basis).reshape(model.numberOfPoints, 3, -1)
         w = U[int(lmId)] * f64(model.variance)[None, :]                   # (3, r)
         return np.abs(np.einsum("pdr,dr->pd", U, w)).sum(axis=1)
@@ -704,6 +710,31 @@ class DeviceModel:
             self.ctx.handle, self.handle, dptr(e), dptr(c), dptr(t), dptr(o), dptr(w), n, iptr(lp), dptr(lx), dptr(lc),
             dptr(mean), dptr(coeffs)), "gingr_model_posterior_mean")
         return mean, coeffs
+
+    def _factor(self, factor):
+        if factor is None:
+            return None
+        W = f64(factor)
+        if W.shape != (self.rank, self.rank):
+            raise ValueError(f"factor must be ({self.rank}, {self.rank}), row-major")
+        return W
+
+    def marginalCovariance(self, factor=None, euler=(0, 0, 0)) -> np.ndarray:
+        """(M_local, 6): {xx, xy, xz, yy, yz, zz} of R (Q0_i W)(Q0_i W)^T R^T per local point, Q0 = U sqrt(variance)
+        (gingr_model_marginal_covariance).  factor None = identity: the prior marginal U_i diag(variance) U_i^T."""
+        W, e = self._factor(factor), f64(euler)
+        out = np.empty((self.M_local, 6))
+        _check(self.ctx.handle, self._lib.gingr_model_marginal_covariance(self.ctx.handle, self.handle, dptr(W), dptr(e), dptr(out)),
+               "gingr_model_marginal_covariance")
+        return out
+
+    def crossCovariance(self, pid: int, factor=None, euler=(0, 0, 0)) -> np.ndarray:
+        """(M_local, 3, 3): R (Q0_i W)(Q0_pid W)^T R^T per local point for one GLOBAL point id (gingr_model_cross_covariance)."""
+        W, e = self._factor(factor), f64(euler)
+        out = np.empty((self.M_local, 3, 3))
+        _check(self.ctx.handle, self._lib.gingr_model_cross_covariance(self.ctx.handle, self.handle, dptr(W), dptr(e), int(pid), dptr(out)),
+               "gingr_model_cross_covariance")
+        return out
 
 
 # ----------------------------------------------------------------------------- state records
@@ -965,6 +996,9 @@ class GingrAlgorithm:
     def _native_update(self, current, n: int):
         raise NotImplementedError
 
+    def _native_posterior_covariance(self, state, out: np.ndarray):
+        raise NotImplementedError
+
     # -- the reference surface ----------------------------------------------------------------
     def initializeState(self, general: GeneralRegistrationState, config):
         raise NotImplementedError
@@ -1171,6 +1205,16 @@ class GingrAlgorithm:
                 return float("-inf")
             raise
 
+    def posteriorCovariance(self, state) -> np.ndarray:
+        """(M, 6): the 3 x 3 posterior covariance block {xx, xy, xz, yy, yz, zz} of every vertex under the posterior model of
+        `state` -- posterior.gp.cov(pid, pid) of model.transform(rigid).posterior(observations) (GingrAlgorithm.scala:297-301; no
+        scale) -- computed exactly on the device: the quantity DemoPosteriorVisualizationFemur estimates from a chain of samples.
+        The state is left as it is.  A posterior that cannot be computed raises GingrNativeError."""
+        self._ensure_device_state(state)
+        out = np.empty((state.general.model.numberOfPoints, 6))
+        self._native_posterior_covariance(state, out)
+        return out
+
     def run(self, initialState, callBackLogger: Optional[Callable] = None, acceptRejectLogger=None, probabilisticSettings=None,
             generators=None, rnd=None):
         """GingrAlgorithm.run (:115-175).  Without probabilisticSettings: the deterministic registration loop -- the chain
@@ -1311,6 +1355,11 @@ class CpdRegistration(GingrAlgorithm):
         _check(self.ctx.handle, self._lib.gingr_fitter_posterior_logpdf_cpd(self._fitter, ctypes.byref(p), dptr(mesh),
                                                                              ctypes.byref(out)), "gingr_fitter_posterior_logpdf_cpd")
         return out.value
+
+    def _native_posterior_covariance(self, state: CpdRegistrationState, out: np.ndarray):
+        p = nat.CpdParams(state.config.w, state.config.lambda_)
+        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_covariance_cpd(self._fitter, ctypes.byref(p), dptr(out)),
+               "gingr_fitter_posterior_covariance_cpd")
 
     # plugin accessors served from one streaming evaluation (the reference recomputes P for each of them)
     def _stats(self, state: CpdRegistrationState) -> dict:
@@ -1458,6 +1507,15 @@ class IcpRegistration(GingrAlgorithm):
         fn = self._lib.gingr_fitter_posterior_logpdf_icp_surface if self._surface(c) else self._lib.gingr_fitter_posterior_logpdf_icp
         _check(self.ctx.handle, fn(self._fitter, ctypes.byref(p), dptr(mesh), ctypes.byref(out)), "gingr_fitter_posterior_logpdf_icp")
         return out.value
+
+    def _native_posterior_covariance(self, state: IcpRegistrationState, out: np.ndarray):
+        c = state.config
+        p = nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
+        self._select_direction(c)
+        if self._surface(c):
+            self._select_surface_method(c)
+        fn = self._lib.gingr_fitter_posterior_covariance_icp_surface if self._surface(c) else self._lib.gingr_fitter_posterior_covariance_icp
+        _check(self.ctx.handle, fn(self._fitter, ctypes.byref(p), dptr(out)), "gingr_fitter_posterior_covariance_icp")
 
     def getCorrespondence(self, state: IcpRegistrationState) -> CorrespondencePairs:
         if state.config.reverseCorrespondenceDirection:                               # ICP.scala:46-50

@@ -390,8 +390,10 @@ __global__ __launch_bounds__(256) void inverse_product_kernel(const double *__re
 // IDENTITY: the blocked Cholesky takes the identity along as border rows, which leaves L^-T there (the rows of a border X become
 // X L^-T), and A^-1 = L^-T L^-1 is one product of that triangle with itself.  C: Mp x Mp, all of it written (exactly symmetric).
 // *flag receives GINGR_ERR_NOT_SPD when a diagonal block fails.  Linv: (Mp / 64) blocks of 64 x 64.
+// C == nullptr: the factor alone -- L^-T stays behind in the border rows (Aw + Mp * Mp, upper triangular, row stride Mp).
 void dense_spd_inverse(gingr_ctx *ctx, double *Aw, int64_t Mp, double *Linv, double *C, int32_t *flag) {
     blocked_cholesky(ctx, Aw, Mp, Linv, flag, true);
+    if (!C) return;
     const int nb = (int)(Mp / kNBc);
     hipLaunchKernelGGL(inverse_product_kernel, dim3((unsigned)nb, (unsigned)nb), dim3(256), 0, ctx->stream, Aw + Mp * Mp, Mp, nb, C);
 }

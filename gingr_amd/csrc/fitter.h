@@ -211,6 +211,9 @@ struct gingr_fitter {
     // GINGR_OPT_SPLIT_EXCHANGE (fitter_sharded_update): 0 the whole column-sum pass; 1 / 2 only the first / second half of the target
     // tiles (phase 0 is then run twice, with the all-reduce of the first half in between on the context's second stream)
     int split_half = 0;
+    // gingr_fitter_posterior_covariance_* (posterior_cov.hip): the bordered system the factor L^-T of I + G is left in, and the
+    // [6 M] result before it goes to the host; allocated on first use, kept across calls
+    DevBuf cov_work, cov_out;
 };
 
 // GINGR_OPT_GRAM_DOWNDATE by default: from this many local rows on.  The downdate pays while fewer than ~20 % of the rows have weight 0

@@ -387,6 +387,20 @@ void launch_small_gemm(gingr_ctx *ctx, int32_t r, int32_t rp, const double *A, c
 // the vector part of the model's PostVec block from the 12 moment vectors V[d][e], W[d] ([12][rp]); one-off at model finalisation
 void launch_postvec(gingr_ctx *ctx, int32_t r, int32_t rp, const double *Binv, const double *moment_vectors, double *pvec);
 
+// ---- per-vertex covariance maps (posterior_cov.hip) ------------------------------------------------------------------------
+// cov6[perm[s]] = {xx, xy, xz, yy, yz, zz} of R (Q0_s W)(Q0_s W)^T R^T for the local rows (MFMA f64; Y = Q0 W is never stored).
+// W: [rp][rp] on the device, row stride ldw, zero beyond the rank; upper = W is upper triangular (its zero tiles are skipped).
+// The rotation is `state`'s when given, else R (row-major, nullptr = identity).  cov6: [6 M] on the device, caller's point order.
+void launch_marginal_covariance(gingr_ctx *ctx, const gingr_model *m, const double *W, int64_t ldw, bool upper, const double R[9],
+                                const DevState *state, double *cov6);
+// cov9[perm[s]] = R (Q0_s W)(Q0_p W)^T R^T (row-major 3 x 3) with p the point at device row `device_row`; Z: [3 rp] scratch
+void launch_cross_covariance(gingr_ctx *ctx, const gingr_model *m, const double *W, int64_t ldw, const double R[9], int64_t device_row,
+                             double *Z, double *cov9);
+// L^-T with L L^T = I + G through the multi-workgroup blocked Cholesky (dense_spd_inverse without its product): returns the factor
+// inside `work` (posterior_factor_work_doubles(rp) doubles), upper triangular, row stride *ldw; **flag != 0 afterwards: not SPD
+int64_t posterior_factor_work_doubles(int32_t rp);
+const double *launch_posterior_factor(gingr_ctx *ctx, int32_t r, int32_t rp, const double *G, double *work, int64_t *ldw, int32_t **flag);
+
 // basis packing: stage is column-major [r][3M] (local rows, ORIGINAL order), out Q0 [3M][rp] in device (perm) order
 void launch_pack_basis(gingr_ctx *ctx, const double *stage_colmajor, const double *variance_dev, int64_t M, int32_t r,
                        int32_t rp, const int32_t *perm, double *Q0);

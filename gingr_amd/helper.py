@@ -5,6 +5,7 @@ log back into shapes, per-vertex variance maps of the sampled shapes, and the pr
   JSONStateLogger.loadLog / jsonFormatToModelFittingParameters / getBestStateFromLog   G/api/sampling/loggers/JSONStateLogger.scala:205-236
   PosteriorHelper.computeDistanceMapFromMeshesTotal / ...Normal      G/api/helper/PosteriorHelper.scala:26-80
   CallBackFunctions.SimpleLogger                                     G/api/helper/CallBackFunctions.scala:23-44
+  covariance6_to_matrices / posteriorVarianceMaps                    the same two maps from the exact posterior covariance (no samples)
 
 The shapes are instantiated on the GPU (one model upload, one basis sweep per sample); the variance maps are O(samples x vertices)
 reductions of arrays that are already on the host."""
@@ -115,6 +116,25 @@ def computeDistanceMapFromMeshesNormal(meshes: Sequence[np.ndarray], ref: Triang
         n = _unit(vertex_normals(ref.points, ref.cells))
     proj = ((X - mean) * n[None]).sum(-1)
     return (proj ** 2).sum(axis=0) * (1.0 / (S - 1))
+
+
+# The analytic counterparts of the two sampled maps: from the exact per-vertex posterior covariance (GingrAlgorithm.posteriorCovariance,
+# DeviceModel.marginalCovariance) instead of the sample covariance of a chain.
+def covariance6_to_matrices(cov6: np.ndarray) -> np.ndarray:
+    """(M, 6) {xx, xy, xz, yy, yz, zz} -> (M, 3, 3) symmetric blocks."""
+    c = np.asarray(cov6, dtype=np.float64).reshape(-1, 6)
+    return c[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
+
+
+def posteriorVarianceMaps(cov6: np.ndarray, normals: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """(total, normal): per vertex the trace of its covariance block -- what computeDistanceMapFromMeshesTotal estimates -- and,
+    given (M, 3) normals, the variance n^T C n along them -- computeDistanceMapFromMeshesNormal; normal is None without normals."""
+    c = np.asarray(cov6, dtype=np.float64).reshape(-1, 6)
+    total = c[:, 0] + c[:, 3] + c[:, 5]
+    if normals is None:
+        return total, None
+    n = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    return total, np.einsum("md,mde,me->m", n, covariance6_to_matrices(c), n)
 
 
 # ---------------------------------------------------------------------------------------------------------------- call-back

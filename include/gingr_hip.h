@@ -402,6 +402,27 @@ int gingr_fitter_update_icp_sample_async(gingr_fitter *f, const gingr_icp_params
 int gingr_fitter_posterior_logpdf_cpd(gingr_fitter *f, const gingr_cpd_params *p, const double *mesh_xyz, double *logpdf);
 int gingr_fitter_posterior_logpdf_icp(gingr_fitter *f, const gingr_icp_params *p, const double *mesh_xyz, double *logpdf);
 
+/* ---- per-vertex covariance maps, exact (no sampling) -----------------------------------------------------------------
+ * For a right factor W (r x r, row-major; NULL = identity) the 3 x 3 block of vertex i is
+ *     C_i = R (Q0_i W)(Q0_i W)^T R^T,   Q0 = U sqrt(lambda),   R = Rotation(euler),
+ * positive semi-definite by construction.  W = I is the prior marginal U_i diag(lambda) U_i^T (the map behind the reference's
+ * VisualizeGPMMCorrelation); W = L^-T with L L^T = I + G gives a posterior's posterior.gp.cov(pid, pid).
+ * gingr_model_marginal_covariance: cov6_out[6 M_local] = {xx, xy, xz, yy, yz, zz} per local point, in the caller's point order.
+ * gingr_model_cross_covariance: cov9_out[9 M_local] = R (Q0_i W)(Q0_pid W)^T R^T, full 3 x 3 row-major, for one GLOBAL point id;
+ * the block at i = pid is the marginal.  A row shard that does not own pid returns GINGR_ERR_STATE.  Both calls synchronise. */
+int gingr_model_marginal_covariance(gingr_ctx *ctx, const gingr_model *model, const double *factor, const double euler[3],
+                                    double *cov6_out);
+int gingr_model_cross_covariance(gingr_ctx *ctx, const gingr_model *model, const double *factor, const double euler[3], int64_t pid,
+                                 double *cov9_out);
+/* The same map for the posterior of the fitter's CURRENT state -- what DemoPosteriorVisualizationFemur estimates from thousands of
+ * Metropolis-Hastings samples: correspondences, Gram matrix (landmarks included) and the Cholesky factor of I + G of the state,
+ * then one pass over the basis with the state's rotation.  cov6_out[6 M].  The posterior is that of model.transform(rigid)
+ * (G/api/GingrAlgorithm.scala:297-301): the state's scale is NOT applied.  Single shard only; synchronises; a failed factorisation
+ * gives GINGR_ERR_NOT_SPD.  State, retry counter and posterior memo are left as gingr_fitter_posterior_logpdf_* leaves them. */
+int gingr_fitter_posterior_covariance_cpd(gingr_fitter *f, const gingr_cpd_params *p, double *cov6_out);
+int gingr_fitter_posterior_covariance_icp(gingr_fitter *f, const gingr_icp_params *p, double *cov6_out);
+int gingr_fitter_posterior_covariance_icp_surface(gingr_fitter *f, const gingr_icp_params *p, double *cov6_out);
+
 /* The retry counter of the probabilistic proposal (G/api/GingrAlgorithm.scala:69-70,196-202,210: `retryCounter`, a private var
  * of the algorithm INSTANCE): a sampled proposal whose posterior cannot be computed returns the state unchanged up to 10 times in
  * a row before the state is marked ModelFlexibilityError; every successful posterior gives one retry back (at most 10).  The
@@ -622,7 +643,7 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * which: 0 = cpd_colsum, 1 = cpd_rowstats, 2 = gram, 3 = whole update, 4 = basis sweep (one streaming pass over Q0),
  * 5 = posterior solve (unfused tail only), 6 / 7 = the device group's exchange of segment 0 / 1 on this shard (from the record of
  * the shard's own event to the end of its sum kernel: includes the wait for the slowest peer; the host-driven sharded update records its two collectives there too), 8 = the
- * nearest-neighbour scan kernel alone.  Returns accumulated ms and launches since
+ * nearest-neighbour scan kernel alone, 9 = the per-vertex covariance pass over the basis alone.  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
