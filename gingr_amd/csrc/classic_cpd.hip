@@ -10,10 +10,11 @@
 // streaming passes of the GiNGR path already produce.  Rigid / affine: two O(M + N) reductions (weighted means, then the centred
 // 3x3 moments) and one thread of 3x3 algebra.  Non-rigid: the M x M system (G + lambda sigma2 diag(1/P1)) W = diag(1/P1) P X - Y is
 // symmetric positive definite (the reference solves it with LU, `A \ B`); it is factored here by a blocked right-looking Cholesky
-// with 64-wide panels -- diagonal block in LDS (one workgroup, gp.hip:chol_block64_kernel), panel and trailing update as 64 x 64 MFMA tiles
-// (v_mfma_f64_16x16x4) over the whole chip -- with the three right-hand sides riding along as extra rows of the matrix (the forward
+// with 64-wide panels (dense_spd.hip: diagonal block in LDS, panel and trailing update as 64 x 64 MFMA tiles, v_mfma_f64_16x16x4,
+// over the whole chip) with the three right-hand sides riding along as extra rows of the matrix (the forward
 // substitution is a by-product), a blocked backward substitution, and TY = Y + G W as one pass over G.
 #include "common.h"
+#include "dense_spd.h"
 #include "svd3.h"
 
 #include <algorithm>
@@ -22,10 +23,8 @@
 
 namespace {
 
-constexpr int kNBc = 64;        // Cholesky panel width
+constexpr int kNBc = DenseSpdWork::kBlock;  // Cholesky panel width
 constexpr int kRedBlocks = 64;  // workgroups of the O(M + N) reductions
-
-typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 Cloud cloud_at(const double *soa, int64_t n) { return Cloud{soa, soa + n, soa + 2 * n, n}; }
 
@@ -193,103 +192,6 @@ __global__ void build_system_kernel(int64_t M, int64_t Mp, const double *__restr
     Aw[r * Mp + c] = v;
 }
 
-// one 64 x 64 tile on the matrix pipe: D = (accumulate ? C : 0) + beta * A B^T with A = 64 rows of Ap, B = 64 rows of Bp, K = 64.
-// Both operands are staged through LDS in two halves of 32 columns (coalesced 256-byte row segments in, conflict-free fragment
-// reads out; a panel tile that overwrites its own A operand is safe because A is consumed from LDS before C is written).
-// Fragment layout of v_mfma_f64_16x16x4: lane l supplies A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] and holds
-// D[i = (l >> 4) + 4 reg][j = l & 15]; wave w owns the output rows 16 w .. 16 w + 15.
-__device__ __forceinline__ void tile_abt(const double *Ap, int64_t lda, const double *Bp, int64_t ldb, double *Cp, int64_t ldc,
-                                         bool accumulate, double beta) {
-    __shared__ double As[kNBc][33], Bs[kNBc][33];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
-    v4f64 acc[4];
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-        const double *pc = Cp + (int64_t)(16 * wave + l4) * ldc + 16 * tj + l15;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[tj][g] = accumulate ? pc[(int64_t)4 * g * ldc] : 0.0;
-    }
-    for (int half = 0; half < 2; ++half) {
-        __syncthreads();
-        double va[8], vb[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int e = tid + 256 * u, r = e >> 5, c = e & 31;
-            va[u] = Ap[(int64_t)r * lda + 32 * half + c];
-            vb[u] = Bp[(int64_t)r * ldb + 32 * half + c];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int e = tid + 256 * u, r = e >> 5, c = e & 31;
-            As[r][c] = beta * va[u];
-            Bs[r][c] = vb[u];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const double a = As[16 * wave + l15][4 * q + l4];
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj) acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bs[16 * tj + l15][4 * q + l4], acc[tj], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-        double *pc = Cp + (int64_t)(16 * wave + l4) * ldc + 16 * tj + l15;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) pc[(int64_t)4 * g * ldc] = acc[tj][g];
-    }
-}
-
-// panel solve: L_ik = A_ik L_kk^-T for the row blocks i > k (the last one is the border with the right-hand sides)
-// (inverse: the border is an identity block of nb block rows -- dense_spd_inverse -- whose block row b is still zero left of column b)
-__global__ __launch_bounds__(256) void chol_panel_kernel(double *__restrict__ Aw, int64_t ld, int k, const double *__restrict__ Linv, int nb,
-                                                         bool inverse) {
-    const int64_t i = k + 1 + blockIdx.x;
-    if (inverse && i >= nb && i - nb > k) return;
-    double *aik = Aw + i * kNBc * ld + (int64_t)k * kNBc;
-    tile_abt(aik, ld, Linv + (int64_t)k * kNBc * kNBc, kNBc, aik, ld, false, 1.0);
-}
-
-// trailing update: A_ij -= L_ik L_jk^T for k < j <= i (j a matrix block, i up to the border block)
-__global__ __launch_bounds__(256) void chol_trailing_kernel(double *__restrict__ Aw, int64_t ld, int k, int nb, bool inverse) {
-    const int64_t i = k + 1 + blockIdx.y, j = k + 1 + blockIdx.x;
-    if (j > i || j >= nb) return;
-    if (inverse && i >= nb && i - nb > k) return;
-    tile_abt(Aw + i * kNBc * ld + (int64_t)k * kNBc, ld, Aw + j * kNBc * ld + (int64_t)k * kNBc, ld, Aw + i * kNBc * ld + j * kNBc, ld, true,
-             -1.0);
-}
-
-// backward substitution L^T W = Z, step k (from the last panel to the first): every workgroup forms W_k = L_kk^-T Z_k from the border
-// rows; workgroup j < k then applies Z_j -= L_kj^T W_k, workgroup k stores W_k (planes of stride Mp)
-__global__ __launch_bounds__(256) void chol_backward_kernel(double *__restrict__ Aw, int64_t ld, int64_t Mp, int k,
-                                                            const double *__restrict__ Linv, double *__restrict__ W) {
-    __shared__ double Z[3][kNBc], Wk[3][kNBc];
-    const int tid = threadIdx.x, c = tid & 63, d = tid >> 6;
-    const int64_t kb = (int64_t)k * kNBc;
-    if (d < 3) Z[d][c] = Aw[(Mp + d) * ld + kb + c];
-    __syncthreads();
-    if (d < 3) {
-        const double *li = Linv + (int64_t)k * kNBc * kNBc;
-        double v = 0.0;
-#pragma unroll 16
-        for (int p = 0; p < kNBc; ++p) v += li[p * kNBc + c] * Z[d][p];  // Linv is lower triangular: the entries p < c are zero
-        Wk[d][c] = v;
-    }
-    __syncthreads();
-    if (d >= 3) return;
-    const int j = blockIdx.x;
-    if (j == k) {
-        W[(int64_t)d * Mp + kb + c] = Wk[d][c];
-        return;
-    }
-    const int64_t jb = (int64_t)j * kNBc;
-    double v = 0.0;
-    const double *lkj = Aw + kb * ld + jb + c;
-#pragma unroll 16
-    for (int p = 0; p < kNBc; ++p) v += lkj[(int64_t)p * ld] * Wk[d][p];
-    Aw[(Mp + d) * ld + jb + c] -= v;
-}
-
 // TY = Y + G W: 16 lanes per row of G
 __global__ __launch_bounds__(256) void deform_kernel(int64_t M, int64_t Mp, const double *__restrict__ G, const double *__restrict__ W,
                                                      double *__restrict__ ty) {
@@ -345,60 +247,6 @@ __global__ void nonrigid_finish_kernel(const double *__restrict__ partial, doubl
     scalars[8] = ns;
     if (!(fabs(ns) <= 1.79769313486231570815e308)) *flag = GINGR_ERR_NONFINITE;
 }
-
-}  // namespace
-
-// Aw ((Mp + 64) x Mp, lower triangle of an SPD matrix + three right-hand sides in the border rows Mp .. Mp + 2, see
-// build_system_kernel) -> W (three planes of stride Mp): blocked right-looking Cholesky, then the blocked backward substitution.
-// *flag receives GINGR_ERR_NOT_SPD when a diagonal block fails.  (Also the posterior solve above rank 256: gp.hip, common.h.)
-static void blocked_cholesky(gingr_ctx *ctx, double *Aw, int64_t Mp, double *Linv, int32_t *flag, bool inverse) {
-    const int nb = (int)(Mp / kNBc);
-    const int nrows = inverse ? 2 * nb : nb + 1;  // block rows: the matrix, then the border
-    for (int k = 0; k < nb; ++k) {
-        launch_chol_block64(ctx, Aw, Mp, k, Linv, flag);
-        const int below = inverse ? nb + k + 1 : nrows;  // (inverse: border block rows past k are still zero)
-        hipLaunchKernelGGL(chol_panel_kernel, dim3((unsigned)(below - k - 1)), dim3(256), 0, ctx->stream, Aw, Mp, k, Linv, nb, inverse);
-        if (k + 1 < nb)
-            hipLaunchKernelGGL(chol_trailing_kernel, dim3((unsigned)(nb - k - 1), (unsigned)(below - k - 1)), dim3(256), 0, ctx->stream, Aw, Mp,
-                               k, nb, inverse);
-    }
-}
-
-void dense_spd_solve3(gingr_ctx *ctx, double *Aw, int64_t Mp, double *Linv, double *W, int32_t *flag) {
-    blocked_cholesky(ctx, Aw, Mp, Linv, flag, false);
-    const int nb = (int)(Mp / kNBc);
-    if (!W) return;  // (the factor alone: the lower triangle of Aw then holds L)
-    for (int k = nb - 1; k >= 0; --k)
-        hipLaunchKernelGGL(chol_backward_kernel, dim3((unsigned)(k + 1)), dim3(256), 0, ctx->stream, Aw, Mp, Mp, k, Linv, W);
-}
-
-namespace {
-// C tile (a, b) = sum over the column blocks kb >= max(a, b) of X_a,kb X_b,kb^T, X = L^-T (upper triangular, row stride ld)
-__global__ __launch_bounds__(256) void inverse_product_kernel(const double *__restrict__ X, int64_t ld, int nb, double *__restrict__ C) {
-    const int a = blockIdx.y, b = blockIdx.x;
-    double *c = C + (int64_t)a * kNBc * ld + (int64_t)b * kNBc;
-    bool first = true;
-    for (int kb = a > b ? a : b; kb < nb; ++kb) {
-        tile_abt(X + (int64_t)a * kNBc * ld + (int64_t)kb * kNBc, ld, X + (int64_t)b * kNBc * ld + (int64_t)kb * kNBc, ld, c, ld, !first, 1.0);
-        first = false;
-        __syncthreads();
-    }
-}
-}  // namespace
-
-// The inverse of an SPD matrix on the matrix pipe.  Aw: (2 Mp) x Mp, Mp a multiple of 64 -- the lower triangle of A on top of an
-// IDENTITY: the blocked Cholesky takes the identity along as border rows, which leaves L^-T there (the rows of a border X become
-// X L^-T), and A^-1 = L^-T L^-1 is one product of that triangle with itself.  C: Mp x Mp, all of it written (exactly symmetric).
-// *flag receives GINGR_ERR_NOT_SPD when a diagonal block fails.  Linv: (Mp / 64) blocks of 64 x 64.
-// C == nullptr: the factor alone -- L^-T stays behind in the border rows (Aw + Mp * Mp, upper triangular, row stride Mp).
-void dense_spd_inverse(gingr_ctx *ctx, double *Aw, int64_t Mp, double *Linv, double *C, int32_t *flag) {
-    blocked_cholesky(ctx, Aw, Mp, Linv, flag, true);
-    if (!C) return;
-    const int nb = (int)(Mp / kNBc);
-    hipLaunchKernelGGL(inverse_product_kernel, dim3((unsigned)nb, (unsigned)nb), dim3(256), 0, ctx->stream, Aw + Mp * Mp, Mp, nb, C);
-}
-
-namespace {
 
 // ------------------------------------------------------------------------------------------------ optimal-step non-rigid ICP
 // Normal equations of the stacked least-squares systems of NonRigidOptimalStepICP.scala (the reference solves `A \ B` on the sparse
@@ -574,11 +422,12 @@ int gingr_classic_cpd_create(gingr_ctx *ctx, int32_t kind, int64_t M, const doub
     const double s0 = tot / (3.0 * (double)N * (double)M);
     CC_TRY(hipMemcpyAsync(h->sc.as<double>() + 8, &s0, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (kind == 2) {
-        const int64_t Mp = h->Mp, nb = Mp / kNBc;
+        const int64_t Mp = h->Mp;
+        const DenseSpdWork sys(Mp, DenseSpdWork::kRhsRows);
         CC_TRY(h->G.alloc((size_t)M * M * sizeof(double)));
-        CC_TRY(h->Aw.alloc((size_t)(Mp + kNBc) * Mp * sizeof(double)));
-        CC_TRY(h->Linv.alloc((size_t)nb * kNBc * kNBc * sizeof(double)));
-        CC_TRY(h->W.alloc((size_t)3 * Mp * sizeof(double)));
+        CC_TRY(h->Aw.alloc((size_t)sys.aw_doubles() * sizeof(double)));
+        CC_TRY(h->Linv.alloc((size_t)sys.linv_doubles() * sizeof(double)));
+        CC_TRY(h->W.alloc((size_t)sys.w_doubles() * sizeof(double)));
         // G = exp(-|y_i - y_j|^2 / (2 beta^2)) over the TEMPLATE points                    (CPDFactory.initializeKernelMatrixG, :54-66)
         launch_gauss_block(ctx, Y, Y, sqrt(2.0) * beta, 1.0, h->G.as<double>());
     }
@@ -684,7 +533,8 @@ int gingr_nicp_solve(gingr_ctx *ctx, int32_t kind, int64_t n, const double *movi
         (n_lm > 0 && (!lm_ids || !lm_target_xyz)) || !(alpha >= 0.0) || !(beta >= 0.0) || !(gamma >= 0.0) || n_lm > n)
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "nicp_solve: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t dim = kind == 0 ? n : 4 * n, Mp = round_up(dim, kNBc), nb = Mp / kNBc;
+    const int64_t dim = kind == 0 ? n : 4 * n, Mp = round_up(dim, kNBc);
+    const DenseSpdWork sys(Mp, DenseSpdWork::kRhsRows);
     // host side: SoA clouds, vertex degrees, the landmark terms per vertex
     std::vector<double> hv((size_t)3 * n), hu((size_t)3 * n), hw((size_t)n), hs((size_t)3 * n, 0.0);
     std::vector<int32_t> hdeg((size_t)n, 0), hcnt((size_t)n, 0);
@@ -717,8 +567,8 @@ int gingr_nicp_solve(gingr_ctx *ctx, int32_t kind, int64_t n, const double *movi
     ScratchPart dv, du, dw, ds, ddeg, dcnt, dedges, Aw, Linv, W, flag, dout;
     {
         const size_t sizes[12] = {hv.size() * 8, hu.size() * 8, hw.size() * 8, hs.size() * 8, hdeg.size() * 4, hcnt.size() * 4,
-                                  (size_t)(n_edges > 0 ? n_edges : 1) * 8, (size_t)(Mp + kNBc) * Mp * sizeof(double),
-                                  (size_t)nb * kNBc * kNBc * sizeof(double), (size_t)3 * Mp * sizeof(double), sizeof(int32_t),
+                                  (size_t)(n_edges > 0 ? n_edges : 1) * 8, (size_t)sys.aw_doubles() * sizeof(double),
+                                  (size_t)sys.linv_doubles() * sizeof(double), (size_t)sys.w_doubles() * sizeof(double), sizeof(int32_t),
                                   (size_t)3 * n * sizeof(double)};
         ScratchPart *parts[12] = {&dv, &du, &dw, &ds, &ddeg, &dcnt, &dedges, &Aw, &Linv, &W, &flag, &dout};
         size_t total = 0;

@@ -1,4 +1,4 @@
-// Low-rank GP kernels (gp.hip): device data structures and launchers.  Internal to libgingr_hip.so.
+// Low-rank GP kernels (gp_sweep.hip, gp_gram.hip, gp_wide.hip, gp_obs.hip, gp.hip, gp_post_solve.hip): device data structures and launchers.  Internal to libgingr_hip.so.
 #pragma once
 
 #include "common.h"
@@ -73,7 +73,7 @@ struct MomentLayout {
     __host__ __device__ int64_t total() const { return (int64_t)rp * rp * 10 + (int64_t)rp * 12; }
 };
 
-// What the post-solve kernel reads besides the state (gp.hip: post_solve_kernel).  Binv = (S_tot / eps + I)^-1 is applied to every
+// What the post-solve kernel reads besides the state (gp_post_solve.hip: post_solve_kernel).  Binv = (S_tot / eps + I)^-1 is applied to every
 // term of the second coefficient projection up front -- to the constant moment vectors once per model (pvec), to S[d][e] alpha and
 // S[d][e] alpha_1 by the mat-vec launch (zbuf) -- so that the kernel itself touches no r x r matrix.
 struct PostVec {
@@ -127,7 +127,7 @@ struct gingr_model {
     bool finalized = false;
 };
 
-// gp.hip: basis rows of a model on a new reference as fixed convex combinations of three source rows (gingr_model_new_reference)
+// gp_sweep.hip: basis rows of a model on a new reference as fixed convex combinations of three source rows (gingr_model_new_reference)
 void launch_interp_pack(gingr_ctx *ctx, const double *Qs, int32_t rp, const int32_t *inv_src, const int32_t *ids, const double *w,
                         const int32_t *perm_new, int64_t row_begin, int64_t M, double *Q0);
 
@@ -191,7 +191,7 @@ __device__ __forceinline__ bool gate_open(const ZeroGate &g) {
     return many == (g.run_if_many != 0);
 }
 
-// ---- basis sweeps ------------------------------------------------------------------------------------------
+// ---- basis sweeps (gp_sweep.hip) ------------------------------------------------------------------------------------------
 enum SweepMode {
     SWEEP_RHS = 0,      // T only: out[k] = sum_i Q0_i^T e_i, e from evec planes
     SWEEP_PROJ1 = 1,    // F(a) then T with e = Q0_i a
@@ -242,7 +242,7 @@ int sweep_num_blocks(int64_t M);
 int64_t sweep_ws_doubles(int64_t M, int32_t rp);
 void launch_sweep(gingr_ctx *ctx, SweepMode mode, const SweepArgs &a);
 
-// ---- weighted Gram (MFMA f64) -----------------------------------------------------------------------------
+// ---- weighted Gram (MFMA f64; gp_gram.hip) -----------------------------------------------------------------------------
 int64_t gram_ws_doubles(int64_t M, int32_t rp);
 // G[rp*rp] (full symmetric) = sum_i w_i Q0_i^T Q0_i over local points; weight == nullptr means w = 1
 // returns the number of slab partials in ws; G == nullptr leaves them unreduced (launch_phase1_finalize adds them up)
@@ -262,7 +262,7 @@ int launch_gram_wide(gingr_ctx *ctx, const double *Q0, int64_t M, int32_t rp, co
 int64_t gram_rows_ws_doubles(int64_t rows, int32_t rp);
 int launch_gram_rows(gingr_ctx *ctx, const double *Z, int64_t rows, int32_t rp, double *ws);
 
-// one launch for the reductions at the end of phase 1 (gp.hip: phase1_finalize_kernel)
+// one launch for the reductions at the end of phase 1 (gp_gram.hip: phase1_finalize_kernel)
 struct Phase1FinalizeArgs {
     int32_t rp;
     const double *gram_partial;   // [nslabs][rp*rp] (upper patches); nslabs == 0: G is not touched, unless scaled_src is given
@@ -293,7 +293,7 @@ void launch_phase1_finalize(gingr_ctx *ctx, const Phase1FinalizeArgs &a);
 int launch_gram_downdate(gingr_ctx *ctx, const double *Q0, int64_t M, int32_t rp, const double *weight, double *ws,
                          const ZeroGate *gate = nullptr);
 
-// ---- observations ------------------------------------------------------------------------------------------
+// ---- observations (gp_obs.hip) ------------------------------------------------------------------------------------------
 // CPD: yhat = y + (PX/P1 - y), weight = 1/(sigma2*lambda/P1)  (CPD.scala:37-46,126); e = w (R^T(yhat - c - t) - (ref - c) - mean)
 void launch_obs_cpd(gingr_ctx *ctx, const gingr_model *m, const DevState *st, Cloud fit, const double *P1,
                     const double *PX, double lambda, const int32_t *lm_mask, double *weight, double *evec);
@@ -309,7 +309,7 @@ void launch_obs_points(gingr_ctx *ctx, const gingr_model *m, const DevState *st,
 void launch_landmarks(gingr_ctx *ctx, const gingr_model *m, const DevState *st, int32_t n_lm, const int32_t *lm_pid_local,
                       const double *lm_xyz, const double *lm_cov, double *G, double *rhs);
 
-// ---- small dense kernels ------------------------------------------------------------------------------------
+// ---- small dense kernels (gp.hip; the post-solve part: gp_post_solve.hip) ------------------------------------------------------------------------------------
 // a = (I + G)^-1 rhs  by Cholesky (work: posterior_work_doubles(rp)); sets st->err on failure
 // zrand (nullable, [r] on the device): standard-normal draws; the result is then a posterior SAMPLE a + L^-T z
 void launch_posterior_solve(gingr_ctx *ctx, int32_t r, int32_t rp, const double *G, const double *rhs, const double *zrand,
@@ -396,7 +396,7 @@ void launch_marginal_covariance(gingr_ctx *ctx, const gingr_model *m, const doub
 // cov9[perm[s]] = R (Q0_s W)(Q0_p W)^T R^T (row-major 3 x 3) with p the point at device row `device_row`; Z: [3 rp] scratch
 void launch_cross_covariance(gingr_ctx *ctx, const gingr_model *m, const double *W, int64_t ldw, const double R[9], int64_t device_row,
                              double *Z, double *cov9);
-// L^-T with L L^T = I + G through the multi-workgroup blocked Cholesky (dense_spd_inverse without its product): returns the factor
+// L^-T with L L^T = I + G through the multi-workgroup blocked Cholesky (dense_spd.h: dense_spd_inverse without its product): returns the factor
 // inside `work` (posterior_factor_work_doubles(rp) doubles), upper triangular, row stride *ldw; **flag != 0 afterwards: not SPD
 int64_t posterior_factor_work_doubles(int32_t rp);
 const double *launch_posterior_factor(gingr_ctx *ctx, int32_t r, int32_t rp, const double *G, double *work, int64_t *ldw, int32_t **flag);

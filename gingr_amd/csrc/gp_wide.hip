@@ -1,7 +1,7 @@
 // Weighted Gram Q^T L Q for model ranks above 112 (rp = 128 .. 512, NT = rp / 16 = 8 .. 32 column tiles) on gfx950.
 //
 // What it replaces: the Q^T L Q of scalismo's DiscreteLowRankGaussianProcess.regression, reached from
-// G/api/GingrAlgorithm.scala:297-301 -- the same product gram_tri_kernel (gp.hip) computes for rp <= 112, at the ranks the
+// G/api/GingrAlgorithm.scala:297-301 -- the same product gram_tri_kernel (gp_gram.hip) computes for rp <= 112, at the ranks the
 // reference's untruncated demo models have (E/CreateBunnyGPMM.scala, E/DemoHelper/DemoDatasetLoader.scala:22;
 // G/api/registration/utils/GPMMHelper.scala:39-69).
 //
@@ -21,7 +21,7 @@
 //   * every address is a wave-uniform base (scalar registers, advanced by scalar adds) plus a per-lane constant;
 //   * the LDS addresses of a wave's tiles are computed once (two registers per tile), the buffer / sub-step parts are immediates.
 // The right-hand side Q0^T e rides along as in gram_tri_kernel (one FMA per fragment value).
-// Output: the same [slab][rp x rp] partial layout, upper tiles only; reduced by phase1_finalize_kernel / gram_reduce_kernel (gp.hip).
+// Output: the same [slab][rp x rp] partial layout, upper tiles only; reduced by phase1_finalize_kernel / gram_reduce_kernel (gp_gram.hip).
 #include "gp.h"
 
 #include <algorithm>

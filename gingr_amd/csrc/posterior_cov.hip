@@ -4,6 +4,7 @@
 // registration state (posterior.gp.cov(pid, pid) of scalismo; G/api/GingrAlgorithm.scala:297-301).  The factored form keeps every
 // block positive semi-definite by construction and never forms (I + G)^-1, whose error relative to a small posterior block grows
 // with cond(I + G).
+#include "dense_spd.h"
 #include "fitter.h"
 
 #include <algorithm>
@@ -25,7 +26,7 @@ constexpr int kCovChunkTiles = 4; // column tiles of Y a wave holds at a time (3
 
 // One column chunk [n0, n0 + 16 NT) of Y = Q0_rows W for the wave's 16 vertices, reduced into the six running sums at once.
 //   D(16x16) += A(16x4) B(4x16): lane l supplies A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; D: lane holds column
-//   j = l & 15 of the rows i = (l >> 4) + 4 reg (the layouts of gram_kernel, gp.hip).
+//   j = l & 15 of the rows i = (l >> 4) + 4 reg (the layouts of gram_kernel, gp_gram.hip).
 // Row tile d holds coordinate d of the 16 vertices (A row i = basis row 3 (v0 + i) + d), so the three coordinates of a vertex sit in
 // the same lane and register of the three tiles and Y_d Y_e needs no exchange.  The 16 k of a step are dealt to the four MFMAs as
 // k0 + 4 (l >> 4) + t: a lane's four A values are 32 contiguous bytes (one load), and B follows the same permutation of k.
@@ -213,20 +214,6 @@ __global__ __launch_bounds__(256) void pad_factor_kernel(int r, int rp, const do
     W[idx] = v;
 }
 
-// Aw ((2 Mp) x Mp): the lower triangle of I + G (identity on the padding) on top of the identity the blocked Cholesky turns into L^-T
-__global__ __launch_bounds__(256) void cov_system_kernel(int r, int n, int64_t Mp, const double *__restrict__ G, double *__restrict__ Aw,
-                                                         int32_t *__restrict__ flag) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
-    if (c == 0 && row == 0) *flag = 0;
-    if (c >= Mp) return;
-    double v = 0.0;
-    if (row >= Mp)
-        v = row - Mp == c ? 1.0 : 0.0;
-    else if (c <= row)
-        v = (row < r && c < r) ? G[row * n + c] + (row == c ? 1.0 : 0.0) : (row == c ? 1.0 : 0.0);
-    Aw[row * Mp + c] = v;
-}
-
 struct FactorBufs {  // device copy of a model operator's factor
     DevBuf host_factor, W;
 };
@@ -273,19 +260,18 @@ void launch_cross_covariance(gingr_ctx *ctx, const gingr_model *m, const double 
 }
 
 int64_t posterior_factor_work_doubles(int32_t rp) {
-    const int64_t Mp = round_up(rp, 64);
-    return 2 * Mp * Mp + (Mp / 64) * 64 * 64 + 1;  // the system over the identity, the inverses of the diagonal blocks, the flag
+    return DenseSpdWork::doubles(rp, DenseSpdWork::kIdentity);  // the system over the identity, the inverses of the diagonal blocks, the flag
 }
 
 const double *launch_posterior_factor(gingr_ctx *ctx, int32_t r, int32_t rp, const double *G, double *work, int64_t *ldw, int32_t **flag) {
-    const int64_t Mp = round_up(rp, 64);
-    double *Aw = work, *Linv = Aw + 2 * Mp * Mp;
-    *flag = reinterpret_cast<int32_t *>(Linv + (Mp / 64) * 64 * 64);
-    *ldw = Mp;
-    hipLaunchKernelGGL(cov_system_kernel, dim3((unsigned)ceil_div(Mp, 256), (unsigned)(2 * Mp)), dim3(256), 0, ctx->stream, (int)r, (int)rp, Mp, G,
-                       Aw, *flag);
-    dense_spd_inverse(ctx, Aw, Mp, Linv, nullptr, *flag);
-    return Aw + Mp * Mp;
+    // Aw: the lower triangle of I + G (identity on the padding) on top of the identity the blocked Cholesky turns into L^-T
+    const DenseSpdWork ws(rp, DenseSpdWork::kIdentity);
+    double *Aw = work + ws.aw(), *Linv = work + ws.linv();
+    *flag = reinterpret_cast<int32_t *>(work + ws.flag());
+    *ldw = ws.Mp;
+    launch_spd_system(ctx->stream, (int)r, ws, SpdIdentityPlus{G, (int)rp}, SpdIdentityBorder{}, Aw, *flag);
+    dense_spd_inverse(ctx, Aw, ws.Mp, Linv, nullptr, *flag);
+    return work + ws.lt();
 }
 
 extern "C" {

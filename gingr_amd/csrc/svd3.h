@@ -1,4 +1,4 @@
-// 3x3 singular value decomposition, polar rotation and the Euler conventions shared by the Umeyama step of the update (gp.hip),
+// 3x3 singular value decomposition, polar rotation and the Euler conventions shared by the Umeyama step of the update (gp_post_solve.hip),
 // the classic rigid CPD (classic_cpd.hip) and the rigid ICP (rigid_icp.hip)
 #pragma once
 #include <hip/hip_runtime.h>

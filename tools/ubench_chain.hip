@@ -1,4 +1,4 @@
-// Latency / issue cost of the instruction kinds on the sequential chains of the one-workgroup kernels (gp.hip: lds_cholesky), one
+// Latency / issue cost of the instruction kinds on the sequential chains of the one-workgroup kernels (solve_blocks.h: lds_cholesky), one
 // wave per SIMD, shader cycles by s_memtime.   hipcc -O3 --offload-arch=gfx950 tools/ubench_chain.hip -o tools/bin/ubench_chain
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -1,4 +1,4 @@
-// Stage timing of chol_block64_kernel (gp.hip): the 64 x 64 diagonal block of the multi-workgroup blocked Cholesky -- factor + inverse with
+// Stage timing of chol_block64_kernel (dense_spd.hip): the 64 x 64 diagonal block of the multi-workgroup blocked Cholesky -- factor + inverse with
 // 64 identity rows riding along -- which sits on the critical path of the posterior solve from rank 241 on, of Binv above rank 112 and of
 // the classic non-rigid CPD (one call per 64 columns).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -I gingr_amd/csrc tools/ubench_chol_block64.hip -o tools/bin/ubench_chol_block64
@@ -19,13 +19,8 @@ __shared__ unsigned long long s_last;
         s_last = now__;                                                  \
     }
 #define GINGR_CHOL64_STAMPS 1
-#include "gp.hip"
-TimerScope::TimerScope(gingr_ctx *c, int w) : ctx(c), which(w) {}
-void TimerScope::stop() {}
-TimerScope::~TimerScope() {}
-int64_t gram_wide_ws_doubles(int64_t, int32_t) { return 0; }
-int launch_gram_wide(gingr_ctx *, const double *, int64_t, int32_t, const double *, double *, const double *, double *, const ZeroGate *) { return 0; }
-void dense_spd_solve3(gingr_ctx *, double *, int64_t, double *, double *, int32_t *) {}
+#include "dense_spd.hip"
+void set_dynamic_lds(const void *func, int bytes) { (void)hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
 #include <cstdio>
 #include <random>
 #include <vector>

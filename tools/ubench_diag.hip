@@ -1,10 +1,7 @@
-// cycles of ONE 16 x 16 diagonal block of lds_cholesky (gp.hip) by itself, cold and warm instruction cache
+// cycles of ONE 16 x 16 diagonal block of lds_cholesky (solve_blocks.h) by itself, cold and warm instruction cache
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -I gingr_amd/csrc tools/ubench_diag.hip -o tools/bin/ubench_diag
 #include <hip/hip_runtime.h>
-#include "gp.hip"
-TimerScope::TimerScope(gingr_ctx *c, int w) : ctx(c), which(w) {}
-void TimerScope::stop() {}
-TimerScope::~TimerScope() {}
+#include "solve_blocks.h"
 #include <cstdio>
 __global__ __launch_bounds__(256) void kd(const double *M, unsigned long long *out, double *res) {
     __shared__ double A[32 * 17 + 64];

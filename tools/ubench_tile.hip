@@ -1,4 +1,4 @@
-// Where one 16 x 16 tile of the trailing update (gp.hip: lds_cholesky) spends its cycles: one wave, shader cycles by s_memtime.
+// Where one 16 x 16 tile of the trailing update (solve_blocks.h: lds_cholesky) spends its cycles: one wave, shader cycles by s_memtime.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 typedef double v4f64 __attribute__((ext_vector_type(4)));
