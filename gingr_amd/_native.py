@@ -177,6 +177,10 @@ SIGNATURES = {
     "gingr_fitter_posterior_covariance_cpd": (c_int, [c_void_p, POINTER(CpdParams), _dp]),
     "gingr_fitter_posterior_covariance_icp": (c_int, [c_void_p, POINTER(IcpParams), _dp]),
     "gingr_fitter_posterior_covariance_icp_surface": (c_int, [c_void_p, POINTER(IcpParams), _dp]),
+    "gingr_model_posterior": (c_int, [c_void_p, c_void_p, _dp, _dp, _dp, _dp, _dp, c_int32, _ip, _dp, _dp, POINTER(c_void_p)]),
+    "gingr_fitter_posterior_model_cpd": (c_int, [c_void_p, POINTER(CpdParams), POINTER(c_void_p)]),
+    "gingr_fitter_posterior_model_icp": (c_int, [c_void_p, POINTER(IcpParams), POINTER(c_void_p)]),
+    "gingr_fitter_posterior_model_icp_surface": (c_int, [c_void_p, POINTER(IcpParams), POINTER(c_void_p)]),
     "gingr_fitter_retry_counter": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
     "gingr_fitter_exchange": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
     "gingr_fitter_cpd_phase_async": (c_int, [c_void_p, POINTER(CpdParams), c_int32]),

@@ -457,6 +457,32 @@ class TruncatedDevicePointDistributionModel(DevicePointDistributionModel):
         return self.to_host(basis=False).mean
 
 
+class PosteriorDevicePointDistributionModel(DevicePointDistributionModel):
+    """model.transform(rigid).posterior(observations) as a model resident in HBM (gingr_model_posterior,
+    gingr_fitter_posterior_model_*; computePosterior, GingrAlgorithm.scala:281-302): wraps the finished native model.  Reference and
+    mean are the posterior's own (read back once, without the basis); basis and variance are downloaded only if somebody asks."""
+
+    def __init__(self, ctx: Context, handle, cells=None):
+        self.ctx = ctx
+        self.cells = cells
+        self._kernels, self._host, self._info = None, None, None
+        self._to_tolerance, self._keep = False, 0
+        self._full = DeviceModel._adopt(ctx, handle, self, int(ctx._lib.gingr_model_num_points(handle)))
+        try:
+            self._host = self._full.download(basis=False)
+        except Exception:
+            self._full.close()
+            raise
+        self.reference = self._host.reference
+
+    def _build(self, ctx: Context, row_begin: int, row_end: int):
+        raise ValueError("a posterior model lives whole on the context of its source; download it (to_host) for anything else")
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self.to_host(basis=False).mean
+
+
 @dataclasses.dataclass
 class GaussianKernelParameters:
     """GPMMHelper.scala:94"""
@@ -710,6 +736,25 @@ class DeviceModel:
             self.ctx.handle, self.handle, dptr(e), dptr(c), dptr(t), dptr(o), dptr(w), n, iptr(lp), dptr(lx), dptr(lc),
             dptr(mean), dptr(coeffs)), "gingr_model_posterior_mean")
         return mean, coeffs
+
+    def posterior(self, obs_points, weights, euler=(0, 0, 0), center=(0, 0, 0), translation=(0, 0, 0),
+                  landmarks: Optional["LandmarkCorrespondences"] = None) -> "DeviceModel":
+        """model.transform(rigid).posterior(observations) as a new resident model (gingr_model_posterior): same arguments as
+        posterior_mean.  The basis is rotated in HBM; the result is an ordinary DeviceModel (download, truncate, instance,
+        coefficients, marginalCovariance, posterior again, a registration's prior), independent of this one; cells are carried over."""
+        o, w, e, c, t = f64(obs_points), f64(weights), f64(euler), f64(center), f64(translation)
+        if landmarks is not None and len(landmarks.pids) > 0:
+            lp = np.ascontiguousarray(landmarks.pids, dtype=np.int32)
+            lx, lc = f64(landmarks.points), f64(landmarks.covs)
+            n = lp.shape[0]
+        else:
+            lp = lx = lc = None
+            n = 0
+        h = c_void_p()
+        _check(self.ctx.handle, self._lib.gingr_model_posterior(
+            self.ctx.handle, self.handle, dptr(e), dptr(c), dptr(t), dptr(o), dptr(w), n, iptr(lp), dptr(lx), dptr(lc),
+            ctypes.byref(h)), "gingr_model_posterior")
+        return PosteriorDevicePointDistributionModel(self.ctx, h, cells=getattr(self.host, "cells", None)).device()
 
     def _factor(self, factor):
         if factor is None:
@@ -999,6 +1044,9 @@ class GingrAlgorithm:
     def _native_posterior_covariance(self, state, out: np.ndarray):
         raise NotImplementedError
 
+    def _native_posterior_model(self, state, out):
+        raise NotImplementedError
+
     # -- the reference surface ----------------------------------------------------------------
     def initializeState(self, general: GeneralRegistrationState, config):
         raise NotImplementedError
@@ -1215,6 +1263,16 @@ class GingrAlgorithm:
         self._native_posterior_covariance(state, out)
         return out
 
+    def posteriorModel(self, state) -> DeviceModel:
+        """The posterior model of `state` -- computePosterior (GingrAlgorithm.scala:281-302): model.transform(rigid).posterior(
+        observations), no scale -- as a new model resident in HBM (gingr_fitter_posterior_model_*): sample from it, save it,
+        truncate it, condition it again, or register with it as the prior.  The state is left as it is.  A posterior that cannot be
+        computed raises GingrNativeError."""
+        self._ensure_device_state(state)
+        h = c_void_p()
+        self._native_posterior_model(state, h)
+        return PosteriorDevicePointDistributionModel(self.ctx, h, cells=getattr(state.general.model, "cells", None)).device()
+
     def run(self, initialState, callBackLogger: Optional[Callable] = None, acceptRejectLogger=None, probabilisticSettings=None,
             generators=None, rnd=None):
         """GingrAlgorithm.run (:115-175).  Without probabilisticSettings: the deterministic registration loop -- the chain
@@ -1360,6 +1418,11 @@ class CpdRegistration(GingrAlgorithm):
         p = nat.CpdParams(state.config.w, state.config.lambda_)
         _check(self.ctx.handle, self._lib.gingr_fitter_posterior_covariance_cpd(self._fitter, ctypes.byref(p), dptr(out)),
                "gingr_fitter_posterior_covariance_cpd")
+
+    def _native_posterior_model(self, state: CpdRegistrationState, out):
+        p = nat.CpdParams(state.config.w, state.config.lambda_)
+        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_model_cpd(self._fitter, ctypes.byref(p), ctypes.byref(out)),
+               "gingr_fitter_posterior_model_cpd")
 
     # plugin accessors served from one streaming evaluation (the reference recomputes P for each of them)
     def _stats(self, state: CpdRegistrationState) -> dict:
@@ -1516,6 +1579,15 @@ class IcpRegistration(GingrAlgorithm):
             self._select_surface_method(c)
         fn = self._lib.gingr_fitter_posterior_covariance_icp_surface if self._surface(c) else self._lib.gingr_fitter_posterior_covariance_icp
         _check(self.ctx.handle, fn(self._fitter, ctypes.byref(p), dptr(out)), "gingr_fitter_posterior_covariance_icp")
+
+    def _native_posterior_model(self, state: IcpRegistrationState, out):
+        c = state.config
+        p = nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
+        self._select_direction(c)
+        if self._surface(c):
+            self._select_surface_method(c)
+        fn = self._lib.gingr_fitter_posterior_model_icp_surface if self._surface(c) else self._lib.gingr_fitter_posterior_model_icp
+        _check(self.ctx.handle, fn(self._fitter, ctypes.byref(p), ctypes.byref(out)), "gingr_fitter_posterior_model_icp")
 
     def getCorrespondence(self, state: IcpRegistrationState) -> CorrespondencePairs:
         if state.config.reverseCorrespondenceDirection:                               # ICP.scala:46-50

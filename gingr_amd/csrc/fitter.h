@@ -269,6 +269,11 @@ void launch_mh_readback(gingr_ctx *ctx, int64_t n, const double *block, int nblo
 // the host's wait for that store into pin[pin_doubles - 1]; false: not seen within the deadline (the caller synchronises the stream)
 bool wait_pinned_flag(gingr_fitter *f, double epoch);
 int pull_small(gingr_fitter *f, const double *src, int n, double *dst);  // n <= 256 doubles from the device to `dst` inside f->pin
+// ---- model.hip: a short-lived fitter posed by (euler, center, translation) with zero shape coefficients, and the posterior system of
+// the stateless observations of gingr_model_posterior_mean: G [rp*rp] then rhs [rp] in `sys`.  The caller destroys the fitter.
+int model_observation_system(gingr_ctx *ctx, const gingr_model *model, const double euler[3], const double center[3],
+                             const double translation[3], const double *obs_xyz, const double *weight, int32_t n_lm, const int32_t *lm_pid,
+                             const double *lm_xyz, const double *lm_cov, gingr_fitter **f_out, DevBuf &sys);
 // ---- fitter_phases.hip
 int gather_fit(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, gingr_allreduce_fn reduce, void *user,
                fitter_gather_fn gather, const char *who);

@@ -334,6 +334,8 @@ void launch_posterior_solve_eig(gingr_ctx *ctx, int32_t r, int32_t rp, const dou
 // component i of eigenvector k); the register kernel of eig.hip up to 192 columns, the two-sided cyclic Jacobi of gpmm.hip above that
 // and for numerically singular matrices (gpmm.hip sym_eig); synchronises the stream
 int launch_jacobi_eig(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, double *evals, double *Vs);
+// the same with the block kernel of eig.hip (sym_eig_blocks) in front of the two-sided one above kSymEigColsMaxN columns
+int launch_jacobi_eig_blocks(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, double *evals, double *Vs);
 // eig.hip: one-sided register Jacobi on the Cholesky factor, n <= kSymEigColsMaxN, up to three problems per launch (see sym_eig, gpmm.hip)
 constexpr int kSymEigColsMaxN = 192;
 int64_t sym_eig_cols_work_doubles(int32_t n);

@@ -874,6 +874,12 @@ int launch_jacobi_eig(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, d
     return sym_eig(ctx, 1, Gs, &ldg, &n, es, vs);
 }
 
+int launch_jacobi_eig_blocks(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, double *evals, double *Vs) {
+    const double *Gs[1] = {G};
+    double *es[1] = {evals}, *vs[1] = {Vs};
+    return sym_eig(ctx, 1, Gs, &ldg, &n, es, vs, true);
+}
+
 extern "C" {
 
 int gingr_pointset_distance_extrema(gingr_ctx *ctx, const double *xyz, int64_t n, double *max_distance,

@@ -255,6 +255,60 @@ static void fill_scalars(gingr_state_scalars *s, const double euler[3], const do
     s->sigma2 = 1.0;
 }
 
+}  // extern "C"
+
+// The posterior system of stateless observations (gingr_model_posterior_mean, gingr_model_posterior): a short-lived fitter whose state
+// is the rigid transform with zero shape coefficients, and G [rp*rp] followed by rhs [rp] of the observations in `sys` (landmarks
+// included).  Synchronises (the staging buffers are its own); on failure no fitter is left behind.
+int model_observation_system(gingr_ctx *ctx, const gingr_model *model, const double euler[3], const double center[3],
+                             const double translation[3], const double *obs_xyz, const double *weight, int32_t n_lm, const int32_t *lm_pid,
+                             const double *lm_xyz, const double *lm_cov, gingr_fitter **f_out, DevBuf &sys) {
+    gingr_fitter *f = nullptr;
+    GINGR_TRY(gingr_fitter_create(ctx, model, &f));
+    const int64_t M = model->M;
+    const int32_t r = model->r, rp = model->rp;
+    int rc = GINGR_OK;
+    std::vector<double> zero((size_t)r, 0.0);
+    gingr_state_scalars s;
+    fill_scalars(&s, euler, center, translation, 1.0);
+    rc = gingr_fitter_set_state(f, zero.data(), &s);
+    if (!rc) rc = gingr_fitter_set_landmarks(f, n_lm, lm_pid, lm_xyz, lm_cov);
+    DevBuf aos, obs, win, gws;
+    if (!rc && (aos.alloc((size_t)3 * M * sizeof(double)) != hipSuccess || obs.alloc((size_t)3 * M * sizeof(double)) != hipSuccess ||
+                win.alloc((size_t)M * sizeof(double)) != hipSuccess ||
+                sys.alloc(((size_t)rp * rp + rp) * sizeof(double)) != hipSuccess ||
+                gws.alloc((size_t)gram_ws_doubles(M, rp) * sizeof(double)) != hipSuccess))
+        rc = gingr_set_error(ctx, GINGR_ERR_HIP, "out of memory");
+    if (!rc) {
+        std::vector<double> wo((size_t)M), wh((size_t)M);
+        for (int64_t i = 0; i < M; ++i) wo[(size_t)i] = weight[i];
+        for (int32_t l = 0; l < n_lm; ++l) wo[(size_t)lm_pid[l]] = 0.0;  // landmark pids carry weight 0
+        for (int64_t sidx = 0; sidx < M; ++sidx) wh[(size_t)sidx] = wo[(size_t)model->hperm[(size_t)sidx]];  // device order
+        (void)hipMemcpyAsync(aos.p, obs_xyz, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        launch_aos_to_soa(ctx, aos.as<double>(), M, obs.as<double>(), model->perm);
+        (void)hipMemcpyAsync(win.p, wh.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        launch_obs_points(ctx, model, f->st, obs.as<double>(), win.as<double>(), f->weight, f->evec);
+        double *Gd = sys.as<double>(), *rhs = Gd + (int64_t)rp * rp;
+        launch_gram(ctx, model->Q0, M, rp, f->weight, gws.as<double>(), Gd);
+        SweepArgs a = base_args(f);
+        a.evec = f->evec;
+        a.out = rhs;
+        launch_sweep(ctx, SWEEP_RHS, a);
+        launch_landmarks(ctx, model, f->st, f->n_lm, f->lm_pid, f->lm_xyz, f->lm_cov, Gd, rhs);
+        rc = check_launch(ctx);
+        // the staging buffers and the host weights go out of scope
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = gingr_set_error(ctx, GINGR_ERR_HIP, "synchronize failed");
+    }
+    if (rc) {
+        gingr_fitter_destroy(f);
+        return rc;
+    }
+    *f_out = f;
+    return GINGR_OK;
+}
+
+extern "C" {
+
 int gingr_model_instance(gingr_ctx *ctx, const gingr_model *model, const double *alpha, const double euler[3],
                          const double center[3], const double translation[3], double scale, double *out_xyz) {
     if (!ctx || !model || !alpha || !euler || !center || !translation || !out_xyz) return GINGR_ERR_BAD_ARGUMENT;
@@ -332,37 +386,14 @@ int gingr_model_posterior_mean(gingr_ctx *ctx, const gingr_model *model, const d
     if (model->M != model->M_total)
         return gingr_set_error(ctx, GINGR_ERR_STATE, "model_posterior_mean: single-shard models only");
     gingr_fitter *f = nullptr;
-    GINGR_TRY(gingr_fitter_create(ctx, model, &f));
+    DevBuf G, aos;
+    GINGR_TRY(model_observation_system(ctx, model, euler, center, translation, obs_xyz, weight, n_lm, lm_pid, lm_xyz, lm_cov, &f, G));
     const int64_t M = model->M;
     const int32_t r = model->r, rp = model->rp;
     int rc = GINGR_OK;
-    std::vector<double> zero((size_t)r, 0.0);
-    gingr_state_scalars s;
-    fill_scalars(&s, euler, center, translation, 1.0);
-    rc = gingr_fitter_set_state(f, zero.data(), &s);
-    if (!rc) rc = gingr_fitter_set_landmarks(f, n_lm, lm_pid, lm_xyz, lm_cov);
-    DevBuf aos, obs, win, G, gws;
-    if (!rc && (aos.alloc((size_t)3 * M * sizeof(double)) != hipSuccess || obs.alloc((size_t)3 * M * sizeof(double)) != hipSuccess ||
-                win.alloc((size_t)M * sizeof(double)) != hipSuccess ||
-                G.alloc(((size_t)rp * rp + rp) * sizeof(double)) != hipSuccess ||
-                gws.alloc((size_t)gram_ws_doubles(M, rp) * sizeof(double)) != hipSuccess))
-        rc = gingr_set_error(ctx, GINGR_ERR_HIP, "out of memory");
+    if (aos.alloc((size_t)3 * M * sizeof(double)) != hipSuccess) rc = gingr_set_error(ctx, GINGR_ERR_HIP, "out of memory");
     if (!rc) {
-        std::vector<double> wo((size_t)M), wh((size_t)M);
-        for (int64_t i = 0; i < M; ++i) wo[(size_t)i] = weight[i];
-        for (int32_t l = 0; l < n_lm; ++l) wo[(size_t)lm_pid[l]] = 0.0;  // landmark pids carry weight 0
-        for (int64_t sidx = 0; sidx < M; ++sidx) wh[(size_t)sidx] = wo[(size_t)model->hperm[(size_t)sidx]];  // device order
-        (void)hipMemcpyAsync(aos.p, obs_xyz, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        launch_aos_to_soa(ctx, aos.as<double>(), M, obs.as<double>(), model->perm);
-        (void)hipMemcpyAsync(win.p, wh.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        launch_obs_points(ctx, model, f->st, obs.as<double>(), win.as<double>(), f->weight, f->evec);
         double *Gd = G.as<double>(), *rhs = Gd + (int64_t)rp * rp;
-        launch_gram(ctx, model->Q0, M, rp, f->weight, gws.as<double>(), Gd);
-        SweepArgs a = base_args(f);
-        a.evec = f->evec;
-        a.out = rhs;
-        launch_sweep(ctx, SWEEP_RHS, a);
-        launch_landmarks(ctx, model, f->st, f->n_lm, f->lm_pid, f->lm_xyz, f->lm_cov, Gd, rhs);
         launch_posterior_solve(ctx, r, rp, Gd, rhs, nullptr, f->work, f->acoef, f->st);
         SweepArgs b = base_args(f);
         b.coef0 = f->acoef;

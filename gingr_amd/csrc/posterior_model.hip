@@ -1,0 +1,284 @@
+// The posterior of a low-rank model as a model of its own (C ABI in include/gingr_hip.h): model.transform(rigid).posterior(obs) of
+// scalismo (DiscreteLowRankGaussianProcess.regression; G/api/GingrAlgorithm.scala:281-302) with the basis staying on the device.
+//   W = L^-T, L L^T = I + G        (launch_posterior_factor; G, rhs: Gram matrix and right-hand side of the observations)
+//   H = W^T diag(lambda) W = V diag(lambda_p) V^T        (r x r; the eigenvalues of scalismo's D Minv D, which is (D W)(D W)^T)
+//   T = W V,   Q0_new = R (Q0 T) = U_p sqrt(lambda_p)    (one pass over the basis: basis_rotate_kernel)
+//   a = W W^T rhs,   mean_new = R (mean + Q0 a),   ref_new = R (ref - c) + c + t
+// No division by a prior variance anywhere: a model with lambda_k = 0 gives lambda_p = 0 for that direction.
+#include "fitter.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace {
+
+typedef double v4f64 __attribute__((ext_vector_type(4)));
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+struct Rot3 {
+    double R[9];  // row-major
+};
+
+constexpr int kRotWaves = 8;       // waves per workgroup, each with 16 vertices of its own (no LDS, no barrier); two per SIMD keep the
+                                   // 96 accumulator registers in VGPRs (marginal_cov_kernel, posterior_cov.hip)
+constexpr int kRotVerts = 16;      // vertices per wave = rows of one MFMA tile
+constexpr int kRotChunkTiles = 4;  // column tiles of the result a wave holds (3 x 4 accumulator tiles = 96 registers)
+
+// The column chunk [n0, n0 + 16 NT) of R (Q0_rows T) for the wave's 16 vertices, stored.  Tile layout of cov_chunk (posterior_cov.hip):
+//   D(16x16) += A(16x4) B(4x16): lane l supplies A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; D: lane holds column
+//   j = l & 15 of the rows i = (l >> 4) + 4 reg.
+// Row tile d holds coordinate d of the 16 vertices (A row i = source basis row 3 src(v0 + i) + d), so the three coordinates of a vertex
+// sit in the same lane and register of the three tiles: the rotation is three FMAs per output, no exchange.  The 16 k of a step are
+// dealt to the four MFMAs as k0 + 4 (l >> 4) + t: a lane's four A values are 32 contiguous bytes (one load), B follows the same
+// permutation of k.
+// Stores: for one register g and tile (d, j) the 16 lanes of a row of lanes write 128 contiguous, 128-byte aligned bytes of result
+// row 3 (v0 + kq + 4 g) + d (rp is a multiple of 16), the four rows of lanes four such rows: every store instruction fills whole
+// cache lines, and the NT tiles of a chunk complete 128 NT contiguous bytes of each row.
+template <int NT>
+__device__ __forceinline__ void rotate_chunk(const double *__restrict__ qrow, int rp, const double *__restrict__ T, int n0, int kq, int cl,
+                                             const Rot3 &rot, double *__restrict__ out, int64_t vleft) {
+    v4f64 acc[3][NT];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[d][j] = v4f64{0, 0, 0, 0};
+    const double *tcol = T + (int64_t)(4 * kq) * rp + n0 + cl;
+    for (int k0 = 0; k0 < rp; k0 += 16) {
+        d4 a[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) a[d] = *reinterpret_cast<const d4 *>(qrow + (int64_t)d * rp + k0 + 4 * kq);
+        double b[4][NT];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) b[t][j] = tcol[(int64_t)(k0 + t) * rp + 16 * j];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) acc[d][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[d][t], b[t][j], acc[d][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int i = kq + 4 * g;  // vertex of the wave this register belongs to
+        if (i >= vleft) continue;
+        double *orow = out + (int64_t)3 * i * rp + n0 + cl;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const double x = acc[0][j][g], y = acc[1][j][g], z = acc[2][j][g];
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+                orow[(int64_t)d * rp + 16 * j] = __builtin_fma(rot.R[3 * d], x, __builtin_fma(rot.R[3 * d + 1], y, rot.R[3 * d + 2] * z));
+        }
+    }
+}
+
+// Qn[3 s + d][:] = sum_e R[d][e] (Qs[3 src(s) + e][:] T) for the device rows s < M of the new model, src(s) = iperm_src[perm_new[s]]: the
+// source row of the vertex the new model keeps at row s (both models order their rows by the Morton code of their own ref + mean).
+// Workgroup b takes the 16 kRotWaves vertices b / nchunks and the column chunk b % nchunks: the workgroups that share basis rows are
+// neighbours in dispatch order.  Qs has kBasisRowSlack zero rows behind row 3 M: the lanes of vertices past the last one read those.
+// T: [rp][rp], zero beyond the rank, so the columns r .. rp - 1 of Qn come out as sums of zeros.  Rows 3 M and beyond are not written.
+__global__ __launch_bounds__(64 * kRotWaves) void basis_rotate_kernel(const double *__restrict__ Qs, int64_t M, int rp, const double *__restrict__ T,
+                                                                      Rot3 rot, const int32_t *__restrict__ perm_new,
+                                                                      const int32_t *__restrict__ iperm_src, int nchunks, double *__restrict__ Qn) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kq = lane >> 4, cl = lane & 15;
+    const int64_t vb = blockIdx.x / nchunks;
+    const int chunk = (int)(blockIdx.x - vb * nchunks);
+    const int64_t v0 = (vb * kRotWaves + wave) * kRotVerts;
+    if (v0 >= M) return;
+    const int64_t v = v0 + cl;
+    const int64_t srow = v < M ? (int64_t)iperm_src[perm_new[v]] : M;
+    const double *qrow = Qs + 3 * srow * (int64_t)rp;
+    double *out = Qn + 3 * v0 * (int64_t)rp;
+    const int nt = rp / 16, t0 = chunk * kRotChunkTiles;
+    switch (min(nt - t0, kRotChunkTiles)) {
+        case 1: rotate_chunk<1>(qrow, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
+        case 2: rotate_chunk<2>(qrow, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
+        case 3: rotate_chunk<3>(qrow, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
+        case 4: rotate_chunk<4>(qrow, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
+        default: break;
+    }
+}
+
+// ---- the r x r step.  W is upper triangular (row stride ldw): only k <= min(i, j) contributes to H, only k >= i to a row of W V.
+// H[i][j] = sum_k W[k][i] lambda_k W[k][j], row stride ldh; the product of the two factor entries first: H[i][j] and H[j][i] are the
+// same float
+__global__ __launch_bounds__(256) void factor_gram_kernel(int r, const double *__restrict__ W, int64_t ldw, const double *__restrict__ lam,
+                                                          double *__restrict__ H, int ldh) {
+    const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (i >= r || j >= r) return;
+    double acc = 0.0;
+    for (int k = 0; k <= min(i, j); ++k) acc = __builtin_fma(W[k * ldw + i] * W[k * ldw + j], lam[k], acc);
+    H[(int64_t)i * ldh + j] = acc;
+}
+
+// T [rp][rp] = W V (V[k * r + j]: component k of eigenvector j), zero beyond the rank
+__global__ __launch_bounds__(256) void factor_vectors_kernel(int r, int rp, const double *__restrict__ W, int64_t ldw, const double *__restrict__ V,
+                                                             double *__restrict__ T) {
+    const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (i >= rp || j >= rp) return;
+    double acc = 0.0;
+    if (i < r && j < r)
+        for (int k = i; k < r; ++k) acc = __builtin_fma(W[i * ldw + k], V[(int64_t)k * r + j], acc);
+    T[(int64_t)i * rp + j] = acc;
+}
+
+// a [rp] = W (W^T rhs) = (I + G)^-1 rhs, zero beyond the rank; one workgroup
+__global__ __launch_bounds__(512) void posterior_coeff_kernel(int r, int rp, const double *__restrict__ W, int64_t ldw, const double *__restrict__ rhs,
+                                                              double *__restrict__ a) {
+    __shared__ double y[512];
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < r) {  // y[k] = sum_{i <= k} W[i][k] rhs[i]: consecutive threads, consecutive columns
+        double acc = 0.0;
+        for (int i = 0; i <= tid; ++i) acc = __builtin_fma(W[i * ldw + tid], rhs[i], acc);
+        y[tid] = acc;
+    }
+    __syncthreads();
+    for (int i = tid >> 6; i < rp; i += 8) {  // a[i] = sum_{k >= i} W[i][k] y[k]: a wave per row
+        double acc = 0.0;
+        if (i < r)
+            for (int k = i + lane; k < r; k += 64) acc = __builtin_fma(W[i * ldw + k], y[k], acc);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        if (lane == 0) a[i] = acc;
+    }
+}
+
+void launch_basis_rotate(gingr_ctx *ctx, const gingr_model *src, const double *T, const Rot3 &rot, gingr_model *dst) {
+    const int nchunks = (int)ceil_div(dst->rp / 16, kRotChunkTiles);
+    const int64_t blocks = ceil_div(dst->M, (int64_t)kRotWaves * kRotVerts) * nchunks;
+    TimerScope ts(ctx, 10);
+    hipLaunchKernelGGL(basis_rotate_kernel, dim3((unsigned)blocks), dim3(64 * kRotWaves), 0, ctx->stream, src->Q0, dst->M, (int)dst->rp, T, rot,
+                       dst->perm, src->iperm, nchunks, dst->Q0);
+}
+
+}  // namespace
+
+// the new model from G and rhs of the observations; f: a fitter on the source model whose state holds the rigid transform
+static int posterior_model_build(gingr_fitter *f, const double *G, const double *rhs, const char *who, gingr_model **out) {
+    gingr_ctx *ctx = f->ctx;
+    const gingr_model *m = f->m;
+    const int64_t M = m->M;
+    const int32_t r = m->r, rp = m->rp;
+    const dim3 tiles((unsigned)(rp / 16), (unsigned)(rp / 16));
+    HIP_TRY(ctx, ensure(f->cov_work, (size_t)posterior_factor_work_doubles(rp) * sizeof(double)));
+    DevBuf small, H, V, T, shape, aos;  // small: lambda [rp], a [rp], lambda_p [rp]
+    HIP_TRY(ctx, small.alloc((size_t)3 * rp * sizeof(double)));
+    HIP_TRY(ctx, H.alloc((size_t)rp * rp * sizeof(double)));
+    HIP_TRY(ctx, V.alloc((size_t)r * r * sizeof(double)));
+    HIP_TRY(ctx, T.alloc((size_t)rp * rp * sizeof(double)));
+    HIP_TRY(ctx, shape.alloc((size_t)3 * M * sizeof(double)));
+    HIP_TRY(ctx, aos.alloc((size_t)3 * M * sizeof(double)));
+    double *lam = small.as<double>(), *a = lam + rp, *lam_p = a + rp;
+    int64_t ldw = 0;
+    int32_t *flag = nullptr;
+    const double *W = launch_posterior_factor(ctx, r, rp, G, f->cov_work.as<double>(), &ldw, &flag);
+    // the posterior mean mesh R (ref + mean + Q0 a - c) + c + t in the caller's point order, with the state's rigid transform
+    hipLaunchKernelGGL(posterior_coeff_kernel, dim3(1), dim3(512), 0, ctx->stream, (int)r, (int)rp, W, ldw, rhs, a);
+    SweepArgs sa = base_args(f);
+    sa.coef0 = a;
+    sa.shape_out = shape.as<double>();
+    launch_sweep(ctx, SWEEP_POSED, sa);
+    launch_soa_to_aos(ctx, shape.as<double>(), M, aos.as<double>(), m->perm);
+    GINGR_TRY(check_launch(ctx));
+    std::vector<double> mesh((size_t)3 * M), href((size_t)3 * M), hmean((size_t)3 * M), lam_h((size_t)r);
+    DevState hst;
+    int32_t bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&hst, f->st, sizeof(hst), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(mesh.data(), aos.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad != 0) return gingr_set_error(ctx, GINGR_ERR_NOT_SPD, "%s: I + G of the observations is not positive definite", who);
+    for (int64_t i = 0; i < 3 * M; ++i)
+        if (!std::isfinite(mesh[(size_t)i])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite posterior mean", who);
+    // H = W^T diag(lambda) W = V diag(lambda_p) V^T (descending), T = W V
+    HIP_TRY(ctx, hipMemcpyAsync(lam, m->variance.data(), (size_t)r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(factor_gram_kernel, tiles, dim3(256), 0, ctx->stream, (int)r, W, ldw, lam, H.as<double>(), (int)rp);
+    GINGR_TRY(check_launch(ctx));
+    GINGR_TRY(launch_jacobi_eig_blocks(ctx, H.as<double>(), rp, r, lam_p, V.as<double>()));
+    hipLaunchKernelGGL(factor_vectors_kernel, tiles, dim3(256), 0, ctx->stream, (int)r, (int)rp, W, ldw, V.as<double>(), T.as<double>());
+    GINGR_TRY(check_launch(ctx));
+    HIP_TRY(ctx, hipMemcpyAsync(lam_h.data(), lam_p, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int32_t k = 0; k < r; ++k) {
+        if (!std::isfinite(lam_h[(size_t)k])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite posterior variance", who);
+        lam_h[(size_t)k] = std::max(lam_h[(size_t)k], 0.0);  // (a direction the prior does not have: rounding around zero)
+    }
+    // reference and mean displacement of the new model (host: they fix its row order)
+    GINGR_TRY(gingr_model_download(ctx, m, href.data(), nullptr, nullptr, nullptr));
+    for (int64_t i = 0; i < M; ++i) {
+        const double p[3] = {href[(size_t)3 * i] - hst.center[0], href[(size_t)3 * i + 1] - hst.center[1], href[(size_t)3 * i + 2] - hst.center[2]};
+        for (int d = 0; d < 3; ++d) {
+            const double x = (hst.R[3 * d] * p[0] + hst.R[3 * d + 1] * p[1]) + hst.R[3 * d + 2] * p[2] + hst.center[d] + hst.t[d];
+            href[(size_t)3 * i + d] = x;
+            hmean[(size_t)3 * i + d] = mesh[(size_t)3 * i + d] - x;
+        }
+    }
+    Rot3 rot;
+    for (int q = 0; q < 9; ++q) rot.R[q] = hst.R[q];
+    auto fill = [&](gingr_model *nm) -> int {
+        launch_basis_rotate(ctx, m, T.as<double>(), rot, nm);
+        return check_launch(ctx);
+    };
+    return model_create_impl(ctx, M, r, href.data(), hmean.data(), lam_h.data(), 0, M, fill, out);
+}
+
+// posterior model of the fitter's current state: built like posterior_covariance (posterior_cov.hip) -- phases 0 and 1 of the state
+// (they do not touch it; landmarks are in G already), then the common part
+static int fitter_posterior_model(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, gingr_model **out) {
+    GINGR_TRY(check_ready(f));
+    gingr_ctx *ctx = f->ctx;
+    const gingr_model *m = f->m;
+    if (m->M != m->M_total || f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "posterior_model: single shard only");
+    f->allow_alt = true;
+    int prc = GINGR_OK;
+    for (int ph = 0; ph < 2 && prc == GINGR_OK; ++ph) prc = fitter_run_phase(f, flavour, cp, ip, ph);
+    f->allow_alt = false;
+    GINGR_TRY(prc);
+    const double *G = f->seg1_live();
+    return posterior_model_build(f, G, G + (int64_t)m->rp * m->rp, "posterior_model", out);
+}
+
+extern "C" {
+
+int gingr_model_posterior(gingr_ctx *ctx, const gingr_model *model, const double euler[3], const double center[3], const double translation[3],
+                          const double *obs_xyz, const double *weight, int32_t n_lm, const int32_t *lm_pid, const double *lm_xyz,
+                          const double *lm_cov, gingr_model **out) {
+    if (!ctx || !out) return GINGR_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    if (!model || !euler || !center || !translation || !obs_xyz || !weight)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_posterior: null argument");
+    if (model->M != model->M_total) return gingr_set_error(ctx, GINGR_ERR_STATE, "model_posterior: single shard only");
+    gingr_fitter *f = nullptr;
+    DevBuf sys;
+    GINGR_TRY(model_observation_system(ctx, model, euler, center, translation, obs_xyz, weight, n_lm, lm_pid, lm_xyz, lm_cov, &f, sys));
+    const double *G = sys.as<double>();
+    const int rc = posterior_model_build(f, G, G + (int64_t)model->rp * model->rp, "model_posterior", out);
+    gingr_fitter_destroy(f);
+    return rc;
+}
+
+int gingr_fitter_posterior_model_cpd(gingr_fitter *f, const gingr_cpd_params *p, gingr_model **out) {
+    if (!f || !out) return GINGR_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    if (!p || !(p->w >= 0.0 && p->w < 1.0) || !(p->lambda > 0.0))
+        return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "cpd params: need 0 <= w < 1 and lambda > 0");
+    return fitter_posterior_model(f, 0, p, nullptr, out);
+}
+
+int gingr_fitter_posterior_model_icp(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out) {
+    if (!f || !out) return GINGR_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
+    return fitter_posterior_model(f, 1, nullptr, p, out);
+}
+
+int gingr_fitter_posterior_model_icp_surface(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out) {
+    if (!f || !out) return GINGR_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
+    return fitter_posterior_model(f, 2, nullptr, p, out);
+}
+
+}  // extern "C"

@@ -423,6 +423,24 @@ int gingr_fitter_posterior_covariance_cpd(gingr_fitter *f, const gingr_cpd_param
 int gingr_fitter_posterior_covariance_icp(gingr_fitter *f, const gingr_icp_params *p, double *cov6_out);
 int gingr_fitter_posterior_covariance_icp_surface(gingr_fitter *f, const gingr_icp_params *p, double *cov6_out);
 
+/* ---- the posterior as a model ------------------------------------------------------------------------------------------
+ * model.transform(rigid).posterior(obs) as a PointDistributionModel of its own (G/api/GingrAlgorithm.scala:281-302, computePosterior;
+ * scalismo DiscreteLowRankGaussianProcess.regression: U_p = U innerU, lambda_p = innerD2 of SVD(D Minv D)): a new, finalized,
+ * independent model of the same rank on the same context -- reference R (ref - c) + c + t, mean displacement R (mean + Q0 a), basis
+ * U_p sqrt(lambda_p) = R (Q0 L^-T V) with L L^T = I + G and L^-1 diag(lambda) L^-T = V diag(lambda_p) V^T, lambda_p descending.  The
+ * basis never leaves the device (one pass over it); reference and mean pass through the host once, they fix the new row order.  No
+ * scale.  The observation arguments of gingr_model_posterior mean exactly what they mean in gingr_model_posterior_mean.  Single
+ * shard only (GINGR_ERR_STATE otherwise); synchronises; a failed factorisation gives GINGR_ERR_NOT_SPD, a non-finite mean or
+ * variance GINGR_ERR_NONFINITE, and *out is NULL then. */
+int gingr_model_posterior(gingr_ctx *ctx, const gingr_model *model, const double euler[3], const double center[3],
+                          const double translation[3], const double *obs_xyz, const double *weight, int32_t n_lm,
+                          const int32_t *lm_pid, const double *lm_xyz, const double *lm_cov, gingr_model **out);
+/* The same for the posterior of the fitter's CURRENT state (what computePosterior returns for it): correspondences and Gram matrix
+ * as gingr_fitter_posterior_covariance_* builds them.  State, retry counter and posterior memo are left as that query leaves them. */
+int gingr_fitter_posterior_model_cpd(gingr_fitter *f, const gingr_cpd_params *p, gingr_model **out);
+int gingr_fitter_posterior_model_icp(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out);
+int gingr_fitter_posterior_model_icp_surface(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out);
+
 /* The retry counter of the probabilistic proposal (G/api/GingrAlgorithm.scala:69-70,196-202,210: `retryCounter`, a private var
  * of the algorithm INSTANCE): a sampled proposal whose posterior cannot be computed returns the state unchanged up to 10 times in
  * a row before the state is marked ModelFlexibilityError; every successful posterior gives one retry back (at most 10).  The
@@ -643,7 +661,7 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * which: 0 = cpd_colsum, 1 = cpd_rowstats, 2 = gram, 3 = whole update, 4 = basis sweep (one streaming pass over Q0),
  * 5 = posterior solve (unfused tail only), 6 / 7 = the device group's exchange of segment 0 / 1 on this shard (from the record of
  * the shard's own event to the end of its sum kernel: includes the wait for the slowest peer; the host-driven sharded update records its two collectives there too), 8 = the
- * nearest-neighbour scan kernel alone, 9 = the per-vertex covariance pass over the basis alone.  Returns accumulated ms and launches since
+ * nearest-neighbour scan kernel alone, 9 = the per-vertex covariance pass over the basis alone, 10 = the basis pass of the posterior model (basis_rotate_kernel) alone.  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
