@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""From registrations to the next prior (needs an MI355X):    PYTHONPATH=. python examples/demo_pca_model.py
+
+The femur GPMM is registered (CPD) to a handful of perturbed femurs -- samples of the model itself, moved rigidly, with noise.  The
+fits are point for point on the reference's vertices, so they go straight into PointDistributionModel.createUsingPCA with
+generalised Procrustes alignment (DataCollection.gpa + createUsingPCA of scalismo, on the device).  The PCA model is saved as a
+statismo .h5.json file and is then the prior of one more CPD registration."""
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: F401,E402  (first: one HIP runtime per process)
+import gingr_amd as ga  # noqa: E402
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+d = np.load(os.path.join(HERE, "..", "tests", "golden", "inputs.npz"))
+m = np.load(os.path.join(HERE, "..", "tests", "golden", "femur_mesh.npz"))
+ref, target = d["femur"].astype(np.float64), d["femur_target"].astype(np.float64)
+cells = m["femur_cells"]
+
+ctx = ga.Context(0)
+gpmm = ga.GPMMTriangleMesh3D(ctx, ref, relativeTolerance=0.01, cells=cells).Gaussian(sigma=70.0, scaling=50.0)
+rng = np.random.default_rng(1)
+cfg = ga.CpdConfiguration(maxIterations=60, w=0.0, threshold=1e-10)
+
+
+def mean_distance(fit, to):
+    return float(np.sqrt(ctx.nn(fit, to)[1]).mean())
+
+
+fits = []
+for i in range(8):
+    angle = rng.normal(0, 0.05, 3)
+    sample = gpmm.device().instance(rng.normal(0, 0.7, gpmm.rank), euler=angle, center=ref.mean(axis=0), translation=rng.normal(0, 3, 3))
+    sample = sample + rng.normal(0, 0.2, sample.shape)
+    cpd = ga.CpdRegistration(ctx)
+    best = cpd.run(cpd.createInitialState(gpmm, sample, cfg, transform=ga.GlobalTranformationType.RigidTransforms))
+    cpd.close()
+    fits.append(best.general.fit)
+    print(f"registration {i}: {best.general.iteration} iterations, mean vertex distance {mean_distance(best.general.fit, sample):.3f} mm")
+
+t0 = time.perf_counter()
+pca = ga.PointDistributionModel.createUsingPCA(ctx, ref, np.stack(fits), alignment="gpa", cells=cells)
+info = pca.pcaInfo
+print(f"PCA model of {len(fits)} registrations: rank {info.rank}, {info.gpa_sweeps} Procrustes sweeps (last change {info.gpa_last_change:.2e} mm), "
+      f"variance kept {info.kept_variance:.1f} of {info.total_variance:.1f} mm^2, built in {1e3 * (time.perf_counter() - t0):.1f} ms")
+
+host = pca.to_host()
+host.cells = cells
+path = os.path.join(tempfile.gettempdir(), "femur_pca.h5.json")
+ga.io.write_statistical_mesh_model(host, path, dtype="float64")
+print(f"wrote {path} (statismo model, {os.path.getsize(path) / 1e6:.1f} MB)")
+
+for name, prior in (("kernel GPMM", gpmm), ("PCA model  ", pca)):
+    cpd = ga.CpdRegistration(ctx)
+    best = cpd.run(cpd.createInitialState(prior, target, cfg, transform=ga.GlobalTranformationType.RigidTransforms))
+    print(f"CPD of the femur pair from the {name} (rank {prior.rank}): {best.general.iteration} iterations, "
+          f"mean vertex distance {mean_distance(best.general.fit, target):.3f} mm")
+    cpd.close()
+pca.device().close()

@@ -9,7 +9,7 @@ from .api import (  # noqa: F401
     FittingStatuses, GeneralRegistrationState, GingrAlgorithm, GlobalTranformationType, IcpConfiguration,
     IcpRegistration, IcpRegistrationState, LandmarkCorrespondences, ModelFittingParameters, PointDistributionModel,
     DevicePointDistributionModel, GaussianKernelParameters, GPMMTriangleMesh3D, PointSetHelper, automaticGPMMfromTemplate,
-    GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel,
+    GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo,
 )
 from ._native import GingrNativeError  # noqa: F401
 from .group import DeviceGroup  # noqa: F401  (in-library multi-GPU group: gingr_group_*)

@@ -93,6 +93,12 @@ class GpmmInfo(ctypes.Structure):
                 ("kept_variance_fraction", c_double)]
 
 
+class PcaInfo(ctypes.Structure):
+    """gingr_pca_info"""
+    _fields_ = [("rank", c_int32), ("gpa_sweeps", c_int32), ("gpa_last_change", c_double), ("total_variance", c_double),
+                ("kept_variance", c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/gingr_hip.h declares
 SIGNATURES = {
     "gingr_device_count": (c_int, []),
@@ -181,6 +187,8 @@ SIGNATURES = {
     "gingr_fitter_posterior_model_cpd": (c_int, [c_void_p, POINTER(CpdParams), POINTER(c_void_p)]),
     "gingr_fitter_posterior_model_icp": (c_int, [c_void_p, POINTER(IcpParams), POINTER(c_void_p)]),
     "gingr_fitter_posterior_model_icp_surface": (c_int, [c_void_p, POINTER(IcpParams), POINTER(c_void_p)]),
+    "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
+                                        POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_fitter_retry_counter": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
     "gingr_fitter_exchange": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
     "gingr_fitter_cpd_phase_async": (c_int, [c_void_p, POINTER(CpdParams), c_int32]),

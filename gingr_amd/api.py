@@ -235,6 +235,28 @@ class PointDistributionModel:
                                       variance=np.array(np.asarray(self.variance)[:k], dtype=np.float64),
                                       cells=None if self.cells is None else np.array(self.cells))
 
+    @staticmethod
+    def createUsingPCA(ctx: "Context", reference, shapes, alignment: str = "none", relativeTolerance: float = 1e-10, maxRank: int = 0,
+                       cells=None, gpaMaxIterations: int = 3, gpaTolerance: float = 1e-5) -> "PcaDevicePointDistributionModel":
+        """DataCollection.gpa(...) + PointDistributionModel.createUsingPCA(...) on the device (gingr_model_from_shapes): the PCA model
+        of `shapes` (n x M x 3, point for point on `reference`'s vertices, 2 <= n <= 512), resident in HBM.  alignment: "none",
+        "rigid" (every shape onto the reference, Kabsch) or "gpa" (generalised Procrustes; the model's reference is then the final
+        Procrustes target).  The leading components with variance > relativeTolerance * the largest are kept, at most maxRank
+        (0: no limit besides n - 1 and 512).  relativeTolerance = 1e-10 is this package's default; scalismo's own cutoff constant
+        is not pinned by anything in reach."""
+        return PcaDevicePointDistributionModel(ctx, reference, shapes, alignment, relativeTolerance, maxRank, cells, gpaMaxIterations,
+                                               gpaTolerance)
+
+
+@dataclasses.dataclass(frozen=True)
+class PcaInfo:
+    """gingr_pca_info: what the build behind PointDistributionModel.createUsingPCA did."""
+    rank: int                # rank of the model
+    gpa_sweeps: int          # Procrustes sweeps run (0 unless alignment = "gpa")
+    gpa_last_change: float   # RMS distance per point between the last two Procrustes targets
+    total_variance: float    # sum of all eigenvalues of the sample covariance
+    kept_variance: float     # sum of the kept ones
+
 
 @dataclasses.dataclass(frozen=True)
 class GpmmBuildInfo:
@@ -477,6 +499,50 @@ class PosteriorDevicePointDistributionModel(DevicePointDistributionModel):
 
     def _build(self, ctx: Context, row_begin: int, row_end: int):
         raise ValueError("a posterior model lives whole on the context of its source; download it (to_host) for anything else")
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self.to_host(basis=False).mean
+
+
+class PcaDevicePointDistributionModel(DevicePointDistributionModel):
+    """PointDistributionModel.createUsingPCA: the PCA model of shapes in correspondence, built in HBM (gingr_model_from_shapes) and
+    adopted like a posterior model.  `pcaInfo` carries gingr_pca_info; reference (the Procrustes target for alignment = "gpa") and
+    mean are read back once, basis and variance only if somebody asks."""
+
+    ALIGNMENTS = {"none": 0, "rigid": 1, "gpa": 2}
+
+    def __init__(self, ctx: Context, reference, shapes, alignment="none", relativeTolerance: float = 1e-10, maxRank: int = 0, cells=None,
+                 gpaMaxIterations: int = 3, gpaTolerance: float = 1e-5):
+        if alignment not in self.ALIGNMENTS:
+            raise ValueError(f"alignment must be one of {sorted(self.ALIGNMENTS)}, not {alignment!r}")
+        ref = f64(reference).reshape(-1, 3)
+        X = f64(shapes)
+        M = ref.shape[0]
+        if X.ndim == 2 and X.shape[1] == 3 * M:
+            X = X.reshape(X.shape[0], M, 3)
+        if X.ndim != 3 or X.shape[1:] != (M, 3):
+            raise ValueError(f"shapes must be (n, {M}, 3): every shape point for point on the reference")
+        self.ctx = ctx
+        self.cells = cells
+        self._kernels, self._host, self._info = None, None, None
+        self._to_tolerance, self._keep = False, 0
+        h, info = c_void_p(), nat.PcaInfo()
+        _check(ctx.handle, ctx._lib.gingr_model_from_shapes(ctx.handle, M, int(X.shape[0]), dptr(ref), dptr(X), self.ALIGNMENTS[alignment],
+                                                            int(gpaMaxIterations), float(gpaTolerance), float(relativeTolerance), int(maxRank),
+                                                            ctypes.byref(h), ctypes.byref(info)), "gingr_model_from_shapes")
+        self.pcaInfo = PcaInfo(int(info.rank), int(info.gpa_sweeps), float(info.gpa_last_change), float(info.total_variance),
+                               float(info.kept_variance))
+        self._full = DeviceModel._adopt(ctx, h, self, M)
+        try:
+            self._host = self._full.download(basis=False)
+        except Exception:
+            self._full.close()
+            raise
+        self.reference = self._host.reference
+
+    def _build(self, ctx: Context, row_begin: int, row_end: int):
+        raise ValueError("a PCA model lives whole on the context it was built on; download it (to_host) for anything else")
 
     @property
     def mean(self) -> np.ndarray:

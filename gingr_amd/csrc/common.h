@@ -86,9 +86,13 @@ struct DevBuf {
     ~DevBuf() {
         if (p) (void)hipFree(p);
     }
-    hipError_t alloc(size_t n) {
+    void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
+        bytes = 0;
+    }
+    hipError_t alloc(size_t n) {
+        release();
         bytes = n;
         const hipError_t e = hipMalloc(&p, n ? n : 8);
         static const bool poison = getenv("GINGR_DEBUG_POISON") != nullptr;  // (diagnostic: see dev_alloc, fitter.h)

@@ -269,11 +269,29 @@ void launch_mh_readback(gingr_ctx *ctx, int64_t n, const double *block, int nblo
 // the host's wait for that store into pin[pin_doubles - 1]; false: not seen within the deadline (the caller synchronises the stream)
 bool wait_pinned_flag(gingr_fitter *f, double epoch);
 int pull_small(gingr_fitter *f, const double *src, int n, double *dst);  // n <= 256 doubles from the device to `dst` inside f->pin
+// The state behind both, for a caller without a fitter (pca_model.hip): a pinned host buffer whose last word is the flag, the device's
+// view of it (nullptr: pull_small copies and synchronises), the read-back kernel's workgroup counter and the launch number.  A view --
+// it owns nothing; the fitter's two functions above go through these with a view of its own fields.
+struct PinnedWords {
+    double *pin = nullptr;
+    size_t pin_doubles = 0;
+    double *pin_dev = nullptr;
+    int32_t *done = nullptr;
+    uint64_t epoch = 0;
+};
+bool wait_pinned_flag(const PinnedWords &w, double epoch);
+int pull_small(gingr_ctx *ctx, PinnedWords &w, const double *src, int n, double *dst);  // `dst` inside w.pin
 // ---- model.hip: a short-lived fitter posed by (euler, center, translation) with zero shape coefficients, and the posterior system of
 // the stateless observations of gingr_model_posterior_mean: G [rp*rp] then rhs [rp] in `sys`.  The caller destroys the fitter.
 int model_observation_system(gingr_ctx *ctx, const gingr_model *model, const double euler[3], const double center[3],
                              const double translation[3], const double *obs_xyz, const double *weight, int32_t n_lm, const int32_t *lm_pid,
                              const double *lm_xyz, const double *lm_cov, gingr_fitter **f_out, DevBuf &sys);
+// ---- posterior_model.hip: dst->Q0 = R (src->Q0 T) on MFMA, one pass over the source basis; both models hold the same points (each in
+// its own row order), T: [src->rp][dst->rp] on the device, zero beyond the two ranks
+struct Rot3 {
+    double R[9];  // row-major
+};
+void launch_basis_rotate(gingr_ctx *ctx, const gingr_model *src, const double *T, const Rot3 &rot, gingr_model *dst);
 // ---- fitter_phases.hip
 int gather_fit(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, gingr_allreduce_fn reduce, void *user,
                fitter_gather_fn gather, const char *who);

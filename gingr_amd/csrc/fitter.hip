@@ -122,8 +122,8 @@ void scalars_of_state(const DevState &hst, gingr_state_scalars *s) {
 // The host side of mh_readback_kernel's flag: spin on the word, look at the clock every 1024 spins, give up 2 s after the call.  The
 // acquire fence orders the reads of the pinned buffer behind the flag.  Not seen = a launch that never finished or a buffer the host
 // does not see coherently: the caller's stream synchronisation reports the one and covers the other.
-bool wait_pinned_flag(gingr_fitter *f, double epoch) {
-    volatile double *flag = f->pin + f->pin_doubles - 1;
+bool wait_pinned_flag(const PinnedWords &w, double epoch) {
+    volatile double *flag = w.pin + w.pin_doubles - 1;
     const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(2);
     bool seen = false;
     for (unsigned spins = 0;; ++spins) {
@@ -140,21 +140,31 @@ bool wait_pinned_flag(gingr_fitter *f, double epoch) {
     return seen;
 }
 
-// n doubles from the device into the pinned buffer at `dst` (a pointer INTO f->pin) without a copy + stream synchronisation: one small
+static PinnedWords pinned_words_of(const gingr_fitter *f) { return PinnedWords{f->pin, f->pin_doubles, f->pin_dev, f->mh_done, f->mh_epoch}; }
+
+bool wait_pinned_flag(gingr_fitter *f, double epoch) { return wait_pinned_flag(pinned_words_of(f), epoch); }
+
+// n doubles from the device into the pinned buffer at `dst` (a pointer INTO w.pin) without a copy + stream synchronisation: one small
 // launch writes them through the buffer's device address and stores the launch number into the flag word, the host spins on it (see
 // mh_readback_kernel).  Everything enqueued before on the stream is complete when this returns.
-int pull_small(gingr_fitter *f, const double *src, int n, double *dst) {
-    gingr_ctx *ctx = f->ctx;
-    if (!f->pin_dev) {
+int pull_small(gingr_ctx *ctx, PinnedWords &w, const double *src, int n, double *dst) {
+    if (!w.pin_dev) {
         HIP_TRY(ctx, hipMemcpyAsync(dst, src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return GINGR_OK;
     }
-    const double epoch = (double)(++f->mh_epoch);
-    launch_mh_readback(ctx, n, src, n, nullptr, 0, nullptr, f->pin_dev + (dst - f->pin), f->pin_dev + f->pin_doubles - 1, f->mh_done, epoch);
+    const double epoch = (double)(++w.epoch);
+    launch_mh_readback(ctx, n, src, n, nullptr, 0, nullptr, w.pin_dev + (dst - w.pin), w.pin_dev + w.pin_doubles - 1, w.done, epoch);
     GINGR_TRY(check_launch(ctx));
-    if (!wait_pinned_flag(f, epoch)) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!wait_pinned_flag(w, epoch)) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GINGR_OK;
+}
+
+int pull_small(gingr_fitter *f, const double *src, int n, double *dst) {
+    PinnedWords w = pinned_words_of(f);
+    const int rc = pull_small(f->ctx, w, src, n, dst);
+    f->mh_epoch = w.epoch;
+    return rc;
 }
 
 extern "C" {

@@ -132,9 +132,11 @@ void launch_interp_pack(gingr_ctx *ctx, const double *Qs, int32_t rp, const int3
                         const int32_t *perm_new, int64_t row_begin, int64_t M, double *Q0);
 
 // model.hip: common part of model construction; fill_basis writes m->Q0 on ctx->stream (see gingr_model_upload)
+// finalize = false leaves a complete model with its moments but without Binv and what follows from it (pca_model.hip: the centred data
+// as a basis, kept only for its Gram matrix and one rotation)
 int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const double *ref, const double *mean,
                       const double *variance, int64_t row_begin, int64_t row_end,
-                      const std::function<int(gingr_model *)> &fill_basis, gingr_model **out);
+                      const std::function<int(gingr_model *)> &fill_basis, gingr_model **out, bool finalize = true);
 
 // fitter.hip hooks for the device group (group.hip): where phases 0 / 1 write this shard's partial exchange segments, and where
 // the gather step of a sharded surface update writes the shard's contribution to the full fit (nullptr: in place)

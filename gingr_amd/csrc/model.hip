@@ -69,7 +69,7 @@ int model_finalize_impl(gingr_ctx *ctx, gingr_model *m) {
 // m->Q0 ([3M][rp], device row order, zero padded) on ctx->stream.
 int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const double *ref, const double *mean,
                       const double *variance, int64_t row_begin, int64_t row_end,
-                      const std::function<int(gingr_model *)> &fill_basis, gingr_model **out) {
+                      const std::function<int(gingr_model *)> &fill_basis, gingr_model **out, bool finalize) {
     if (!ctx || !out) return GINGR_ERR_BAD_ARGUMENT;
     *out = nullptr;
     if (M_total < 1 || rank < 1 || rank > 512 || !ref || !mean || !variance)
@@ -185,7 +185,7 @@ int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const doubl
             for (int e = 0; e < 3; ++e) m->Pp[d * 3 + e] += pt[d] * pt[e];
         }
     }
-    if (row_begin == 0 && row_end == M_total) {
+    if (row_begin == 0 && row_end == M_total && finalize) {
         rc = model_finalize_impl(ctx, m);
         if (rc) return fail(rc);
     }

@@ -15,9 +15,7 @@ namespace {
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-struct Rot3 {
-    double R[9];  // row-major; read from `state` instead when that is given
-};
+// Rot3 (fitter.h): row-major; the kernels here read the rotation from `state` instead when that is given
 
 constexpr int kCovWaves = 8;      // waves per workgroup, each with 16 vertices of its own (no LDS, no barrier); two per SIMD keep the
                                   // 96 accumulator registers in VGPRs (four waves: the compiler moves them through AGPRs every step)

@@ -15,10 +15,6 @@ namespace {
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-struct Rot3 {
-    double R[9];  // row-major
-};
-
 constexpr int kRotWaves = 8;       // waves per workgroup, each with 16 vertices of its own (no LDS, no barrier); two per SIMD keep the
                                    // 96 accumulator registers in VGPRs (marginal_cov_kernel, posterior_cov.hip)
 constexpr int kRotVerts = 16;      // vertices per wave = rows of one MFMA tile
@@ -27,7 +23,7 @@ constexpr int kRotChunkTiles = 4;  // column tiles of the result a wave holds (3
 // The column chunk [n0, n0 + 16 NT) of R (Q0_rows T) for the wave's 16 vertices, stored.  Tile layout of cov_chunk (posterior_cov.hip):
 //   D(16x16) += A(16x4) B(4x16): lane l supplies A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; D: lane holds column
 //   j = l & 15 of the rows i = (l >> 4) + 4 reg.
-// Row tile d holds coordinate d of the 16 vertices (A row i = source basis row 3 src(v0 + i) + d), so the three coordinates of a vertex
+// Row tile d holds coordinate d of the 16 vertices (A row i = source basis row 3 src(v0 + i) + d, rs columns wide), so the three coordinates of a vertex
 // sit in the same lane and register of the three tiles: the rotation is three FMAs per output, no exchange.  The 16 k of a step are
 // dealt to the four MFMAs as k0 + 4 (l >> 4) + t: a lane's four A values are 32 contiguous bytes (one load), B follows the same
 // permutation of k.
@@ -35,7 +31,7 @@ constexpr int kRotChunkTiles = 4;  // column tiles of the result a wave holds (3
 // row 3 (v0 + kq + 4 g) + d (rp is a multiple of 16), the four rows of lanes four such rows: every store instruction fills whole
 // cache lines, and the NT tiles of a chunk complete 128 NT contiguous bytes of each row.
 template <int NT>
-__device__ __forceinline__ void rotate_chunk(const double *__restrict__ qrow, int rp, const double *__restrict__ T, int n0, int kq, int cl,
+__device__ __forceinline__ void rotate_chunk(const double *__restrict__ qrow, int rs, int rp, const double *__restrict__ T, int n0, int kq, int cl,
                                              const Rot3 &rot, double *__restrict__ out, int64_t vleft) {
     v4f64 acc[3][NT];
 #pragma unroll
@@ -43,10 +39,10 @@ __device__ __forceinline__ void rotate_chunk(const double *__restrict__ qrow, in
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[d][j] = v4f64{0, 0, 0, 0};
     const double *tcol = T + (int64_t)(4 * kq) * rp + n0 + cl;
-    for (int k0 = 0; k0 < rp; k0 += 16) {
+    for (int k0 = 0; k0 < rs; k0 += 16) {
         d4 a[3];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) a[d] = *reinterpret_cast<const d4 *>(qrow + (int64_t)d * rp + k0 + 4 * kq);
+        for (int d = 0; d < 3; ++d) a[d] = *reinterpret_cast<const d4 *>(qrow + (int64_t)d * rs + k0 + 4 * kq);
         double b[4][NT];
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -78,8 +74,10 @@ __device__ __forceinline__ void rotate_chunk(const double *__restrict__ qrow, in
 // source row of the vertex the new model keeps at row s (both models order their rows by the Morton code of their own ref + mean).
 // Workgroup b takes the 16 kRotWaves vertices b / nchunks and the column chunk b % nchunks: the workgroups that share basis rows are
 // neighbours in dispatch order.  Qs has kBasisRowSlack zero rows behind row 3 M: the lanes of vertices past the last one read those.
-// T: [rp][rp], zero beyond the rank, so the columns r .. rp - 1 of Qn come out as sums of zeros.  Rows 3 M and beyond are not written.
-__global__ __launch_bounds__(64 * kRotWaves) void basis_rotate_kernel(const double *__restrict__ Qs, int64_t M, int rp, const double *__restrict__ T,
+// T: [rs][rp] (rs: padded width of the source basis -- the posterior keeps it, rs == rp; a PCA model has fewer columns than the data
+// it comes from, pca_model.hip), zero beyond the ranks, so the columns r .. rp - 1 of Qn come out as sums of zeros.  Rows 3 M and
+// beyond are not written.
+__global__ __launch_bounds__(64 * kRotWaves) void basis_rotate_kernel(const double *__restrict__ Qs, int64_t M, int rs, int rp, const double *__restrict__ T,
                                                                       Rot3 rot, const int32_t *__restrict__ perm_new,
                                                                       const int32_t *__restrict__ iperm_src, int nchunks, double *__restrict__ Qn) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kq = lane >> 4, cl = lane & 15;
@@ -89,14 +87,14 @@ __global__ __launch_bounds__(64 * kRotWaves) void basis_rotate_kernel(const doub
     if (v0 >= M) return;
     const int64_t v = v0 + cl;
     const int64_t srow = v < M ? (int64_t)iperm_src[perm_new[v]] : M;
-    const double *qrow = Qs + 3 * srow * (int64_t)rp;
+    const double *qrow = Qs + 3 * srow * (int64_t)rs;
     double *out = Qn + 3 * v0 * (int64_t)rp;
     const int nt = rp / 16, t0 = chunk * kRotChunkTiles;
     switch (min(nt - t0, kRotChunkTiles)) {
-        case 1: rotate_chunk<1>(qrow, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
-        case 2: rotate_chunk<2>(qrow, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
-        case 3: rotate_chunk<3>(qrow, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
-        case 4: rotate_chunk<4>(qrow, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
+        case 1: rotate_chunk<1>(qrow, rs, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
+        case 2: rotate_chunk<2>(qrow, rs, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
+        case 3: rotate_chunk<3>(qrow, rs, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
+        case 4: rotate_chunk<4>(qrow, rs, rp, T, 16 * t0, kq, cl, rot, out, M - v0); break;
         default: break;
     }
 }
@@ -145,15 +143,15 @@ __global__ __launch_bounds__(512) void posterior_coeff_kernel(int r, int rp, con
     }
 }
 
+}  // namespace
+
 void launch_basis_rotate(gingr_ctx *ctx, const gingr_model *src, const double *T, const Rot3 &rot, gingr_model *dst) {
     const int nchunks = (int)ceil_div(dst->rp / 16, kRotChunkTiles);
     const int64_t blocks = ceil_div(dst->M, (int64_t)kRotWaves * kRotVerts) * nchunks;
     TimerScope ts(ctx, 10);
-    hipLaunchKernelGGL(basis_rotate_kernel, dim3((unsigned)blocks), dim3(64 * kRotWaves), 0, ctx->stream, src->Q0, dst->M, (int)dst->rp, T, rot,
-                       dst->perm, src->iperm, nchunks, dst->Q0);
+    hipLaunchKernelGGL(basis_rotate_kernel, dim3((unsigned)blocks), dim3(64 * kRotWaves), 0, ctx->stream, src->Q0, dst->M, (int)src->rp, (int)dst->rp, T,
+                       rot, dst->perm, src->iperm, nchunks, dst->Q0);
 }
-
-}  // namespace
 
 // the new model from G and rhs of the observations; f: a fitter on the source model whose state holds the rigid transform
 static int posterior_model_build(gingr_fitter *f, const double *G, const double *rhs, const char *who, gingr_model **out) {

@@ -227,3 +227,17 @@ __device__ inline bool polar3_rotation(const double A[9], double R[9], double *t
     *trace_RtA = tr;
     return true;
 }
+
+// The Kabsch rotation of a 3x3 cross-covariance S (target x^T): the rotation R that maximises trace(R^T S).  The polar factor where it
+// applies, otherwise U diag(1, 1, s3) V^T from the SVD with s3 = -1 when det S < 0 (the last singular vector flipped); *trace_ds is
+// trace(R^T S) = d1 + d2 + s3 d3, what a similarity transform's scale is made of.
+__device__ inline void kabsch3_rotation(const double S[9], double R[9], double *trace_ds) {
+    if (polar3_rotation(S, R, trace_ds)) return;
+    double U[9], D[3], V[9];
+    svd3(S, U, D, V);
+    const double det = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
+    const double s3 = det < 0 ? -1.0 : 1.0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) R[a * 3 + b] = U[a * 3] * V[b * 3] + U[a * 3 + 1] * V[b * 3 + 1] + s3 * U[a * 3 + 2] * V[b * 3 + 2];
+    *trace_ds = D[0] + D[1] + s3 * D[2];
+}

@@ -2,6 +2,7 @@
 log back into shapes, per-vertex variance maps of the sampled shapes, and the progress call-back.
 
   LogHelper.samplesFromLog / logSamples2shapes                      G/api/helper/LogHelper.scala:28-56
+  modelFromLog                                                       logSamples2shapes -> PointDistributionModel.createUsingPCA
   JSONStateLogger.loadLog / jsonFormatToModelFittingParameters / getBestStateFromLog   G/api/sampling/loggers/JSONStateLogger.scala:205-236
   PosteriorHelper.computeDistanceMapFromMeshesTotal / ...Normal      G/api/helper/PosteriorHelper.scala:26-80
   CallBackFunctions.SimpleLogger                                     G/api/helper/CallBackFunctions.scala:23-44
@@ -16,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import io as gio
-from .api import Context, DeviceModel, EulerAngles, ModelFittingParameters
+from .api import Context, DeviceModel, EulerAngles, ModelFittingParameters, PointDistributionModel
 from .sampling import RegistrationComparison, TriangleMesh3D
 
 
@@ -75,6 +76,20 @@ def logSamples2shapes(ctx: Context, model, log: Sequence[gio.JsonLogEntry]) -> L
         return shapes
     finally:
         dm.close()
+
+
+def modelFromLog(ctx: Context, model, log: Sequence[gio.JsonLogEntry], alignment: str = "none", relativeTolerance: float = 1e-10,
+                 maxRank: int = 0, cells=None, gpaMaxIterations: int = 3, gpaTolerance: float = 1e-5):
+    """The PCA model of a chain's shapes: logSamples2shapes, then PointDistributionModel.createUsingPCA on the device with the
+    model's reference -- the prior of the next round of registrations, without the shapes leaving the process as meshes.  The
+    shapes themselves still pass through host memory once (logSamples2shapes returns arrays, gingr_model_from_shapes takes host
+    pointers); what stays on the device is everything from the alignment to the finished model."""
+    shapes = logSamples2shapes(ctx, model, log)
+    if cells is None:
+        cells = getattr(model, "cells", None)
+    return PointDistributionModel.createUsingPCA(ctx, model.reference, np.stack(shapes), alignment=alignment,
+                                                 relativeTolerance=relativeTolerance, maxRank=maxRank, cells=cells,
+                                                 gpaMaxIterations=gpaMaxIterations, gpaTolerance=gpaTolerance)
 
 
 # ---------------------------------------------------------------------------------------------------------------- posterior maps

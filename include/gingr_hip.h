@@ -441,6 +441,33 @@ int gingr_fitter_posterior_model_cpd(gingr_fitter *f, const gingr_cpd_params *p,
 int gingr_fitter_posterior_model_icp(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out);
 int gingr_fitter_posterior_model_icp_surface(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out);
 
+/* ---- a PCA model from shapes in correspondence ----------------------------------------------------------------------------
+ * What DataCollection.gpa(...) followed by PointDistributionModel.createUsingPCA(...) gives a scalismo user, built on the device: a
+ * new, finalized, single-shard model on this context.  ref_xyz [3 M]: the reference; shapes_xyz [n_shapes][3 M]: the shapes, point
+ * for point on the reference's vertices, 2 <= n_shapes <= 512.
+ * alignment: 0 none; 1 every shape rigidly onto the reference (Kabsch: centroids, 3 x 3 cross-covariance, SVD, last singular vector
+ * flipped for a negative determinant, no scale); 2 generalised Procrustes -- from target = reference, sweeps of "align every shape to
+ * the target, target := mean of the aligned shapes", at most gpa_max_iterations of them (<= 0: 3), ended early when the RMS distance
+ * per point between successive targets falls below gpa_tolerance (1e-5 is the customary value).  The model's reference is the final
+ * target in mode 2 and ref_xyz otherwise.
+ * Model: mean displacement = mean shape - reference; with Xc = [X_i - mean] / sqrt(n - 1) and Xc^T Xc = V diag(lambda) V^T, the leading
+ * k components with lambda_j > relative_tolerance lambda_1 are kept, k <= min(n - 1, max_rank or 512): variance lambda[:k], basis
+ * U sqrt(lambda) = Xc V[:, :k].  relative_tolerance: 1e-10 is this library's customary value; the cutoff constant of scalismo's own
+ * createUsingPCA is not pinned by anything in reach.
+ * info (nullable) reports the rank, the Procrustes sweeps run and the last target change, and the total / kept variance (sums of
+ * eigenvalues).  Two calls with the same input give the same bits.  Synchronises.  GINGR_ERR_BAD_ARGUMENT: n_shapes outside 2..512,
+ * M < 1, alignment outside 0..2, all shapes identical (rank 0); GINGR_ERR_NONFINITE: non-finite input; *out is NULL then. */
+typedef struct {
+    int32_t rank;
+    int32_t gpa_sweeps;
+    double gpa_last_change;
+    double total_variance;
+    double kept_variance;
+} gingr_pca_info;
+int gingr_model_from_shapes(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const double *ref_xyz, const double *shapes_xyz,
+                            int32_t alignment, int32_t gpa_max_iterations, double gpa_tolerance, double relative_tolerance,
+                            int32_t max_rank, gingr_model **out, gingr_pca_info *info);
+
 /* The retry counter of the probabilistic proposal (G/api/GingrAlgorithm.scala:69-70,196-202,210: `retryCounter`, a private var
  * of the algorithm INSTANCE): a sampled proposal whose posterior cannot be computed returns the state unchanged up to 10 times in
  * a row before the state is marked ModelFlexibilityError; every successful posterior gives one retry back (at most 10).  The

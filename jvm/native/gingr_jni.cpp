@@ -325,6 +325,21 @@ JFN(jlong, modelNewReference)(JNIEnv *env, jclass, jlong ctx, jlong src, jdouble
         return 0;
     return reinterpret_cast<jlong>(m);
 }
+JFN(jlong, modelFromShapes)(JNIEnv *env, jclass, jlong ctx, jdoubleArray ref, jdoubleArray shapes, jint alignment, jint gpaMaxIterations,
+                             jdouble gpaTolerance, jdouble relTol, jint maxRank, jdoubleArray info5) {
+    Arr<double> a(env, ref, true); Arr<double> b(env, shapes, true); Arr<double> c(env, info5, false);
+    if (a.buf.empty() || a.buf.size() % 3 != 0 || b.buf.size() % a.buf.size() != 0) return 0;  // (x, y, z per point; whole shapes)
+    gingr_model *m = nullptr;
+    gingr_pca_info info;
+    if (gingr_model_from_shapes(P<gingr_ctx>(ctx), (int64_t)a.buf.size() / 3, (int32_t)(b.buf.size() / a.buf.size()), a.ptr(), b.ptr(), alignment,
+                                gpaMaxIterations, gpaTolerance, relTol, maxRank, &m, &info) != GINGR_OK)
+        return 0;
+    if (c.buf.size() >= 5) {
+        c.buf[0] = info.rank; c.buf[1] = info.gpa_sweeps; c.buf[2] = info.gpa_last_change; c.buf[3] = info.total_variance;
+        c.buf[4] = info.kept_variance;
+    }
+    return reinterpret_cast<jlong>(m);
+}
 JFN(jlong, rigidIcpCreate)(JNIEnv *env, jclass, jlong ctx, jint kind, jdoubleArray tpl, jdoubleArray target) {
     Arr<double> a(env, tpl, true); Arr<double> b(env, target, true);
     gingr_rigid_icp *h = nullptr;

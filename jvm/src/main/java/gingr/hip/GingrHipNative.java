@@ -100,6 +100,12 @@ public final class GingrHipNative {
      *  returns the model handle or 0 */
     public static native long modelNewReference(long ctx, long sourceModel, double[] newRefXyz, int[] vertexIds, double[] weights,
                                                 long rowBegin, long rowEnd);
+    /** gingr_model_from_shapes: DataCollection.gpa + PointDistributionModel.createUsingPCA on the device.  shapesXyz = n shapes of
+     *  refXyz.length values each, one after the other; alignment 0 none, 1 rigid to the reference, 2 generalised Procrustes;
+     *  info5 (nullable, length >= 5) receives { rank, gpa sweeps, last gpa change, total variance, kept variance };
+     *  returns the model handle or 0 */
+    public static native long modelFromShapes(long ctx, double[] refXyz, double[] shapesXyz, int alignment, int gpaMaxIterations,
+                                              double gpaTolerance, double relativeTolerance, int maxRank, double[] info5);
     // ---- classic rigid / similarity ICP (other/algorithms/icp/RigidICP.scala; kind 0 = RigidRegistrator3D, 1 = AffineRegistrator3D)
     public static native long rigidIcpCreate(long ctx, int kind, double[] templateXyz, double[] targetXyz);
     public static native void rigidIcpDestroy(long handle);
