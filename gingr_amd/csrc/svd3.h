@@ -110,10 +110,16 @@ __host__ __device__ inline void rot_to_euler_wave(const double R[9], double e[3]
 
 // one-sided Jacobi SVD of a 3x3 matrix: A = U diag(s) V^T, s descending.  Out of line: it is the rarely taken fallback of
 // polar3_rotation, and its dynamically indexed arrays would otherwise put the whole calling kernel on scratch memory.
-__device__ __attribute__((noinline)) inline void svd3(const double Ain[9], double U[9], double s[3], double V[9]) {
-    double A[9];
+__host__ __device__ __attribute__((noinline)) inline void svd3(const double Ain[9], double U[9], double s[3], double V[9]) {
+    // The sweeps work on A scaled by a power of two to a largest entry in [0.5, 1): the products of squared column norms below
+    // neither overflow (entries past 1e77) nor vanish (below 1e-77).  The scaling is exact, so U, V and -- scaled back -- s have the
+    // bits they had without it wherever it was not needed.
+    double A[9], top = 0.0;
+    for (int q = 0; q < 9; ++q) top = fmax(top, fabs(Ain[q]));
+    int ex = 0;
+    if (top > 0.0 && top <= 1.79769313486231570815e308) (void)frexp(top, &ex);
     for (int q = 0; q < 9; ++q) {
-        A[q] = Ain[q];
+        A[q] = ldexp(Ain[q], -ex);
         V[q] = (q % 4 == 0) ? 1.0 : 0.0;
     }
     for (int sweep = 0; sweep < 60; ++sweep) {
@@ -163,12 +169,35 @@ __device__ __attribute__((noinline)) inline void svd3(const double Ain[9], doubl
         }
     }
     for (int q = 0; q < 9; ++q) V[q] = Vs[q];
-    // complete a rank-deficient U to an orthonormal basis (third column = cross product)
-    if (!(s[2] > 1e-300 * s[0])) {
-        U[2] = U[3] * U[7] - U[6] * U[4];
-        U[5] = U[6] * U[1] - U[0] * U[7];
-        U[8] = U[0] * U[4] - U[3] * U[1];
+    // Complete a rank-deficient U to an orthonormal basis.  A column of A V whose norm is within 1e-15 of the largest (4 eps: below the
+    // rounding of A's own entries) carries no direction: normalised it is noise, and it need not even be orthogonal to the others (a
+    // matrix with two equal rows keeps every column in a plane, the sweeps then shrink the third until it underflows).  Replacing
+    // it changes U diag(s) V^T by less than 2e-15 s1.  Rank 1: the second column is the coordinate axis least aligned with the
+    // first, orthogonalised; rank 0: U = I.  The third column is the cross product of the first two ...
+    const double kNull = 1e-15;
+    if (!(s[0] > 0.0)) {
+        for (int q = 0; q < 9; ++q) U[q] = (q % 4 == 0) ? 1.0 : 0.0;
+    } else if (!(s[1] > kNull * s[0])) {
+        int k = 0;
+        if (fabs(U[3]) < fabs(U[k * 3])) k = 1;
+        if (fabs(U[6]) < fabs(U[k * 3])) k = 2;
+        const double uk = U[k * 3];
+        double w[3] = {-uk * U[0], -uk * U[3], -uk * U[6]};
+        w[k] += 1.0;
+        const double wn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);  // >= sqrt(2 / 3): |u_k| <= 1 / sqrt(3)
+        for (int i = 0; i < 3; ++i) U[i * 3 + 1] = w[i] / wn;
     }
+    if (!(s[2] > kNull * s[0])) {
+        // ... on the side of the plane the column it replaces points to (none: the right-handed one).  The one-sided sweeps give a tiny
+        // column A v3 to high relative accuracy, so where it is more than noise its side IS that of the singular vector, and
+        // det(U) det(V) stays what it was: a caller that pairs it with the sign of det S, as the reference does, sees no change.
+        const double c0 = U[3] * U[7] - U[6] * U[4], c1 = U[6] * U[1] - U[0] * U[7], c2 = U[0] * U[4] - U[3] * U[1];
+        const double side = (c0 * U[2] + c1 * U[5] + c2 * U[8]) < 0.0 ? -1.0 : 1.0;
+        U[2] = side * c0;
+        U[5] = side * c1;
+        U[8] = side * c2;
+    }
+    for (int j = 0; j < 3; ++j) s[j] = ldexp(s[j], ex);
 }
 
 
@@ -178,10 +207,19 @@ __device__ __attribute__((noinline)) inline void svd3(const double Ain[9], doubl
 // so the Umeyama step needs no SVD in that case: ~8 short iterations of 3x3 cofactor algebra instead of Jacobi sweeps full of
 // dependent float64 square roots and divisions run by ONE thread (the latency of that thread is on the critical path of every
 // iteration: everything after the posterior solve is replicated O(r^2) work).  Returns false -- the caller falls back to svd3 --
-// when det A <= 0, A is not finite, or the iteration does not settle (ill-conditioned A).
-__device__ inline bool polar3_rotation(const double A[9], double R[9], double *trace_RtA) {
+// when det A is not above 2^-44 |A|_F^3 (negative, or without a reliable sign), A is not finite, or the iteration does not settle.
+__host__ __device__ inline bool polar3_rotation(const double A[9], double R[9], double *trace_RtA) {
     const double det0 = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
     if (!(det0 > 0.0) || !(det0 < 1.79769313486231570815e308)) return false;
+    // A determinant within rounding of zero has no sign.  det0 is a sum of six triple products, each below |A|_F^3 / (3 sqrt 3) and
+    // each rounded twice, so its error stays below 2.5e-16 |A|_F^3; with the margin of 256 a determinant below 2^-44 |A|_F^3 (5.7e-14)
+    // is left to svd3.  Without the rule a rank-1 matrix whose computed determinant happened to be positive was iterated on and
+    // "settled" on an orthogonal matrix that is not the maximiser of trace(R^T A) (off by a third of s1 in a host sweep).  A
+    // slab of thickness ratio 1e-4 (s3 / s1 = 1e-8, determinant 1e-9 |A|_F^3) keeps the polar path.
+    double nf2 = 0.0;
+    for (int q = 0; q < 9; ++q) nf2 += A[q] * A[q];
+    const double nf = sqrt(nf2);
+    if (!(det0 > 5.6843418860808015e-14 * (nf * nf * nf))) return false;
     double X[9];
     for (int q = 0; q < 9; ++q) X[q] = A[q];
     bool done = false;
@@ -229,13 +267,18 @@ __device__ inline bool polar3_rotation(const double A[9], double R[9], double *t
 }
 
 // The Kabsch rotation of a 3x3 cross-covariance S (target x^T): the rotation R that maximises trace(R^T S).  The polar factor where it
-// applies, otherwise U diag(1, 1, s3) V^T from the SVD with s3 = -1 when det S < 0 (the last singular vector flipped); *trace_ds is
+// applies, otherwise U diag(1, 1, s3) V^T from the SVD with s3 = det(U V^T): -1 when det S < 0 (the last singular vector flipped); *trace_ds is
 // trace(R^T S) = d1 + d2 + s3 d3, what a similarity transform's scale is made of.
-__device__ inline void kabsch3_rotation(const double S[9], double R[9], double *trace_ds) {
+__host__ __device__ inline void kabsch3_rotation(const double S[9], double R[9], double *trace_ds) {
     if (polar3_rotation(S, R, trace_ds)) return;
     double U[9], D[3], V[9];
     svd3(S, U, D, V);
-    const double det = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
+    // s3 = det(U) det(V), the sign of det S wherever that sign is more than rounding (and then the same -1 or +1 as before); for a
+    // rank-deficient or denormal S, whose computed determinant is zero or noise, it is still the sign that makes R a proper rotation
+    double W[9];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) W[a * 3 + b] = U[a * 3] * V[b * 3] + U[a * 3 + 1] * V[b * 3 + 1] + U[a * 3 + 2] * V[b * 3 + 2];
+    const double det = W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
     const double s3 = det < 0 ? -1.0 : 1.0;
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) R[a * 3 + b] = U[a * 3] * V[b * 3] + U[a * 3 + 1] * V[b * 3 + 1] + s3 * U[a * 3 + 2] * V[b * 3 + 2];
