@@ -1,7 +1,8 @@
 """Random sizes and ranks against numpy for the wide-rank paths (gp_wide.hip, the super-panel solve): not collected by pytest
 (`python tests/fuzz_wide_rank.py [cases] [seed]` on a GPU box).  Each case: a random model (M points, rank r in 113 .. 512, 3 M >= r),
 random weights over a wide range with zeros, a pose; the stateless posterior mean (weighted Gram + right-hand side + solve + posed
-instance) against the normal equations solved in numpy; then two fused CPD updates against the oracle for every fifth case."""
+instance) against the normal equations solved in numpy; then two fused CPD updates against the oracle for every fifth case, followed above rank 256 by a sampled
+proposal (the 32-column super-panel solve) with the oracle's draw."""
 import sys
 import os
 
@@ -56,6 +57,17 @@ def main():
                 state = algo.update(state)
                 st = go.cpd_update(mo, target, st, w=0.2)
                 assert state.general.status == st.status == 0 and rel(state.general.fit, st.fit) < 1e-5, (c, M, N, rank)
+            if rank > 256:  # the sampled proposal above padded rank 256: posterior_solve_wide_kernel<32>, a + L^-T z with the same z
+                z = rng.standard_normal(rank)
+
+                class _Fixed:
+                    def standard_normal(self, n):
+                        return z[:n].copy()
+
+                state = algo.update(state, probabilistic=True, rnd=_Fixed())
+                st = go.cpd_update(mo, target, st, w=0.2, z=z)
+                assert state.general.status == st.status == 0 and rel(state.general.fit, st.fit) < 1e-5, (c, M, N, rank, "sampled")
+                assert rel(state.general.modelParameters.shape, st.alpha) < 1e-4, (c, M, N, rank, "sampled")
             algo.close()
         if c % 10 == 9:
             print(f"{c + 1} cases, worst coefficient error {worst:.2e}", flush=True)
