@@ -4,7 +4,9 @@
 The femur GPMM is registered (CPD) to a handful of perturbed femurs -- samples of the model itself, moved rigidly, with noise.  The
 fits are point for point on the reference's vertices, so they go straight into PointDistributionModel.createUsingPCA with
 generalised Procrustes alignment (DataCollection.gpa + createUsingPCA of scalismo, on the device).  The PCA model is saved as a
-statismo .h5.json file and is then the prior of one more CPD registration."""
+statismo .h5.json file and is then the prior of one more CPD registration.  A model of eight fits has rank 7 at most and is far too
+stiff to reach a new femur, so a third prior is the PCA model augmented with a Gaussian kernel model on its own reference
+(PointDistributionModel.augmentModel: the covariances are added and re-diagonalised on the device)."""
 import os
 import sys
 import tempfile
@@ -55,10 +57,17 @@ path = os.path.join(tempfile.gettempdir(), "femur_pca.h5.json")
 ga.io.write_statistical_mesh_model(host, path, dtype="float64")
 print(f"wrote {path} (statismo model, {os.path.getsize(path) / 1e6:.1f} MB)")
 
-for name, prior in (("kernel GPMM", gpmm), ("PCA model  ", pca)):
+t0 = time.perf_counter()
+augmented = ga.PointDistributionModel.augmentModel(ctx, pca, [ga.GaussianKernelParameters(sigma=70.0, scaling=20.0)], biasTolerance=0.01)
+ainfo = augmented.augmentInfo
+print(f"PCA model + Gaussian kernel (sigma 70, scaling 20): {ainfo.columns} columns, rank {ainfo.rank}, variance kept {ainfo.kept_variance:.1f} of "
+      f"{ainfo.total_variance:.1f} mm^2, built in {1e3 * (time.perf_counter() - t0):.1f} ms")
+
+for name, prior in (("kernel GPMM     ", gpmm), ("PCA model       ", pca), ("PCA + kernel    ", augmented)):
     cpd = ga.CpdRegistration(ctx)
     best = cpd.run(cpd.createInitialState(prior, target, cfg, transform=ga.GlobalTranformationType.RigidTransforms))
     print(f"CPD of the femur pair from the {name} (rank {prior.rank}): {best.general.iteration} iterations, "
           f"mean vertex distance {mean_distance(best.general.fit, target):.3f} mm")
     cpd.close()
+augmented.device().close()
 pca.device().close()

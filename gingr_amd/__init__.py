@@ -10,6 +10,7 @@ from .api import (  # noqa: F401
     IcpRegistration, IcpRegistrationState, LandmarkCorrespondences, ModelFittingParameters, PointDistributionModel,
     DevicePointDistributionModel, GaussianKernelParameters, GPMMTriangleMesh3D, PointSetHelper, automaticGPMMfromTemplate,
     GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo,
+    AugmentedDevicePointDistributionModel, AugmentInfo,
 )
 from ._native import GingrNativeError  # noqa: F401
 from .group import DeviceGroup  # noqa: F401  (in-library multi-GPU group: gingr_group_*)

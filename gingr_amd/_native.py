@@ -99,6 +99,11 @@ class PcaInfo(ctypes.Structure):
                 ("kept_variance", c_double)]
 
 
+class AugmentInfo(ctypes.Structure):
+    """gingr_augment_info"""
+    _fields_ = [("columns", c_int32), ("rank", c_int32), ("total_variance", c_double), ("kept_variance", c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/gingr_hip.h declares
 SIGNATURES = {
     "gingr_device_count": (c_int, []),
@@ -189,6 +194,7 @@ SIGNATURES = {
     "gingr_fitter_posterior_model_icp_surface": (c_int, [c_void_p, POINTER(IcpParams), POINTER(c_void_p)]),
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
+    "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),
     "gingr_fitter_retry_counter": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
     "gingr_fitter_exchange": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
     "gingr_fitter_cpd_phase_async": (c_int, [c_void_p, POINTER(CpdParams), c_int32]),

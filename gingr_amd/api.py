@@ -247,6 +247,28 @@ class PointDistributionModel:
         return PcaDevicePointDistributionModel(ctx, reference, shapes, alignment, relativeTolerance, maxRank, cells, gpaMaxIterations,
                                                gpaTolerance)
 
+    @staticmethod
+    def augmentModel(ctx: "Context", model, bias, relativeTolerance: float = 1e-10, maxRank: int = 0, biasTolerance: float = 0.01,
+                     cells=None) -> "AugmentedDevicePointDistributionModel":
+        """PointDistributionModel.augmentModel(pcaModel, biasModel) on the device (gingr_model_augment): the model on `model`'s
+        reference with mean model.mean + bias.mean and covariance cov(model) + cov(bias), re-diagonalised, resident in HBM.  model /
+        bias: device-built models, DeviceModels or host PointDistributionModels (those are uploaded), on the same reference and of at
+        most 512 columns together.  bias may also be a sequence of GaussianKernelParameters: the bias is then the Gaussian-mixture
+        kernel model GPMMTriangleMesh3D(ctx, model.reference, biasTolerance, cells).GaussianMixture(...) built on the model's own
+        reference (for a GPA-aligned PCA model: the Procrustes target).  The leading components with variance > relativeTolerance *
+        the largest are kept, at most maxRank (0: no limit besides 512).  The sum of the means and relativeTolerance = 1e-10 are this
+        package's definition; scalismo's own are not pinned by anything in reach."""
+        return AugmentedDevicePointDistributionModel(ctx, model, bias, relativeTolerance, maxRank, biasTolerance, cells)
+
+
+@dataclasses.dataclass(frozen=True)
+class AugmentInfo:
+    """gingr_augment_info: what the build behind PointDistributionModel.augmentModel / DeviceModel.augment did."""
+    columns: int             # columns of the two bases together (ra + rb)
+    rank: int                # rank of the model
+    total_variance: float    # sum of all eigenvalues of the summed covariance (= the two models' total variances)
+    kept_variance: float     # sum of the kept ones
+
 
 @dataclasses.dataclass(frozen=True)
 class PcaInfo:
@@ -549,6 +571,68 @@ class PcaDevicePointDistributionModel(DevicePointDistributionModel):
         return self.to_host(basis=False).mean
 
 
+class AugmentedDevicePointDistributionModel(DevicePointDistributionModel):
+    """PointDistributionModel.augmentModel: covariance and mean of two resident models added (gingr_model_augment), built in HBM and
+    adopted like a PCA model.  `augmentInfo` carries gingr_augment_info; reference and mean are read back once, basis and variance only
+    if somebody asks.  cells: the argument's, else the model's, else the bias's."""
+
+    def __init__(self, ctx: Context, model, bias, relativeTolerance: float = 1e-10, maxRank: int = 0, biasTolerance: float = 0.01, cells=None,
+                 _handle=None, _info=None):
+        self.ctx = ctx
+        self._kernels, self._host, self._info = None, None, None
+        self._to_tolerance, self._keep = False, 0
+        if _handle is None:
+            if cells is None:
+                cells = _cells_of(model)
+            if not isinstance(bias, (DeviceModel, DevicePointDistributionModel, PointDistributionModel)):
+                pars = list(bias)
+                if not pars or not all(isinstance(p, GaussianKernelParameters) for p in pars):
+                    raise ValueError("bias must be a model or a non-empty sequence of GaussianKernelParameters")
+                ref = f64((model.host if isinstance(model, DeviceModel) else model).reference)
+                bias = GPMMTriangleMesh3D(ctx, ref, biasTolerance, cells=cells).GaussianMixture(pars)
+            if cells is None:
+                cells = _cells_of(bias)
+            (da, own_a), (db, own_b) = _resident(ctx, model), _resident(ctx, bias)
+            try:
+                _handle, _info = da._augment_native(db, relativeTolerance, maxRank)
+            finally:
+                for d, own in ((da, own_a), (db, own_b)):
+                    if own:
+                        d.close()
+        self.cells = cells
+        self.augmentInfo = _info
+        self._full = DeviceModel._adopt(ctx, _handle, self, int(ctx._lib.gingr_model_num_points(_handle)))
+        try:
+            self._host = self._full.download(basis=False)
+        except Exception:
+            self._full.close()
+            raise
+        self.reference = self._host.reference
+
+    def _build(self, ctx: Context, row_begin: int, row_end: int):
+        raise ValueError("an augmented model lives whole on the context it was built on; download it (to_host) for anything else")
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self.to_host(basis=False).mean
+
+
+def _cells_of(model):
+    return getattr(model.host if isinstance(model, DeviceModel) else model, "cells", None)
+
+
+def _resident(ctx: Context, model) -> Tuple["DeviceModel", bool]:
+    """(the complete model resident on ctx, whether the caller must close it): a DeviceModel as it is, a device-built model through its
+    own handle, a host model uploaded"""
+    if isinstance(model, DeviceModel):
+        return model, False
+    if isinstance(model, DevicePointDistributionModel):
+        if model.ctx is not ctx:
+            raise ValueError("the model lives on another context; download it (to_host) first")
+        return model.device(), False
+    return DeviceModel(ctx, model), True
+
+
 @dataclasses.dataclass
 class GaussianKernelParameters:
     """GPMMHelper.scala:94"""
@@ -738,6 +822,24 @@ class DeviceModel:
             _check(self.ctx.handle, self._lib.gingr_model_truncate(self.ctx.handle, self.handle, int(k), ctypes.byref(h)), "gingr_model_truncate")
             return DeviceModel._adopt(self.ctx, h, host, host.numberOfPoints)
         return TruncatedDevicePointDistributionModel(self, k, cells=getattr(self.host, "cells", None)).device()
+
+    def _augment_native(self, other: "DeviceModel", relativeTolerance: float, maxRank: int):
+        if not isinstance(other, DeviceModel):
+            raise TypeError("augment: the other model must be a DeviceModel")
+        h, info = c_void_p(), nat.AugmentInfo()
+        _check(self.ctx.handle, self._lib.gingr_model_augment(self.ctx.handle, self.handle, other.handle, float(relativeTolerance), int(maxRank),
+                                                              ctypes.byref(h), ctypes.byref(info)), "gingr_model_augment")
+        return h, AugmentInfo(int(info.columns), int(info.rank), float(info.total_variance), float(info.kept_variance))
+
+    def augment(self, other: "DeviceModel", relativeTolerance: float = 1e-10, maxRank: int = 0) -> "DeviceModel":
+        """This model augmented with `other` as a new resident model (gingr_model_augment): mean = the sum of the two means, covariance =
+        the sum of the two covariances, re-diagonalised; both complete models of this context on the same reference, at most 512
+        columns together.  The result is an ordinary DeviceModel, independent of both; its host (an
+        AugmentedDevicePointDistributionModel) carries `augmentInfo`; cells are carried over from this model, else from the other."""
+        h, info = self._augment_native(other, relativeTolerance, maxRank)
+        cells = _cells_of(self)
+        return AugmentedDevicePointDistributionModel(self.ctx, None, None, cells=cells if cells is not None else _cells_of(other), _handle=h,
+                                                     _info=info).device()
 
     def download(self, basis: bool = True) -> "PointDistributionModel":
         """Local rows back on the host in gingr_model_upload's layout (gingr_model_download)."""

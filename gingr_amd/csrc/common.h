@@ -13,7 +13,7 @@
 
 #include "../../include/gingr_hip.h"
 
-#define GINGR_TIMERS 11
+#define GINGR_TIMERS 13
 
 struct gingr_ctx {
     int device = 0;

@@ -468,6 +468,30 @@ int gingr_model_from_shapes(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const d
                             int32_t alignment, int32_t gpa_max_iterations, double gpa_tolerance, double relative_tolerance,
                             int32_t max_rank, gingr_model **out, gingr_pca_info *info);
 
+/* ---- a model augmented with a second one ----------------------------------------------------------------------------------
+ * What PointDistributionModel.augmentModel(pcaModel, biasModel) gives a scalismo user, with both bases staying on the device: a new,
+ * finalized, independent model on the same reference with mean displacement mean_a + mean_b and covariance Q_a Q_a^T + Q_b Q_b^T
+ * (Q = U sqrt(lambda)), re-diagonalised.  The sum of the means and the cutoff below are this library's definition; nothing in reach
+ * pins scalismo's own.  a, b: complete (single-shard, finalized) models of this context on references that are equal coordinate for
+ * coordinate, ra + rb <= 512 columns together (truncate first otherwise); b may be a itself.
+ * With G = [Q_a | Q_b]^T [Q_a | Q_b] = V diag(lambda) V^T (lambda descending; the diagonal blocks are the models' resident moments, used
+ * as stored, the cross block Q_a^T Q_b is one pass over the two bases) the leading k eigenvalues with lambda_j > relative_tolerance
+ * lambda_1 and > 0 are kept, k <= max_rank when max_rank > 0 and k <= 512: variance lambda[:k], basis U sqrt(lambda) =
+ * Q_a V[:ra, :k] + Q_b V[ra:, :k], rows in the order of ref + mean_a + mean_b.  relative_tolerance: 1e-10 is this library's customary value.
+ * Only reference and mean pass through the host.  a and b are not changed.  Two calls with the same input give the same bits.
+ * Synchronises.  GINGR_ERR_BAD_ARGUMENT (the text names the cause): a null argument, a model of another context, a row shard or a
+ * model that is not finalized, different point counts, references that differ (the text names the first differing point), more than
+ * 512 columns, a negative tolerance or max_rank, no eigenvalue above the cutoff (rank 0); GINGR_ERR_NONFINITE: a non-finite Gram
+ * matrix or eigenvalue; *out is NULL then and the context stays usable. */
+typedef struct gingr_augment_info {
+    int32_t columns;        /* ra + rb */
+    int32_t rank;           /* rank of the returned model */
+    double total_variance;  /* sum of all eigenvalues = trace S_a + trace S_b */
+    double kept_variance;
+} gingr_augment_info;
+int gingr_model_augment(gingr_ctx *ctx, const gingr_model *a, const gingr_model *b, double relative_tolerance,
+                        int32_t max_rank, gingr_model **out, gingr_augment_info *info /* may be NULL */);
+
 /* The retry counter of the probabilistic proposal (G/api/GingrAlgorithm.scala:69-70,196-202,210: `retryCounter`, a private var
  * of the algorithm INSTANCE): a sampled proposal whose posterior cannot be computed returns the state unchanged up to 10 times in
  * a row before the state is marked ModelFlexibilityError; every successful posterior gives one retry back (at most 10).  The
@@ -688,7 +712,8 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * which: 0 = cpd_colsum, 1 = cpd_rowstats, 2 = gram, 3 = whole update, 4 = basis sweep (one streaming pass over Q0),
  * 5 = posterior solve (unfused tail only), 6 / 7 = the device group's exchange of segment 0 / 1 on this shard (from the record of
  * the shard's own event to the end of its sum kernel: includes the wait for the slowest peer; the host-driven sharded update records its two collectives there too), 8 = the
- * nearest-neighbour scan kernel alone, 9 = the per-vertex covariance pass over the basis alone, 10 = the basis pass of the posterior model (basis_rotate_kernel) alone.  Returns accumulated ms and launches since
+ * nearest-neighbour scan kernel alone, 9 = the per-vertex covariance pass over the basis alone, 10 = the basis pass of the posterior model (basis_rotate_kernel) alone,
+ * 11 / 12 = the cross Gram pass / the two-source basis pass of gingr_model_augment alone.  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
