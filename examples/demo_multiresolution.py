@@ -5,7 +5,9 @@
 
 Coarse CPD (100 points) -> medium CPD (500 points, sigma2 carried over) -> fine ICP (1000 points, no global transform), every
 stage starting from the previous stage's parameters, on the femur pair with a rigid offset of the target.  The coarse meshes come
-from the package's deterministic vertex clustering (scalismo's decimation is not restated)."""
+from the package's deterministic vertex clustering (scalismo's decimation is not restated), computed on the device
+(`Context.mesh_decimate`; `GingrInterface(..., decimate=gingr_amd.simple.cluster_decimate)` selects the host definition, which gives
+the same meshes bit for bit)."""
 import os
 import sys
 import time

@@ -75,7 +75,7 @@ _dp = POINTER(c_double)
 _ip = POINTER(c_int32)
 
 KERNEL_GAUSSIAN_MIXTURE, KERNEL_DOT, KERNEL_LOOKUP = 0, 1, 2
-OPT_CULL, OPT_FINE_CULL, OPT_NN_GRID, OPT_TRI_GRID, OPT_SPLIT_EXCHANGE, OPT_GRAM_DOWNDATE = 0, 1, 2, 3, 4, 5  # gingr_ctx_option
+OPT_CULL, OPT_FINE_CULL, OPT_NN_GRID, OPT_TRI_GRID, OPT_SPLIT_EXCHANGE, OPT_GRAM_DOWNDATE, OPT_DECIMATE_BATCH = 0, 1, 2, 3, 4, 5, 6  # gingr_ctx_option
 
 
 class ScalarKernel(ctypes.Structure):
@@ -153,6 +153,7 @@ SIGNATURES = {
     "gingr_nicp_solve": (c_int, [c_void_p, c_int32, c_int64, _dp, c_int64, _ip, _dp, _dp, c_int32, _ip, _dp, c_double, c_double, c_double,
                                  _dp, _dp]),
     "gingr_mesh_closest_points": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_int64, _ip, _dp, _dp, _ip, _dp]),
+    "gingr_mesh_decimate": (c_int, [c_void_p, c_int64, _dp, c_int64, _ip, c_int64, POINTER(c_int64), _ip, POINTER(c_int64), _ip, _dp]),
     "gingr_model_new_reference": (c_int, [c_void_p, c_void_p, c_int64, _dp, _ip, _dp, c_int64, c_int64, POINTER(c_void_p)]),
     "gingr_gpmm_build_diagonal": (c_int, [c_void_p, c_int64, _dp, POINTER(ScalarKernel), POINTER(ScalarKernel), POINTER(ScalarKernel),
                                           c_double, c_int32, c_int64, c_int64, POINTER(c_void_p)]),

@@ -205,6 +205,20 @@ class Context:
                "gingr_mesh_closest_points")
         return cp, d2, tid, bary
 
+    def mesh_decimate(self, vertices, cells, n_target: int) -> Tuple[np.ndarray, Optional[np.ndarray], float]:
+        """Vertex clustering to about `n_target` vertices on the device -- gingr_mesh_decimate, the result of
+        `gingr_amd.simple.cluster_decimate` bit for bit: (kept vertex ids, ascending (k,) int32; the re-indexed triangles (t,3) int32,
+        or None for a point cloud (cells=None); the chosen cube size, 0.0 when nothing was decimated)."""
+        v = f64(vertices).reshape(-1, 3)
+        c = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n, t = v.shape[0], 0 if c is None else c.shape[0]
+        kept = np.empty(max(n, 1), dtype=np.int32)
+        out = None if c is None else np.empty((max(t, 1), 3), dtype=np.int32)
+        nk, nt, h = c_int64(), c_int64(), ctypes.c_double()
+        _check(self.handle, self._lib.gingr_mesh_decimate(self.handle, n, dptr(v), t, iptr(c), int(n_target), ctypes.byref(nk), iptr(kept),
+                                                          ctypes.byref(nt), iptr(out), ctypes.byref(h)), "gingr_mesh_decimate")
+        return kept[:nk.value].copy(), None if c is None else out[:nt.value].copy(), h.value
+
 
 # ----------------------------------------------------------------------------- model
 @dataclasses.dataclass

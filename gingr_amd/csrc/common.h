@@ -13,7 +13,7 @@
 
 #include "../../include/gingr_hip.h"
 
-#define GINGR_TIMERS 13
+#define GINGR_TIMERS 17
 
 struct gingr_ctx {
     int device = 0;
@@ -52,6 +52,7 @@ struct gingr_ctx {
     // where the native all-reduce is enqueued right now (nullptr = the context's stream).
     int split_exchange = 0;
     int gram_downdate = -1;  // GINGR_OPT_GRAM_DOWNDATE: 0 / 1 weights of the surface ICP -> the model's moment minus the rejected rows (fitter_phases.hip: phase1_gram); -1: by size
+    int decimate_batch = 16;  // GINGR_OPT_DECIMATE_BATCH: bisection steps of gingr_mesh_decimate enqueued per read-back of its control block
     hipStream_t side_stream = nullptr, exchange_stream = nullptr;
     hipEvent_t split_ev[2] = {nullptr, nullptr};
     // scratch kept across calls (grown on demand, never shrunk) so steady-state updates do not allocate

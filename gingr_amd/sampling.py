@@ -95,16 +95,25 @@ class IndependentPointDistanceEvaluator:
     """Sum over the compared points of log N(|p - closestPointOnSurface(p)|; 0, uncertainty), reduced on the GPU.
 
     `uncertainty` stands for the reference's `likelihoodModel = Gaussian(0, uncertainty)` (Evaluator.scala:47).  The reference's
-    numberOfPointsForComparison decimates instance and target with scalismo's mesh decimation, which is not restated; its effect
-    -- the first n' vertices of the sample (point ids of the decimated instance, :49-50,55) and the points of the decimated target
-    (:49) -- is passed in as modelPointCount / targetPoints."""
+    numberOfPointsForComparison decimates instance and target (:44-50); scalismo's mesh decimation is not restated, so the vertex
+    clustering of this package stands in for it (`Context.mesh_decimate` on the algorithm's context, the result of
+    `simple.cluster_decimate`): `sample`'s fit with the model's cells and its target are decimated once, here.  What the
+    comparison then uses -- the first n' vertices of a sample (point ids of the decimated instance, :49-50,55) and the points of
+    the decimated target (:49) -- can be passed in directly as modelPointCount / targetPoints instead; both at once is an error."""
 
     def __init__(self, algorithm: GingrAlgorithm, sample, uncertainty: float, evaluationMode: str = ModelToTargetEvaluation,
                  numberOfPointsForComparison: Optional[int] = None, modelPointCount: Optional[int] = None, targetPoints=None):
-        if numberOfPointsForComparison is not None:
-            raise NotImplementedError("mesh decimation is scalismo's: pass modelPointCount / targetPoints")
         if evaluationMode not in (ModelToTargetEvaluation, TargetToModelEvaluation, SymmetricEvaluation):
             raise ValueError(evaluationMode)
+        if numberOfPointsForComparison is not None:
+            if modelPointCount is not None or targetPoints is not None:
+                raise ValueError("numberOfPointsForComparison and modelPointCount / targetPoints exclude each other")
+            g, n = sample.general, int(numberOfPointsForComparison)
+            kept, _, _ = algorithm.ctx.mesh_decimate(g.fit, g.model.cells, n)
+            modelPointCount = int(kept.shape[0])
+            target = np.ascontiguousarray(g.target, dtype=np.float64).reshape(-1, 3)
+            tkept, _, _ = algorithm.ctx.mesh_decimate(target, g.targetCells, n)
+            targetPoints = target[tkept]
         self.algorithm, self.uncertainty, self.evaluationMode = algorithm, float(uncertainty), evaluationMode
         self.modelPointCount = modelPointCount
         self.targetPoints = None if targetPoints is None else np.ascontiguousarray(targetPoints, dtype=np.float64)

@@ -5,9 +5,11 @@ DemoICP.scala, DemoMultiResolution.scala).  Host control flow only: states are c
 resident fitter, the final fit is instantiated on the FULL model and scored by `RegistrationComparison` on the GPU.
 
 Mesh decimation: scalismo's `mesh.operations.decimate(n)` lives in the un-vendored dependency and is not restated.  `runDecimated`
-takes a `decimate(vertices, cells, n) -> (vertices, cells)` callable; the default (`cluster_decimate`) is a deterministic vertex
-clustering whose vertices are a subset of the input's.  A different coarse mesh changes the intermediate states of a coarse-to-fine
-schedule, not what a stage computes from its inputs -- the decimated meshes are inputs of the path."""
+takes a `decimate(vertices, cells, n) -> (vertices, cells)` callable.  `cluster_decimate` below is the definition: a deterministic
+vertex clustering whose vertices are a subset of the input's, in host numpy.  The default (`decimate=None`) is `device_decimate(ctx)`,
+the same computation on the device (`Context.mesh_decimate`, gingr_mesh_decimate) with the same result bit for bit, so which of the
+two runs changes no state of a registration.  A different coarse mesh changes the intermediate states of a coarse-to-fine schedule,
+not what a stage computes from its inputs -- the decimated meshes are inputs of the path."""
 from __future__ import annotations
 
 import dataclasses
@@ -139,17 +141,29 @@ def cluster_decimate(vertices, cells, n_target: int) -> Tuple[np.ndarray, np.nda
     return v[rep_sorted].copy(), tri.astype(np.int32)
 
 
+def device_decimate(ctx: Context) -> Callable:
+    """`cluster_decimate` on the device of `ctx`: a callable with its signature and its return value (the kept vertices as a copy, the
+    cells as int32 or None), computed by `Context.mesh_decimate`."""
+    def decimate(vertices, cells, n_target: int) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        v = f64(vertices).reshape(-1, 3)
+        kept, c, _ = ctx.mesh_decimate(v, cells, n_target)
+        return v[kept].copy(), c
+    return decimate
+
+
 # ------------------------------------------------------------------------------------------------ SimpleRegistrator
 class SimpleRegistrator:
     """G/api/registration/SimpleRegistrator.scala:46-159.  `target` is a TriangleMesh3D (points + cells; cells may be None for the
-    point-cloud flavours); landmarks are `gingr_amd.io.Landmark` lists; `initialModelParameterTransform` a TranslationAfterRotation."""
+    point-cloud flavours); landmarks are `gingr_amd.io.Landmark` lists; `initialModelParameterTransform` a TranslationAfterRotation.
+    `decimate=None` decimates on the device of `algorithm.ctx` (`device_decimate`); `cluster_decimate` or any other callable of its
+    signature is used as given."""
 
     def __init__(self, algorithm, config, model: PointDistributionModel, target: TriangleMesh3D,
                  initialModelParameterTransform: Optional[TranslationAfterRotation] = None,
                  modelLandmarks: Optional[Sequence] = None, targetLandmarks: Optional[Sequence] = None,
                  evaluationMode: str = ModelToTargetEvaluation, evaluatorUncertainty: float = 1.0,
                  evaluatedPoints: Optional[int] = None, logFileFittingParameters: Optional[str] = None,
-                 rnd: Optional[Random] = None, decimate: Callable = cluster_decimate, verbose: bool = True):
+                 rnd: Optional[Random] = None, decimate: Optional[Callable] = None, verbose: bool = True):
         self.algorithm, self.config, self.model, self.target = algorithm, config, model, target
         self.ctx: Context = algorithm.ctx
         self.initialModelParameterTransform = initialModelParameterTransform
@@ -157,7 +171,7 @@ class SimpleRegistrator:
         self.evaluationMode, self.evaluatorUncertainty, self.evaluatedPoints = evaluationMode, evaluatorUncertainty, evaluatedPoints
         self.logFileFittingParameters = logFileFittingParameters
         self.rnd = rnd if rnd is not None else Random(0)
-        self.decimate, self.verbose = decimate, verbose
+        self.decimate, self.verbose = decimate if decimate is not None else device_decimate(self.ctx), verbose
 
     # -- helpers -----------------------------------------------------------------------------------------------------------
     def _landmarks(self, model: PointDistributionModel):
@@ -262,7 +276,7 @@ class GingrInterface:
                  modelLandmarks: Optional[Sequence] = None, targetLandmarks: Optional[Sequence] = None,
                  evaluatorUncertainty: float = 1.0, evaluatedPoints: Optional[int] = None,
                  evaluationMode: str = ModelToTargetEvaluation, logFileFittingParameters: Optional[str] = None,
-                 rnd: Optional[Random] = None, decimate: Callable = cluster_decimate, verbose: bool = True):
+                 rnd: Optional[Random] = None, decimate: Optional[Callable] = None, verbose: bool = True):
         self.ctx = ctx
         self._kw = dict(model=model, target=target, initialModelParameterTransform=initialModelParameterTransform,
                         modelLandmarks=modelLandmarks, targetLandmarks=targetLandmarks, evaluationMode=evaluationMode,

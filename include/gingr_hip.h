@@ -94,6 +94,8 @@ const char *gingr_build_info(void);
  *                        this option: the two forms round differently, and the exact `intersection point != vertex` comparison of the
  *                        self-intersection test (ClosestPointRegistrator.scala:67) can turn a last-bit difference into a different
  *                        accept / reject decision in the next iteration.
+ *   GINGR_OPT_DECIMATE_BATCH  16 (default), 1 .. 60: gingr_mesh_decimate enqueues this many steps of its cube-size bisection before it reads
+ *                        the control block back; the steps behind the deciding one return at once.  1 = one read-back per step.
  * No reference counterpart (the reference has one code path per operation). */
 typedef enum gingr_ctx_option {
     GINGR_OPT_CULL = 0,
@@ -101,7 +103,8 @@ typedef enum gingr_ctx_option {
     GINGR_OPT_NN_GRID = 2,
     GINGR_OPT_TRI_GRID = 3,
     GINGR_OPT_SPLIT_EXCHANGE = 4,
-    GINGR_OPT_GRAM_DOWNDATE = 5
+    GINGR_OPT_GRAM_DOWNDATE = 5,
+    GINGR_OPT_DECIMATE_BATCH = 6
 } gingr_ctx_option;
 int gingr_ctx_set_option(gingr_ctx *ctx, int32_t option, int32_t value);
 int gingr_ctx_get_option(gingr_ctx *ctx, int32_t option, int32_t *value);
@@ -374,6 +377,20 @@ int gingr_mesh_distance_stats(gingr_ctx *ctx, int64_t n_points, const double *po
 int gingr_mesh_closest_points(gingr_ctx *ctx, int64_t n_points, const double *points, int64_t n_vertices, const double *vertices,
                               int64_t n_triangles, const int32_t *triangles, double *cp_xyz, double *d2, int32_t *tri_id,
                               double *bary);
+/* Mesh decimation by vertex clustering (the step behind SimpleRegistrator.scala:84-106, IndependentPointDistanceEvaluator.scala:44-50
+ * and examples/DemoHelper/DemoDatasetLoader.scala:34; scalismo's own mesh.operations.decimate is not restated): the bounding box is
+ * cut into cubes, every occupied cube keeps its vertex closest to the mean of the cube's vertices (lowest index on ties), the
+ * triangles are re-indexed, and the collapsed and the repeated ones (same corner set: the first stays) are dropped.  The cube size is
+ * bisected so that the number of kept vertices is the closest reachable to n_target from above.  The definition is
+ * gingr_amd/simple.py: cluster_decimate, and the result is that function's, bit for bit.
+ * kept_ids[*n_kept] (capacity n_vertices): original vertex indices, ascending.  out_triangles[3 * *n_out_triangles] (capacity
+ * 3 n_triangles) index into kept_ids and keep their original order.  triangles == NULL: a point cloud (n_triangles,
+ * n_out_triangles and out_triangles are ignored).  n_target >= n_vertices is the identity: all ids, the triangles untouched.
+ * *cube_size = the chosen cube edge, 0 when nothing was decimated.  n_target < 1, n_vertices < 1 or > INT32_MAX, a triangle id out
+ * of range and a non-finite coordinate are GINGR_ERR_BAD_ARGUMENT.  Host arrays in and out; the call synchronises. */
+int gingr_mesh_decimate(gingr_ctx *ctx, int64_t n_vertices, const double *vertices, int64_t n_triangles, const int32_t *triangles,
+                        int64_t n_target, int64_t *n_kept, int32_t *kept_ids, int64_t *n_out_triangles, int32_t *out_triangles,
+                        double *cube_size);
 /* model.newReference(newReference, interpolator) (scalismo PointDistributionModel; used as
  * SimpleRegistrator.scala:89-90 with NearestNeighborInterpolator and as examples/DemoHelper/DemoDatasetLoader.scala:58-62 with
  * TriangleMeshInterpolator3D): mean and every basis function of the new point i are the fixed combination
@@ -713,7 +730,9 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * 5 = posterior solve (unfused tail only), 6 / 7 = the device group's exchange of segment 0 / 1 on this shard (from the record of
  * the shard's own event to the end of its sum kernel: includes the wait for the slowest peer; the host-driven sharded update records its two collectives there too), 8 = the
  * nearest-neighbour scan kernel alone, 9 = the per-vertex covariance pass over the basis alone, 10 = the basis pass of the posterior model (basis_rotate_kernel) alone,
- * 11 / 12 = the cross Gram pass / the two-source basis pass of gingr_model_augment alone.  Returns accumulated ms and launches since
+ * 11 / 12 = the cross Gram pass / the two-source basis pass of gingr_model_augment alone, 13 .. 16 = the stages of gingr_mesh_decimate:
+ * bounding box, bisection (every enqueued step, the ones that return at once included), clusters and representatives (insertion at
+ * the chosen size, sort, means, argmin), compaction of vertices and triangles.  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
