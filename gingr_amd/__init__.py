@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     DevicePointDistributionModel, GaussianKernelParameters, GPMMTriangleMesh3D, PointSetHelper, automaticGPMMfromTemplate,
     GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo,
     AugmentedDevicePointDistributionModel, AugmentInfo,
+    TemplateConfiguration, TemplateRegistration, TemplateRegistrationState,
 )
 from ._native import GingrNativeError  # noqa: F401
 from .group import DeviceGroup  # noqa: F401  (in-library multi-GPU group: gingr_group_*)

@@ -193,6 +193,18 @@ SIGNATURES = {
     "gingr_fitter_posterior_model_cpd": (c_int, [c_void_p, POINTER(CpdParams), POINTER(c_void_p)]),
     "gingr_fitter_posterior_model_icp": (c_int, [c_void_p, POINTER(IcpParams), POINTER(c_void_p)]),
     "gingr_fitter_posterior_model_icp_surface": (c_int, [c_void_p, POINTER(IcpParams), POINTER(c_void_p)]),
+    # correspondences given by the caller (flavour 3, fitter_pairs.hip)
+    "gingr_fitter_set_pairs": (c_int, [c_void_p, c_int64, _ip, _dp, _dp]),
+    "gingr_fitter_set_pairs_cov": (c_int, [c_void_p, c_int64, _ip, _dp, _dp]),
+    "gingr_fitter_get_pair_observations": (c_int, [c_void_p, _dp, _dp]),
+    "gingr_fitter_set_sigma2": (c_int, [c_void_p, c_double]),
+    "gingr_fitter_last_update_error": (c_int, [c_void_p, POINTER(c_int32)]),
+    "gingr_fitter_update_pairs_async": (c_int, [c_void_p, c_int32]),
+    "gingr_fitter_pairs_phase_async": (c_int, [c_void_p, c_int32]),
+    "gingr_fitter_update_pairs_sample_async": (c_int, [c_void_p, _dp]),
+    "gingr_fitter_posterior_logpdf_pairs": (c_int, [c_void_p, _dp, _dp]),
+    "gingr_fitter_posterior_covariance_pairs": (c_int, [c_void_p, _dp]),
+    "gingr_fitter_posterior_model_pairs": (c_int, [c_void_p, POINTER(c_void_p)]),
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),

@@ -1794,3 +1794,183 @@ class IcpRegistration(GingrAlgorithm):
         idx = np.empty(M, dtype=np.int32)
         _check(self.ctx.handle, self._lib.gingr_fitter_get_icp_idx(self._fitter, iptr(idx), None), "gingr_fitter_get_icp_idx")
         return idx
+
+
+# ----------------------------------------------------------------------------- Template: correspondence and uncertainty from the host
+@dataclasses.dataclass(frozen=True)
+class TemplateConfiguration:
+    """TemplateConfiguration (G/api/registration/config/Template.scala:24-29)."""
+    maxIterations: int = 1
+    threshold: float = 1e-5
+    converged: Callable = _never_converged
+    useLandmarkCorrespondence: bool = True
+
+
+@dataclasses.dataclass(frozen=True)
+class TemplateRegistrationState:
+    general: GeneralRegistrationState
+    config: TemplateConfiguration
+
+    def updateGeneral(self, update: GeneralRegistrationState) -> "TemplateRegistrationState":
+        return dataclasses.replace(self, general=update)
+
+
+def _empty_pairs() -> CorrespondencePairs:
+    return CorrespondencePairs(np.empty(0, dtype=np.int64), np.empty((0, 3)))
+
+
+class TemplateRegistration(GingrAlgorithm):
+    """A registration algorithm from its three inputs (Template.scala:46-60; the plugin surface of GingrAlgorithm.scala:65-74,256-258):
+
+    getCorrespondence(state) -> CorrespondencePairs   pids in any order, repeated or not, any subset.  Default: no pairs.
+    getUncertainty(pids, state)                       a scalar variance, a (K,) array of variances or a (K, 3, 3) array of covariances
+                                                      for the K pairs AT ONCE -- vectorised, where the reference asks pid by pid.
+                                                      Default: variance 1 (the identity covariance, Template.scala:50-52).
+    updateSigma2(newState) -> float                   Default: sigma2 stays (GingrAlgorithm.scala:256-258).  Called with the state an
+                                                      update committed, fit already refreshed; not called after a failed update.
+
+    Covariances that are exact multiples of the identity go to the fitter's isotropic list (one consolidated observation per
+    vertex, the weighted Gram pass), the others to its covariance list (the landmark pass: meant for few pairs).  Everything else
+    -- posterior, projections, step length, global transform, failure rules and retries, the sampled proposal, the transition
+    density, posteriorCovariance / posteriorModel -- is the device's, as for CPD and ICP (flavour 3 of the fitter).
+    The callbacks run once per `update`; a later query about the SAME state object (logTransitionProbability, posteriorCovariance
+    ...) reuses what they returned, and the lists are uploaded again only when a callback returned other objects than the fitter
+    holds (arrays are treated as immutable).  There is no fused Metropolis-Hastings step for this algorithm (the correspondences
+    come from the host): enableFusedSteps keeps the call-by-call path."""
+    name = "Template"
+
+    def __init__(self, ctx: Context, getCorrespondence: Optional[Callable] = None, getUncertainty: Optional[Callable] = None,
+                 updateSigma2: Optional[Callable] = None):
+        super().__init__(ctx)
+        self.getCorrespondence = getCorrespondence if getCorrespondence is not None else (lambda state: _empty_pairs())
+        self.getUncertainty = getUncertainty if getUncertainty is not None else (lambda pids, state: 1.0)
+        self._update_sigma2 = updateSigma2
+        self._observed = None      # (state, pairs, uncertainty, split lists): what the callbacks said about `state`
+        self._held = None          # (pids, points, uncertainty) objects behind the lists the fitter holds
+
+    def updateSigma2(self, state) -> float:
+        return float(state.general.sigma2) if self._update_sigma2 is None else float(self._update_sigma2(state))
+
+    @staticmethod
+    def splitObservations(pairs: CorrespondencePairs, uncertainty):
+        """(pids, points, variances), (pids, points, covariances): the isotropic and the full-covariance list of the fitter.  Raises
+        ValueError for pids / points of different length and for an uncertainty that is neither a scalar, (K,) nor (K, 3, 3)."""
+        pids = np.asarray(pairs.pids)
+        pts = np.asarray(pairs.points, dtype=np.float64)
+        if pids.ndim != 1 or pts.shape != (pids.shape[0], 3):
+            raise ValueError(f"getCorrespondence: {pids.shape[0] if pids.ndim == 1 else pids.shape} pids but points of shape {pts.shape}; "
+                             "need (K,) and (K, 3)")
+        K = pids.shape[0]
+        pid32 = np.ascontiguousarray(pids, dtype=np.int32)
+        pts = np.ascontiguousarray(pts)
+        u = np.asarray(uncertainty, dtype=np.float64)
+        none = (np.empty(0, dtype=np.int32), np.empty((0, 3)), np.empty((0, 3, 3)))
+        if u.ndim == 0:
+            return (pid32, pts, np.full(K, float(u))), none
+        if u.shape == (K,):
+            return (pid32, pts, np.ascontiguousarray(u)), none
+        if u.shape != (K, 3, 3):
+            raise ValueError(f"getUncertainty: shape {u.shape} for {K} pairs; need a scalar, ({K},) variances or ({K}, 3, 3) covariances")
+        d = u[:, 0, 0]
+        iso = np.all(u == d[:, None, None] * np.eye(3)[None], axis=(1, 2))      # exact multiples of the identity
+        ki, kc = np.flatnonzero(iso), np.flatnonzero(~iso)
+        return ((np.ascontiguousarray(pid32[ki]), np.ascontiguousarray(pts[ki]), np.ascontiguousarray(d[ki])),
+                (np.ascontiguousarray(pid32[kc]), np.ascontiguousarray(pts[kc]), np.ascontiguousarray(u[kc])))
+
+    def _observe(self, state):
+        """The callbacks' answer for `state`, asked once per state object."""
+        if self._observed is None or self._observed[0] is not state:
+            pairs = self.getCorrespondence(state)
+            unc = self.getUncertainty(pairs.pids, state)
+            self._observed = (state, pairs, unc, self.splitObservations(pairs, unc))
+        return self._observed
+
+    def _push_pairs(self, state):
+        _, pairs, unc, (iso, cov) = self._observe(state)
+        h = self._held
+        same_unc = h is not None and (h[2] is unc or (np.ndim(unc) == 0 and np.ndim(h[2]) == 0 and float(h[2]) == float(unc)))
+        if h is not None and h[0] is pairs.pids and h[1] is pairs.points and same_unc:
+            return
+        n = h[3] if h is not None else (0, 0)          # what the fitter holds: nothing to clear in an empty list
+        if iso[0].shape[0] or n[0]:
+            k = iso[0].shape[0]
+            _check(self.ctx.handle, self._lib.gingr_fitter_set_pairs(self._fitter, k, iptr(iso[0]) if k else None, dptr(iso[1]) if k else None,
+                                                                     dptr(iso[2]) if k else None), "gingr_fitter_set_pairs")
+        if cov[0].shape[0] or n[1]:
+            k = cov[0].shape[0]
+            _check(self.ctx.handle, self._lib.gingr_fitter_set_pairs_cov(self._fitter, k, iptr(cov[0]) if k else None,
+                                                                         dptr(cov[1]) if k else None, dptr(cov[2]) if k else None),
+                   "gingr_fitter_set_pairs_cov")
+        self._held = (pairs.pids, pairs.points, unc, (iso[0].shape[0], cov[0].shape[0]))
+
+    def _release(self):
+        super()._release()
+        self._held = None          # (the lists went with the fitter)
+
+    def createInitialState(self, model: PointDistributionModel, target, config: Optional[TemplateConfiguration] = None,
+                           transform: int = GlobalTranformationType.RigidTransforms, stepLength: float = 1.0,
+                           landmarks: Optional[LandmarkCorrespondences] = None, initial_pose=None,
+                           targetCells: Optional[np.ndarray] = None, sigma2: float = 1.0) -> TemplateRegistrationState:
+        g = _initial_general(self.ctx, model, target, float(sigma2), transform, stepLength, landmarks, initial_pose, targetCells)
+        return self.initializeState(g, config if config is not None else TemplateConfiguration())
+
+    def initializeState(self, general: GeneralRegistrationState, config: TemplateConfiguration) -> TemplateRegistrationState:
+        return TemplateRegistrationState(general, config)                      # Template.scala:55-60
+
+    def update(self, current, probabilistic: bool = False, rnd: Optional[np.random.Generator] = None):
+        self._observe(current)     # (argument errors of the callbacks' results surface before anything is sent to the device)
+        out = super().update(current, probabilistic, rnd)
+        if self._update_sigma2 is None:
+            return out
+        err = ctypes.c_int32()
+        _check(self.ctx.handle, self._lib.gingr_fitter_last_update_error(self._fitter, ctypes.byref(err)), "gingr_fitter_last_update_error")
+        if err.value != 0:         # the update did not commit: no newState, no updateSigma2 (GingrAlgorithm.scala:238-247)
+            return out
+        s2 = float(self._update_sigma2(out))
+        if s2 == out.general.sigma2:
+            return out
+        _check(self.ctx.handle, self._lib.gingr_fitter_set_sigma2(self._fitter, s2), "gingr_fitter_set_sigma2")
+        new = out.updateGeneral(out.general.updateSigma2(s2))
+        self._device_state = new
+        return new
+
+    def _run_resident(self, state):
+        # the callbacks run on the host every iteration: the generic loop of `run`, never a block of updates enqueued at once
+        return GingrAlgorithm.run(self, state, callBackLogger=lambda s: None)
+
+    def _native_update(self, current: TemplateRegistrationState, n: int):
+        if n != 1:
+            raise ValueError("Template: one update per call (the correspondences of the next one come from the host)")
+        self._push_pairs(current)
+        _check(self.ctx.handle, self._lib.gingr_fitter_update_pairs_async(self._fitter, 1), "gingr_fitter_update_pairs_async")
+
+    def _native_update_sample(self, current: TemplateRegistrationState, z: np.ndarray):
+        self._push_pairs(current)
+        _check(self.ctx.handle, self._lib.gingr_fitter_update_pairs_sample_async(self._fitter, dptr(z)), "gingr_fitter_update_pairs_sample_async")
+
+    def _native_logpdf(self, state: TemplateRegistrationState, mesh: np.ndarray) -> float:
+        self._push_pairs(state)
+        out = ctypes.c_double()
+        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_logpdf_pairs(self._fitter, dptr(mesh), ctypes.byref(out)),
+               "gingr_fitter_posterior_logpdf_pairs")
+        return out.value
+
+    def _native_posterior_covariance(self, state: TemplateRegistrationState, out: np.ndarray):
+        self._push_pairs(state)
+        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_covariance_pairs(self._fitter, dptr(out)),
+               "gingr_fitter_posterior_covariance_pairs")
+
+    def _native_posterior_model(self, state: TemplateRegistrationState, out):
+        self._push_pairs(state)
+        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_model_pairs(self._fitter, ctypes.byref(out)),
+               "gingr_fitter_posterior_model_pairs")
+
+    def pairObservations(self, state) -> Tuple[np.ndarray, np.ndarray]:
+        """The isotropic pairs of `state` as the device consolidated them: (observed point (M, 3), weight (M,)) per vertex -- the
+        precision-weighted mean of a vertex's pairs and their summed precision; weight 0 = no pair."""
+        self._ensure_device_state(state)
+        self._push_pairs(state)
+        M = state.general.model.numberOfPoints
+        obs, w = np.empty((M, 3)), np.empty(M)
+        _check(self.ctx.handle, self._lib.gingr_fitter_get_pair_observations(self._fitter, dptr(obs), dptr(w)), "gingr_fitter_get_pair_observations")
+        return obs, w

@@ -72,6 +72,7 @@ struct gingr_fitter {
     double step_length = 1.0;
     double stop_threshold = -1.0;  // gingr_fitter_set_stop_threshold: the run's stopping rule, applied by post_solve_kernel (< 0: none)
     int32_t stop_hit = 0;          // DevState::stopped as of the last gingr_fitter_get_state
+    int32_t last_err = 0;          // DevState::pad (error code of the last update, 0: it committed) as of the last gingr_fitter_get_state
     bool has_state = false;
     // ---- ICP surface correspondence (surface.hip): triangles in device vertex positions and a spatial triangle order
     bool icp_surface = false;                      // correspondence flavour of the ICP phases
@@ -214,6 +215,21 @@ struct gingr_fitter {
     // gingr_fitter_posterior_covariance_* (posterior_cov.hip): the bordered system the factor L^-T of I + G is left in, and the
     // [6 M] result before it goes to the host; allocated on first use, kept across calls
     DevBuf cov_work, cov_out;
+    // ---- correspondences given by the caller, flavour 3 (fitter_pairs.hip).  Isotropic pairs: the list as uploaded (ppid global ids,
+    // pxyz interleaved, pvar), the sort buffers, and the per-vertex planes they are consolidated into once per gingr_fitter_set_pairs
+    // -- pobs [3][M] / pwin [M], what launch_obs_points reads every iteration.  All sized for pairs_cap pairs, grown only.
+    bool pairs = false;  // correspondence flavour of the ICP phases: the pairs as they stand (set by the phase entry points)
+    int64_t n_pairs = 0, pairs_cap = -1;
+    int32_t *ppid = nullptr, *pkeys = nullptr, *pvals = nullptr, *pskeys = nullptr, *psvals = nullptr;
+    double *pxyz = nullptr, *pvar = nullptr, *pobs = nullptr, *pwin = nullptr;
+    void *psort = nullptr;
+    size_t psort_bytes = 0;
+    // Pairs with a full covariance ride in the landmark pass: cat_* = [covariance pairs | landmarks] (device rows, -1 = another shard's
+    // or a vertex a landmark overrides), rebuilt from the host copies below by whichever of set_pairs_cov / set_landmarks came last
+    int32_t n_pc = 0, n_cat = 0;  // covariance pairs; entries of cat_* (n_pc + the landmarks they were built with)
+    std::vector<int32_t> h_pc_row, h_lm_row, h_lm_mask;
+    std::vector<double> h_pc_xyz, h_pc_cov, h_lm_xyz, h_lm_cov;
+    DevBuf cat_pid, cat_xyz, cat_cov;
 };
 
 // GINGR_OPT_GRAM_DOWNDATE by default: from this many local rows on.  The downdate pays while fewer than ~20 % of the rows have weight 0
@@ -297,3 +313,7 @@ int gather_fit(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const g
                fitter_gather_fn gather, const char *who);
 // ---- fitter_surface.hip
 void free_meshes(gingr_fitter *f);
+// ---- fitter_pairs.hip
+int pairs_ensure_planes(gingr_fitter *f);  // pobs / pwin exist (all zero before the first gingr_fitter_set_pairs)
+int pairs_rebuild_cov_list(gingr_fitter *f);  // cat_* from the host copies of the covariance pairs and the landmarks
+void free_pairs(gingr_fitter *f);

@@ -254,6 +254,7 @@ void gingr_fitter_destroy(gingr_fitter *f) {
     nn_grid_free(&f->tgrid);
     tri_grid_free(&f->ttgrid);
     free_meshes(f);
+    free_pairs(f);
     delete f;
 }
 
@@ -349,6 +350,15 @@ int gingr_fitter_set_landmarks(gingr_fitter *f, int32_t n_lm, const int32_t *lm_
         }
     }
     HIP_TRY(ctx, hipMemcpy(f->lm_mask, mask.data(), (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice));
+    // host copies for the pairs flavour: its covariance pairs share the landmark launch (fitter_pairs.hip)
+    f->h_lm_mask = mask;
+    f->h_lm_row.assign(local.begin(), local.begin() + n_lm);
+    f->h_lm_xyz.clear(), f->h_lm_cov.clear();
+    if (n_lm > 0) {
+        f->h_lm_xyz.assign(lm_xyz, lm_xyz + (size_t)3 * n_lm);
+        f->h_lm_cov.assign(lm_cov, lm_cov + (size_t)9 * n_lm);
+    }
+    if (f->n_pc > 0) GINGR_TRY(pairs_rebuild_cov_list(f));
     if (n_lm > 0) {
         GINGR_TRY(dev_alloc(ctx, &f->lm_pid, (size_t)n_lm));
         GINGR_TRY(dev_alloc(ctx, &f->lm_xyz, (size_t)3 * n_lm));
@@ -384,6 +394,12 @@ int gingr_fitter_set_stop_threshold(gingr_fitter *f, double threshold) {
 int gingr_fitter_stop_rule_hit(gingr_fitter *f, int32_t *hit) {
     if (!f || !hit) return GINGR_ERR_BAD_ARGUMENT;
     *hit = f->stop_hit;
+    return GINGR_OK;
+}
+
+int gingr_fitter_last_update_error(gingr_fitter *f, int32_t *code) {
+    if (!f || !code) return GINGR_ERR_BAD_ARGUMENT;
+    *code = f->last_err;
     return GINGR_OK;
 }
 
@@ -469,6 +485,7 @@ int gingr_fitter_get_state(gingr_fitter *f, double *alpha, gingr_state_scalars *
     if (fit_xyz) memcpy(fit_xyz, f->pin + head, (size_t)3 * M * sizeof(double));
     if (s) scalars_of_state(hst, s);
     f->stop_hit = hst.stopped;
+    f->last_err = hst.pad;
     if (alpha) {  // what was just read IS the device state: the posterior memo can recognise it without a gingr_fitter_set_state
         f->state_key.v = state_key_values(f->m->r, alpha, hst.euler, hst.center, hst.t, hst.scale, hst.sigma2);
         f->state_key_valid = true;

@@ -83,6 +83,8 @@ int gingr_fitter_update_icp_surface_sample_async(gingr_fitter *f, const gingr_ic
     return sample_update(f, 2, nullptr, p, z);
 }
 
+int gingr_fitter_update_pairs_sample_async(gingr_fitter *f, const double *z) { return sample_update(f, 3, nullptr, nullptr, z); }
+
 static int posterior_logpdf(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip,
                             const double *mesh_xyz, double *logpdf) {
     GINGR_TRY(check_ready(f));
@@ -145,6 +147,11 @@ int gingr_fitter_posterior_logpdf_icp_surface(gingr_fitter *f, const gingr_icp_p
     return posterior_logpdf(f, 2, nullptr, p, mesh_xyz, logpdf);
 }
 
+int gingr_fitter_posterior_logpdf_pairs(gingr_fitter *f, const double *mesh_xyz, double *logpdf) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    return posterior_logpdf(f, 3, nullptr, nullptr, mesh_xyz, logpdf);
+}
+
 }  // extern "C"
 
 // ---- transition density on a row shard: the two halves around the exchange of segment 1 (the device group drives them itself)
@@ -202,14 +209,14 @@ int fitter_sharded_logpdf(gingr_fitter *f, int flavour, const gingr_cpd_params *
                           gingr_allreduce_fn reduce, void *user, double *logpdf, fitter_gather_fn gather) {
     GINGR_TRY(check_ready(f));
     gingr_ctx *ctx = f->ctx;
-    if (!mesh_xyz_full || !logpdf || !reduce || flavour < 0 || flavour > 2)
+    if (!mesh_xyz_full || !logpdf || !reduce || flavour < 0 || flavour > 3)
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sharded posterior_logpdf: bad arguments");
     if (f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded posterior_logpdf: this fitter belongs to a device group");
     if ((flavour == 2 || (flavour == 1 && f->reversed)) && f->sharded()) GINGR_TRY(gather_fit(f, flavour, cp, ip, reduce, user, gather, "sharded posterior_logpdf"));
     GINGR_TRY(fitter_run_phase(f, flavour, cp, ip, 0));
     if (flavour == 0 && reduce(user, 0, f->xch + f->off[0], f->cnt[0]) != 0)
         return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded posterior_logpdf: the all-reduce callback failed (segment 0)");
-    if (flavour != 0 && f->reversed && f->sharded() && reduce(user, GINGR_SEGMENT_REVSUM, f->revsum, 4 * f->m->M_total) != 0)
+    if ((flavour == 1 || flavour == 2) && f->reversed && f->sharded() && reduce(user, GINGR_SEGMENT_REVSUM, f->revsum, 4 * f->m->M_total) != 0)
         return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded posterior_logpdf: the all-reduce callback failed (reversal sums)");
     GINGR_TRY(fitter_run_phase(f, flavour, cp, ip, 1));
     GINGR_TRY(fitter_logpdf_prepare(f, mesh_xyz_full));

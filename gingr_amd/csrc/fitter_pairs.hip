@@ -1,0 +1,260 @@
+// Correspondences given by the caller -- flavour 3, "pairs" (C ABI in include/gingr_hip.h): the lists a host's getCorrespondence /
+// getUncertainty produce, brought into the form phase 1 of the fitter already reads.
+//   isotropic pairs   (pid, point, variance) x K  ->  one observation per vertex, once per gingr_fitter_set_pairs:
+//                     keys kernel (global pid -> device row, or the sentinel M for another shard's rows), stable radix sort over the
+//                     bits a key can have, one gather thread per local vertex that walks its run in ascending pair position.
+//   covariance pairs  (pid, point, 3 x 3)          ->  in front of the landmarks in the list the landmark pass sums (gp_obs.hip)
+// The phases themselves are in fitter_phases.hip (run_phase), the probabilistic queries next to their siblings.
+#include "fitter.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+
+namespace {
+
+// keys[k] = device row of pair k when this shard owns its vertex, else `M` (sorts last); vals[k] = k.  pid: GLOBAL ids, checked on the
+// host against [0, M_total)
+__global__ __launch_bounds__(256) void pairs_keys_kernel(int64_t K, const int32_t *__restrict__ pid, int64_t row_begin, int64_t M,
+                                                         const int32_t *__restrict__ iperm, int32_t *__restrict__ keys,
+                                                         int32_t *__restrict__ vals) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= K) return;
+    const int64_t l = (int64_t)pid[k] - row_begin;
+    keys[k] = (l >= 0 && l < M) ? iperm[l] : (int32_t)M;
+    vals[k] = (int32_t)k;
+}
+
+// Per local vertex i (device row): its pairs are a run of the stably sorted keys, walked in ascending pair position.
+//   weight_in[i] = sum 1 / var_k,   obs[.][i] = (sum x_k / var_k) / weight_in[i];   no pair (or total weight 0): weight 0, obs 0
+// -- k isotropic observations of one point are one observation of their precision-weighted mean (the identity the reversed ICP
+// direction uses with equal weights: reversal_gather_kernel, surface.hip).  Non-finite values are passed on: they fail the posterior.
+__global__ __launch_bounds__(256) void pairs_gather_kernel(int64_t M, int64_t K, const int32_t *__restrict__ skeys,
+                                                           const int32_t *__restrict__ svals, const double *__restrict__ xyz,
+                                                           const double *__restrict__ var, double *__restrict__ obs,
+                                                           double *__restrict__ weight_in) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    int64_t lo = 0, hi = K;  // first position with key >= i
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (skeys[mid] < (int32_t)i)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
+    for (int64_t p = lo; p < K && skeys[p] == (int32_t)i; ++p) {
+        const int64_t k = svals[p];
+        const double v = var[k];
+        sw += 1.0 / v;
+        sx += xyz[3 * k] / v;
+        sy += xyz[3 * k + 1] / v;
+        sz += xyz[3 * k + 2] / v;
+    }
+    const bool none = sw == 0.0;
+    obs[i] = none ? 0.0 : sx / sw;
+    obs[M + i] = none ? 0.0 : sy / sw;
+    obs[2 * M + i] = none ? 0.0 : sz / sw;
+    weight_in[i] = sw;
+}
+
+// sigma2 of the device state and of the scalars it was initialised from (one thread)
+__global__ void set_sigma2_kernel(DevState *st, gingr_state_scalars *hs, double sigma2) {
+    st->sigma2 = sigma2;
+    hs->sigma2 = sigma2;
+}
+
+// bits of the largest sort key (device rows 0 .. M - 1 and the sentinel M)
+int pair_key_bits(int64_t M) {
+    int b = 1;
+    while (b < 31 && ((int64_t)1 << b) <= M) ++b;
+    return b;
+}
+
+size_t pair_sort_temp_bytes(int64_t K) {
+    size_t bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
+                                             (int32_t *)nullptr, (int)K);
+    return bytes;
+}
+
+void free_pair_list(gingr_fitter *f) {
+    void *ptrs[] = {f->ppid, f->pkeys, f->pvals, f->pskeys, f->psvals, f->pxyz, f->pvar, f->psort};
+    for (void *q : ptrs) dev_free(q);
+    f->ppid = f->pkeys = f->pvals = f->pskeys = f->psvals = nullptr;
+    f->pxyz = f->pvar = nullptr;
+    f->psort = nullptr;
+    f->psort_bytes = 0;
+    f->pairs_cap = -1;
+}
+
+// room for K pairs (grow only); failure-atomic as far as the capacity goes: pairs_cap is raised once everything exists
+int reserve_pairs(gingr_fitter *f, int64_t K) {
+    if (K <= f->pairs_cap) return GINGR_OK;
+    gingr_ctx *ctx = f->ctx;
+    free_pair_list(f);
+    f->n_pairs = 0;
+    const size_t n = (size_t)K;
+    GINGR_TRY(dev_alloc(ctx, &f->ppid, n));
+    GINGR_TRY(dev_alloc(ctx, &f->pkeys, n));
+    GINGR_TRY(dev_alloc(ctx, &f->pvals, n));
+    GINGR_TRY(dev_alloc(ctx, &f->pskeys, n));
+    GINGR_TRY(dev_alloc(ctx, &f->psvals, n));
+    GINGR_TRY(dev_alloc(ctx, &f->pxyz, 3 * n));
+    GINGR_TRY(dev_alloc(ctx, &f->pvar, n));
+    f->psort_bytes = pair_sort_temp_bytes(K);
+    HIP_TRY(ctx, hipMalloc(&f->psort, f->psort_bytes ? f->psort_bytes : 8));
+    f->pairs_cap = K;
+    return GINGR_OK;
+}
+
+}  // namespace
+
+int pairs_ensure_planes(gingr_fitter *f) {
+    if (f->pobs && f->pwin) return GINGR_OK;
+    gingr_ctx *ctx = f->ctx;
+    const int64_t M = f->m->M;
+    if (!f->pobs) GINGR_TRY(dev_alloc(ctx, &f->pobs, (size_t)3 * M));
+    if (!f->pwin) GINGR_TRY(dev_alloc(ctx, &f->pwin, (size_t)M));
+    HIP_TRY(ctx, hipMemsetAsync(f->pobs, 0, (size_t)3 * M * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(f->pwin, 0, (size_t)M * sizeof(double), ctx->stream));
+    return GINGR_OK;
+}
+
+int pairs_rebuild_cov_list(gingr_fitter *f) {
+    gingr_ctx *ctx = f->ctx;
+    const size_t npc = (size_t)f->n_pc, nlm = f->h_lm_row.size(), n = npc + nlm;
+    std::vector<int32_t> row(n ? n : 1);
+    std::vector<double> xyz(3 * n + 1), cov(9 * n + 1);
+    for (size_t k = 0; k < npc; ++k) {  // a vertex a landmark overrides loses its pairs (GingrAlgorithm.scala:288-296)
+        const int32_t r = f->h_pc_row[k];
+        row[k] = (r >= 0 && !f->h_lm_mask.empty() && f->h_lm_mask[(size_t)r]) ? -1 : r;
+    }
+    std::copy(f->h_pc_xyz.begin(), f->h_pc_xyz.end(), xyz.begin());
+    std::copy(f->h_pc_cov.begin(), f->h_pc_cov.end(), cov.begin());
+    std::copy(f->h_lm_row.begin(), f->h_lm_row.end(), row.begin() + npc);
+    std::copy(f->h_lm_xyz.begin(), f->h_lm_xyz.end(), xyz.begin() + 3 * npc);
+    std::copy(f->h_lm_cov.begin(), f->h_lm_cov.end(), cov.begin() + 9 * npc);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (an update in flight may still read the old list)
+    f->n_cat = 0;
+    HIP_TRY(ctx, ensure(f->cat_pid, (n ? n : 1) * sizeof(int32_t)));
+    HIP_TRY(ctx, ensure(f->cat_xyz, (3 * n + 1) * sizeof(double)));
+    HIP_TRY(ctx, ensure(f->cat_cov, (9 * n + 1) * sizeof(double)));
+    if (n > 0) {
+        HIP_TRY(ctx, hipMemcpy(f->cat_pid.p, row.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(f->cat_xyz.p, xyz.data(), 3 * n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(f->cat_cov.p, cov.data(), 9 * n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    f->n_cat = (int32_t)n;
+    return GINGR_OK;
+}
+
+void free_pairs(gingr_fitter *f) {
+    free_pair_list(f);
+    dev_free(f->pobs), dev_free(f->pwin);
+    f->pobs = f->pwin = nullptr;
+    f->n_pairs = 0;
+    f->n_pc = 0;
+}
+
+extern "C" {
+
+int gingr_fitter_set_pairs(gingr_fitter *f, int64_t K, const int32_t *pid, const double *xyz, const double *var) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    const gingr_model *m = f->m;
+    if (K < 0 || K > INT32_MAX || (K > 0 && (!pid || !xyz || !var))) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_pairs: bad argument");
+    for (int64_t k = 0; k < K; ++k)
+        if (pid[k] < 0 || pid[k] >= m->M_total)
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_pairs: point id %d of pair %lld outside the model's %lld points", pid[k],
+                                   (long long)k, (long long)m->M_total);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    f->forget_posteriors();  // the same state with other pairs is another posterior
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (an update in flight reads the planes)
+    GINGR_TRY(pairs_ensure_planes(f));
+    const int64_t M = m->M;
+    if (K > 0) {
+        GINGR_TRY(reserve_pairs(f, K));
+        HIP_TRY(ctx, hipMemcpyAsync(f->ppid, pid, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(f->pxyz, xyz, (size_t)3 * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(f->pvar, var, (size_t)K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(pairs_keys_kernel, dim3((unsigned)ceil_div(K, 256)), dim3(256), 0, ctx->stream, K, f->ppid, m->row_begin, M, m->iperm,
+                           f->pkeys, f->pvals);
+        // LSD radix sort: stable, so equal keys keep ascending pair positions; only the bits a key can have (keys <= M, the sentinel)
+        HIP_TRY(ctx, hipcub::DeviceRadixSort::SortPairs(f->psort, f->psort_bytes, f->pkeys, f->pskeys, f->pvals, f->psvals, (int)K, 0,
+                                                        pair_key_bits(M), ctx->stream));
+    }
+    f->n_pairs = K;
+    // (K = 0: no run is found, every vertex gets weight 0; the list pointers are not read)
+    hipLaunchKernelGGL(pairs_gather_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, K, f->pskeys, f->psvals, f->pxyz, f->pvar,
+                       f->pobs, f->pwin);
+    GINGR_TRY(check_launch(ctx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the caller's arrays are free again
+    return GINGR_OK;
+}
+
+int gingr_fitter_set_pairs_cov(gingr_fitter *f, int64_t K, const int32_t *pid, const double *xyz, const double *cov) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    const gingr_model *m = f->m;
+    if (K < 0 || K > (1 << 24) || (K > 0 && (!pid || !xyz || !cov))) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_pairs_cov: bad argument");
+    for (int64_t k = 0; k < K; ++k)
+        if (pid[k] < 0 || pid[k] >= m->M_total)
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_pairs_cov: point id %d of pair %lld outside the model's %lld points", pid[k],
+                                   (long long)k, (long long)m->M_total);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    f->forget_posteriors();
+    f->h_pc_row.assign((size_t)K, -1);
+    for (int64_t k = 0; k < K; ++k) {
+        const int64_t lp = (int64_t)pid[k] - m->row_begin;
+        if (lp >= 0 && lp < m->M) f->h_pc_row[(size_t)k] = m->hiperm[(size_t)lp];  // device row of the original point
+    }
+    f->h_pc_xyz.clear(), f->h_pc_cov.clear();
+    if (K > 0) {
+        f->h_pc_xyz.assign(xyz, xyz + 3 * K);
+        f->h_pc_cov.assign(cov, cov + 9 * K);
+    }
+    f->n_pc = (int32_t)K;
+    return pairs_rebuild_cov_list(f);
+}
+
+int gingr_fitter_get_pair_observations(gingr_fitter *f, double *obs_xyz, double *weight) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    GINGR_TRY(pairs_ensure_planes(f));
+    const int64_t M = f->m->M;
+    DevBuf tmp, tmpw;
+    if (obs_xyz) {  // back to the caller's point order
+        HIP_TRY(ctx, tmp.alloc((size_t)3 * M * sizeof(double)));
+        launch_soa_to_aos(ctx, f->pobs, M, tmp.as<double>(), f->m->perm);
+        HIP_TRY(ctx, hipMemcpyAsync(obs_xyz, tmp.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (weight) {
+        HIP_TRY(ctx, tmpw.alloc((size_t)M * sizeof(double)));
+        launch_scatter(ctx, f->pwin, M, f->m->perm, tmpw.as<double>());
+        HIP_TRY(ctx, hipMemcpyAsync(weight, tmpw.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    GINGR_TRY(check_launch(ctx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GINGR_OK;
+}
+
+int gingr_fitter_set_sigma2(gingr_fitter *f, double sigma2) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    if (!f->has_state) return gingr_set_error(ctx, GINGR_ERR_STATE, "set_sigma2: no state set");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(set_sigma2_kernel, dim3(1), dim3(1), 0, ctx->stream, f->st, f->hs_dev, sigma2);
+    f->forget_posteriors();  // sigma2 is part of the state the memo is keyed by
+    f->mh_saved = false;
+    // a state the host knows by value stays known: its key ends in sigma2 (state_key_values)
+    if (f->state_key_valid && f->state_key.v.size() == (size_t)f->m->r + 11)
+        f->state_key.v.back() = sigma2;
+    else
+        f->state_key_valid = false;
+    return check_launch(ctx);
+}
+
+}  // extern "C"

@@ -131,7 +131,8 @@ bool memo_enter(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, int phase
     if (phase == 0) {
         f->skip_phase1 = false;
         gingr_fitter::Key k;
-        k.flavour = !icp ? 0 : ((f->icp_surface ? 2 : 1) + 4 * f->surface_method + 16 * (f->reversed ? 1 : 0));
+        // (3: the pairs as they stand -- gingr_fitter_set_pairs / _set_pairs_cov forget the memo, so the key need not describe them)
+        k.flavour = !icp ? 0 : f->pairs ? 3 : ((f->icp_surface ? 2 : 1) + 4 * f->surface_method + 16 * (f->reversed ? 1 : 0));
         if (!icp) {
             k.p0 = cp->w;
             k.p1 = cp->lambda;
@@ -385,7 +386,10 @@ void phase1_observations(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, 
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
     const int64_t M = m->M;
-    if (icp) {
+    if (icp && f->pairs) {  // the caller's pairs, consolidated per vertex by gingr_fitter_set_pairs; weight 0: no pair
+        launch_obs_points(ctx, m, f->st, f->pobs, f->pwin, f->weight, f->evec, f->lm_mask);
+        fa.scalar_mode = 0;
+    } else if (icp) {
         if (f->reversed && f->sharded())  // the totals over all shards' query ranges are in place: this shard's rows of them
             hipLaunchKernelGGL(reversal_local_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, m->row_begin, m->perm,
                                m->M_total, f->revsum, &f->st->sigma2, f->robs, f->rwin);
@@ -439,7 +443,7 @@ struct GramOutcome {
 //                    pass launched behind them carries `many` and writes its slabs (alt_nslabs) and right-hand-side partials over
 //                    the same gram_ws / sweep_ws (at rp >= 128 its ungated row expansion writes behind the WIDE plan's slab count).
 //                    The gate sums THIS shard's zero_counts against THIS shard's M: the shards of one update may decide differently.
-//   weighted pass    everything else: each shard contributes the pass over its own rows; the pass may leave the right-hand-side
+//   weighted pass    everything else -- always for the pairs flavour, whose weights are the caller's: each shard contributes the pass over its own rows; the pass may leave the right-hand-side
 //                    partials as well (rhs_done).
 GramOutcome phase1_gram(gingr_fitter *f, bool icp, double *gram_ws, double *sweep_ws, Phase1FinalizeArgs &fa) {
     gingr_ctx *ctx = f->ctx;
@@ -447,13 +451,13 @@ GramOutcome phase1_gram(gingr_fitter *f, bool icp, double *gram_ws, double *swee
     const int64_t M = m->M;
     const int32_t rp = m->rp;
     GramOutcome out{false, ZeroGate{}};
-    if (icp && !f->icp_surface && !f->reversed && f->n_lm == 0) {
+    if (icp && !f->pairs && !f->icp_surface && !f->reversed && f->n_lm == 0) {
         // (ICP.scala:90-92; written by the phase-1 finalize kernel: one launch less than a copy kernel of its own)
         fa.nslabs = 0;
         fa.scaled_src = m->mom + MomentLayout{rp}.stot();
         fa.sigma2 = &f->st->sigma2;
         fa.scaled_contribute = m->row_begin == 0 ? 1 : 0;
-    } else if (icp && f->icp_surface && !f->reversed &&
+    } else if (icp && !f->pairs && f->icp_surface && !f->reversed &&
                (ctx->gram_downdate == 1 || (ctx->gram_downdate < 0 && M >= kGramDowndateMinRows))) {
         // surface correspondence: an accepted pair has the weight 1 / sigma2, a rejected one (and a vertex a landmark overrides) 0
         // (ICP.scala:50,90-92) -- the weighted Gram is the model's moment minus the rows of the zero-weight vertices, scaled.
@@ -489,7 +493,7 @@ void phase2_solve_and_commit(gingr_fitter *f, bool icp, const gingr_icp_params *
     const int32_t r = m->r, rp = m->rp;
     // the posterior mean of the uniform-weight case comes from the model's eigen-decomposition (no factorisation); a sampled
     // proposal needs the Cholesky factor itself (its square root of the covariance is part of the parity contract)
-    const bool eig = icp && !f->icp_surface && !f->reversed && f->n_lm == 0 && !f->zrand_active && m->eig_ready;
+    const bool eig = icp && !f->pairs && !f->icp_surface && !f->reversed && f->n_lm == 0 && !f->zrand_active && m->eig_ready;
     if (eig)
         launch_posterior_solve_eig(ctx, r, rp, m->eigV, m->eigL, &f->st->sigma2, s.rhs, f->acoef, f->st);
     else if (f->zrand_active && f->allow_alt && f->post_stage == 2 && f->nf_valid[f->live] && m->M == m->M_total && !f->partial_out)
@@ -506,8 +510,8 @@ void phase2_solve_and_commit(gingr_fitter *f, bool icp, const gingr_icp_params *
     a.zbuf = f->zbuf;
     a.alpha = f->alpha;
     a.scalars = s.sc8;
-    a.is_icp = icp ? 1 : 0;
-    if (icp) {
+    a.is_icp = !icp ? 0 : f->pairs ? 2 : 1;  // sigma2 of the next state: CPD's sums / ICP's schedule / kept (the caller's updateSigma2)
+    if (icp && !f->pairs) {
         a.icp_step = (ip->initial_sigma - ip->end_sigma) / (double)ip->max_iterations;  // ICP.scala:65
         a.icp_end = ip->end_sigma;
     }
@@ -559,6 +563,8 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
     if (memo_enter(f, icp, cp, phase)) return GINGR_OK;
     switch (phase) {
         case 0:
+            if (icp && f->pairs)
+                break;  // the correspondences are the caller's: nothing to compute, nothing to exchange
             if (icp && f->reversed)
                 GINGR_TRY(phase0_reversed(f, fit, tgt, meshc));
             else if (icp && f->icp_surface)
@@ -587,7 +593,7 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
                 a.partial = sweep_ws;
                 a.no_reduce = 1;
                 a.gate = gram.rhs_gate;
-                if (icp && !f->icp_surface && !f->reversed && f->n_lm == 0) {  // point-cloud ICP: observation + Q^T e in one pass
+                if (icp && !f->pairs && !f->icp_surface && !f->reversed && f->n_lm == 0) {  // point-cloud ICP: observation + Q^T e in one pass
                     a.state = f->st;
                     a.icp_idx = f->nn_idx;
                     a.tx = tgt.x, a.ty = tgt.y, a.tz = tgt.z;
@@ -601,7 +607,11 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
                 fa.sweep_blocks = sweep_num_blocks(M);
             }
             launch_phase1_finalize(ctx, fa);
-            launch_landmarks(ctx, m, f->st, f->n_lm, f->lm_pid, f->lm_xyz, f->lm_cov, s.Gw, s.rhsw);
+            if (icp && f->pairs && f->n_pc > 0)  // one launch over [covariance pairs | landmarks]: a defined summation order
+                launch_landmarks(ctx, m, f->st, f->n_cat, f->cat_pid.as<int32_t>(), f->cat_xyz.as<double>(), f->cat_cov.as<double>(),
+                                 s.Gw, s.rhsw);
+            else
+                launch_landmarks(ctx, m, f->st, f->n_lm, f->lm_pid, f->lm_xyz, f->lm_cov, s.Gw, s.rhsw);
             break;
         }
         case 2:
@@ -615,10 +625,11 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
 
 }  // namespace
 
-// One phase of flavour 0 CPD / 1 ICP point cloud / 2 ICP surface (GINGR_PHASE_GATHER included)
+// One phase of flavour 0 CPD / 1 ICP point cloud / 2 ICP surface / 3 pairs given (GINGR_PHASE_GATHER included)
 int fitter_run_phase(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int phase) {
     if (flavour == 0) return gingr_fitter_cpd_phase_async(f, cp, phase);
     if (flavour == 1) return gingr_fitter_icp_phase_async(f, ip, phase);
+    if (flavour == 3) return gingr_fitter_pairs_phase_async(f, phase);
     return gingr_fitter_icp_surface_phase_async(f, ip, phase);
 }
 
@@ -644,7 +655,22 @@ int gingr_fitter_icp_phase_async(gingr_fitter *f, const gingr_icp_params *p, int
     GINGR_TRY(check_ready(f));
     if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
     f->icp_surface = false;
+    f->pairs = false;
     return run_phase(f, true, nullptr, p, phase);
+}
+
+int gingr_fitter_pairs_phase_async(gingr_fitter *f, int32_t phase) {
+    GINGR_TRY(check_ready(f));
+    GINGR_TRY(pairs_ensure_planes(f));  // (no gingr_fitter_set_pairs yet: no pairs)
+    f->pairs = true;
+    return run_phase(f, true, nullptr, nullptr, phase);
+}
+
+int gingr_fitter_update_pairs_async(gingr_fitter *f, int32_t n_iterations) {
+    GINGR_TRY(check_ready(f));
+    if (f->m->M != f->m->M_total)
+        return gingr_set_error(f->ctx, GINGR_ERR_STATE, "update_pairs_async: a row shard needs the sharded update (gingr_fitter_update_sharded_async)");
+    return update_loop(f, 3, nullptr, nullptr, n_iterations);
 }
 
 int gingr_fitter_update_cpd_async(gingr_fitter *f, const gingr_cpd_params *p, int32_t n_iterations) {
@@ -666,6 +692,7 @@ int gingr_fitter_icp_surface_phase_async(gingr_fitter *f, const gingr_icp_params
     if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
     if (!f->Tm || !f->Tt) return gingr_set_error(f->ctx, GINGR_ERR_STATE, "icp surface: no meshes set (gingr_fitter_set_meshes)");
     f->icp_surface = true;
+    f->pairs = false;
     return run_phase(f, true, nullptr, p, phase);
 }
 
@@ -702,7 +729,7 @@ int fitter_sharded_update(gingr_fitter *f, int flavour, const gingr_cpd_params *
                           const double *z, gingr_allreduce_fn reduce, void *user, fitter_gather_fn gather, bool split_native) {
     GINGR_TRY(check_ready(f));
     gingr_ctx *ctx = f->ctx;
-    if (n_iterations < 0 || !reduce || flavour < 0 || flavour > 2) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sharded update: bad arguments");
+    if (n_iterations < 0 || !reduce || flavour < 0 || flavour > 3) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sharded update: bad arguments");
     if (f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded update: this fitter belongs to a device group");
     if (z && n_iterations != 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sharded update: a sampled proposal is one iteration");
     if (z) GINGR_TRY(fitter_upload_zrand(f, z));
@@ -762,7 +789,7 @@ int fitter_sharded_update(gingr_fitter *f, int flavour, const gingr_cpd_params *
                 if (reduce(user, ph, f->xch + f->off[ph], f->cnt[ph]) != 0)
                     rc = gingr_set_error(ctx, GINGR_ERR_STATE, "sharded update: the all-reduce callback failed (segment %d)", ph);
             }
-            if (!rc && ph == 0 && flavour != 0 && f->reversed && f->sharded() &&
+            if (!rc && ph == 0 && (flavour == 1 || flavour == 2) && f->reversed && f->sharded() &&
                 reduce(user, GINGR_SEGMENT_REVSUM, f->revsum, 4 * f->m->M_total) != 0)
                 rc = gingr_set_error(ctx, GINGR_ERR_STATE, "sharded update: the all-reduce callback failed (reversal sums)");
         }

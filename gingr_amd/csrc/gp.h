@@ -372,7 +372,7 @@ struct PostSolveArgs {
     const double *zbuf;     // [rp][28] from launch_post_matvecs (PostVec::kZa ...)
     double *alpha;          // in/out: shape coefficients of the state
     const double *scalars;  // reduced {Np, xPx, trPXY, yPy, ...} (CPD) or nullptr
-    int32_t is_icp;
+    int32_t is_icp;  // sigma2 of the next state -- 0: CPD's sums (scalars), 1: the ICP schedule (icp_step, icp_end), 2: kept as it is
     double icp_step, icp_end;
     double step;
     int32_t global_transform;

@@ -223,7 +223,9 @@ __device__ void post_pose_step(const PostSolveArgs &A, const DevState *st, const
             L.stage[15 + q] = t2[q];
         }
         L.stage[18] = c;
-        if (A.is_icp) {
+        if (A.is_icp == 2) {  // the pairs flavour: the trait's default updateSigma2 (GingrAlgorithm.scala:256-258), sigma2 stays
+            L.stage[19] = st->sigma2;
+        } else if (A.is_icp) {
             const double ns = st->sigma2 - A.icp_step;  // ICP.scala:96-99
             L.stage[19] = ns > A.icp_end ? ns : A.icp_end;
         } else {

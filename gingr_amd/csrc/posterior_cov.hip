@@ -363,4 +363,9 @@ int gingr_fitter_posterior_covariance_icp_surface(gingr_fitter *f, const gingr_i
     return posterior_covariance(f, 2, nullptr, p, cov6_out);
 }
 
+int gingr_fitter_posterior_covariance_pairs(gingr_fitter *f, double *cov6_out) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    return posterior_covariance(f, 3, nullptr, nullptr, cov6_out);
+}
+
 }  // extern "C"

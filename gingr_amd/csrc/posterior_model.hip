@@ -231,4 +231,10 @@ int gingr_fitter_posterior_model_icp_surface(gingr_fitter *f, const gingr_icp_pa
     return fitter_posterior_model(f, 2, nullptr, p, out);
 }
 
+int gingr_fitter_posterior_model_pairs(gingr_fitter *f, gingr_model **out) {
+    if (!f || !out) return GINGR_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return fitter_posterior_model(f, 3, nullptr, nullptr, out);
+}
+
 }  // extern "C"

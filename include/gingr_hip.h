@@ -307,6 +307,11 @@ int gingr_fitter_set_options(gingr_fitter *f, int32_t global_transform, double s
  * gingr_fitter_stop_rule_hit: the mark as of the last gingr_fitter_get_state (no transfer of its own). */
 int gingr_fitter_set_stop_threshold(gingr_fitter *f, double threshold);
 int gingr_fitter_stop_rule_hit(gingr_fitter *f, int32_t *hit);
+/* Whether the last update committed, as of the last gingr_fitter_get_state (no transfer of its own): 0, or the error code
+ * (GINGR_ERR_NOT_SPD / GINGR_ERR_NONFINITE) of the failure the Try rules of `update` turned into "state unchanged" or
+ * ModelFlexibilityError.  A host that applies an updateSigma2 of its own applies it to committed updates only
+ * (G/api/GingrAlgorithm.scala:238-247). */
+int gingr_fitter_last_update_error(gingr_fitter *f, int32_t *code);
 /* state in: alpha[r] + scalars; the fit is recomputed on the device (modelInstanceShapePoseScale). */
 int gingr_fitter_set_state(gingr_fitter *f, const double *alpha, const gingr_state_scalars *s);
 /* state out (synchronises): alpha[r], scalars, fit_xyz[3*M_local]; any pointer may be NULL. */
@@ -458,6 +463,54 @@ int gingr_fitter_posterior_model_cpd(gingr_fitter *f, const gingr_cpd_params *p,
 int gingr_fitter_posterior_model_icp(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out);
 int gingr_fitter_posterior_model_icp_surface(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out);
 
+/* ---- correspondences given by the caller: the "pairs" flavour (flavour 3) --------------------------------------------------
+ * GiNGR's plugin surface is getCorrespondence: State => CorrespondencePairs, getUncertainty: (PointId, State) =>
+ * MultivariateNormalDistribution and updateSigma2 (G/api/GingrAlgorithm.scala:65-74,256-258; registration/config/Template.scala is
+ * the skeleton).  With this flavour the host supplies the first two as lists and the device runs everything `update` does around
+ * them: the posterior, both coefficient projections, step length, global transform, the Try failure rules and the retry counter,
+ * the fit refresh, the sampled proposal, the transition density, the covariance maps and the posterior as a model.
+ *
+ * gingr_fitter_set_pairs: K >= 0 isotropic pairs (pid[k], xyz[3k..3k+2], var[k]), host arrays.  Pids are GLOBAL ids in the
+ * caller's point order, in any order, repeated or not, covering any subset of the vertices.  They are consolidated ONCE, here,
+ * into one observation per vertex -- k isotropic observations of one point are one observation of their precision-weighted mean:
+ *     weight_i = sum_k 1 / var_k,     obs_i = (sum_k x_k / var_k) / weight_i      (both sums in ascending pair position),
+ * weight_i = 0 (and obs_i = 0) for a vertex without pairs -- by a stable radix sort of the device rows (only the bits a row can
+ * have) and one gather thread per local vertex.  A row shard is given the WHOLE list and keeps the pairs of its own rows.  The
+ * working memory belongs to the fitter and is reused while K does not grow.  K = 0 clears the list.
+ * gingr_fitter_set_pairs_cov: a second, independent list with a full 3 x 3 covariance per pair (row-major).  It is summed into G
+ * and the right-hand side by the landmark pass, in ONE launch over "covariance pairs first, then the landmarks"; that pass costs
+ * O(K r^2) -- it is meant for tens to hundreds of pairs, NOT for one pair per vertex (there is no 3 x 3-weighted Gram pass).
+ * A vertex that a landmark overrides (gingr_fitter_set_landmarks) loses its isotropic and its covariance pairs
+ * (GingrAlgorithm.scala:288-296); the two calls and gingr_fitter_set_landmarks may come in any order.
+ * Both calls synchronise and forget the posterior memo (the same state with other pairs is another posterior).  A pid outside
+ * [0, M_total) is GINGR_ERR_BAD_ARGUMENT (nothing is changed).  VALUES are not validated; they follow the Try rules of `update`, as
+ * the ICP flavours' do: a non-finite point, variance or covariance fails the posterior on the device (state unchanged at
+ * iteration 0, ModelFlexibilityError later, a retry when sampled); var = +inf is weight 0, a dropped pair.
+ * gingr_fitter_get_pair_observations (synchronises): the consolidated planes, obs_xyz[3 M_local] / weight[M_local] in the caller's
+ * point order; either may be NULL.
+ *
+ * gingr_fitter_update_pairs_async: n_iterations updates + fit refresh with the pairs as they stand.  sigma2 is LEFT AS IT IS, the
+ * trait's default updateSigma2 (GingrAlgorithm.scala:256-258); a host with a rule of its own applies it between updates with
+ * gingr_fitter_set_sigma2: asynchronous, writes sigma2 of the device state only (no fit recomputation), forgets the memo.
+ * _sample / _logpdf / _covariance / _model: the contracts of their _icp siblings, memo reuse included (exactly the same state set
+ * again, pairs and landmarks untouched in between).  Without pairs and landmarks G = 0 and rhs = 0: the posterior mean is the
+ * prior mean and the update proceeds; with landmarks only it is a landmark registration.  The general weighted Gram pass and the
+ * Cholesky solve are always taken: the uniform-weight shortcuts of the ICP flavours do not apply.  A target must be set
+ * (gingr_fitter_set_target sizes the exchange buffers), though this flavour never reads it.
+ * gingr_fitter_update_sharded_async / gingr_fitter_posterior_logpdf_sharded accept flavour = 3 (cp and ip unused): no segment-0
+ * exchange.  NOT covered: gingr_fitter_mh_step (the correspondences come from the host, a step cannot be fused; call by call works),
+ * the gingr_group_* and RCCL entry points. */
+int gingr_fitter_set_pairs(gingr_fitter *f, int64_t K, const int32_t *pid, const double *xyz, const double *var);
+int gingr_fitter_set_pairs_cov(gingr_fitter *f, int64_t K, const int32_t *pid, const double *xyz, const double *cov);
+int gingr_fitter_get_pair_observations(gingr_fitter *f, double *obs_xyz, double *weight);
+int gingr_fitter_set_sigma2(gingr_fitter *f, double sigma2);
+int gingr_fitter_update_pairs_async(gingr_fitter *f, int32_t n_iterations);
+int gingr_fitter_pairs_phase_async(gingr_fitter *f, int32_t phase);
+int gingr_fitter_update_pairs_sample_async(gingr_fitter *f, const double *z);
+int gingr_fitter_posterior_logpdf_pairs(gingr_fitter *f, const double *mesh_xyz, double *logpdf);
+int gingr_fitter_posterior_covariance_pairs(gingr_fitter *f, double *cov6_out);
+int gingr_fitter_posterior_model_pairs(gingr_fitter *f, gingr_model **out);
+
 /* ---- a PCA model from shapes in correspondence ----------------------------------------------------------------------------
  * What DataCollection.gpa(...) followed by PointDistributionModel.createUsingPCA(...) gives a scalismo user, built on the device: a
  * new, finalized, single-shard model on this context.  ref_xyz [3 M]: the reference; shapes_xyz [n_shapes][3 M]: the shapes, point
@@ -567,7 +620,9 @@ int gingr_fitter_update_icp_sharded_async(gingr_fitter *f, const gingr_icp_param
  * G/api/registration/config/ICP.scala:63 -- the probabilistic proposal and the transition density are row-sharded too).
  *   flavour 0 CPD (cp), 1 ICP point cloud (ip), 2 ICP surface (ip; gingr_fitter_set_meshes on every shard with the triangles of the
  *   WHOLE template -- vertex ids of the full model -- and of the target; the shard's queries are its own rows, the tests against the
- *   template itself see all of it through the gathered fit, exchange segment GINGR_SEGMENT_FULLFIT).
+ *   template itself see all of it through the gathered fit, exchange segment GINGR_SEGMENT_FULLFIT), 3 the caller's pairs (cp and ip
+ *   unused; gingr_fitter_set_pairs / _set_pairs_cov on every shard with the WHOLE lists, each keeps the pairs of its own rows; like
+ *   ICP, no segment-0 exchange).
  *   z (nullable): rank standard-normal draws = update(current, probabilistic = true), n_iterations must be 1; the same z on every
  *   shard (the sample a + L^-T z is replicated r x r algebra).
  * gingr_fitter_posterior_logpdf_sharded: posterior(state).gp.logpdf(posterior.coefficients(mesh))

@@ -588,6 +588,44 @@ JFN(jint, fitterMhStep)(JNIEnv *env, jclass, jlong f, jint flavour, jint kind, j
     return rc;
 }
 JFN(jint, fitterMhRestore)(JNIEnv *, jclass, jlong f) { return gingr_fitter_mh_restore(P<gingr_fitter>(f)); }
+// ---- correspondences given by the caller (flavour 3: gingr_fitter_set_pairs ... in include/gingr_hip.h); null / empty arrays clear a list
+JFN(jint, fitterSetPairs)(JNIEnv *env, jclass, jlong f, jintArray pid, jdoubleArray xyz, jdoubleArray var) {
+    const jsize n = pid ? env->GetArrayLength(pid) : 0;
+    Arr<int32_t> a(env, pid, true); Arr<double> b(env, xyz, true); Arr<double> c(env, var, true);
+    return gingr_fitter_set_pairs(P<gingr_fitter>(f), n, a.ptr(), b.ptr(), c.ptr());
+}
+JFN(jint, fitterSetPairsCov)(JNIEnv *env, jclass, jlong f, jintArray pid, jdoubleArray xyz, jdoubleArray cov) {
+    const jsize n = pid ? env->GetArrayLength(pid) : 0;
+    Arr<int32_t> a(env, pid, true); Arr<double> b(env, xyz, true); Arr<double> c(env, cov, true);
+    return gingr_fitter_set_pairs_cov(P<gingr_fitter>(f), n, a.ptr(), b.ptr(), c.ptr());
+}
+JFN(jint, fitterGetPairObservations)(JNIEnv *env, jclass, jlong f, jdoubleArray obs, jdoubleArray w) {
+    Arr<double> a(env, obs, false); Arr<double> b(env, w, false);
+    return gingr_fitter_get_pair_observations(P<gingr_fitter>(f), a.ptr(), b.ptr());
+}
+JFN(jint, fitterSetSigma2)(JNIEnv *, jclass, jlong f, jdouble sigma2) { return gingr_fitter_set_sigma2(P<gingr_fitter>(f), sigma2); }
+JFN(jint, fitterLastUpdateError)(JNIEnv *, jclass, jlong f) {  // >= 0: the code of the last update (0: it committed); < 0: -(error code)
+    int32_t code = 0;
+    const int rc = gingr_fitter_last_update_error(P<gingr_fitter>(f), &code);
+    return rc == GINGR_OK ? code : -rc;
+}
+JFN(jint, fitterUpdatePairs)(JNIEnv *, jclass, jlong f, jint n) { return gingr_fitter_update_pairs_async(P<gingr_fitter>(f), n); }
+JFN(jint, fitterUpdatePairsSample)(JNIEnv *env, jclass, jlong f, jdoubleArray z) {
+    Arr<double> a(env, z, true);
+    return gingr_fitter_update_pairs_sample_async(P<gingr_fitter>(f), a.ptr());
+}
+JFN(jint, fitterPosteriorLogpdfPairs)(JNIEnv *env, jclass, jlong f, jdoubleArray mesh, jdoubleArray out) {
+    Arr<double> a(env, mesh, true); Arr<double> b(env, out, false);
+    return gingr_fitter_posterior_logpdf_pairs(P<gingr_fitter>(f), a.ptr(), b.ptr());
+}
+JFN(jint, fitterPosteriorCovariancePairs)(JNIEnv *env, jclass, jlong f, jdoubleArray cov6) {
+    Arr<double> a(env, cov6, false);
+    return gingr_fitter_posterior_covariance_pairs(P<gingr_fitter>(f), a.ptr());
+}
+JFN(jlong, fitterPosteriorModelPairs)(JNIEnv *, jclass, jlong f) {  // 0: failed (lastError of the context says why)
+    gingr_model *m = nullptr;
+    return gingr_fitter_posterior_model_pairs(P<gingr_fitter>(f), &m) == GINGR_OK ? H(m) : 0;
+}
 #else
 // No JDK headers on this machine: the shim is not built (the C ABI it wraps is still covered by the Python tests).
 #endif

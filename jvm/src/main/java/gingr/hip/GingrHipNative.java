@@ -192,4 +192,24 @@ public final class GingrHipNative {
                                           double evalSdev, long evalPoints, boolean needForward, double[] alphaOut, double[] fitOut,
                                           double[] poseOut11, int[] intOut4, double[] dblOut6);
     public static native int fitterMhRestore(long fitter);
+
+    // ---- correspondences given by the caller: the "pairs" flavour of the fitter (gingr_fitter_set_pairs ..., include/gingr_hip.h) -- what a
+    // TemplateRegistration's getCorrespondence / getUncertainty produce, while update, the failure rules, the sampled proposal and the
+    // transition density stay on the device.  pid: GLOBAL point ids, any order, repeated or not; null or empty arrays clear a list.
+    /** isotropic pairs (pid, xyz[3 K], variance[K]): consolidated once into one observation per vertex */
+    public static native int fitterSetPairs(long fitter, int[] pid, double[] xyz, double[] variance);
+    /** pairs with a full covariance (cov9[9 K], row-major); summed by the landmark pass, O(K r^2): for few pairs */
+    public static native int fitterSetPairsCov(long fitter, int[] pid, double[] xyz, double[] cov9);
+    /** the consolidated isotropic pairs: obs[3 M], weight[M] (0 = no pair) in the model's point order */
+    public static native int fitterGetPairObservations(long fitter, double[] obsXyz, double[] weight);
+    /** sigma2 of the device state only (a host's own updateSigma2 between updates) */
+    public static native int fitterSetSigma2(long fitter, double sigma2);
+    /** >= 0: error code of the last update as of the last fitterGetState (0: it committed); < 0: -(error code of this call) */
+    public static native int fitterLastUpdateError(long fitter);
+    public static native int fitterUpdatePairs(long fitter, int nIterations);
+    public static native int fitterUpdatePairsSample(long fitter, double[] z);
+    public static native int fitterPosteriorLogpdfPairs(long fitter, double[] meshXyz, double[] out1);
+    public static native int fitterPosteriorCovariancePairs(long fitter, double[] cov6);
+    /** the posterior of the current state as a new resident model (0: failed) */
+    public static native long fitterPosteriorModelPairs(long fitter);
 }

@@ -81,19 +81,20 @@ final class HipSession(device: Int) extends AutoCloseable {
 
   /** Pushes (alpha, pose, sigma2), runs ONE update, pulls the result.  Returns (alpha, pose11, status). */
   /** push the parameters of `general` (the device re-instantiates the fit) and run a query on the fitter */
-  def withState(general: GeneralRegistrationState, run: Long => Int): Unit = {
+  def withState(general: GeneralRegistrationState, run: Long => Int, useLandmarks: Boolean = false): Unit = {
     val mp = general.modelParameters
     val a = mp.pose.rotation.angles
     val c = mp.pose.rotation.center
     val t = mp.pose.translation
     val pose = Array(a.phi, a.theta, a.psi, c.x, c.y, c.z, t.x, t.y, t.z, mp.scale.s, general.sigma2)
     val status = if (general.status == FittingStatuses.ModelFlexibilityError) 3 else 0
-    bind(general, useLandmarks = false)
+    bind(general, useLandmarks)
     check(GingrHipNative.fitterSetState(fitter, mp.shape.parameters.toArray, pose, general.iteration, status), "gingr_fitter_set_state")
     check(run(fitter), "gingr_fitter query")
   }
 
-  def updateOnce(general: GeneralRegistrationState, run: Long => Int): (Array[Double], Array[Double], Int) = {
+  // after (optional): runs once the state is back, with the fitter (HipTemplate.scala asks whether the update committed)
+  def updateOnce(general: GeneralRegistrationState, run: Long => Int, after: Long => Unit = _ => ()): (Array[Double], Array[Double], Int) = {
     val mp = general.modelParameters
     val a = mp.pose.rotation.angles
     val c = mp.pose.rotation.center
@@ -106,8 +107,12 @@ final class HipSession(device: Int) extends AutoCloseable {
     val poseOut = new Array[Double](11)
     val iterStatus = new Array[Int](2)
     check(GingrHipNative.fitterGetState(fitter, alpha, poseOut, iterStatus, null), "gingr_fitter_get_state")
+    after(fitter)
     (alpha, poseOut, iterStatus(1))
   }
+
+  /** sigma2 of the device state only: a plugin's own updateSigma2 applied between updates */
+  def setSigma2(sigma2: Double): Unit = check(GingrHipNative.fitterSetSigma2(fitter, sigma2), "gingr_fitter_set_sigma2")
 
   // flattened copies of the last meshes seen (a TriangleMesh is immutable: identity is enough); the target of a registration
   // never changes and a state's fit is asked for several times (getCorrespondence, getUncertainty, updateSigma2)
