@@ -4,6 +4,7 @@
 #pragma once
 
 #include "gp.h"
+#include "surface.h"
 
 #include <cstdlib>
 #include <vector>
@@ -74,7 +75,7 @@ struct gingr_fitter {
     int32_t stop_hit = 0;          // DevState::stopped as of the last gingr_fitter_get_state
     int32_t last_err = 0;          // DevState::pad (error code of the last update, 0: it committed) as of the last gingr_fitter_get_state
     bool has_state = false;
-    // ---- ICP surface correspondence (surface.hip): triangles in device vertex positions and a spatial triangle order
+    // ---- ICP surface correspondence (surface.h, surface*.hip): triangles in device vertex positions and a spatial triangle order
     bool icp_surface = false;                      // correspondence flavour of the ICP phases
     int32_t surface_method = 0;                    // 0 TriangularClosestPoint, 1 AlongNormalClosestPoint (ICP.scala:32-34)
     // reversed correspondence direction (ICP.scala:46-48): per TARGET vertex buffers, then one observation per model vertex
@@ -168,7 +169,7 @@ struct gingr_fitter {
     bool surf_tri_warm = false;
     bool nn_warm = false, surf_nn_warm = false;  // nn_idx / surf_nn hold last time's matches against the CURRENT target
     NNGrid tgrid;  // uniform grid over the target cloud (set_target): the point-cloud ICP's closest-point search (nn_grid.hip)
-    TriGrid ttgrid;  // uniform grid over the target TRIANGLES (set_meshes): the surface ICP's closest surface point (surface.hip)
+    TriGrid ttgrid;  // uniform grid over the target TRIANGLES (set_meshes): the surface ICP's closest surface point (surface_grid.hip, surface.hip)
     MovGrid mgrid;   // the same over the TEMPLATE's triangles, rebuilt on the device every iteration: the self-intersection test (round 5)
     void forget_posteriors() {
         post_stage = 0;

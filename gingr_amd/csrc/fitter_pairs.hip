@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void pairs_keys_kernel(int64_t K, const int32_
 // Per local vertex i (device row): its pairs are a run of the stably sorted keys, walked in ascending pair position.
 //   weight_in[i] = sum 1 / var_k,   obs[.][i] = (sum x_k / var_k) / weight_in[i];   no pair (or total weight 0): weight 0, obs 0
 // -- k isotropic observations of one point are one observation of their precision-weighted mean (the identity the reversed ICP
-// direction uses with equal weights: reversal_gather_kernel, surface.hip).  Non-finite values are passed on: they fail the posterior.
+// direction uses with equal weights: reversal_gather_kernel, surface_reversal.hip).  Non-finite values are passed on: they fail the posterior.
 __global__ __launch_bounds__(256) void pairs_gather_kernel(int64_t M, int64_t K, const int32_t *__restrict__ skeys,
                                                            const int32_t *__restrict__ svals, const double *__restrict__ xyz,
                                                            const double *__restrict__ var, double *__restrict__ obs,

@@ -95,7 +95,7 @@ def modelFromLog(ctx: Context, model, log: Sequence[gio.JsonLogEntry], alignment
 # ---------------------------------------------------------------------------------------------------------------- posterior maps
 def vertex_normals(vertices: np.ndarray, cells: np.ndarray) -> np.ndarray:
     """scalismo TriangleMesh.vertexNormals [SCALISMO-RECALL]: mean of the unit normals (b - a) x (c - a) of the adjacent cells
-    (same rule as gingr_amd/csrc/surface.hip: vertex_normals_kernel)."""
+    (same rule as gingr_amd/csrc/surface_mesh.hip: vertex_normals_kernel)."""
     v, c = np.asarray(vertices, dtype=np.float64), np.asarray(cells, dtype=np.int64)
     n = np.cross(v[c[:, 1]] - v[c[:, 0]], v[c[:, 2]] - v[c[:, 0]])
     n = n / np.sqrt((n * n).sum(1))[:, None]

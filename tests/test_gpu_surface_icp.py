@@ -204,7 +204,7 @@ def test_along_normal_flavour(ctx):
 @pytest.mark.parametrize("case", ["inside", "offset", "flat"])
 def test_along_normal_search_orders_and_culls_exactly(ctx, case):
     """The along-normal search visits the target's triangle tiles in shells round a workgroup's points and culls by the hits found so
-    far (surface.hip line_nearest_kernel): a template well INSIDE the target (no hit in the first shells, both sides of the closed
+    far (surface_line.hip line_nearest_kernel): a template well INSIDE the target (no hit in the first shells, both sides of the closed
     target pierced), one offset so that lines leave the target on one side only, and an exactly flat template (vertex normals exactly
     (0, 0, 1): the lines are parallel to an axis, the slab test's zero-direction branch) -- all against the oracle's exhaustive search."""
     import gingr_amd as ga
@@ -570,3 +570,33 @@ def test_gram_downdate_leaves_to_the_pass_over_the_basis_when_many_rows_are_reje
         json.dump(rec, fh)
     # loose bound here (a wall-clock figure in a test); the measured difference is recorded above and in profiles/
     assert per_it[-1] <= 1.25 * per_it[0] + 10e-6, rec
+
+
+@pytest.fixture(scope="module")
+def sheet_queries():
+    """16 385 queries against the 288-triangle sheet and their brute-force closest points, computed once: the special queries come
+    first, so every prefix the test below takes holds them."""
+    from oracle import c_oracle as co
+    from tests.tri_grid_cases import sheet
+    V, C = sheet()
+    rng = np.random.default_rng(21)
+    P = np.concatenate([V[:40],                                                   # exactly on vertices
+                        0.5 * (V[C[:40, 0]] + V[C[:40, 1]]),                      # exactly on edges
+                        (V[C[:40, 0]] + V[C[:40, 1]] + V[C[:40, 2]]) / 3.0,       # inside triangles
+                        rng.uniform([-1.0, -1.0, -1.0], [2.0, 2.0, 1.0], (16385 - 120, 3))])   # within one sheet width of the sheet
+    want_cp, want_d2, _ = co.mesh_closest_point(P, V, C)
+    return V, C, P, want_cp, want_d2
+
+
+@pytest.mark.parametrize("nq", [4096, 4097, 16384, 16385])
+def test_tile_scan_instances_on_both_sides_of_their_query_count_thresholds(ctx, sheet_queries, nq):
+    """The tile scan holds 16, 8 or 4 copies of a query per workgroup, chosen by the number of queries (surface.h: surface_h, up to
+    4 096 -> 16, up to 16 384 -> 8, else 4): every instance, on a mesh whose last tile (32 of 256 triangles) and last quarter are
+    partial, against the brute-force oracle (tolerances of test_closest_points_with_triangle_and_barycentric_weights, extent 1)."""
+    V, C, P, want_cp, want_d2 = sheet_queries
+    assert C.shape == (288, 3) and P.shape == (16385, 3)
+    cp, d2, tid, bary = ctx.mesh_closest_points(P[:nq], V, C)
+    assert np.allclose(cp, want_cp[:nq], atol=1e-10) and np.allclose(d2, want_d2[:nq], atol=1e-9)
+    assert tid.min() >= 0 and tid.max() < C.shape[0]
+    rebuilt = (bary[:, :, None] * V[C[tid]]).sum(1)                               # the weights reproduce the closest point
+    assert np.allclose(rebuilt, cp, atol=1e-10)
