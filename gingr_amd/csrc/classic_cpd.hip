@@ -1,5 +1,5 @@
 // Classic Coherent Point Drift (the reference's `other/` family, Myronenko & Song 2010) on the device: a second consumer of the
-// streaming affinity statistics (affinity.hip) and of the Gaussian kernel block.
+// streaming affinity statistics (cpd_pairs.hip) and of the Gaussian kernel block.
 //
 //   CPDFactory(templatePoints, lambda, beta, w)         G/other/algorithms/cpd/CPDFactory.scala:28-80   (G = exp(-|a-b|^2 / 2 beta^2))
 //   RigidCPD.Expectation / Maximization / Registration  G/other/algorithms/cpd/RigidCPD.scala:59-139
@@ -14,6 +14,7 @@
 // over the whole chip) with the three right-hand sides riding along as extra rows of the matrix (the forward
 // substitution is a by-product), a blocked backward substitution, and TY = Y + G W as one pass over G.
 #include "common.h"
+#include "block_sum.h"
 #include "dense_spd.h"
 #include "svd3.h"
 
@@ -27,17 +28,6 @@ constexpr int kNBc = DenseSpdWork::kBlock;  // Cholesky panel width
 constexpr int kRedBlocks = 64;  // workgroups of the O(M + N) reductions
 
 Cloud cloud_at(const double *soa, int64_t n) { return Cloud{soa, soa + n, soa + 2 * n, n}; }
-
-__device__ __forceinline__ double block_sum256(double v, double *sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
 
 // partial[b][0..2] = sum_j Pt1_j x_j, [3..5] = sum_i P1_i y_i
 __global__ __launch_bounds__(256) void means_kernel(Cloud X, const double *__restrict__ Pt1, Cloud Y, const double *__restrict__ P1,
@@ -57,7 +47,8 @@ __global__ __launch_bounds__(256) void means_kernel(Cloud X, const double *__res
         a[5] += p * Y.z[i];
     }
     for (int q = 0; q < 6; ++q) {
-        const double t = block_sum256(a[q], sh);
+        __syncthreads();  // sh is reused by every pass
+        const double t = block_sum<256>(a[q], sh);
         if (threadIdx.x == 0) partial[blockIdx.x * 6 + q] = t;
     }
 }
@@ -95,7 +86,8 @@ __global__ __launch_bounds__(256) void moments_kernel(Cloud X, const double *__r
         a[18] += Pt1[j] * ((dx * dx + dy * dy) + dz * dz);
     }
     for (int q = 0; q < 19; ++q) {
-        const double t = block_sum256(a[q], sh);
+        __syncthreads();  // sh is reused by every pass
+        const double t = block_sum<256>(a[q], sh);
         if (threadIdx.x == 0) partial[blockIdx.x * 19 + q] = t;
     }
 }
@@ -228,8 +220,10 @@ __global__ __launch_bounds__(256) void nonrigid_sums_kernel(int64_t M, const dou
         a += P1[i] * ((x * x + y * y) + z * z);
         b += (x * PX[i] + y * PX[M + i]) + z * PX[2 * M + i];
     }
-    const double ta = block_sum256(a, sh);
-    const double tb = block_sum256(b, sh);
+    __syncthreads();
+    const double ta = block_sum<256>(a, sh);
+    __syncthreads();  // sh is reused
+    const double tb = block_sum<256>(b, sh);
     if (threadIdx.x == 0) {
         partial[blockIdx.x * 2] = ta;
         partial[blockIdx.x * 2 + 1] = tb;

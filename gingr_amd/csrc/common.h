@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/gingr_hip.h"
+#include "host_device.h"
 
 #define GINGR_TIMERS 17
 
@@ -30,7 +31,7 @@ struct gingr_ctx {
     std::vector<hipEvent_t> pool;  // recycled events
     double t_ms[GINGR_TIMERS] = {0};
     int64_t t_n[GINGR_TIMERS] = {0};
-    // exact-zero tile culling of the CPD passes and exact pruning of the closest-point scans (affinity.hip); gingr_ctx_set_option
+    // exact-zero tile culling of the CPD passes and exact pruning of the closest-point scans (cpd_pairs.hip, nn_scan.hip); gingr_ctx_set_option
     // (GINGR_OPT_CULL, 0) disables both (results must stay bit-identical: the culling test compares the two)
     int cull = 1;
     // GINGR_OPT_TRI_GRID: closest surface point over the target's triangle grid (surface.hip) in front of the tile scan: 0 never, 1 from
@@ -128,38 +129,23 @@ struct TimerScope {
     ~TimerScope();
 };
 
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
-
-// ---------------------------------------------------------------------------- affinity.hip (launchers, all async)
+// All launchers are asynchronous on the context's stream.
 // Points on the device are SoA: x[n], y[n], z[n] contiguous planes of one allocation (plane stride = n).
 struct Cloud {
     const double *x, *y, *z;
     int64_t n;
 };
 
+// ---------------------------------------------------------------------------- cpd_pairs.hip (the two all-pairs passes of CPD)
 // workspace sizes (in doubles) the launchers need
 int64_t cpd_colsum_ws_doubles(int64_t M, int64_t N);
 int64_t cpd_rowstats_ws_doubles(int64_t M, int64_t N);
-int64_t nn_ws_bytes(int64_t M, int64_t N);
-// all pairs of two small clouds, both in the caller's order: one launch of ~4 000 single-wave workgroups + the combination of their
-// slices (affinity.hip: nn_small_kernel); the stateless gingr_nn uses it where it applies
-bool nn_small_applies(int64_t M, int64_t N);
-int64_t nn_small_ws_bytes(int64_t M, int64_t N);
-void launch_nn_small(gingr_ctx *ctx, Cloud query, Cloud target, void *ws, int32_t *idx, double *d2);
-
 // den_partial[N] = sum_{i in fit} exp(-|x_j - y_i|^2 / (2 sigma2))   (no outlier constant)
 // aux (GINGR_AUX doubles on the device): [2..4] centroid of the target cloud (launch_cloud_centroid); [0] / [1] largest
 // |coordinate - centroid| of the target / fit cloud (launch_cloud_absmax).  From them the kernels decide, wave-uniformly,
 // (a) whether the exponent argument needs clamping and (b) whether the cheaper norm-expansion form of c|x-y|^2 is
-// accurate enough (affinity.hip: use_expansion).
+// accurate enough (cpd_pairs.hip: use_expansion).
 #define GINGR_AUX 8
-void launch_cloud_centroid(gingr_ctx *ctx, Cloud c, double *out3);
-void launch_cloud_absmax(gingr_ctx *ctx, Cloud c, const double *ctr, double *slot);
-// boxes[tile] = {lo[3], hi[3]} of every 256-point tile of a cloud: input of the exact-zero tile culling
-// with absmax_slot != nullptr also *absmax_slot = max |coordinate - ctr| (same value launch_cloud_absmax produces); the slot
-// must have been zeroed by an earlier launch on the stream
-void launch_tile_bbox(gingr_ctx *ctx, Cloud c, double *boxes, const double *ctr = nullptr, double *absmax_slot = nullptr);
 // returns the number of chunk partials left in ws ([chunk][N]); den_partial == nullptr skips their reduction (the caller passes
 // ws and the count to launch_cpd_den_finalize, which then adds them up itself: single shard, one launch less)
 // forced_chunks > 0: exactly that many chunks of the streamed rows, balanced to a quarter (a half of a split column-sum pass keeps
@@ -192,6 +178,13 @@ void launch_cpd_rowstats(gingr_ctx *ctx, Cloud fit, Cloud target, const double *
                          const double *inv_den, const double *tgt_boxes, const int32_t *tile_bad, double *ws, double *P1,
                          double *PX_soa, double *part, double *scalars_dev, double *xch8 = nullptr, int contribute_xpx = 1,
                          const CpdObsArgs *obs = nullptr, bool finish_scalars = true);
+// ---------------------------------------------------------------------------- nn_scan.hip (exact nearest neighbour)
+int64_t nn_ws_bytes(int64_t M, int64_t N);
+// all pairs of two small clouds, both in the caller's order: one launch of ~4 000 single-wave workgroups + the combination of their
+// slices (nn_scan.hip: nn_small_kernel); the stateless gingr_nn uses it where it applies
+bool nn_small_applies(int64_t M, int64_t N);
+int64_t nn_small_ws_bytes(int64_t M, int64_t N);
+void launch_nn_small(gingr_ctx *ctx, Cloud query, Cloud target, void *ws, int32_t *idx, double *d2);
 // idx[i] = POSITION (in the device order of `target`) of the nearest target; exact ties are broken by the lowest ORIGINAL
 // index, taken from target_orig[position] (nullptr: the device order is the original order).
 // tgt_boxes (nullable): bounding boxes of the 256-point target tiles (launch_tile_bbox) for exact nearest-first pruning.
@@ -230,6 +223,13 @@ int nn_grid_build(gingr_ctx *ctx, const double *target_xyz, int64_t N, const int
 void nn_grid_free(NNGrid *g);
 bool launch_nn_grid(gingr_ctx *ctx, Cloud query, Cloud target, const int32_t *target_orig, NNGrid &g, const int32_t *warm,
                     int32_t *idx, double *d2);
+// ---------------------------------------------------------------------------- cloud_ops.hip (per-cloud kernels, layouts, k-d order)
+void launch_cloud_centroid(gingr_ctx *ctx, Cloud c, double *out3);
+void launch_cloud_absmax(gingr_ctx *ctx, Cloud c, const double *ctr, double *slot);
+// boxes[tile] = {lo[3], hi[3]} of every 256-point tile of a cloud: input of the exact-zero tile culling
+// with absmax_slot != nullptr also *absmax_slot = max |coordinate - ctr| (same value launch_cloud_absmax produces); the slot
+// must have been zeroed by an earlier launch on the stream
+void launch_tile_bbox(gingr_ctx *ctx, Cloud c, double *boxes, const double *ctr = nullptr, double *absmax_slot = nullptr);
 void launch_gauss_block(gingr_ctx *ctx, Cloud A, Cloud B, double sigma, double scaling, double *out);
 // sum over all pairs of |a_i - b_j|^2 (computeInitialSigma2, CPD.scala:81-90); ws: sumsq_pairs_ws_doubles(A.n) doubles
 int64_t sumsq_pairs_ws_doubles(int64_t nA);
@@ -243,4 +243,4 @@ void launch_soa_to_aos(gingr_ctx *ctx, const double *soa, int64_t n, double *aos
 void launch_scatter(gingr_ctx *ctx, const double *in, int64_t n, const int32_t *perm, double *out);
 // spatial (balanced k-d tree, leaf = one 256-point tile) order of interleaved points: perm[s] = original index of the
 // point stored at device position s
-void morton_order(const double *xyz, int64_t n, std::vector<int32_t> &perm);
+void kd_leaf_order(const double *xyz, int64_t n, std::vector<int32_t> &perm);

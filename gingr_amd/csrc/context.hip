@@ -365,8 +365,8 @@ int gingr_nn(gingr_ctx *ctx, int64_t M, const double *query, int64_t N, const do
         }
     } grid_guard{ctx, &grid};
     if (ordered) {
-        morton_order(target, N, perm);
-        morton_order(query, M, qperm);
+        kd_leaf_order(target, N, perm);
+        kd_leaf_order(query, M, qperm);
         HIP_TRY(ctx, st.alloc((size_t)N * 3 * sizeof(double)));
         HIP_TRY(ctx, dt.alloc((size_t)N * 3 * sizeof(double)));
         HIP_TRY(ctx, sq.alloc((size_t)M * 3 * sizeof(double)));

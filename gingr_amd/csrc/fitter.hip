@@ -304,7 +304,7 @@ int gingr_fitter_set_target(gingr_fitter *f, int64_t N, const double *target_xyz
     GINGR_TRY(dev_alloc(ctx, &aos, (size_t)3 * big));
     f->aos = aos;
     HIP_TRY(ctx, hipMemcpyAsync(aos, target_xyz, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    morton_order(target_xyz, N, f->h_tperm);
+    kd_leaf_order(target_xyz, N, f->h_tperm);
     GINGR_TRY(nn_grid_build(ctx, target_xyz, N, f->h_tperm.data(), M, &f->tgrid));
     GINGR_TRY(dev_alloc(ctx, &f->tperm, (size_t)N));
     HIP_TRY(ctx, hipMemcpyAsync(f->tperm, f->h_tperm.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));

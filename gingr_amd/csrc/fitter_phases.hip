@@ -295,7 +295,7 @@ int build_template_order(gingr_fitter *f) {
     for (int64_t g = 0; g < Mt; ++g)
         for (int d = 0; d < 3; ++d) aosv[(size_t)(3 * g + d)] = soa[(size_t)(d * Mt + g)];
     std::vector<int32_t> order;
-    morton_order(aosv.data(), Mt, order);
+    kd_leaf_order(aosv.data(), Mt, order);
     int32_t *gperm = nullptr, *rnn_pos = nullptr;
     double *gsorted = nullptr;
     int rc = dev_alloc(ctx, &gperm, (size_t)Mt);

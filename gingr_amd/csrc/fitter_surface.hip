@@ -112,7 +112,7 @@ int gingr_fitter_set_meshes(gingr_fitter *f, int64_t n_model_tri, const int32_t 
                 for (int k = 0; k < 3; ++k) c += coord(tri[3 * t + k], d);
                 cen[(size_t)3 * t + d] = c / 3.0;
             }
-        morton_order(cen.data(), T, b.orig);  // orig[s] = original index of the triangle at device position s
+        kd_leaf_order(cen.data(), T, b.orig);  // orig[s] = original index of the triangle at device position s
         std::vector<int32_t> tpos2((size_t)T);
         b.tri.resize((size_t)3 * T);
         for (int64_t s2 = 0; s2 < T; ++s2) {
@@ -371,8 +371,8 @@ int run_distance_stats(gingr_ctx *ctx, Cloud q, Cloud v, const int32_t *tri, con
 void mesh_orders(int64_t n_points, const double *points, int64_t n_vertices, const double *vertices, int64_t n_triangles,
                  const int32_t *triangles, std::vector<int32_t> &qorder, std::vector<int32_t> &vorder, std::vector<int32_t> &torder,
                  std::vector<int32_t> &vinv, std::vector<int32_t> &tri) {
-    morton_order(points, n_points, qorder);
-    morton_order(vertices, n_vertices, vorder);
+    kd_leaf_order(points, n_points, qorder);
+    kd_leaf_order(vertices, n_vertices, vorder);
     vinv.resize((size_t)n_vertices);
     for (int64_t s2 = 0; s2 < n_vertices; ++s2) vinv[(size_t)vorder[(size_t)s2]] = (int32_t)s2;
     std::vector<double> cen((size_t)3 * n_triangles);
@@ -382,7 +382,7 @@ void mesh_orders(int64_t n_points, const double *points, int64_t n_vertices, con
             for (int k = 0; k < 3; ++k) c += vertices[(size_t)3 * triangles[3 * t + k] + d];
             cen[(size_t)3 * t + d] = c / 3.0;
         }
-    morton_order(cen.data(), n_triangles, torder);
+    kd_leaf_order(cen.data(), n_triangles, torder);
     tri.resize((size_t)3 * n_triangles);
     for (int64_t s2 = 0; s2 < n_triangles; ++s2)
         for (int k = 0; k < 3; ++k) tri[(size_t)3 * s2 + k] = vinv[(size_t)triangles[(size_t)3 * torder[(size_t)s2] + k]];
@@ -429,7 +429,7 @@ int gingr_fitter_surface_distance_stats(gingr_fitter *f, int32_t direction, int6
                                   out, f->pin, f->mtribox, f);
     if (n_points < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "surface_distance_stats: empty point list");
     std::vector<int32_t> order;
-    morton_order(points, n_points, order);
+    kd_leaf_order(points, n_points, order);
     std::vector<double> soa;
     gather_soa(points, order, soa);
     DevBuf q;

@@ -280,7 +280,7 @@ struct Phase1FinalizeArgs {
     int32_t sweep_blocks;
     double *rhs;
     int32_t scalar_mode;          // 0: clear the 8 scalars (ICP); 1: the four sums of the CPD passes from `part`
-    const double *part;           // GINGR_SCALAR_PART block partials (affinity.hip)
+    const double *part;           // GINGR_SCALAR_PART block partials (cpd_pairs.hip)
     double *scalars_local;        // nullable: the shard's own copy {Np, xPx, trPXY, yPy}
     double *sc8;                  // the 8 scalars of the exchange segment
     int32_t contribute_xpx;

@@ -118,7 +118,7 @@ int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const doubl
     {
         std::vector<double> pts((size_t)3 * M);
         for (int64_t i = 0; i < 3 * M; ++i) pts[(size_t)i] = ref[3 * row_begin + i] + mean[3 * row_begin + i];
-        morton_order(pts.data(), M, m->hperm);
+        kd_leaf_order(pts.data(), M, m->hperm);
         m->hiperm.resize((size_t)M);
         for (int64_t sidx = 0; sidx < M; ++sidx) m->hiperm[(size_t)m->hperm[(size_t)sidx]] = (int32_t)sidx;
         if ((rc = dev_alloc(ctx, &m->perm, (size_t)M)) || (rc = dev_alloc(ctx, &m->iperm, (size_t)M))) return fail(rc);

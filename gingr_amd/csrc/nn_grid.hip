@@ -1,6 +1,6 @@
 // Exact nearest neighbour over a uniform grid of the (fixed) target cloud: the closest-point step of the ICP update
 // (G/api/registration/utils/ClosestPointRegistrator.scala:33-44: closest target point per model vertex; ties -> lowest original
-// index, as the reference's linear argmin).  Same distances and the same answer as nn_kernel (affinity.hip) -- separately rounded
+// index, as the reference's linear argmin).  Same distances and the same answer as nn_kernel (nn_scan.hip) -- separately rounded
 // dx*dx + dy*dy + dz*dz, lowest original index on equal distances -- but each query tests the targets of a few grid cells instead of
 // whole 64-point tiles: ~15 tests per query instead of ~740 at 50k points.
 //
@@ -13,6 +13,7 @@
 // sqrt(best), up to kMaxR; a query that needs more (far from every target, nothing in its 27 cells, not finite) is FLAGGED and left
 // to nn_kernel, which runs masked right after (workgroups without a flagged query exit at once).
 #include "common.h"
+#include "box_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -25,10 +26,6 @@ constexpr int kMaxR = 3;  // largest half-width (in cells) of the block a query 
 // not scanned by its one lane: the query is flagged and the tile scan, which spreads the work over a workgroup, answers it.
 constexpr int kMaxRowTargets = 1024;
 constexpr int64_t kBruteTargets = 4096;  // target clouds up to this size: uncertified queries scan everything inside nn_grid_kernel
-
-__device__ __forceinline__ double grid_norm2_exact(double dx, double dy, double dz) {
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
 
 __device__ __forceinline__ int clamp_cell(double f, int g) {  // floor(f) clamped to [0, g - 1]; NaN -> 0
     const double c = floor(f);
@@ -76,7 +73,7 @@ __global__ __launch_bounds__(kGridBlock) void nn_grid_kernel(Cloud q, Cloud tgt,
         if (crowded) flagged = true;  // a row was left out: the answer may be incomplete
     };
     auto test = [&](const GridPoint &p) {
-        const double d = grid_norm2_exact(p.x - qx, p.y - qy, p.z - qz);
+        const double d = norm2_exact(p.x - qx, p.y - qy, p.z - qz);
         if (d < best || (d == best && p.orig < bo)) best = d, bo = p.orig, bi = p.pos;
     };
     // the block of cells [c - R, c + R] per axis, clamped to the grid (an interval wholly outside the grid is empty: nrows = 0)
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(kGridBlock) void nn_grid_kernel(Cloud q, Cloud tgt,
     if (warm && ok) {
         const int32_t p = warm[i];
         if (p >= 0 && p < tgt.n) {
-            const double d = grid_norm2_exact(tgt.x[p] - qx, tgt.y[p] - qy, tgt.z[p] - qz);
+            const double d = norm2_exact(tgt.x[p] - qx, tgt.y[p] - qy, tgt.z[p] - qz);
             if (d == d) best = d, bo = orig ? orig[p] : p, bi = p;
         }
     }

@@ -166,7 +166,7 @@ int gingr_rigid_icp_create(gingr_ctx *ctx, int32_t kind, int64_t M, const double
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipMemcpyAsync(h->stage.p, target_xyz, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     std::vector<int32_t> order;
-    morton_order(target_xyz, N, order);
+    kd_leaf_order(target_xyz, N, order);
     (void)hipMemcpyAsync(h->torig.p, order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
     launch_aos_to_soa(ctx, h->stage.as<double>(), N, h->tgt.as<double>(), h->torig.as<int32_t>());
     const double *t = h->tgt.as<double>();

@@ -14,7 +14,7 @@
 //
 // Triangles live in a spatial (k-d leaf) order with one bounding box per 256-triangle tile; a wave owns 64 spatially
 // coherent queries and skips every tile whose box cannot hold anything closer than what each lane already has -- the same
-// exact pruning as the nearest-neighbour kernel (affinity.hip).
+// exact pruning as the nearest-neighbour kernel (nn_scan.hip).
 #include "surface_device.h"
 
 namespace {
@@ -99,8 +99,7 @@ __global__ __launch_bounds__(kCpThreads) void surface_cp_queue_kernel(Cloud q, C
     __syncthreads();
     double best = __builtin_bit_cast(double, wbits), bound = __builtin_huge_val();
     WaveQueue wq{wqueue[wave], lane, 0};
-    double wb[6];
-    wave_box(ok, qx, qy, qz, wb);
+    const Box wb = wave_box(ok, qx, qy, qz);
     const int nt = (int)((T + kTriTile - 1) / kTriTile);
     const double *qboxes = boxes + (int64_t)nt * 6;
     // what every lane does with the pair it pops (WaveQueue::flush)
@@ -133,18 +132,18 @@ __global__ __launch_bounds__(kCpThreads) void surface_cp_queue_kernel(Cloud q, C
         best = __builtin_bit_cast(double, qbest[wave][ql]);  // every copy of the query prunes against the shared best
     };
     double gmin = __builtin_huge_val();
-    for (int t = lane; t < nt; t += 64) gmin = fmin(gmin, box_box_gap2(wb, boxes + (int64_t)t * 6));
+    for (int t = lane; t < nt; t += 64) gmin = fmin(gmin, box_gap2(wb, boxes + (int64_t)t * 6));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) gmin = fmin(gmin, __shfl_xor(gmin, off));
-    gmin = uniform_dd(gmin);
+    gmin = uniform_d(gmin);
     for (int phase = 0; phase < 2; ++phase) {
         double bmax = ok ? bound : 0.0;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) bmax = fmax(bmax, __shfl_xor(bmax, off));
-        bmax = uniform_dd(bmax) * (1.0 + 1e-12);
+        bmax = uniform_d(bmax) * (1.0 + 1e-12);
         for (int tc = 0; tc < nt; tc += 64) {
             const int tl = tc + lane;
-            const double g = tl < nt ? box_box_gap2(wb, boxes + (int64_t)tl * 6) : __builtin_huge_val();
+            const double g = tl < nt ? box_gap2(wb, boxes + (int64_t)tl * 6) : __builtin_huge_val();
             unsigned long long cand = __ballot(tl < nt && (phase == 0 ? !(g > gmin) : (g > gmin && !(g > bmax))));
             while (cand) {  // workgroup-uniform (same queries, same bound in every wave)
                 const int t = tc + __builtin_ctzll(cand);

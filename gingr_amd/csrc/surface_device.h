@@ -1,7 +1,9 @@
-// Device helpers of the surface kernels (surface*.hip): small vectors, the point / triangle and line / triangle routines, box gaps,
+// Device helpers of the surface kernels (surface*.hip): small vectors, the point / triangle and line / triangle routines, the point
+// to box gap (wave boxes and box to box gaps: box_device.h),
 // and the routines more than one kernel runs -- each has ONE body here.  Everything is inlined into its caller; arithmetic is written
 // without FMA contraction in the oracle's operation order, so a helper gives the bits its callers' own expressions gave.
 #pragma once
+#include "box_device.h"
 #include "surface.h"
 
 namespace {  // (one private copy per translation unit, like the kernels that use it)
@@ -14,12 +16,6 @@ struct V3 {
 __device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ double dot3(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ V3 cross3(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-
-__device__ __forceinline__ double uniform_dd(double v) {
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 
 // closest point of triangle (A, B, C) to p: Ericson, Real-Time Collision Detection 5.1.5, with his region tests in his order but
 // evaluated as selects: on a wavefront every lane lands in a different Voronoi region, so the branching form executes all seven
@@ -88,34 +84,6 @@ struct Corners { V3 A, B, C; };  // of triangle t of the mesh (v, tri)
 __device__ __forceinline__ Corners gather_corners(Cloud v, const int32_t *__restrict__ tri, int64_t t) {
     const int32_t a = tri[3 * t], b = tri[3 * t + 1], c = tri[3 * t + 2];
     return Corners{V3{v.x[a], v.y[a], v.z[a]}, V3{v.x[b], v.y[b], v.z[b]}, V3{v.x[c], v.y[c], v.z[c]}};
-}
-
-// wave-wide bounding box of the valid lanes' points
-__device__ __forceinline__ void wave_box(bool ok, double qx, double qy, double qz, double wb[6]) {
-    double lo[3] = {ok ? qx : __builtin_huge_val(), ok ? qy : __builtin_huge_val(), ok ? qz : __builtin_huge_val()};
-    double hi[3] = {ok ? qx : -__builtin_huge_val(), ok ? qy : -__builtin_huge_val(), ok ? qz : -__builtin_huge_val()};
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            lo[d] = fmin(lo[d], __shfl_xor(lo[d], off));
-            hi[d] = fmax(hi[d], __shfl_xor(hi[d], off));
-        }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        wb[d] = uniform_dd(lo[d]);
-        wb[3 + d] = uniform_dd(hi[d]);
-    }
-}
-
-__device__ __forceinline__ double box_box_gap2(const double a[6], const double *__restrict__ b) {
-    double s = 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const double g = fmax(fmax(a[d] - b[3 + d], b[d] - a[3 + d]), 0.0);
-        s = __builtin_fma(g, g, s);
-    }
-    return s;
 }
 
 // bb[6] = the box of triangle tt: as tri_tile_bbox_kernel left it in tribox (one contiguous read), or rebuilt from its corners

@@ -91,10 +91,9 @@ __global__ __launch_bounds__(kSurfThreads) void line_nearest_kernel(Cloud fit, c
     // patches.  A tile belongs to the shell its box's gap from the points' centre falls into; the sweeps end when every line has a hit
     // nearer than the shell reached, or the farthest box corner is inside it.
     const int ngroups = (nt + kLineGroup - 1) / kLineGroup;
-    double wb[6];
-    wave_box(ok, p.x, p.y, p.z, wb);
-    const double cx = 0.5 * (wb[0] + wb[3]), cy = 0.5 * (wb[1] + wb[4]), cz = 0.5 * (wb[2] + wb[5]);
-    const double ext = sqrt((wb[3] - wb[0]) * (wb[3] - wb[0]) + (wb[4] - wb[1]) * (wb[4] - wb[1]) + (wb[5] - wb[2]) * (wb[5] - wb[2]));
+    const Box wb = wave_box(ok, p.x, p.y, p.z);
+    const double cx = 0.5 * (wb.lo[0] + wb.hi[0]), cy = 0.5 * (wb.lo[1] + wb.hi[1]), cz = 0.5 * (wb.lo[2] + wb.hi[2]);
+    const double ext = sqrt((wb.hi[0] - wb.lo[0]) * (wb.hi[0] - wb.lo[0]) + (wb.hi[1] - wb.lo[1]) * (wb.hi[1] - wb.lo[1]) + (wb.hi[2] - wb.lo[2]) * (wb.hi[2] - wb.lo[2]));
     double gmin2 = __builtin_huge_val(), gfar2 = 0.0;  // nearest gap / farthest corner of the group boxes from the centre
     for (int g = 0; g < ngroups; ++g) {
         const double *gb = gboxes + (int64_t)g * 6;

@@ -76,15 +76,14 @@ __global__ __launch_bounds__(kCpThreads) void self_intersect_queue_kernel(Cloud 
     };
     const int nt = (int)((T + kTriTile - 1) / kTriTile);
     const double *qboxes = boxes + (int64_t)nt * 6;
-    double wb[6];
-    wave_box(ok, p.x, p.y, p.z, wb);
+    const Box wb = wave_box(ok, p.x, p.y, p.z);
     double vmax = ok ? vv : 0.0;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, off));
-    vmax = uniform_dd(vmax) * (1.0 + 1e-12);
+    vmax = uniform_d(vmax) * (1.0 + 1e-12);
     for (int tc = 0; tc < nt; tc += 64) {
         const int tl = tc + lane;
-        unsigned long long cand = __ballot(tl < nt && !(box_box_gap2(wb, boxes + (int64_t)tl * 6) > vmax));
+        unsigned long long cand = __ballot(tl < nt && !(box_gap2(wb, boxes + (int64_t)tl * 6) > vmax));
         while (cand) {  // workgroup-uniform
             const int t = tc + __builtin_ctzll(cand);
             cand &= cand - 1;

@@ -8,11 +8,7 @@
 #include <cstring>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define GINGR_HD __host__ __device__
-#else
-#define GINGR_HD
-#endif
+#include "host_device.h"
 
 constexpr int kTriRec = 10;          // doubles per grid entry behind its box: corners A, B, C, {position | original index << 32}
 constexpr int kTriGridMaxSpan = 3;   // a listed triangle's box spans at most this many cell steps per axis (wider ones: the short list)

@@ -1,6 +1,6 @@
 """Element-wise tests of the two CPD pair passes with exact-zero culling ON, at every kernel instance and arithmetic form.
 
-The stateless `Context.cpd_stats` runs `cpd_colsum_kernel` / `cpd_rowstats_kernel` (gingr_amd/csrc/affinity.hip) without boxes,
+The stateless `Context.cpd_stats` runs `cpd_colsum_kernel` / `cpd_rowstats_kernel` (gingr_amd/csrc/cpd_pairs.hip) without boxes,
 so the dense-reference tests never see `PartWalk` with boxes, the MASKED tile loops, the FINE kernels or the `tile_bad`
 exemption.  Here the statistics come out of the fitter (the only caller that culls): set_state -> one update -> get_cpd_stats,
 which are the statistics of the evaluation at the state that was set, and are compared
@@ -15,7 +15,7 @@ Inputs are clustered clouds (seven boxes of half-width 6 on corners of a cube of
 be skipped, and the cluster sizes are off the 64 grid, so that tiles and 64-point quarters straddling two clusters give partly
 set slot masks.  Which arithmetic form a case runs (norm expansion / plain differences / clamped differences) and whether
 anything can be culled is asserted in numpy from the actual inputs with the kernels' own predicates (`regime_of`): a later
-change of the thresholds in affinity.hip or fastexp.h makes these tests fail instead of silently testing another branch.
+change of the thresholds in cpd_pairs.hip, cpd_plan.h or fastexp.h makes these tests fail instead of silently testing another branch.
 """
 import functools
 

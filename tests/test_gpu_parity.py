@@ -90,7 +90,7 @@ def test_initial_sigma2(ctx):
 
 @pytest.mark.parametrize("offset", [0.0, 1e4])
 def test_initial_sigma2_from_moments(ctx, offset):
-    """From 2^20 pairs on the sum over all pairs comes from the clouds' moments about the first point (affinity.hip
+    """From 2^20 pairs on the sum over all pairs comes from the clouds' moments about the first point (cloud_ops.hip
     cloud_moments_kernel); clouds 10^4 away from the origin (200 times their extent) must not cost digits."""
     y, x = clouds(2100, 3000, seed=6)
     y, x = y + offset, x + offset + 3.0

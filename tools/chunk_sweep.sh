@@ -1,6 +1,6 @@
 #!/bin/bash
 # Launch-round experiment: iteration time for forced chunk counts of the two all-pairs passes.  The counts are BUILD-time knobs
-# (-DGINGR_COLSUM_CHUNKS / -DGINGR_ROWSTATS_CHUNKS, affinity.hip): every count is its own library, built here (needs hipcc on the box).
+# (-DGINGR_COLSUM_CHUNKS / -DGINGR_ROWSTATS_CHUNKS, cpd_plan.h): every count is its own library, built here (needs hipcc on the box).
 # usage: tools/chunk_sweep.sh "<colsum counts>" "<rowstats counts>" [bench args]
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 CS=$1; RS=$2; shift 2

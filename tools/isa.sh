@@ -1,5 +1,5 @@
 #!/bin/bash
-# Device ISA of one translation unit of the library: tools/isa.sh affinity [extra -D flags] -> /tmp/<name>.s, then the register / scratch /
+# Device ISA of one translation unit of the library: tools/isa.sh cpd_pairs [extra -D flags] -> /tmp/<name>.s, then the register / scratch /
 # occupancy lines of the kernels whose mangled name matches $KERNELS (regular expression; default: all).
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift

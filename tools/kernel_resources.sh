@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / LDS / occupancy figures of every kernel of one HIP source, as the compiler reports them
-# (-Rpass-analysis=kernel-resource-usage).  usage: tools/kernel_resources.sh gingr_amd/csrc/affinity.hip [name filter]
+# (-Rpass-analysis=kernel-resource-usage).  usage: tools/kernel_resources.sh gingr_amd/csrc/cpd_pairs.hip [name filter]
 SRC=$1; PAT=${2:-.}
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -c $SRC -o /dev/null \
   -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "

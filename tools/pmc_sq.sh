@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ issue / LDS counters of the affinity kernels (two PMC passes, kernel-trace only).  Run on the GPU box via gpurun.
+# SQ issue / LDS counters of the CPD pair kernels (cpd_pairs.hip) (two PMC passes, kernel-trace only).  Needs a GPU.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc_sq

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-wave time stamps of the two CPD pair loops on a row shard (diagnostic build, see affinity.hip: GINGR_STAMPS).
+"""Per-wave time stamps of the two CPD pair loops on a row shard (diagnostic build, see cpd_pairs.hip: GINGR_STAMPS).
 
 usage (GPU box):  make -C gingr_amd/csrc variant NAME=stamps DEFS=-DGINGR_STAMPS        (here, cross-compiled)
                   GINGR_HIP_LIB=gingr_amd/libgingr_hip_stamps.so python3 tools/stamps_shard.py [world] [points] > profile.txt
