@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GINGR_HIP_LIB") or os.path.join(_HERE, "libgingr_hip.so")
 
 GINGR_OK = 0
-ERR_BAD_ARGUMENT, ERR_HIP, ERR_NONFINITE, ERR_NOT_SPD, ERR_NO_DEVICE, ERR_STATE = 1, 2, 3, 4, 5, 6
+ERR_BAD_ARGUMENT, ERR_HIP, ERR_NONFINITE, ERR_NOT_SPD, ERR_NO_DEVICE, ERR_STATE, ERR_NOT_CONVERGED = 1, 2, 3, 4, 5, 6, 7
 NUM_PHASES = 3
 NUM_SEGMENTS = 2
 SEGMENT_FULLFIT = 2   # the gather of a sharded surface update (gingr_hip.h)
@@ -26,7 +26,7 @@ RCCL_UNIQUE_ID_BYTES = 128
 
 _STATUS_NAMES = {
     1: "GINGR_ERR_BAD_ARGUMENT", 2: "GINGR_ERR_HIP", 3: "GINGR_ERR_NONFINITE", 4: "GINGR_ERR_NOT_SPD",
-    5: "GINGR_ERR_NO_DEVICE", 6: "GINGR_ERR_STATE",
+    5: "GINGR_ERR_NO_DEVICE", 6: "GINGR_ERR_STATE", 7: "GINGR_ERR_NOT_CONVERGED",
 }
 
 
@@ -104,6 +104,11 @@ class AugmentInfo(ctypes.Structure):
     _fields_ = [("columns", c_int32), ("rank", c_int32), ("total_variance", c_double), ("kept_variance", c_double)]
 
 
+class NicpInfo(ctypes.Structure):
+    """gingr_nicp_info"""
+    _fields_ = [("iterations", c_int32), ("converged", c_int32), ("residual", c_double * 3), ("rhs_norm", c_double * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/gingr_hip.h declares
 SIGNATURES = {
     "gingr_device_count": (c_int, []),
@@ -152,6 +157,10 @@ SIGNATURES = {
     "gingr_fitter_set_fit_points": (c_int, [c_void_p, _dp]),
     "gingr_nicp_solve": (c_int, [c_void_p, c_int32, c_int64, _dp, c_int64, _ip, _dp, _dp, c_int32, _ip, _dp, c_double, c_double, c_double,
                                  _dp, _dp]),
+    "gingr_nicp_create": (c_int, [c_void_p, c_int32, c_int64, c_int64, _ip, c_int32, _ip, POINTER(c_void_p)]),
+    "gingr_nicp_destroy": (None, [c_void_p]),
+    "gingr_nicp_step": (c_int, [c_void_p, _dp, _dp, _dp, _dp, c_double, c_double, c_double, c_double, c_int32, _dp, _dp, POINTER(NicpInfo)]),
+    "gingr_nicp_get_solution": (c_int, [c_void_p, _dp]),
     "gingr_mesh_closest_points": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_int64, _ip, _dp, _dp, _ip, _dp]),
     "gingr_mesh_decimate": (c_int, [c_void_p, c_int64, _dp, c_int64, _ip, c_int64, POINTER(c_int64), _ip, POINTER(c_int64), _ip, _dp]),
     "gingr_model_new_reference": (c_int, [c_void_p, c_void_p, c_int64, _dp, _ip, _dp, c_int64, c_int64, POINTER(c_void_p)]),

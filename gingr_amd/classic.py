@@ -267,17 +267,29 @@ class NonRigidOptimalStepICP:
     Registration"): `kind` "T" = N-ICP-T (one displacement per vertex), "A" = N-ICP-A (one affine 4 x 3 map per vertex).
     Both halves of an iteration run on the GPU: the correspondence (closest target surface point + the three rejection tests of
     ClosestPointTriangleMesh3D: the surface-ICP query of the GiNGR path, asked for the current template through
-    gingr_fitter_set_fit_points) and the least-squares step (gingr_nicp_solve: normal equations, blocked MFMA Cholesky).
+    gingr_fitter_set_fit_points) and the least-squares step.  `solver`: "dense" (gingr_nicp_solve: the normal equations as a dense
+    matrix, blocked MFMA Cholesky; templates of a few thousand vertices) or "sparse" (gingr_nicp_step: the same equations matrix-free,
+    block-Jacobi preconditioned conjugate gradients over the edge graph; no size limit but the card's memory for a dozen vectors).
+    relTol / maxSolverIterations: the sparse solver's stop (None: 1e-12, 20 000); `solveInfo` holds its last info block.
     Landmarks: two mappings id -> point; the common ids are used (:45-55)."""
 
     def __init__(self, ctx: Context, templateMesh, targetMesh, templateLandmarks=None, targetLandmarks=None, gamma: float = 1.0,
-                 kind: str = "T"):
+                 kind: str = "T", solver: str = "dense", relTol: Optional[float] = None, maxSolverIterations: Optional[int] = None):
         from . import api as ga
         if gamma < 0:
             raise ValueError("gamma >= 0 required")
         if kind not in ("T", "A"):
             raise ValueError("kind is 'T' or 'A'")
+        if solver not in ("dense", "sparse"):
+            raise ValueError("solver is 'dense' or 'sparse'")
+        if relTol is not None and not 0.0 < relTol <= 1.0:
+            raise ValueError("0 < relTol <= 1 required")
+        if maxSolverIterations is not None and maxSolverIterations < 1:
+            raise ValueError("maxSolverIterations >= 1 required")
         self.ctx, self.kind, self.gamma = ctx, kind, float(gamma)
+        self.solver, self.relTol, self.maxSolverIterations = solver, relTol, maxSolverIterations
+        self.solveInfo = None
+        self._nicp = None
         self.template = f64(templateMesh[0])
         self.cells = np.ascontiguousarray(templateMesh[1], dtype=np.int32).reshape(-1, 3)
         self.target = f64(targetMesh[0])
@@ -301,11 +313,37 @@ class NonRigidOptimalStepICP:
         self._state = self._algo.createInitialState(self._model, self.target, cfg, transform=ga.GlobalTranformationType.NoTransforms,
                                                     targetCells=self.targetCells)
         self._lib = ctx._lib
+        if solver == "sparse":
+            from ._native import iptr
+            h = c_void_p()
+            L = self.lmIdsOnTemplate.shape[0]
+            _check(ctx.handle, self._lib.gingr_nicp_create(ctx.handle, 0 if kind == "T" else 1, self.n, self.edges.shape[0], iptr(self.edges), L,
+                                                           iptr(self.lmIdsOnTemplate) if L else None, ctypes.byref(h)), "gingr_nicp_create")
+            self._nicp = h
 
     def close(self):
-        if self._algo is not None:
+        if getattr(self, "_nicp", None):
+            self._lib.gingr_nicp_destroy(self._nicp)
+            self._nicp = None
+        if getattr(self, "_algo", None) is not None:
             self._algo.close()
             self._algo = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_nicp", None):
+                self._lib.gingr_nicp_destroy(self._nicp)
+                self._nicp = None
+        except Exception:
+            pass
+
+    def solution(self) -> np.ndarray:
+        """the unknowns X of the last sparse step: (n, 3) displacements (T) or (4 n, 3), row 4 i + a of vertex i (A)"""
+        if self._nicp is None:
+            raise ValueError("solver='sparse' required")
+        x = np.empty(((1 if self.kind == "T" else 4) * self.n, 3))
+        _check(self.ctx.handle, self._lib.gingr_nicp_get_solution(self._nicp, dptr(x)), "gingr_nicp_get_solution")
+        return x
 
     def getClosestPoints(self, template) -> Tuple[np.ndarray, np.ndarray, float]:
         """(:118-128) (closest target surface points, weights in {0, 1}, mean distance) of the given template points."""
@@ -337,6 +375,16 @@ class NonRigidOptimalStepICP:
         pts = f64(template)
         cp, w, dist = self.getClosestPoints(pts)
         out, lm = np.empty((self.n, 3)), np.empty((self.lmIdsOnTemplate.shape[0], 3))
+        if self.solver == "sparse":
+            from ._native import NicpInfo
+            info = NicpInfo()
+            rc = self._lib.gingr_nicp_step(self._nicp, dptr(pts), dptr(w), dptr(cp), dptr(self.UL) if len(self.UL) else None, float(alpha),
+                                           float(beta), self.gamma, float(self.relTol or 0.0), int(self.maxSolverIterations or 0), dptr(out),
+                                           dptr(lm) if len(lm) else None, ctypes.byref(info))
+            self.solveInfo = {"iterations": int(info.iterations), "converged": bool(info.converged),
+                              "residual": np.array(info.residual[:]), "rhs_norm": np.array(info.rhs_norm[:])}
+            _check(self.ctx.handle, rc, "gingr_nicp_step")
+            return out, dist, lm
         _check(self.ctx.handle, self._lib.gingr_nicp_solve(
             self.ctx.handle, 0 if self.kind == "T" else 1, self.n, dptr(pts), self.edges.shape[0], iptr(self.edges), dptr(w), dptr(cp),
             self.lmIdsOnTemplate.shape[0], iptr(self.lmIdsOnTemplate) if len(self.lmIdsOnTemplate) else None,
@@ -365,9 +413,13 @@ class NonRigidOptimalStepICP:
         return fit
 
 
-def NonRigidOptimalStepICP_T(ctx, templateMesh, targetMesh, templateLandmarks=None, targetLandmarks=None, gamma: float = 1.0):
-    return NonRigidOptimalStepICP(ctx, templateMesh, targetMesh, templateLandmarks, targetLandmarks, gamma, "T")
+def NonRigidOptimalStepICP_T(ctx, templateMesh, targetMesh, templateLandmarks=None, targetLandmarks=None, gamma: float = 1.0,
+                             solver: str = "dense", relTol: Optional[float] = None, maxSolverIterations: Optional[int] = None):
+    return NonRigidOptimalStepICP(ctx, templateMesh, targetMesh, templateLandmarks, targetLandmarks, gamma, "T", solver, relTol,
+                                  maxSolverIterations)
 
 
-def NonRigidOptimalStepICP_A(ctx, templateMesh, targetMesh, templateLandmarks=None, targetLandmarks=None, gamma: float = 1.0):
-    return NonRigidOptimalStepICP(ctx, templateMesh, targetMesh, templateLandmarks, targetLandmarks, gamma, "A")
+def NonRigidOptimalStepICP_A(ctx, templateMesh, targetMesh, templateLandmarks=None, targetLandmarks=None, gamma: float = 1.0,
+                             solver: str = "dense", relTol: Optional[float] = None, maxSolverIterations: Optional[int] = None):
+    return NonRigidOptimalStepICP(ctx, templateMesh, targetMesh, templateLandmarks, targetLandmarks, gamma, "A", solver, relTol,
+                                  maxSolverIterations)

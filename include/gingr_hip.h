@@ -37,7 +37,8 @@ typedef enum gingr_status {
     GINGR_ERR_NONFINITE = 3,    /* a result is NaN/Inf (reference: exception inside Try => ModelFlexibilityError) */
     GINGR_ERR_NOT_SPD = 4,      /* Cholesky pivot <= 0 in the posterior solve (same mapping) */
     GINGR_ERR_NO_DEVICE = 5,
-    GINGR_ERR_STATE = 6         /* call order violated (e.g. update before target upload) */
+    GINGR_ERR_STATE = 6,        /* call order violated (e.g. update before target upload) */
+    GINGR_ERR_NOT_CONVERGED = 7 /* an iterative solve reached its iteration cap (gingr_nicp_step) */
 } gingr_status;
 
 /* G/api/GlobalTranformationType.scala:20-24 */
@@ -854,6 +855,33 @@ int gingr_fitter_set_fit_points(gingr_fitter *f, const double *fit_xyz);
 int gingr_nicp_solve(gingr_ctx *ctx, int32_t kind, int64_t n, const double *moving_xyz, int64_t n_edges, const int32_t *edges,
                      const double *w, const double *cp_xyz, int32_t n_lm, const int32_t *lm_ids, const double *lm_target_xyz, double alpha,
                      double beta, double gamma, double *out_xyz, double *out_lm_xyz);
+
+/* The same step past dense sizes: a handle over the template's edge graph, and the normal equations solved matrix-free by block-Jacobi
+ * preconditioned conjugate gradients (nicp_sparse.hip; the system, its quirks and the arguments are gingr_nicp_solve's).  The handle
+ * owns the CSR adjacency on the device and every work vector: a step allocates nothing.  gingr_nicp_create: an edge that is not
+ * p1 < p2 < n, a REPEATED edge and a landmark id out of range are GINGR_ERR_BAD_ARGUMENT.  gingr_nicp_step: lm_target_xyz [3L] for the
+ * lm_ids given at create (nullable when L = 0).  The three right-hand sides stop when |r| <= rel_tol |b| holds for each of them on the
+ * recurrence residual (rel_tol <= 0: 1e-12), or after max_iterations (<= 0: 20 000): then the status is GINGR_ERR_NOT_CONVERGED, with
+ * info and the outputs filled from the last iterate.  info (nullable): the iterations taken, converged 0 / 1, and per coordinate the
+ * TRUE residual |b - A x| of the returned solution (one more pass behind the stop) and |b|.  A mesh component without any weighted
+ * vertex or landmark term, or a vertex block that is not positive definite, is GINGR_ERR_NOT_SPD (nothing is iterated on); a non-finite
+ * result GINGR_ERR_NONFINITE.  Two calls with the same input give the same bits.  Synchronises.
+ * gingr_nicp_get_solution: the unknowns X of the last step that returned its outputs (GINGR_ERR_STATE without one), row-major
+ * [n][3] (N-ICP-T, the displacements) or [4 n][3] (N-ICP-A, row 4 i + a of vertex i), the layout of the reference's `A \ B`. */
+typedef struct gingr_nicp gingr_nicp;
+typedef struct gingr_nicp_info {
+    int32_t iterations;
+    int32_t converged;
+    double residual[3];
+    double rhs_norm[3];
+} gingr_nicp_info;
+int gingr_nicp_create(gingr_ctx *ctx, int32_t kind, int64_t n, int64_t n_edges, const int32_t *edges, int32_t n_lm, const int32_t *lm_ids,
+                      gingr_nicp **out);
+void gingr_nicp_destroy(gingr_nicp *h);
+int gingr_nicp_step(gingr_nicp *h, const double *moving_xyz, const double *w, const double *cp_xyz, const double *lm_target_xyz, double alpha,
+                    double beta, double gamma, double rel_tol, int32_t max_iterations, double *out_xyz, double *out_lm_xyz,
+                    gingr_nicp_info *info);
+int gingr_nicp_get_solution(gingr_nicp *h, double *x);
 
 #ifdef __cplusplus
 }

@@ -377,6 +377,35 @@ JFN(jint, nicpSolve)(JNIEnv *env, jclass, jlong ctx, jint kind, jdoubleArray tpl
     return gingr_nicp_solve(P<gingr_ctx>(ctx), kind, n, a.ptr(), ne, e.ptr(), ww.ptr(), c.ptr(), nl, li.ptr(), lt.ptr(), alpha, beta, gamma,
                             o.ptr(), ol.ptr());
 }
+// the sparse step: handle over the template's edge graph (gingr_nicp_create / _step / _destroy / _get_solution)
+JFN(jlong, nicpCreate)(JNIEnv *env, jclass, jlong ctx, jint kind, jlong n, jintArray edges, jintArray lmIds) {
+    const jlong ne = edges ? env->GetArrayLength(edges) / 2 : 0;
+    const jint nl = lmIds ? env->GetArrayLength(lmIds) : 0;
+    Arr<int32_t> e(env, edges, true); Arr<int32_t> li(env, lmIds, true);
+    gingr_nicp *h = nullptr;
+    if (gingr_nicp_create(P<gingr_ctx>(ctx), kind, n, ne, e.ptr(), nl, li.ptr(), &h) != GINGR_OK) return 0;
+    return reinterpret_cast<jlong>(h);
+}
+JFN(void, nicpDestroy)(JNIEnv *, jclass, jlong h) { gingr_nicp_destroy(P<gingr_nicp>(h)); }
+// info8 (nullable): iterations, converged, residual[3], rhs_norm[3]
+JFN(jint, nicpStep)(JNIEnv *env, jclass, jlong h, jdoubleArray tpl, jdoubleArray w, jdoubleArray cp, jdoubleArray lmTargets, jdouble alpha,
+                    jdouble beta, jdouble gamma, jdouble relTol, jint maxIterations, jdoubleArray out, jdoubleArray outLm, jdoubleArray info8) {
+    Arr<double> a(env, tpl, true); Arr<double> ww(env, w, true); Arr<double> c(env, cp, true); Arr<double> lt(env, lmTargets, true);
+    Arr<double> o(env, out, false); Arr<double> ol(env, outLm, false);
+    gingr_nicp_info info;
+    const int rc = gingr_nicp_step(P<gingr_nicp>(h), a.ptr(), ww.ptr(), c.ptr(), lt.ptr(), alpha, beta, gamma, relTol, maxIterations, o.ptr(),
+                                   ol.ptr(), &info);
+    if (info8) {
+        const jdouble v[8] = {(jdouble)info.iterations, (jdouble)info.converged, info.residual[0], info.residual[1], info.residual[2],
+                              info.rhs_norm[0], info.rhs_norm[1], info.rhs_norm[2]};
+        env->SetDoubleArrayRegion(info8, 0, 8, v);
+    }
+    return rc;
+}
+JFN(jint, nicpGetSolution)(JNIEnv *env, jclass, jlong h, jdoubleArray x) {
+    Arr<double> a(env, x, false);
+    return gingr_nicp_get_solution(P<gingr_nicp>(h), a.ptr());
+}
 JFN(jint, pointsetDistanceExtrema)(JNIEnv *env, jclass, jlong ctx, jdoubleArray xyz, jdoubleArray out2) {
     const jlong n = env->GetArrayLength(xyz) / 3;
     Arr<double> a(env, xyz, true); Arr<double> b(env, out2, false);

@@ -122,6 +122,17 @@ public final class GingrHipNative {
     public static native int fitterIcpSurfacePhase(long fitter, double initialSigma, double endSigma, int maxIterations, int phase);
     public static native int nicpSolve(long ctx, int kind, double[] templateXyz, int[] edges, double[] w, double[] cpXyz, int[] lmIds,
                                        double[] lmTargetXyz, double alpha, double beta, double gamma, double[] outXyz, double[] outLmXyz);
+    // the same step past dense sizes: a handle over the template's edge graph, the normal equations solved matrix-free by
+    // preconditioned conjugate gradients (gingr_nicp_create / _step / _get_solution / _destroy).  relTol <= 0 / maxIterations <= 0: the
+    // defaults (1e-12, 20 000); info8 (nullable): iterations, converged, residual[3], rhs_norm[3]; status 7 = not converged
+    /** 0 on failure (lastError(ctx) says why: a repeated edge, an edge that is not p1 < p2 < n, a landmark id out of range) */
+    public static native long nicpCreate(long ctx, int kind, long n, int[] edges, int[] lmIds);
+    public static native void nicpDestroy(long nicp);
+    public static native int nicpStep(long nicp, double[] templateXyz, double[] w, double[] cpXyz, double[] lmTargetXyz, double alpha,
+                                      double beta, double gamma, double relTol, int maxIterations, double[] outXyz, double[] outLmXyz,
+                                      double[] info8);
+    /** x: [n][3] (N-ICP-T) or [4 n][3] (N-ICP-A), row-major */
+    public static native int nicpGetSolution(long nicp, double[] x);
     /** out2 = { maximumPointDistance, minimumPointDistance } (PointSetHelper) */
     public static native int pointsetDistanceExtrema(long ctx, double[] xyz, double[] out2);
     /** any array may be null; basisColMajor is 3 M_local x rank, unit columns */
