@@ -318,7 +318,7 @@ int gingr_model_augment(gingr_ctx *ctx, const gingr_model *a, const gingr_model 
     if (bad) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite Gram matrix of the two bases", who);
 
     // ---- 3. G = V diag(lambda) V^T, lambda descending
-    GINGR_TRY(launch_jacobi_eig_blocks(ctx, Gs.as<double>(), n, n, evals.as<double>(), V.as<double>()));
+    GINGR_TRY(launch_jacobi_eig(ctx, Gs.as<double>(), n, n, evals.as<double>(), V.as<double>(), true));
     std::vector<double> lam((size_t)n);
     HIP_TRY(ctx, hipMemcpyAsync(lam.data(), evals.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

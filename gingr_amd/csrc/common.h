@@ -78,6 +78,12 @@ void gingr_ctx_rccl_release(gingr_ctx *ctx);  // rccl_exchange.hip: destroys the
         if (s__ != GINGR_OK) return s__; \
     } while (0)
 
+// did the launches so far go through?
+inline int check_launch(gingr_ctx *ctx) {
+    HIP_TRY(ctx, hipGetLastError());
+    return GINGR_OK;
+}
+
 // RAII device buffer for the stateless operators
 struct DevBuf {
     void *p = nullptr;

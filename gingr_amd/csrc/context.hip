@@ -246,11 +246,6 @@ int upload_cloud(gingr_ctx *ctx, int64_t n, const double *host_xyz, DevBuf &stag
     return GINGR_OK;
 }
 
-int check_launch(gingr_ctx *ctx) {
-    HIP_TRY(ctx, hipGetLastError());
-    return GINGR_OK;
-}
-
 }  // namespace
 
 extern "C" {

@@ -4,7 +4,7 @@
 // basis of a kernel model: G/api/registration/utils/GPMMHelper.scala:39-69, E/CreateBunnyGPMM.scala), and the eigenbasis of the
 // model's moment S_tot = Q^T Q the uniform-weight posterior uses (gp.hip posterior_solve_eig_kernel).
 //
-// The two-sided cyclic Jacobi it takes over from (gpmm.hip jacobi_eig_kernel, still the path above n = 192 and for numerically
+// The two-sided cyclic Jacobi it takes over from (sym_eig.hip jacobi_eig_kernel, still the path above n = 192 and for numerically
 // singular matrices) keeps A and V in global memory and spends a round trip to L2 per load-store of every rotation round: 40 us a
 // round at n = 171, 61 ms a decomposition.  Here:
 //   * G = C C^T first (right-looking Cholesky, a column at a time through LDS), then the ONE-SIDED (Hestenes) Jacobi on the columns
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(W * 64) void sym_eig_cols_kernel(EigBatch batch) {
 
 // ---- 193 .. 512 columns: the same decomposition (Cholesky, then one-sided Jacobi on the factor's columns) on many workgroups ----
 //
-// The register kernel ends at 192 columns (one workgroup's registers); the two-sided grid kernel of gpmm.hip that served everything
+// The register kernel ends at 192 columns (one workgroup's registers); the two-sided grid kernel of sym_eig.hip that served everything
 // larger meets its 64 workgroups at a spin-wait barrier once a round.  Here every step is a launch of its own and the workgroups of
 // a launch never wait for each other:
 //   * the factor C (G = C C^T) is kept column-major, [columns padded to blocks of 16][rows padded to 64], zero padded;

@@ -259,11 +259,6 @@ int dev_alloc(gingr_ctx *ctx, T **p, size_t count) {
 
 inline void dev_free(void *p) { if (p) (void)hipFree(p); }
 
-inline int check_launch(gingr_ctx *ctx) {
-    HIP_TRY(ctx, hipGetLastError());
-    return GINGR_OK;
-}
-
 inline Cloud cloud_of(const double *soa, int64_t n) { return Cloud{soa, soa + n, soa + 2 * n, n}; }
 
 // grow-only: steady-state queries (one likelihood evaluation per Metropolis-Hastings step) do not allocate

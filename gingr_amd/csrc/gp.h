@@ -332,13 +332,16 @@ void launch_posterior_sample_cached(gingr_ctx *ctx, int32_t r, int32_t rp, const
 // The posterior of point-cloud ICP without landmarks -- every row weighs 1 / sigma2 (ICP.scala:90-92) -- needs no factorisation.
 void launch_posterior_solve_eig(gingr_ctx *ctx, int32_t r, int32_t rp, const double *eigV, const double *eigL, const double *sigma2,
                                 const double *rhs, double *a, DevState *st);
-// eigen-decomposition of the leading n x n block of the symmetric G (row stride ldg): evals [n] descending, Vs [n*n] (Vs[i*n + k] =
-// component i of eigenvector k); the register kernel of eig.hip up to 192 columns, the two-sided cyclic Jacobi of gpmm.hip above that
-// and for numerically singular matrices (gpmm.hip sym_eig); synchronises the stream
-int launch_jacobi_eig(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, double *evals, double *Vs);
-// the same with the block kernel of eig.hip (sym_eig_blocks) in front of the two-sided one above kSymEigColsMaxN columns
-int launch_jacobi_eig_blocks(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, double *evals, double *Vs);
-// eig.hip: one-sided register Jacobi on the Cholesky factor, n <= kSymEigColsMaxN, up to three problems per launch (see sym_eig, gpmm.hip)
+// sym_eig.hip: eigen-decompositions of the leading n[q] x n[q] blocks of `count` <= 3 symmetric matrices G[q] (row stride ldg[q]), every
+// n[q] in 1 .. kJacMaxN: evals[q] [n] descending, Vs[q] [n*n] (Vs[i*n + k] = component i of eigenvector k).  The register kernel of
+// eig.hip up to kSymEigColsMaxN columns; above that -- and for numerically singular matrices -- the two-sided cyclic Jacobi of
+// sym_eig.hip, with `blocks` the block kernel of eig.hip (sym_eig_blocks) in front of it.  Synchronises the stream.
+constexpr int kJacMaxN = 512;
+int sym_eig(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ldg, const int32_t *n, double *const *evals,
+            double *const *Vs, bool blocks = false);
+// the same for one matrix
+int launch_jacobi_eig(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, double *evals, double *Vs, bool blocks = false);
+// eig.hip: one-sided register Jacobi on the Cholesky factor, n <= kSymEigColsMaxN, up to three problems per launch (see sym_eig)
 constexpr int kSymEigColsMaxN = 192;
 int64_t sym_eig_cols_work_doubles(int32_t n);
 // eig.hip: the same decomposition for kSymEigColsMaxN < n <= 512 on many workgroups, a launch per round (no grid barrier); work[q]:

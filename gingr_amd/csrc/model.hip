@@ -1,5 +1,5 @@
-// Model upload, finalize and re-sampling on a new reference, and the stateless model operators (instance, coefficients, posterior
-// mean), which borrow a short-lived fitter (C ABI in include/gingr_hip.h).
+// Model upload, finalize, download, truncation and re-sampling on a new reference, and the stateless model operators (instance,
+// coefficients, posterior mean), which borrow a short-lived fitter (C ABI in include/gingr_hip.h).
 #include "fitter.h"
 
 #include <algorithm>
@@ -7,6 +7,29 @@
 #include <functional>
 
 namespace {
+
+// stage[k*3M + 3*perm[s] + d] = Q0[(3s+d)*rp + k] / sqrt(variance[k])   (inverse of pack_basis_kernel)
+__global__ __launch_bounds__(256) void unpack_basis_kernel(const double *__restrict__ Q0, const double *__restrict__ variance,
+                                                           int64_t M, int32_t r, int32_t rp,
+                                                           const int32_t *__restrict__ perm, double *__restrict__ stage) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 3 * M * r) return;
+    const int64_t row = idx / r;
+    const int32_t k = (int32_t)(idx - row * r);
+    const int64_t s = row / 3, d = row - 3 * s;
+    const double sd = sqrt(variance[k]);
+    stage[(int64_t)k * 3 * M + 3 * (int64_t)(perm ? perm[s] : s) + d] = sd > 0.0 ? Q0[row * rp + k] / sd : 0.0;
+}
+
+// Q[(row) * rpn + q] = q < k ? Qs[row * rps + q] : 0 for the 3M basis rows (the slack rows behind them are cleared by model_create_impl)
+__global__ __launch_bounds__(256) void truncate_basis_kernel(const double *__restrict__ Qs, int32_t rps, int64_t rows, int32_t k, int32_t rpn,
+                                                             double *__restrict__ Q) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * rpn) return;
+    const int64_t row = idx / rpn;
+    const int32_t q = (int32_t)(idx - row * rpn);
+    Q[idx] = q < k ? Qs[row * rps + q] : 0.0;
+}
 
 int model_finalize_impl(gingr_ctx *ctx, gingr_model *m) {
     DevBuf work, flag;
@@ -450,6 +473,63 @@ int gingr_model_new_reference(gingr_ctx *ctx, const gingr_model *src, int64_t M_
         return check_launch(ctx);
     };
     return model_create_impl(ctx, M_new, src->r, new_ref, nmean.data(), src->variance.data(), row_begin, row_end, fill, out);
+}
+
+int gingr_model_download(gingr_ctx *ctx, const gingr_model *m, double *ref, double *mean, double *basis_colmajor,
+                         double *variance) {
+    if (!ctx || !m) return GINGR_ERR_BAD_ARGUMENT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t M = m->M;
+    DevBuf aos, var, stage;
+    HIP_TRY(ctx, aos.alloc((size_t)3 * M * sizeof(double)));
+    if (ref) {
+        launch_soa_to_aos(ctx, m->ref, M, aos.as<double>(), m->perm);
+        HIP_TRY(ctx, hipMemcpyAsync(ref, aos.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (mean) {
+        launch_soa_to_aos(ctx, m->mean, M, aos.as<double>(), m->perm);
+        HIP_TRY(ctx, hipMemcpyAsync(mean, aos.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (variance) memcpy(variance, m->variance.data(), (size_t)m->r * sizeof(double));
+    if (basis_colmajor) {
+        HIP_TRY(ctx, var.alloc((size_t)m->r * sizeof(double)));
+        HIP_TRY(ctx, stage.alloc((size_t)3 * M * m->r * sizeof(double)));
+        HIP_TRY(ctx, hipMemcpyAsync(var.p, m->variance.data(), (size_t)m->r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        const int64_t total = 3 * M * m->r;
+        hipLaunchKernelGGL(unpack_basis_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, m->Q0,
+                           var.as<double>(), M, m->r, m->rp, m->perm, stage.as<double>());
+        GINGR_TRY(check_launch(ctx));
+        HIP_TRY(ctx, hipMemcpyAsync(basis_colmajor, stage.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return GINGR_OK;
+}
+
+int gingr_model_truncate(gingr_ctx *ctx, const gingr_model *src, int32_t k, gingr_model **out) {
+    if (!ctx || !out) return GINGR_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    if (!src) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: no model");
+    if (src->ctx != ctx || !src->finalized)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: the source must be a finalized model of this context");
+    if (src->row_begin != 0 || src->row_end != src->M_total)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: the source is a row shard; truncate the complete model (or build the shard with keep_rank)");
+    if (k < 1 || k > src->r)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: k = %d outside 1..%d (the model's rank)", (int)k, (int)src->r);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t M = src->M;
+    std::vector<double> href((size_t)3 * M), hmean((size_t)3 * M);
+    GINGR_TRY(gingr_model_download(ctx, src, href.data(), hmean.data(), nullptr, nullptr));
+    auto fill = [&](gingr_model *m) -> int {
+        // the same points and mean give the same row order (Morton order of ref + mean): rows are copied in place
+        if (m->M != M || m->hperm != src->hperm) return gingr_set_error(ctx, GINGR_ERR_STATE, "model_truncate: row order differs from the source's");
+        const int64_t total = 3 * M * m->rp;
+        hipLaunchKernelGGL(truncate_basis_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, src->Q0, src->rp, 3 * M, k, m->rp,
+                           m->Q0);
+        return check_launch(ctx);
+    };
+    return model_create_impl(ctx, src->M_total, k, href.data(), hmean.data(), src->variance.data(), 0, src->M_total, fill, out);
 }
 
 }  // extern "C"

@@ -401,7 +401,7 @@ int gingr_model_from_shapes(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const d
     HIP_TRY(ctx, Gs.alloc((size_t)n * n * sizeof(double)));
     hipLaunchKernelGGL(gram_shift_kernel, dim3((unsigned)ceil_div((int64_t)n * n, 256)), dim3(256), 0, ctx->stream, G, np, n, shift, Gs.as<double>());
     GINGR_TRY(check_launch(ctx));
-    GINGR_TRY(launch_jacobi_eig_blocks(ctx, Gs.as<double>(), n, n, evals.as<double>(), V.as<double>()));
+    GINGR_TRY(launch_jacobi_eig(ctx, Gs.as<double>(), n, n, evals.as<double>(), V.as<double>(), true));
     std::vector<double> lam((size_t)n);
     HIP_TRY(ctx, hipMemcpy(lam.data(), evals.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     double total = 0.0;

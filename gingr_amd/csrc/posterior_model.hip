@@ -146,7 +146,7 @@ static int posterior_model_build(gingr_fitter *f, const double *G, const double 
     HIP_TRY(ctx, hipMemcpyAsync(lam, m->variance.data(), (size_t)r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(factor_gram_kernel, tiles, dim3(256), 0, ctx->stream, (int)r, W, ldw, lam, H.as<double>(), (int)rp);
     GINGR_TRY(check_launch(ctx));
-    GINGR_TRY(launch_jacobi_eig_blocks(ctx, H.as<double>(), rp, r, lam_p, V.as<double>()));
+    GINGR_TRY(launch_jacobi_eig(ctx, H.as<double>(), rp, r, lam_p, V.as<double>(), true));
     hipLaunchKernelGGL(factor_vectors_kernel, tiles, dim3(256), 0, ctx->stream, (int)r, (int)rp, W, ldw, V.as<double>(), T.as<double>());
     GINGR_TRY(check_launch(ctx));
     HIP_TRY(ctx, hipMemcpyAsync(lam_h.data(), lam_p, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -125,11 +125,6 @@ __global__ __launch_bounds__(256) void icp_apply_kernel(int64_t n, double *__res
     pz[i] = s * (tr[7] * x + tr[8] * y + tr[9] * z) + tr[12];
 }
 
-int check(gingr_ctx *ctx) {
-    HIP_TRY(ctx, hipGetLastError());
-    return GINGR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -211,7 +206,7 @@ int gingr_rigid_icp_iterate(gingr_rigid_icp *h, int32_t n_iterations, double *di
                            h->c0[2], (int)h->kind, h->tr.as<double>());
         hipLaunchKernelGGL(icp_apply_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, p, p + M, p + 2 * M,
                            h->tr.as<double>());
-        GINGR_TRY(check(ctx));
+        GINGR_TRY(check_launch(ctx));
         double res[2] = {0, 0};
         HIP_TRY(ctx, hipMemcpyAsync(res, h->tr.as<double>() + 13, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -1,4 +1,4 @@
-"""CPU restatements of three model set-up kernels of gingr_amd/csrc/gpmm.hip whose round-6 forms claim to give the bits of the forms they
+"""CPU restatements of three model set-up kernels (gingr_amd/csrc/cloud_ops.hip, gpmm.hip, sym_eig.hip) whose round-6 forms claim to give the bits of the forms they
 replaced.  The claims rest on small pieces of index arithmetic and algebra; these tests state them in numpy / plain Python so that
 they can be checked without a GPU (the GPU side is tools/experiments/gpmm_build_ab.py: eleven models, two libraries, bit for bit).
 
