@@ -148,6 +148,132 @@ class AffineCPDRegistration(RigidCPDRegistration):
     _kind = AFFINE
 
 
+# ------------------------------------------------------------------------------------------------ Bayesian coherent point drift
+class BCPD:
+    """Bayesian coherent point drift (Hirose 2020) over csrc/bcpd.hip -- the method of the reference's draft cpd/BCPD.scala in this
+    package's definition (include/gingr_hip.h; DESIGN.md section 5 lists where it follows the paper against the draft).  The reference
+    takes any PDKernel; here the kernel is the Gaussian of CPDFactory, g(a, b) = exp(-|a - b|^2 / (2 beta^2)).  `k` is the paper's
+    kappa (math.inf: constant mixing weights 1 / M).  The state (yhat, sigma_m^2, <alpha_m>, s, R, t, sigma2) lives on the device."""
+
+    def __init__(self, ctx: Context, templatePoints, targetPoints, w: float = 0.0, lambda_: float = 2.0, gamma: float = 1.0,
+                 k: float = 1.0, beta: float = 2.0):
+        self.ctx, self._lib = ctx, ctx._lib
+        self.template, self.target = f64(templatePoints), f64(targetPoints)
+        self.M, self.N = self.template.shape[0], self.target.shape[0]
+        self.w, self.lambda_, self.gamma, self.k, self.beta = w, lambda_, gamma, k, beta
+        self._h = None
+        h = c_void_p()
+        _check(ctx.handle, self._lib.gingr_bcpd_create(ctx.handle, self.M, dptr(self.template), self.N, dptr(self.target), float(w),
+                                                       float(lambda_), float(gamma), float(k), float(beta), ctypes.byref(h)),
+               "gingr_bcpd_create")
+        self._h = h
+        self._sigma2_init = self.sigma2()
+
+    def close(self):
+        if self._h:
+            self._lib.gingr_bcpd_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _get(self, *args):
+        _check(self.ctx.handle, self._lib.gingr_bcpd_get(self._h, *args), "gingr_bcpd_get")
+
+    # -- device state ---------------------------------------------------------------------------------------------
+    def state(self) -> dict:
+        """the state and the by-products of the iteration that left it: yhat, vhat (M x 3), sigma_diag, alpha, nu (M), nu_prime (N),
+        s, R, t, sigma2, Nhat, sigma_bar2"""
+        yh, vh = np.empty((self.M, 3)), np.empty((self.M, 3))
+        sig, alpha, nu, nup = np.empty(self.M), np.empty(self.M), np.empty(self.M), np.empty(self.N)
+        p, sc = np.empty(13), np.empty(3)
+        self._get(dptr(yh), dptr(vh), dptr(sig), dptr(alpha), dptr(nu), dptr(nup), dptr(p), dptr(sc))
+        return dict(yhat=yh, vhat=vh, sigma_diag=sig, alpha=alpha, nu=nu, nu_prime=nup, s=float(p[0]), R=p[1:10].reshape(3, 3).copy(),
+                    t=p[10:13].copy(), sigma2=float(sc[0]), Nhat=float(sc[1]), sigma_bar2=float(sc[2]))
+
+    def points(self) -> np.ndarray:
+        yh = np.empty((self.M, 3))
+        self._get(dptr(yh), None, None, None, None, None, None, None)
+        return yh
+
+    def sigma2(self) -> float:
+        sc = np.empty(3)
+        self._get(None, None, None, None, None, None, None, dptr(sc))
+        return float(sc[0])
+
+    def set_state(self, yhat=None, sigma_diag=None, alpha=None, s=None, R=None, t=None, sigma2=None):
+        """inject any part of the state (None: left as it is; s, R, t go together)"""
+        p = None
+        if s is not None or R is not None or t is not None:
+            p = np.concatenate([[float(s)], f64(R).reshape(9), f64(t).reshape(3)])
+        yhat, sigma_diag, alpha = (None if a is None else f64(a) for a in (yhat, sigma_diag, alpha))
+        if (yhat is not None and yhat.shape != (self.M, 3)) or any(a is not None and a.shape != (self.M,) for a in (sigma_diag, alpha)):
+            raise ValueError("BCPD.set_state: shape mismatch")
+        _check(self.ctx.handle, self._lib.gingr_bcpd_set(self._h, dptr(yhat), dptr(sigma_diag), dptr(alpha), dptr(p),
+                                                         0.0 if sigma2 is None else float(sigma2)), "gingr_bcpd_set")
+
+    def reset(self):
+        """back to the start: (template, 1, 1 / M, s = 1, R = I, t = 0, the initial variance)"""
+        self.set_state(self.template, np.ones(self.M), np.full(self.M, 1.0 / self.M), 1.0, np.eye(3), np.zeros(3), self._sigma2_init)
+
+    def transform(self) -> Tuple[float, np.ndarray, np.ndarray]:
+        """(s, R, t) of the last iteration: yhat = s (y + vhat) R^T + 1 t^T"""
+        p = np.empty(13)
+        self._get(None, None, None, None, None, None, dptr(p), None)
+        return float(p[0]), p[1:10].reshape(3, 3).copy(), p[10:13].copy()
+
+    def correspondenceWeights(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(nu = P 1, nu' = P^T 1) of the last iteration: how much of the target a template point explains, and the probability that a
+        target point is no outlier"""
+        nu, nup = np.empty(self.M), np.empty(self.N)
+        self._get(None, None, None, None, dptr(nu), dptr(nup), None, None)
+        return nu, nup
+
+    # -- the reference surface ------------------------------------------------------------------------------------
+    def Iteration(self) -> Tuple[np.ndarray, float]:
+        _check(self.ctx.handle, self._lib.gingr_bcpd_iterate(self._h, 1), "gingr_bcpd_iterate")
+        return self.points(), self.sigma2()
+
+    def Registration(self, max_iteration: int, tolerance: float = 1e-6, verbose: bool = False) -> np.ndarray:
+        """the reference's loop: from the start, iterate until |sigma2' - sigma2| < tolerance or max_iteration non-converged iterations;
+        returns the state left on the device (yhat)"""
+        self.reset()
+        i, converged, current = 0, False, self._sigma2_init
+        while i < max_iteration and not converged:
+            if verbose:
+                print(f"BCPD, iteration: {i}, variance: {current}")
+            _check(self.ctx.handle, self._lib.gingr_bcpd_iterate(self._h, 1), "gingr_bcpd_iterate")
+            new = self.sigma2()
+            if abs(new - current) < tolerance:
+                if verbose:
+                    print("Converged")
+                converged = True
+            else:
+                i += 1
+            current = new
+        self.iterations, self.converged = i, converged
+        return self.points()
+
+
+class BCPDRegistration:
+    """BCPDRegistration.scala with its defaults: register(target) returns the warped template points."""
+
+    def __init__(self, ctx: Context, template, w: float = 0.0, lambda_: float = 2.0, gamma: float = 1.0, k: float = 1.0, beta: float = 2.0,
+                 max_iterations: int = 100):
+        self.ctx, self.template, self.max_iterations = ctx, f64(template), max_iterations
+        self.w, self.lambda_, self.gamma, self.k, self.beta = w, lambda_, gamma, k, beta
+
+    def register(self, target) -> np.ndarray:
+        task = BCPD(self.ctx, self.template, target, self.w, self.lambda_, self.gamma, self.k, self.beta)
+        try:
+            return task.Registration(self.max_iterations)
+        finally:
+            task.close()
+
+
 # ------------------------------------------------------------------------------------------------ classic rigid ICP
 RIGID_REGISTRATOR, AFFINE_REGISTRATOR = 0, 1   # PoseRegistrator.RigidRegistrator3D / AffineRegistrator3D (= similarity)
 

@@ -818,6 +818,34 @@ int gingr_classic_cpd_iterate(gingr_classic_cpd *h, int32_t n_iterations);
 int gingr_classic_cpd_get(gingr_classic_cpd *h, double *ty_xyz, double *sigma2, double *transform13, double *w_xyz);
 int gingr_classic_cpd_set(gingr_classic_cpd *h, const double *ty_xyz, double sigma2);
 
+/* ---- Bayesian coherent point drift (Hirose 2020; the reference's draft other/algorithms/cpd/BCPD.scala, BCPDRegistration.scala) ----
+ * One handle = BCPD(templatePoints, targetPoints, w, lambda, gamma, k, beta) with the Gaussian kernel of CPDFactory,
+ * g(a, b) = exp(-|a - b|^2 / (2 beta^2)).  The definition is this package's (DESIGN.md section 5 lists where it follows the paper
+ * against the draft): soft assignment with the row weights <alpha_m> exp(-1.5 s^2 sigma_m^2 / sigma2) and the outlier density 1 / V
+ * (V: the volume of the target's bounding box), the deformation v^ = c2 Sigma r and sigma_m^2 = Sigma_mm through the Woodbury form of
+ * Sigma = (lambda G^-1 + c2 diag nu)^-1 (one blocked Cholesky of I + D^1/2 (G / lambda) D^1/2 per iteration, G never inverted), the
+ * similarity (s, R, t) from the singular vectors of S_xu, then y^ = s R (y + v^) + t and sigma2.  Nothing divides by nu_m.
+ * The state (y^, sigma_m^2, <alpha_m>, s, R, t, sigma2) lives on the device and starts at (template, 1, 1 / M, 1, I, 0,
+ * gamma sum |x_n - y_m|^2 / (3 N M)).  gingr_bcpd_iterate runs n iterations back to back and synchronises; the caller owns the
+ * convergence test |sigma2' - sigma2| < tolerance.  It fails with GINGR_ERR_NONFINITE (w = 0 and a target point out of reach of every
+ * template point) or GINGR_ERR_NOT_SPD; the handle stays usable after gingr_bcpd_set.
+ * gingr_bcpd_create refuses (GINGR_ERR_BAD_ARGUMENT): w outside [0, 1), non-positive lambda, gamma, kappa, beta (kappa = +inf is
+ * allowed: <alpha_m> = 1 / M), M or N < 1, a target whose bounding box has no volume while w > 0, and M > 32768 (the iteration keeps
+ * M x M double buffers: G, the bordered system of twice that size and its workspace, 43 GB at the cap).
+ * moving_xyz = the templatePoints [3 M], target_xyz = the targetPoints [3 N].
+ * gingr_bcpd_get: every pointer may be NULL.  yhat_xyz, vhat_xyz [3 M] interleaved, sigma_diag, alpha, nu [M], nu_prime [N],
+ * transform13 = {s, R row-major [9], t [3]} (x = s R u + t), scalars3 = {sigma2, N^ = sum nu, the nu-weighted mean of sigma_m^2}.
+ * gingr_bcpd_set injects a state: NULL pointers and a sigma2 that is not > 0 leave their part as it is. */
+typedef struct gingr_bcpd gingr_bcpd;
+int gingr_bcpd_create(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, double w, double lambda,
+                      double gamma, double kappa, double beta, gingr_bcpd **out);
+void gingr_bcpd_destroy(gingr_bcpd *h);
+int gingr_bcpd_iterate(gingr_bcpd *h, int32_t n_iterations);
+int gingr_bcpd_get(gingr_bcpd *h, double *yhat_xyz, double *vhat_xyz, double *sigma_diag, double *alpha, double *nu, double *nu_prime,
+                   double *transform13, double *scalars3);
+int gingr_bcpd_set(gingr_bcpd *h, const double *yhat_xyz, const double *sigma_diag, const double *alpha, const double *transform13,
+                   double sigma2);
+
 /* ---- classic rigid / similarity ICP (the reference's other/ baseline) ------------------------------------------------
  * G/other/algorithms/icp/RigidICP.scala:24-84 (Iteration / Registration), ICPFactory.scala:28-38, RigidICPRegistration.scala:24-46
  * with the two registrators of G/other/utils/PoseRegistrator.scala:27-43: kind 0 = RigidRegistrator3D
