@@ -123,17 +123,8 @@ __global__ void transform_finish_kernel(const double *__restrict__ partial, cons
         s2 = sc * trAR;
     } else {
         // B = Xhat^T P^T Yhat (Yhat^T P1 Yhat)^-1; s2 = tr(Xhat^T P^T Yhat B^T)                              (AffineCPD.scala:51-56)
-        const double det = det3(YPY);
         double inv[9];
-        inv[0] = (YPY[4] * YPY[8] - YPY[5] * YPY[7]) / det;
-        inv[1] = (YPY[2] * YPY[7] - YPY[1] * YPY[8]) / det;
-        inv[2] = (YPY[1] * YPY[5] - YPY[2] * YPY[4]) / det;
-        inv[3] = (YPY[5] * YPY[6] - YPY[3] * YPY[8]) / det;
-        inv[4] = (YPY[0] * YPY[8] - YPY[2] * YPY[6]) / det;
-        inv[5] = (YPY[2] * YPY[3] - YPY[0] * YPY[5]) / det;
-        inv[6] = (YPY[3] * YPY[7] - YPY[4] * YPY[6]) / det;
-        inv[7] = (YPY[1] * YPY[6] - YPY[0] * YPY[7]) / det;
-        inv[8] = (YPY[0] * YPY[4] - YPY[1] * YPY[3]) / det;
+        spd3_inverse(YPY, inv);  // Yhat^T diag(P1) Yhat is symmetric positive definite unless the template is planar: NaNs then, flagged below
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) L[r * 3 + c] = A[r * 3] * inv[c] + A[r * 3 + 1] * inv[3 + c] + A[r * 3 + 2] * inv[6 + c];
         s2 = 0.0;

@@ -1,5 +1,6 @@
 // Observations of the GiNGR update (CPD, ICP, given points) and landmarks, one thread per model point (gfx950, MI355X).
 #include "gp.h"
+#include "svd3.h"
 
 namespace {
 
@@ -116,18 +117,8 @@ __global__ __launch_bounds__(kLmChunk) void landmarks_kernel(const double *__res
             double o0 = 0.0, o1 = 0.0, o2 = 0.0;
             if (p >= 0) {
                 const double *C = cov + 9 * (int64_t)l;
-                const double det = C[0] * (C[4] * C[8] - C[5] * C[7]) - C[1] * (C[3] * C[8] - C[5] * C[6]) +
-                                   C[2] * (C[3] * C[7] - C[4] * C[6]);
                 double Ci[9];
-                Ci[0] = (C[4] * C[8] - C[5] * C[7]) / det;
-                Ci[1] = (C[2] * C[7] - C[1] * C[8]) / det;
-                Ci[2] = (C[1] * C[5] - C[2] * C[4]) / det;
-                Ci[3] = (C[5] * C[6] - C[3] * C[8]) / det;
-                Ci[4] = (C[0] * C[8] - C[2] * C[6]) / det;
-                Ci[5] = (C[2] * C[3] - C[0] * C[5]) / det;
-                Ci[6] = (C[3] * C[7] - C[4] * C[6]) / det;
-                Ci[7] = (C[1] * C[6] - C[0] * C[7]) / det;
-                Ci[8] = (C[0] * C[4] - C[1] * C[3]) / det;
+                spd3_inverse(C, Ci);  // NaNs for a matrix that is no covariance: the solve then fails by the status path
                 const double *R = st->R;
                 double T[9], W[9];  // T = Ci * R
                 for (int i = 0; i < 3; ++i)

@@ -1,5 +1,6 @@
 // 3x3 singular value decomposition, polar rotation and the Euler conventions shared by the Umeyama step of the update (gp_post_solve.hip),
-// the classic rigid CPD (classic_cpd.hip) and the rigid ICP (rigid_icp.hip)
+// the classic rigid CPD (classic_cpd.hip) and the rigid ICP (rigid_icp.hip); at the end the 3x3 SPD inverse of the landmark observations
+// (gp_obs.hip) and of the classic affine CPD
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -283,4 +284,39 @@ __host__ __device__ inline void kabsch3_rotation(const double S[9], double R[9],
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) R[a * 3 + b] = U[a * 3] * V[b * 3] + U[a * 3 + 1] * V[b * 3 + 1] + s3 * U[a * 3 + 2] * V[b * 3 + 2];
     *trace_ds = D[0] + D[1] + s3 * D[2];
+}
+
+// Inverse of a symmetric positive definite 3x3 matrix (row-major; the two triangles are averaged): Cholesky factor L, its inverse M,
+// C^-1 = M^T M.  Backward stable: the relative error of the result is of order cond(C) eps, where the cofactor formula loses
+// lambda1^2 / (lambda2 lambda3) to the cancellation of its determinant (five digits more for a covariance that is tight in two directions
+// and free along the third).  A pivot that is not positive and finite -- C singular, indefinite or not finite -- makes every entry NaN: the
+// caller's system then fails through its own status path instead of carrying the inverse of something that is no covariance.
+// The inverse of the identity is the identity bit for bit (no negative zero).
+__host__ __device__ inline void spd3_inverse(const double C[9], double Ci[9]) {
+    const double kMax = 1.79769313486231570815e308;
+    const double c10 = 0.5 * (C[3] + C[1]), c20 = 0.5 * (C[6] + C[2]), c21 = 0.5 * (C[7] + C[5]);
+    bool ok = C[0] > 0.0 && C[0] <= kMax;
+    const double l00 = sqrt(C[0]);
+    const double l10 = c10 / l00, l20 = c20 / l00;
+    const double p1 = C[4] - l10 * l10;
+    ok = ok && p1 > 0.0 && p1 <= kMax;
+    const double l11 = sqrt(p1);
+    const double l21 = (c21 - l20 * l10) / l11;
+    const double p2 = (C[8] - l20 * l20) - l21 * l21;
+    ok = ok && p2 > 0.0 && p2 <= kMax;
+    const double l22 = sqrt(p2);
+    const double m00 = 1.0 / l00, m11 = 1.0 / l11, m22 = 1.0 / l22;
+    const double m10 = (0.0 - l10 * m00) * m11;
+    const double m21 = (0.0 - l21 * m11) * m22;
+    const double m20 = (0.0 - (l20 * m00 + l21 * m10)) * m22;
+    if (!ok) {
+        for (int q = 0; q < 9; ++q) Ci[q] = __builtin_nan("");
+        return;
+    }
+    Ci[0] = (m00 * m00 + m10 * m10) + m20 * m20;
+    Ci[1] = Ci[3] = m10 * m11 + m20 * m21;
+    Ci[2] = Ci[6] = m20 * m22;
+    Ci[4] = m11 * m11 + m21 * m21;
+    Ci[5] = Ci[7] = m21 * m22;
+    Ci[8] = m22 * m22;
 }

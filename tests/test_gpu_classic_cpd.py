@@ -122,3 +122,51 @@ def test_nonrigid_system_residual_at_2000_points(ctx):
     want = (xPx - 2 * float((TY * PX).sum()) + float(P1 @ (TY * TY).sum(1))) / (P1.sum() * 3)
     assert abs(s2n - want) < 1e-9 * abs(want)
     reg.close()
+
+
+def elongated_pair(M=200, N=200, seed=21):
+    """A template whose spread is 100 : 1 : 1 along a skew axis (the first column of rot3_cases.TILT), and a target that is an affine
+    image of it, permuted, with noise: Yhat^T diag(P1) Yhat, which the affine step inverts, has eigenvalues in the ratio 1e4 : 1 : 1."""
+    from tests import rot3_cases as rc
+    rng = np.random.default_rng(seed)
+    Y = (rng.normal(size=(M, 3)) * np.array([100.0, 1.0, 1.0])) @ rc.TILT.T + np.array([5.0, -3.0, 2.0])
+    B0 = np.eye(3) + 0.05 * rng.normal(size=(3, 3))
+    X = Y[rng.permutation(M)[:N]] @ B0.T + np.array([1.0, 2.0, -1.0]) + rng.normal(0, 0.05, (N, 3))
+    return Y, X
+
+
+def test_affine_iteration_at_an_elongated_template(ctx):
+    """One affine Iteration from the oracle's state against go.classic_cpd_maximization_affine.  Bound per quantity: the larger of the
+    tolerance of test_rigid_and_affine_iterations and 10 x the oracle's own spread over 8 perturbations of 2^-52 of its inputs
+    (rot3_cases.oracle_spread), the rule of test_gpu_rotation_step.py.
+    Host emulation of the step with the three inverses of the 3 x 3 matrix (deviation from the oracle, B / t / TY relative):
+    cofactor formula 2.3e-10 / 4.9e-10 / 9.5e-11, 60-digit inverse 1.4e-13 / 5.9e-13 / 7.0e-14; oracle spread 3.0e-13 / 2.1e-12 / 9.2e-13.
+    On an MI355X: 1.3e-13 / 1.1e-12 / 3.9e-14 with spd3_inverse; the cofactor formula the kernel had before gave 6.8e-11 / 2.0e-10 /
+    2.6e-10 and missed the bound of TY (1e-10)."""
+    from gingr_amd import classic as cl
+    from tests import rot3_cases as rc
+    w = 0.1
+    Y, X = elongated_pair()
+    sd = np.sqrt(np.linalg.eigvalsh(np.cov(Y.T)))
+    assert 70 < sd[2] / sd[1] < 130 and sd[1] / sd[0] < 1.3 and np.abs(rc.TILT[:, 0]).min() > 0.3     # 100 : 1 : 1, along no coordinate axis
+    s0 = go.classic_cpd_initial_sigma2(Y, X)
+
+    def oracle(X, Y):
+        TY, s2, (B, t) = go.classic_cpd_maximization_affine(X, Y, go.classic_cpd_expectation(X, Y, s0, w))
+        return {"TY": TY, "sigma2": s2, "B": B, "t": t}
+
+    want, spread = rc.oracle_spread(oracle, (X, Y))
+    reg = cl.CPDFactory(ctx, Y, w=w).registerAffine(X)
+    gTY, gs2 = reg.Iteration(Y, s0)
+    _, gB, gt = reg.transform()
+    reg.close()
+    nTY = np.linalg.norm(want["TY"])
+    os2 = float(want["sigma2"])
+    sTY = spread["TY"] * np.sqrt(gTY.size) / nTY
+    rows = {"TY (relative)": (rel(gTY, want["TY"]), sTY, max(1e-10, 10 * sTY)),
+            "sigma2": (abs(gs2 - os2), spread["sigma2"], max(1e-9 * abs(os2) + 1e-12, 10 * spread["sigma2"])),
+            "B": (np.abs(gB - want["B"]).max(), spread["B"], max(1e-9, 10 * spread["B"])),
+            "t": (np.abs(gt - want["t"]).max(), spread["t"], max(1e-8, 10 * spread["t"]))}
+    print("affine, elongated template: " + "; ".join(f"{k} dev {d:.2e} spread {s:.2e} bound {b:.2e}" for k, (d, s, b) in rows.items()))
+    for k, (d, s, b) in rows.items():
+        assert d <= b, (k, d, s, b)
