@@ -10,7 +10,7 @@ from .api import (  # noqa: F401
     IcpRegistration, IcpRegistrationState, LandmarkCorrespondences, ModelFittingParameters, PointDistributionModel,
     DevicePointDistributionModel, GaussianKernelParameters, GPMMTriangleMesh3D, PointSetHelper, automaticGPMMfromTemplate,
     GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo,
-    AugmentedDevicePointDistributionModel, AugmentInfo,
+    AugmentedDevicePointDistributionModel, AugmentInfo, LaplacianDevicePointDistributionModel, LaplacianInfo,
     TemplateConfiguration, TemplateRegistration, TemplateRegistrationState,
 )
 from ._native import GingrNativeError  # noqa: F401

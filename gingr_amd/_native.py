@@ -104,6 +104,12 @@ class AugmentInfo(ctypes.Structure):
     _fields_ = [("columns", c_int32), ("rank", c_int32), ("total_variance", c_double), ("kept_variance", c_double)]
 
 
+class LaplacianInfo(ctypes.Structure):
+    """gingr_laplacian_info"""
+    _fields_ = [("n_components", c_int32), ("n_dropped", c_int32), ("block_columns", c_int32), ("outer_iterations", c_int32),
+                ("total_degree", c_int32), ("converged", c_int32), ("max_residual", c_double), ("cut_gap", c_double)]
+
+
 class NicpInfo(ctypes.Structure):
     """gingr_nicp_info"""
     _fields_ = [("iterations", c_int32), ("converged", c_int32), ("residual", c_double * 3), ("rhs_norm", c_double * 3)]
@@ -222,6 +228,8 @@ SIGNATURES = {
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),
+    "gingr_model_from_laplacian": (c_int, [c_void_p, c_int64, _dp, c_int64, _ip, c_double, c_int32, c_double, c_int32,
+                                           POINTER(LaplacianInfo), POINTER(c_void_p)]),
     "gingr_fitter_retry_counter": (c_int, [c_void_p, c_int32, POINTER(c_int32)]),
     "gingr_fitter_exchange": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64)]),
     "gingr_fitter_cpd_phase_async": (c_int, [c_void_p, POINTER(CpdParams), c_int32]),

@@ -295,6 +295,19 @@ class PcaInfo:
 
 
 @dataclasses.dataclass(frozen=True)
+class LaplacianInfo:
+    """gingr_laplacian_info: what the eigensolver behind GPMMTriangleMesh3D.InverseLaplacianSpectral did."""
+    n_components: int        # connected components of the edge graph (an isolated vertex is one)
+    n_dropped: int           # eigenvalues <= 1e-5 (the components' null vectors and whatever else lies below the cut-off)
+    block_columns: int       # columns of the iteration block
+    outer_iterations: int    # filter + orthonormalisation + Rayleigh-Ritz steps
+    total_degree: int        # products of the Laplacian with the block
+    converged: bool          # every wanted residual within the tolerance
+    max_residual: float      # largest |L v - mu v| / (2 max degree) of the wanted pairs
+    cut_gap: float           # (mu_{k+1} - mu_k) / mu_k at the cut; inf when no eigenvalue is left beyond it
+
+
+@dataclasses.dataclass(frozen=True)
 class GpmmBuildInfo:
     """gingr_gpmm_info: what the factorisation behind a device-built model did."""
     columns: int                   # factor columns of the pivoted Cholesky (= the model's rank before truncation)
@@ -585,6 +598,47 @@ class PcaDevicePointDistributionModel(DevicePointDistributionModel):
         return self.to_host(basis=False).mean
 
 
+class LaplacianDevicePointDistributionModel(DevicePointDistributionModel):
+    """The inverse-Laplacian model from the sparse graph Laplacian's own smallest eigenpairs (gingr_model_from_laplacian), built in
+    HBM and adopted like a PCA model.  `laplacianInfo` carries gingr_laplacian_info -- also on the exception of a solve that did not
+    converge (`.laplacianInfo` of the GingrNativeError); reference and mean are read back once, basis and variance only if somebody asks."""
+
+    def __init__(self, ctx: Context, reference, cells, scaling: float, pairs: int, tolerance: Optional[float] = None,
+                 maxDegree: Optional[int] = None):
+        ref = f64(reference).reshape(-1, 3)
+        tri = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        M = ref.shape[0]
+        self.ctx = ctx
+        self.cells = tri
+        self._kernels, self._host, self._info = None, None, None
+        self._to_tolerance, self._keep = False, 0
+        h, info = c_void_p(), nat.LaplacianInfo()
+        rc = ctx._lib.gingr_model_from_laplacian(ctx.handle, M, dptr(ref), tri.shape[0], iptr(tri), float(scaling), int(pairs),
+                                                 0.0 if tolerance is None else float(tolerance), 0 if maxDegree is None else int(maxDegree),
+                                                 ctypes.byref(info), ctypes.byref(h))
+        self.laplacianInfo = LaplacianInfo(int(info.n_components), int(info.n_dropped), int(info.block_columns), int(info.outer_iterations),
+                                           int(info.total_degree), bool(info.converged), float(info.max_residual), float(info.cut_gap))
+        try:
+            _check(ctx.handle, rc, "gingr_model_from_laplacian")
+        except nat.GingrNativeError as e:
+            e.laplacianInfo = self.laplacianInfo
+            raise
+        self._full = DeviceModel._adopt(ctx, h, self, M)
+        try:
+            self._host = self._full.download(basis=False)
+        except Exception:
+            self._full.close()
+            raise
+        self.reference = self._host.reference
+
+    def _build(self, ctx: Context, row_begin: int, row_end: int):
+        raise ValueError("a spectral inverse-Laplacian model lives whole on the context it was built on; download it (to_host) for anything else")
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self.to_host(basis=False).mean
+
+
 class AugmentedDevicePointDistributionModel(DevicePointDistributionModel):
     """PointDistributionModel.augmentModel: covariance and mean of two resident models added (gingr_model_augment), built in HBM and
     adopted like a PCA model.  `augmentInfo` carries gingr_augment_info; reference and mean are read back once, basis and variance only
@@ -722,6 +776,23 @@ class GPMMTriangleMesh3D:
         host work exactly as in the reference (LaplacianHelper, MatrixHelper.pinv); the low-rank factorisation runs on the device."""
         k = ScalarKernelSpec("lookup", scaling=scaling, lookup=LaplacianHelper(self.reference.shape[0], self._need_cells()).inverseLaplacianMatrix())
         return self._diagonal(k, k, k)
+
+    def InverseLaplacianSpectral(self, scaling: float, rank: int, tolerance: Optional[float] = None,
+                                 maxDegree: Optional[int] = None) -> "LaplacianDevicePointDistributionModel":
+        """The model of InverseLaplacian(scaling) built to a tight tolerance and truncated to `rank`, without the n x n pseudo-inverse
+        (gingr_model_from_laplacian): its leading components are the rank / 3 smallest non-zero eigenpairs of the sparse graph
+        Laplacian, each on x, y and z, found by a block eigensolver on the device.  `rank` is the model's rank, a multiple of 3, at most
+        510.  tolerance: the residual bound relative to 2 * (largest vertex degree), default 1e-10; maxDegree: the budget of
+        products of the Laplacian with the block (default: the library's).  A solve that does not converge within the budget raises;
+        `.laplacianInfo` of the model (or of the exception) says what the solver did.
+        There is no tolerance-driven rank: the trace of pinv(L) is not available without the whole spectrum, and the spectrum decays
+        so slowly (1 % of the trace needs 629 of 660 components at 221 vertices) that a trace rule would mean nothing."""
+        cells = self._need_cells()
+        rank = int(rank)
+        if rank < 3 or rank % 3 != 0:
+            raise ValueError(f"rank = {rank}: the spectral inverse-Laplacian model holds every eigenvector on x, y and z, so its rank is a "
+                             "positive multiple of 3")
+        return LaplacianDevicePointDistributionModel(self.ctx, self.reference, cells, scaling, rank // 3, tolerance, maxDegree)
 
     def InverseLaplacianDot(self, scaling: float, gamma: float) -> DevicePointDistributionModel:
         """GPMMHelper.scala:138-142: DotProductKernel(LookupKernel(..), gamma) * scaling = scaling * x.y (see GaussianDot); the

@@ -302,6 +302,18 @@ class InvLapKernel:
 
 
 @dataclasses.dataclass(frozen=True)
+class InvLapSpectralKernel:
+    """InvLapKernel at a fixed rank (a multiple of 3) from the sparse Laplacian's own eigenpairs: GPMMTriangleMesh3D.InverseLaplacianSpectral"""
+    scaling: float
+    rank: int
+    name = "InvLapSpectral"
+
+    @property
+    def printpars(self) -> str:
+        return f"{self.scaling}_{self.rank}"
+
+
+@dataclasses.dataclass(frozen=True)
 class InvLapDotKernel:
     scaling: float
     gamma: float
@@ -361,6 +373,8 @@ class SimpleTriangleModels3D:
                                toTolerance=toTolerance)
         if isinstance(kernelSelect, InvLapKernel):
             return g.InverseLaplacian(scaling=kernelSelect.scaling)
+        if isinstance(kernelSelect, InvLapSpectralKernel):
+            return g.InverseLaplacianSpectral(scaling=kernelSelect.scaling, rank=kernelSelect.rank)
         if isinstance(kernelSelect, InvLapDotKernel):
             return g.InverseLaplacianDot(scaling=kernelSelect.scaling, gamma=kernelSelect.gamma)
         if isinstance(kernelSelect, GaussKernel):

@@ -563,6 +563,39 @@ typedef struct gingr_augment_info {
 int gingr_model_augment(gingr_ctx *ctx, const gingr_model *a, const gingr_model *b, double relative_tolerance,
                         int32_t max_rank, gingr_model **out, gingr_augment_info *info /* may be NULL */);
 
+/* ---- the inverse-Laplacian model from the sparse Laplacian's own eigenpairs -------------------------------------------------
+ * The model of DiagonalKernel(LookupKernel(pinv(L)) * scaling) (GPMMHelper.scala:132-136, InvLapKernel) without the n x n
+ * pseudo-inverse: a new, finalized, single-shard model on this context.  Everything is host memory: ref_xyz [3 M] the reference,
+ * cells [3 n_cells] its triangles.
+ * Definition.  L = D - A, A the adjacency of the unique undirected edges of the triangulation (LaplacianHelper.laplacianMatrix; a
+ * cell that names a vertex twice adds no loop).  (mu_j, v_j): its eigenpairs, |v_j| = 1, mu ascending, those with mu <= 1e-5 dropped
+ * (the cut-off of MatrixHelper.pinv, MatrixHelper.scala:21-26: one null vector per connected component, isolated vertices included);
+ * j = 0 .. k - 1 over what is left, k = n_pairs.  The model has rank 3 k, mean 0 and the reference as given; for d in {x, y, z}
+ * variance[3 j + d] = scaling / mu_j and basis[(i, d), 3 j + d] = v_j[i], every other entry exactly 0.  The sign of v_j makes its
+ * component of largest magnitude positive (the lowest vertex index on a tie).  These are the leading 3 k components of the reference's
+ * model built to a tight tolerance.  A cut inside a cluster of equal eigenvalues is allowed: the vectors are then some orthonormal
+ * vectors of that eigenspace, and info->cut_gap says so.
+ * Solve: Chebyshev-filtered subspace iteration on the device (lap_spectral.hip), stopped when |L v - mu v| <= tolerance * Lambda for
+ * every wanted pair, Lambda = 2 * (largest vertex degree); tolerance <= 0: 1e-10.  max_degree: the budget of products of L with the
+ * block, <= 0: the default (4 000).  A solve that does not reach the tolerance within the budget returns GINGR_ERR_NOT_CONVERGED and
+ * no model -- never a less accurate one.  Two calls with the same input give the same bits.  Synchronises.
+ * GINGR_ERR_BAD_ARGUMENT (gingr_last_error names the cause): n_pairs outside 1 .. 170 (3 k <= 512), n_pairs larger than the number of
+ * eigenvalues above the cut-off, n_cells < 1, a cell index outside [0, M), scaling not positive; GINGR_ERR_NONFINITE: a non-finite
+ * coordinate.  *out is NULL then; info (nullable) is filled in as far as the call came. */
+typedef struct gingr_laplacian_info {
+    int32_t n_components;     /* connected components of the edge graph (an isolated vertex is one) */
+    int32_t n_dropped;        /* eigenvalues <= 1e-5: the components' null vectors and whatever else lies below the cut-off */
+    int32_t block_columns;    /* columns of the iteration block (wanted + guard, padded to a multiple of 16) */
+    int32_t outer_iterations; /* filter + orthonormalisation + Rayleigh-Ritz steps */
+    int32_t total_degree;     /* products of L with the block */
+    int32_t converged;        /* 1: every wanted residual is within the tolerance */
+    double max_residual;      /* largest |L v - mu v| / Lambda of the wanted pairs at the end */
+    double cut_gap;           /* (mu_{k+1} - mu_k) / mu_k from the first guard column's Ritz value; +inf when no eigenvalue is left */
+} gingr_laplacian_info;
+int gingr_model_from_laplacian(gingr_ctx *ctx, int64_t M, const double *ref_xyz, int64_t n_cells, const int32_t *cells, double scaling,
+                               int32_t n_pairs, double tolerance, int32_t max_degree, gingr_laplacian_info *info /* may be NULL */,
+                               gingr_model **out);
+
 /* The retry counter of the probabilistic proposal (G/api/GingrAlgorithm.scala:69-70,196-202,210: `retryCounter`, a private var
  * of the algorithm INSTANCE): a sampled proposal whose posterior cannot be computed returns the state unchanged up to 10 times in
  * a row before the state is marked ModelFlexibilityError; every successful posterior gives one retry back (at most 10).  The
@@ -788,7 +821,8 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * nearest-neighbour scan kernel alone, 9 = the per-vertex covariance pass over the basis alone, 10 = the basis pass of the posterior model (basis_rotate_kernel) alone,
  * 11 / 12 = the cross Gram pass / the two-source basis pass of gingr_model_augment alone, 13 .. 16 = the stages of gingr_mesh_decimate:
  * bounding box, bisection (every enqueued step, the ones that return at once included), clusters and representatives (insertion at
- * the chosen size, sort, means, argmin), compaction of vertices and triangles.  Returns accumulated ms and launches since
+ * the chosen size, sort, means, argmin), compaction of vertices and triangles, 17 = the Chebyshev step of gingr_model_from_laplacian
+ * (lap_cheb_kernel) alone.  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);

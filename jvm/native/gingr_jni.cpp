@@ -340,6 +340,20 @@ JFN(jlong, modelFromShapes)(JNIEnv *env, jclass, jlong ctx, jdoubleArray ref, jd
     }
     return reinterpret_cast<jlong>(m);
 }
+JFN(jlong, modelFromLaplacian)(JNIEnv *env, jclass, jlong ctx, jdoubleArray ref, jintArray cells, jdouble scaling, jint nPairs, jdouble tolerance,
+                                jint maxDegree, jdoubleArray info8) {
+    Arr<double> a(env, ref, true); Arr<int32_t> b(env, cells, true); Arr<double> c(env, info8, false);
+    if (a.buf.empty() || a.buf.size() % 3 != 0 || b.buf.size() % 3 != 0) return 0;  // (x, y, z per point; whole triangles)
+    gingr_model *m = nullptr;
+    gingr_laplacian_info info{};
+    const int rc = gingr_model_from_laplacian(P<gingr_ctx>(ctx), (int64_t)a.buf.size() / 3, a.ptr(), (int64_t)b.buf.size() / 3, b.ptr(), scaling,
+                                              nPairs, tolerance, maxDegree, &info, &m);
+    if (c.buf.size() >= 8) {  // (filled in as far as the call came, also when it fails)
+        c.buf[0] = info.n_components; c.buf[1] = info.n_dropped; c.buf[2] = info.block_columns; c.buf[3] = info.outer_iterations;
+        c.buf[4] = info.total_degree; c.buf[5] = info.converged; c.buf[6] = info.max_residual; c.buf[7] = info.cut_gap;
+    }
+    return rc == GINGR_OK ? reinterpret_cast<jlong>(m) : 0;
+}
 JFN(jlong, rigidIcpCreate)(JNIEnv *env, jclass, jlong ctx, jint kind, jdoubleArray tpl, jdoubleArray target) {
     Arr<double> a(env, tpl, true); Arr<double> b(env, target, true);
     gingr_rigid_icp *h = nullptr;

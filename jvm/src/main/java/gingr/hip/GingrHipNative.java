@@ -106,6 +106,12 @@ public final class GingrHipNative {
      *  returns the model handle or 0 */
     public static native long modelFromShapes(long ctx, double[] refXyz, double[] shapesXyz, int alignment, int gpaMaxIterations,
                                               double gpaTolerance, double relativeTolerance, int maxRank, double[] info5);
+    /** gingr_model_from_laplacian: the inverse-Laplacian model (InvLapKernel) from the nPairs smallest non-zero eigenpairs of the sparse
+     *  graph Laplacian of the triangulation, rank 3 nPairs, no n x n matrix; tolerance / maxDegree <= 0: the library's defaults;
+     *  info8 (nullable, length >= 8) receives { components, dropped eigenvalues, block columns, outer iterations, total degree,
+     *  converged, largest residual, relative gap at the cut }; returns the model handle or 0 */
+    public static native long modelFromLaplacian(long ctx, double[] refXyz, int[] cells, double scaling, int nPairs, double tolerance,
+                                                 int maxDegree, double[] info8);
     // ---- classic rigid / similarity ICP (other/algorithms/icp/RigidICP.scala; kind 0 = RigidRegistrator3D, 1 = AffineRegistrator3D)
     public static native long rigidIcpCreate(long ctx, int kind, double[] templateXyz, double[] targetXyz);
     public static native void rigidIcpDestroy(long handle);
