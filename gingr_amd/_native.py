@@ -93,6 +93,14 @@ class GpmmInfo(ctypes.Structure):
                 ("kept_variance_fraction", c_double)]
 
 
+CLASSIC_CPD_MAX_COLUMNS = 512
+
+
+class ClassicCpdLowRankInfo(ctypes.Structure):
+    """gingr_classic_cpd_lowrank_info"""
+    _fields_ = [("columns", c_int32), ("tolerance_reached", c_int32), ("residual_fraction", c_double), ("factor_bytes", c_int64)]
+
+
 class PcaInfo(ctypes.Structure):
     """gingr_pca_info"""
     _fields_ = [("rank", c_int32), ("gpa_sweeps", c_int32), ("gpa_last_change", c_double), ("total_variance", c_double),
@@ -152,6 +160,9 @@ SIGNATURES = {
     "gingr_classic_cpd_iterate": (c_int, [c_void_p, c_int32]),
     "gingr_classic_cpd_get": (c_int, [c_void_p, _dp, POINTER(c_double), _dp, _dp]),
     "gingr_classic_cpd_set": (c_int, [c_void_p, _dp, c_double]),
+    "gingr_classic_cpd_create_lowrank": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_double, c_double, c_double, c_double, c_int32,
+                                                 POINTER(ClassicCpdLowRankInfo), POINTER(c_void_p)]),
+    "gingr_classic_cpd_get_factor": (c_int, [c_void_p, _ip, _dp]),
     "gingr_bcpd_create": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_double, c_double, c_double, c_double, c_double, POINTER(c_void_p)]),
     "gingr_bcpd_destroy": (None, [c_void_p]),
     "gingr_bcpd_iterate": (c_int, [c_void_p, c_int32]),

@@ -20,18 +20,40 @@ from ._native import f64, dptr
 RIGID, AFFINE, NONRIGID = 0, 1, 2
 
 
-class RigidCPD:
-    """RigidCPD / AffineCPD / NonRigidCPD (one class, `kind` selects the Maximization)."""
+class LowRankG:
+    """The non-rigid kind over a low-rank factor of the kernel matrix, G ~ L L^T (Myronenko & Song 2010, "fast implementation"):
+    the pivoted Cholesky of the Gaussian over the template, stopped when the residual trace falls below relativeTolerance * trace or
+    at maxColumns (0: the library's ceiling of 512 columns).  No M x M matrix is formed: templates past the dense limit register."""
 
-    def __init__(self, factory: "CPDFactory", targetPoints, kind: int):
+    def __init__(self, relativeTolerance: float = 1e-8, maxColumns: int = 0):
+        self.relativeTolerance, self.maxColumns = float(relativeTolerance), int(maxColumns)
+
+
+class RigidCPD:
+    """RigidCPD / AffineCPD / NonRigidCPD (one class, `kind` selects the Maximization; lowRank: a LowRankG, non-rigid only)."""
+
+    def __init__(self, factory: "CPDFactory", targetPoints, kind: int, lowRank: Optional[LowRankG] = None):
+        if lowRank is not None and kind != NONRIGID:
+            raise ValueError("lowRank applies to the non-rigid kind only")
         self.cpd, self.kind = factory, kind
         self.target = f64(targetPoints)
         self.N = self.target.shape[0]
         self._lib = factory.ctx._lib
+        self._h, self.lowRankInfo = None, None
         h = c_void_p()
-        _check(factory.ctx.handle, self._lib.gingr_classic_cpd_create(factory.ctx.handle, kind, factory.M, dptr(factory.template), self.N,
-                                                                      dptr(self.target), float(factory.lambda_), float(factory.beta),
-                                                                      float(factory.w), ctypes.byref(h)), "gingr_classic_cpd_create")
+        if lowRank is None:
+            _check(factory.ctx.handle, self._lib.gingr_classic_cpd_create(factory.ctx.handle, kind, factory.M, dptr(factory.template), self.N,
+                                                                          dptr(self.target), float(factory.lambda_), float(factory.beta),
+                                                                          float(factory.w), ctypes.byref(h)), "gingr_classic_cpd_create")
+        else:
+            from ._native import ClassicCpdLowRankInfo
+            info = ClassicCpdLowRankInfo()
+            _check(factory.ctx.handle, self._lib.gingr_classic_cpd_create_lowrank(
+                factory.ctx.handle, factory.M, dptr(factory.template), self.N, dptr(self.target), float(factory.lambda_), float(factory.beta),
+                float(factory.w), float(lowRank.relativeTolerance), int(lowRank.maxColumns), ctypes.byref(info), ctypes.byref(h)),
+                "gingr_classic_cpd_create_lowrank")
+            self.lowRankInfo = {"columns": int(info.columns), "tolerance_reached": bool(info.tolerance_reached),
+                                "residual_fraction": float(info.residual_fraction), "factor_bytes": int(info.factor_bytes)}
         self._h = h
         self._sigma2_init = self.sigma2()      # initializeGaussianKernel of the factory's template against this target
 
@@ -72,6 +94,14 @@ class RigidCPD:
         w = np.empty((self.cpd.M, 3))
         _check(self.cpd.ctx.handle, self._lib.gingr_classic_cpd_get(self._h, None, None, None, dptr(w)), "gingr_classic_cpd_get")
         return w
+
+    def factor(self) -> np.ndarray:
+        """L (M, k) of a low-rank task: G ~ L @ L.T"""
+        k = ctypes.c_int32()
+        _check(self.cpd.ctx.handle, self._lib.gingr_classic_cpd_get_factor(self._h, ctypes.byref(k), None), "gingr_classic_cpd_get_factor")
+        L = np.empty((self.cpd.M, k.value))
+        _check(self.cpd.ctx.handle, self._lib.gingr_classic_cpd_get_factor(self._h, None, dptr(L)), "gingr_classic_cpd_get_factor")
+        return L
 
     # -- the reference surface ------------------------------------------------------------------------------------
     def Iteration(self, Y=None, sigma2: Optional[float] = None) -> Tuple[np.ndarray, float]:
@@ -116,8 +146,8 @@ class CPDFactory:
     def registerRigidly(self, targetPoints) -> RigidCPD:
         return RigidCPD(self, targetPoints, RIGID)
 
-    def registerNonRigidly(self, targetPoints) -> RigidCPD:
-        return RigidCPD(self, targetPoints, NONRIGID)
+    def registerNonRigidly(self, targetPoints, lowRank: Optional[LowRankG] = None) -> RigidCPD:
+        return RigidCPD(self, targetPoints, NONRIGID, lowRank)
 
     def registerAffine(self, targetPoints) -> RigidCPD:
         return RigidCPD(self, targetPoints, AFFINE)
@@ -129,11 +159,14 @@ class RigidCPDRegistration:
 
     _kind = RIGID
 
-    def __init__(self, ctx: Context, template, lambda_: float = 2.0, beta: float = 2.0, w: float = 0.0, max_iterations: int = 100):
-        self.cpd, self.max_iterations = CPDFactory(ctx, template, lambda_, beta, w), max_iterations
+    def __init__(self, ctx: Context, template, lambda_: float = 2.0, beta: float = 2.0, w: float = 0.0, max_iterations: int = 100,
+                 lowRank: Optional[LowRankG] = None):
+        if lowRank is not None and self._kind != NONRIGID:
+            raise ValueError("lowRank applies to the non-rigid kind only")
+        self.cpd, self.max_iterations, self.lowRank = CPDFactory(ctx, template, lambda_, beta, w), max_iterations, lowRank
 
     def register(self, target) -> np.ndarray:
-        task = RigidCPD(self.cpd, target, self._kind)
+        task = RigidCPD(self.cpd, target, self._kind, self.lowRank)
         try:
             return task.Registration(self.max_iterations)
         finally:

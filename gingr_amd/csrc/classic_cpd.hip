@@ -15,11 +15,13 @@
 // substitution is a by-product), a blocked backward substitution, and TY = Y + G W as one pass over G.
 #include "common.h"
 #include "block_sum.h"
+#include "classic_cpd_lowrank.h"
 #include "dense_spd.h"
 #include "svd3.h"
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 namespace {
@@ -332,6 +334,16 @@ struct gingr_classic_cpd {
     int64_t M = 0, N = 0, Mp = 0;
     double lambda = 2.0, beta = 2.0, w = 0.0;
     DevBuf X, TY, den, inv_den, Pt1, P1, PX, ws, part, sc, aux, red, mu, params, flag, G, Aw, Linv, W, stage;
+    std::unique_ptr<LowRankCpd> lowrank;  // gingr_classic_cpd_create_lowrank: G, Aw and Linv stay empty
+};
+
+static_assert(GINGR_CLASSIC_CPD_MAX_COLUMNS == lowrank_plan::kMaxColumns, "the header's ceiling is the plan's");
+
+// what gingr_classic_cpd_create_lowrank adds to the arguments of gingr_classic_cpd_create
+struct LowRankRequest {
+    double relative_tolerance;
+    int32_t max_columns;
+    gingr_classic_cpd_lowrank_info *info;
 };
 
 extern "C" {
@@ -342,15 +354,16 @@ void gingr_classic_cpd_destroy(gingr_classic_cpd *h) {
     delete h;
 }
 
-int gingr_classic_cpd_create(gingr_ctx *ctx, int32_t kind, int64_t M, const double *template_xyz, int64_t N, const double *target_xyz,
-                             double lambda, double beta, double w, gingr_classic_cpd **out) {
+static int classic_cpd_create_impl(gingr_ctx *ctx, int32_t kind, int64_t M, const double *template_xyz, int64_t N,
+                                   const double *target_xyz, double lambda, double beta, double w, const LowRankRequest *lowrank,
+                                   gingr_classic_cpd **out) {
     if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
     if (!out || !template_xyz || !target_xyz || M < 1 || N < 1 || kind < 0 || kind > 2)
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "classic_cpd_create: bad argument");
     // CPDFactory's requirements (CPDFactory.scala:43-45); w = 1 divides by zero in the outlier constant
     if (!(w >= 0.0 && w < 1.0) || !(beta > 0.0) || !(lambda > 0.0))
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "classic_cpd_create: need 0 <= w < 1, beta > 0, lambda > 0");
-    if (kind == 2 && M > 46000) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "classic_cpd_create: non-rigid template too large");
+    if (kind == 2 && !lowrank && M > 46000) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "classic_cpd_create: non-rigid template too large");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     gingr_classic_cpd *h = new gingr_classic_cpd;
     h->ctx = ctx;
@@ -406,7 +419,20 @@ int gingr_classic_cpd_create(gingr_ctx *ctx, int32_t kind, int64_t M, const doub
     CC_TRY(hipStreamSynchronize(ctx->stream));
     const double s0 = tot / (3.0 * (double)N * (double)M);
     CC_TRY(hipMemcpyAsync(h->sc.as<double>() + 8, &s0, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (kind == 2) {
+    if (lowrank) {
+        h->lowrank.reset(new LowRankCpd);
+        CC_TRY(h->W.alloc((size_t)3 * h->Mp * sizeof(double)));
+        CC_TRY(hipMemsetAsync(h->W.p, 0, (size_t)3 * h->Mp * sizeof(double), ctx->stream));
+        const int rc = lowrank_cpd_build(ctx, Y, beta, lowrank->relative_tolerance, lowrank->max_columns, *h->lowrank);
+        if (rc != GINGR_OK) {
+            (void)hipGetLastError();  // (a refused allocation must not surface again in the next call's launch check)
+            return fail(rc);
+        }
+        if (lowrank->info) {
+            const LowRankCpd &lr = *h->lowrank;
+            *lowrank->info = gingr_classic_cpd_lowrank_info{lr.plan.k, lr.tolerance_reached, lr.residual_fraction, (int64_t)lr.L.bytes};
+        }
+    } else if (kind == 2) {
         const int64_t Mp = h->Mp;
         const DenseSpdWork sys(Mp, DenseSpdWork::kRhsRows);
         CC_TRY(h->G.alloc((size_t)M * M * sizeof(double)));
@@ -420,6 +446,35 @@ int gingr_classic_cpd_create(gingr_ctx *ctx, int32_t kind, int64_t M, const doub
     CC_TRY(hipStreamSynchronize(ctx->stream));
 #undef CC_TRY
     *out = h;
+    return GINGR_OK;
+}
+
+int gingr_classic_cpd_create(gingr_ctx *ctx, int32_t kind, int64_t M, const double *template_xyz, int64_t N, const double *target_xyz,
+                             double lambda, double beta, double w, gingr_classic_cpd **out) {
+    return classic_cpd_create_impl(ctx, kind, M, template_xyz, N, target_xyz, lambda, beta, w, nullptr, out);
+}
+
+int gingr_classic_cpd_create_lowrank(gingr_ctx *ctx, int64_t M, const double *template_xyz, int64_t N, const double *target_xyz,
+                                     double lambda, double beta, double w, double relative_tolerance, int32_t max_columns,
+                                     gingr_classic_cpd_lowrank_info *info, gingr_classic_cpd **out) {
+    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
+    if (info) memset(info, 0, sizeof(*info));
+    if (!(relative_tolerance >= 0.0) || !(relative_tolerance < 1.0))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "classic_cpd_create_lowrank: relative tolerance must be in [0, 1)");
+    if (max_columns > GINGR_CLASSIC_CPD_MAX_COLUMNS)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "classic_cpd_create_lowrank: max_columns = %d is above the ceiling of %d factor columns",
+                               (int)max_columns, GINGR_CLASSIC_CPD_MAX_COLUMNS);
+    const LowRankRequest req{relative_tolerance, max_columns, info};
+    return classic_cpd_create_impl(ctx, 2, M, template_xyz, N, target_xyz, lambda, beta, w, &req, out);
+}
+
+int gingr_classic_cpd_get_factor(gingr_classic_cpd *h, int32_t *columns, double *L_rowmajor_M_by_k) {
+    if (!h) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = h->ctx;
+    if (!h->lowrank) return gingr_set_error(ctx, GINGR_ERR_STATE, "classic_cpd_get_factor: the handle holds the dense kernel matrix, not a factor");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (columns) *columns = h->lowrank->plan.k;
+    if (L_rowmajor_M_by_k) return lowrank_cpd_get_factor(ctx, *h->lowrank, L_rowmajor_M_by_k);
     return GINGR_OK;
 }
 
@@ -440,7 +495,9 @@ int gingr_classic_cpd_iterate(gingr_classic_cpd *h, int32_t n_iterations) {
                                 h->part.as<double>(), sc);
         launch_cpd_rowstats(ctx, Y, X, s2, aux, h->inv_den.as<double>(), nullptr, nullptr, h->ws.as<double>(), h->P1.as<double>(),
                             h->PX.as<double>(), h->part.as<double>(), sc);
-        if (h->kind != 2) {
+        if (h->lowrank) {
+            lowrank_cpd_mstep(ctx, *h->lowrank, h->P1.as<double>(), h->PX.as<double>(), ty, sc, h->lambda, h->W.as<double>(), Mp, flag);
+        } else if (h->kind != 2) {
             hipLaunchKernelGGL(means_kernel, dim3(kRedBlocks), dim3(256), 0, ctx->stream, X, h->Pt1.as<double>(), Y, h->P1.as<double>(),
                                h->red.as<double>());
             hipLaunchKernelGGL(means_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, h->red.as<double>(), sc, h->mu.as<double>());

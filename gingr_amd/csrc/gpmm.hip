@@ -25,6 +25,7 @@
 #include "gp.h"
 
 #include "fastexp.h"
+#include "gpmm_factor.h"
 #include "gpmm_plan.h"
 
 #include <algorithm>
@@ -32,14 +33,13 @@
 
 namespace {
 
-constexpr int kMaxMix = 8;
-constexpr int kPcBlock = 256;
+using gpmm_factor::Factor;
+using gpmm_factor::kMaxMix;
+using gpmm_factor::KSpec;
+using gpmm_factor::KSpec3;
+using gpmm_factor::Mixture;
 
-struct Mixture {
-    int32_t n;
-    double c[kMaxMix];  // -2048 log2(e) / sigma^2
-    double s[kMaxMix];  // scaling
-};
+constexpr int kPcBlock = 256;
 
 __device__ __forceinline__ double mixture_value(const Mixture &mix, double d2, const double *T) {
     double v = 0.0;
@@ -49,20 +49,6 @@ __device__ __forceinline__ double mixture_value(const Mixture &mix, double d2, c
     }
     return v;
 }
-
-// One scalar kernel of a DiagonalKernel(k_x, k_y, k_z) (GPMMHelper.scala:96-142, KernelHelper.scala:25-84):
-//   kind 0  sum_i scaling_i exp(-|x-y|^2/sigma_i^2)  [+ mirror * the same kernel at (Mx, y), M = diag(-1,1,1): the x-mirrored
-//           kernel of KernelHelper.symmetrizeKernel -- xMirroredKernel3D evaluates kernel(Point(-x0, x1, x2), y)]
-//   kind 1  scale * (x . y)          DotProductKernel.k returns x.dot(y) whatever kernel / gamma it wraps (KernelHelper.scala:43-51)
-//   kind 2  scale * m[i][j]          LookupKernel on the reference points themselves (closest reference point of a reference
-//                                     point = the point), m = pinv(graph Laplacian) (LaplacianHelper.scala:27-41)
-struct KSpec {
-    int32_t kind;
-    Mixture mix;
-    double mirror;
-    double scale;
-    const double *lookup;  // device, M x M row-major
-};
 
 __device__ __forceinline__ double kspec_value(const KSpec &k, const Cloud &pts, int64_t c, int64_t p, double px, double py,
                                               double pz, const double *T) {
@@ -155,10 +141,6 @@ __device__ __forceinline__ void block_best_sum(Best &b, double &sum, Best *shb, 
 // GEN = false: one scalar kernel, entries = points.  GEN = true: the generic factorisation over the 3M (point, coordinate) entries
 // of a DiagonalKernel(k_x, k_y, k_z) whose coordinates have DIFFERENT kernels (entry e = 3 point + coordinate; entries of
 // different coordinates never interact: their column values are exact zeros).
-struct KSpec3 {
-    KSpec k[3];
-};
-
 template <bool GEN>
 __global__ __launch_bounds__(kPcBlock) void pc_init_kernel(Cloud pts, KSpec3 specs, double *__restrict__ diag,
                                                            int32_t *__restrict__ pivoted, double *__restrict__ pmax,
@@ -412,70 +394,61 @@ __global__ __launch_bounds__(256) void gpmm_pack_generic_kernel(const double *__
     Q0[idx] = q < r ? B[(int64_t)q * 3 * M_total + 3 * (row_begin + (perm ? perm[s] : s)) + d] : 0.0;
 }
 
-// The pivoted Cholesky factorisation on the device: over the M points for one scalar kernel, or (gen) over the 3M (point,
-// coordinate) entries of a DiagonalKernel whose coordinates have different kernels.
-struct Factor {
-    gingr_ctx *ctx = nullptr;
-    KSpec3 specs{};
-    Cloud pts{};
-    decltype(&pc_step_kernel<false>) step_kernel = nullptr;  // pc_step_kernel<gen>
-    int64_t n = 0;     // entries
-    int nb = 0;
-    int32_t kcap = 0;  // columns the buffers can hold
-    int32_t ks = 0;    // columns computed
-    DevBuf Lb, diag, piv, part, ctl, trace, pivots, swd, swo;
-    std::vector<double> htrace;
-    double *pmaxv[2]{}, *ptrv[2]{};
-    int32_t *pidxv[2]{};
+}  // namespace
 
-    int init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap) {
-        ctx = c, specs = k, pts = p, n = gen ? 3 * p.n : p.n, kcap = cap;
-        step_kernel = gen ? pc_step_kernel<true> : pc_step_kernel<false>;
-        nb = (int)ceil_div(n, kPcBlock);
-        HIP_TRY(ctx, Lb.alloc((size_t)kcap * n * sizeof(double)));
-        HIP_TRY(ctx, diag.alloc((size_t)n * sizeof(double)));
-        HIP_TRY(ctx, piv.alloc((size_t)n * sizeof(int32_t)));
-        HIP_TRY(ctx, part.alloc((size_t)2 * nb * (2 * sizeof(double) + sizeof(int32_t)) + 64));
-        HIP_TRY(ctx, ctl.alloc(2 * sizeof(int32_t)));
-        HIP_TRY(ctx, trace.alloc((size_t)(kcap + 1) * sizeof(double)));
-        HIP_TRY(ctx, pivots.alloc((size_t)(kcap + 1) * sizeof(int32_t)));
-        HIP_TRY(ctx, swd.alloc((size_t)(kcap + 1) * sizeof(int32_t)));
-        HIP_TRY(ctx, swo.alloc((size_t)(kcap + 1) * sizeof(int32_t)));
-        pmaxv[0] = part.as<double>(), pmaxv[1] = part.as<double>() + nb;
-        ptrv[0] = part.as<double>() + 2 * nb, ptrv[1] = part.as<double>() + 3 * nb;
-        pidxv[0] = reinterpret_cast<int32_t *>(part.as<double>() + 4 * nb), pidxv[1] = pidxv[0] + nb;
-        hipLaunchKernelGGL(gen ? pc_init_kernel<true> : pc_init_kernel<false>, dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs,
-                           diag.as<double>(), piv.as<int32_t>(), pmaxv[0], pidxv[0], ptrv[0], ctl.as<int32_t>());
-        return check_launch(ctx);
-    }
+// The pivoted Cholesky factorisation (gpmm_factor.h) over the kernels above
+namespace gpmm_factor {
 
-    void launch(int32_t k, double rel_tol) {
-        const int in = k & 1, o = in ^ 1;
-        hipLaunchKernelGGL(step_kernel, dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs, k, kcap, rel_tol, nb, Lb.as<double>(),
-                           diag.as<double>(), piv.as<int32_t>(), pmaxv[in], pidxv[in], ptrv[in], pmaxv[o], pidxv[o], ptrv[o],
-                           ctl.as<int32_t>(), trace.as<double>(), pivots.as<int32_t>(), swd.as<int32_t>(), swo.as<int32_t>());
-    }
+int Factor::init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap) {
+    ctx = c, specs = k, pts = p, n = gen ? 3 * p.n : p.n, kcap = cap;
+    step_kernel = gen ? pc_step_kernel<true> : pc_step_kernel<false>;
+    nb = (int)ceil_div(n, kPcBlock);
+    HIP_TRY(ctx, Lb.alloc((size_t)kcap * n * sizeof(double)));
+    HIP_TRY(ctx, diag.alloc((size_t)n * sizeof(double)));
+    HIP_TRY(ctx, piv.alloc((size_t)n * sizeof(int32_t)));
+    HIP_TRY(ctx, part.alloc((size_t)2 * nb * (2 * sizeof(double) + sizeof(int32_t)) + 64));
+    HIP_TRY(ctx, ctl.alloc(2 * sizeof(int32_t)));
+    HIP_TRY(ctx, trace.alloc((size_t)(kcap + 1) * sizeof(double)));
+    HIP_TRY(ctx, pivots.alloc((size_t)(kcap + 1) * sizeof(int32_t)));
+    HIP_TRY(ctx, swd.alloc((size_t)(kcap + 1) * sizeof(int32_t)));
+    HIP_TRY(ctx, swo.alloc((size_t)(kcap + 1) * sizeof(int32_t)));
+    pmaxv[0] = part.as<double>(), pmaxv[1] = part.as<double>() + nb;
+    ptrv[0] = part.as<double>() + 2 * nb, ptrv[1] = part.as<double>() + 3 * nb;
+    pidxv[0] = reinterpret_cast<int32_t *>(part.as<double>() + 4 * nb), pidxv[1] = pidxv[0] + nb;
+    hipLaunchKernelGGL(gen ? pc_init_kernel<true> : pc_init_kernel<false>, dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs,
+                       diag.as<double>(), piv.as<int32_t>(), pmaxv[0], pidxv[0], ptrv[0], ctl.as<int32_t>());
+    return check_launch(ctx);
+}
 
-    // the whole factorisation under the device's stopping rule (residual trace below rel_tol * trace, capacity, exhaustion)
-    int run_to_tolerance(double rel_tol) {
-        int32_t hctl[2] = {0, 0};
-        for (int32_t k = 0; k <= kcap; ++k) {
-            launch(k, rel_tol);
-            if ((k & 15) == 15 || k == kcap) {  // look at the stop flag now and then instead of queueing no-op launches
-                GINGR_TRY(check_launch(ctx));
-                HIP_TRY(ctx, hipMemcpyAsync(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                if (hctl[1]) break;
-            }
+void Factor::launch(int32_t k, double rel_tol) {
+    const int in = k & 1, o = in ^ 1;
+    hipLaunchKernelGGL(step_kernel, dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs, k, kcap, rel_tol, nb, Lb.as<double>(),
+                       diag.as<double>(), piv.as<int32_t>(), pmaxv[in], pidxv[in], ptrv[in], pmaxv[o], pidxv[o], ptrv[o],
+                       ctl.as<int32_t>(), trace.as<double>(), pivots.as<int32_t>(), swd.as<int32_t>(), swo.as<int32_t>());
+}
+
+int Factor::run_to_tolerance(double rel_tol) {
+    int32_t hctl[2] = {0, 0};
+    for (int32_t k = 0; k <= kcap; ++k) {
+        launch(k, rel_tol);
+        if ((k & 15) == 15 || k == kcap) {  // look at the stop flag now and then instead of queueing no-op launches
+            GINGR_TRY(check_launch(ctx));
+            HIP_TRY(ctx, hipMemcpyAsync(hctl, ctl.p, sizeof(hctl), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (hctl[1]) break;
         }
-        if (!hctl[1]) return gingr_set_error(ctx, GINGR_ERR_STATE, "gpmm_build: pivoted Cholesky did not terminate");
-        ks = hctl[0];
-        htrace.resize((size_t)ks + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(htrace.data(), trace.p, htrace.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return GINGR_OK;
     }
-};
+    if (!hctl[1]) return gingr_set_error(ctx, GINGR_ERR_STATE, "gpmm_build: pivoted Cholesky did not terminate");
+    ks = hctl[0];
+    htrace.resize((size_t)ks + 1);
+    HIP_TRY(ctx, hipMemcpyAsync(htrace.data(), trace.p, htrace.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GINGR_OK;
+}
+
+}  // namespace gpmm_factor
+
+namespace {
 
 bool same_kernel(const gingr_scalar_kernel *a, const gingr_scalar_kernel *b) {
     if (a == b) return true;

@@ -1,0 +1,76 @@
+// The pivoted Cholesky factorisation of a scalar kernel over a point cloud on the device (gpmm.hip), for the translation units that
+// consume its factor: the GPMM construction itself and the low-rank non-rigid CPD (classic_cpd.hip).  Internal to libgingr_hip.so.
+#pragma once
+
+#include "common.h"
+#include "fastexp.h"
+
+namespace gpmm_factor {
+
+constexpr int kMaxMix = 8;
+
+struct Mixture {
+    int32_t n;
+    double c[kMaxMix];  // -2048 log2(e) / sigma^2
+    double s[kMaxMix];  // scaling
+};
+
+// One scalar kernel of a DiagonalKernel(k_x, k_y, k_z) (GPMMHelper.scala:96-142, KernelHelper.scala:25-84):
+//   kind 0  sum_i scaling_i exp(-|x-y|^2/sigma_i^2)  [+ mirror * the same kernel at (Mx, y), M = diag(-1,1,1): the x-mirrored
+//           kernel of KernelHelper.symmetrizeKernel -- xMirroredKernel3D evaluates kernel(Point(-x0, x1, x2), y)]
+//   kind 1  scale * (x . y)          DotProductKernel.k returns x.dot(y) whatever kernel / gamma it wraps (KernelHelper.scala:43-51)
+//   kind 2  scale * m[i][j]          LookupKernel on the reference points themselves (closest reference point of a reference
+//                                     point = the point), m = pinv(graph Laplacian) (LaplacianHelper.scala:27-41)
+struct KSpec {
+    int32_t kind;
+    Mixture mix;
+    double mirror;
+    double scale;
+    const double *lookup;  // device, M x M row-major
+};
+
+struct KSpec3 {
+    KSpec k[3];
+};
+
+// one Gaussian term scaling * exp(-|x-y|^2 / sigma^2) for all three coordinates
+inline KSpec3 gaussian_specs(double sigma, double scaling) {
+    KSpec3 s;
+    memset(&s, 0, sizeof(s));
+    for (KSpec &k : s.k) {
+        k.kind = GINGR_KERNEL_GAUSSIAN_MIXTURE;
+        k.mix.n = 1;
+        k.mix.c[0] = -(double)GINGR_EXP_TABLE * 1.4426950408889634074 / (sigma * sigma);
+        k.mix.s[0] = scaling;
+    }
+    return s;
+}
+
+// pc_step_kernel<gen> of gpmm.hip
+using StepKernel = void (*)(Cloud, KSpec3, int32_t, int32_t, double, int32_t, double *, double *, int32_t *, const double *,
+                            const int32_t *, const double *, double *, int32_t *, double *, int32_t *, double *, int32_t *, int32_t *,
+                            int32_t *);
+
+// The pivoted Cholesky factorisation on the device: over the M points for one scalar kernel, or (gen) over the 3M (point,
+// coordinate) entries of a DiagonalKernel whose coordinates have different kernels.
+struct Factor {
+    gingr_ctx *ctx = nullptr;
+    KSpec3 specs{};
+    Cloud pts{};
+    StepKernel step_kernel = nullptr;
+    int64_t n = 0;     // entries
+    int nb = 0;
+    int32_t kcap = 0;  // columns the buffers can hold
+    int32_t ks = 0;    // columns computed
+    DevBuf Lb, diag, piv, part, ctl, trace, pivots, swd, swo;  // Lb: [kcap][n], column r of the factor in row r
+    std::vector<double> htrace;                                // residual trace after 0 .. ks columns
+    double *pmaxv[2]{}, *ptrv[2]{};
+    int32_t *pidxv[2]{};
+
+    int init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap);
+    void launch(int32_t k, double rel_tol);
+    // the whole factorisation under the device's stopping rule (residual trace below rel_tol * trace, capacity, exhaustion)
+    int run_to_tolerance(double rel_tol);
+};
+
+}  // namespace gpmm_factor

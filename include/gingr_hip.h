@@ -852,6 +852,29 @@ int gingr_classic_cpd_iterate(gingr_classic_cpd *h, int32_t n_iterations);
 int gingr_classic_cpd_get(gingr_classic_cpd *h, double *ty_xyz, double *sigma2, double *transform13, double *w_xyz);
 int gingr_classic_cpd_set(gingr_classic_cpd *h, const double *ty_xyz, double sigma2);
 
+/* The non-rigid kind past dense sizes (Myronenko & Song 2010, "fast implementation"): G ~ L L^T by the pivoted Cholesky of the
+ * Gaussian over the template (the factorisation of gingr_gpmm_build_*: at most GINGR_CLASSIC_CPD_MAX_COLUMNS columns, stopped when
+ * the residual trace falls below relative_tolerance * trace) and the Woodbury identity: with D = diag(P1), c = lambda sigma2,
+ *     (c I + L^T D L) z = L^T (P X - D Y),   TY = Y + L z,   W = D (D^-1 P X - Y - L z) / c,
+ * which is the step of kind 2 with L L^T in place of G.  Nothing of size M x M is formed: no limit on M but the card's memory
+ * (the factor takes 8 bytes x M rounded up to 32 x k rounded up to 64; the factorisation, at create time only, as much again for the
+ * columns it may reach).  relative_tolerance in [0, 1); max_columns <= 0: to the tolerance under the ceiling, > 0: the
+ * caller's stop, above the ceiling: GINGR_ERR_BAD_ARGUMENT.  Stopping at max_columns or at the ceiling before the tolerance is met is
+ * no error: info (nullable) reports it.  The handle is a gingr_classic_cpd of kind 2 for iterate / get / set / destroy; w_xyz of
+ * gingr_classic_cpd_get is the W above.  gingr_classic_cpd_get_factor: *columns (nullable) and L row-major [M][columns] (nullable);
+ * GINGR_ERR_STATE on a handle of gingr_classic_cpd_create. */
+#define GINGR_CLASSIC_CPD_MAX_COLUMNS 512
+typedef struct {
+    int32_t columns;           /* k */
+    int32_t tolerance_reached; /* 1: residual trace < relative_tolerance * trace (or k = M) */
+    double residual_fraction;  /* trace(G - L L^T) / trace(G) */
+    int64_t factor_bytes;      /* device memory held for L */
+} gingr_classic_cpd_lowrank_info;
+int gingr_classic_cpd_create_lowrank(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz,
+                                     double lambda, double beta, double w, double relative_tolerance, int32_t max_columns,
+                                     gingr_classic_cpd_lowrank_info *info, gingr_classic_cpd **out);
+int gingr_classic_cpd_get_factor(gingr_classic_cpd *h, int32_t *columns, double *L_rowmajor_M_by_k);
+
 /* ---- Bayesian coherent point drift (Hirose 2020; the reference's draft other/algorithms/cpd/BCPD.scala, BCPDRegistration.scala) ----
  * One handle = BCPD(templatePoints, targetPoints, w, lambda, gamma, k, beta) with the Gaussian kernel of CPDFactory,
  * g(a, b) = exp(-|a - b|^2 / (2 beta^2)).  The definition is this package's (DESIGN.md section 5 lists where it follows the paper

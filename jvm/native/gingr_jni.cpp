@@ -244,6 +244,24 @@ JFN(jlong, classicCpdCreate)(JNIEnv *env, jclass, jlong ctx, jint kind, jdoubleA
     if (gingr_classic_cpd_create(P<gingr_ctx>(ctx), kind, m, a.ptr(), n, b.ptr(), lambda, beta, w, &h) != GINGR_OK) return 0;
     return reinterpret_cast<jlong>(h);
 }
+JFN(jlong, classicCpdCreateLowRank)(JNIEnv *env, jclass, jlong ctx, jdoubleArray tmpl, jdoubleArray target, jdouble lambda, jdouble beta,
+                                    jdouble w, jdouble relativeTolerance, jint maxColumns, jdoubleArray info4) {
+    const jlong m = env->GetArrayLength(tmpl) / 3, n = env->GetArrayLength(target) / 3;
+    Arr<double> a(env, tmpl, true); Arr<double> b(env, target, true); Arr<double> o(env, info4, false);
+    gingr_classic_cpd *h = nullptr;
+    gingr_classic_cpd_lowrank_info info;
+    const int rc = gingr_classic_cpd_create_lowrank(P<gingr_ctx>(ctx), m, a.ptr(), n, b.ptr(), lambda, beta, w, relativeTolerance, maxColumns,
+                                                    &info, &h);
+    if (o.ptr()) {
+        o.ptr()[0] = info.columns; o.ptr()[1] = info.tolerance_reached; o.ptr()[2] = info.residual_fraction;
+        o.ptr()[3] = (double)info.factor_bytes;
+    }
+    return rc == GINGR_OK ? reinterpret_cast<jlong>(h) : 0;
+}
+JFN(jint, classicCpdGetFactor)(JNIEnv *env, jclass, jlong h, jintArray columns1, jdoubleArray factor) {
+    Arr<int32_t> k(env, columns1, false); Arr<double> l(env, factor, false);   // a null array gives a null pointer
+    return gingr_classic_cpd_get_factor(P<gingr_classic_cpd>(h), k.ptr(), l.ptr());
+}
 JFN(void, classicCpdDestroy)(JNIEnv *, jclass, jlong h) { gingr_classic_cpd_destroy(P<gingr_classic_cpd>(h)); }
 JFN(jint, classicCpdIterate)(JNIEnv *, jclass, jlong h, jint n) { return gingr_classic_cpd_iterate(P<gingr_classic_cpd>(h), n); }
 JFN(jint, classicCpdGet)(JNIEnv *env, jclass, jlong h, jdoubleArray ty, jdoubleArray s2, jdoubleArray tr, jdoubleArray w) {

@@ -75,6 +75,11 @@ public final class GingrHipNative {
     // gingr_classic_cpd_*: kind 0 rigid, 1 affine, 2 non-rigid; the handle owns (TY, sigma2) on the device
     public static native long classicCpdCreate(long ctx, int kind, double[] templateXyz, double[] targetXyz, double lambda, double beta,
                                                double w);                                                            // 0 on failure
+    // gingr_classic_cpd_create_lowrank: the non-rigid kind over G ~ L L^T; info4 (nullable) = {columns, tolerance reached, residual
+    // fraction, factor bytes}.  gingr_classic_cpd_get_factor: columns1 / factor [M * columns] row-major, either may be null
+    public static native long classicCpdCreateLowRank(long ctx, double[] templateXyz, double[] targetXyz, double lambda, double beta,
+                                                      double w, double relativeTolerance, int maxColumns, double[] info4OrNull); // 0 on failure
+    public static native int classicCpdGetFactor(long h, int[] columnsOrNull1, double[] factorOrNull);
     public static native void classicCpdDestroy(long h);
     public static native int classicCpdIterate(long h, int nIterations);
     public static native int classicCpdGet(long h, double[] tyXyzOrNull, double[] sigma2OrNull1, double[] transform13OrNull,

@@ -478,13 +478,29 @@ object HipRegistrationComparison {
   * (gingr/other/algorithms/cpd/CPDFactory.scala:68-79): Expectation and Maximization run on the GPU (no M x N matrix; blocked
   * Cholesky for the non-rigid M x M system), the Registration loop with its tolerance test (RigidCPD.scala:59-83) stays here. */
 final class HipClassicCPD(templatePoints: Seq[scalismo.geometry.Point[_3D]], targetPoints: Seq[scalismo.geometry.Point[_3D]], kind: Int,
-                          lambda: Double = 2, beta: Double = 2, w: Double = 0, device: Int = 0) extends AutoCloseable {
+                          lambda: Double = 2, beta: Double = 2, w: Double = 0, device: Int = 0,
+                          lowRank: Option[(Double, Int)] = None) extends AutoCloseable {
   require(0.0 <= w && w <= 1.0); require(beta > 0); require(lambda > 0)
+  require(lowRank.isEmpty || kind == 2, "lowRank applies to the non-rigid kind only")
   private def flat(ps: Seq[scalismo.geometry.Point[_3D]]): Array[Double] = ps.flatMap(p => Seq(p.x, p.y, p.z)).toArray
   private val ctx = GingrHipNative.ctxCreate(device)
   require(ctx != 0L, "gingr_ctx_create failed: no usable GPU")
-  private val h = GingrHipNative.classicCpdCreate(ctx, kind, flat(templatePoints), flat(targetPoints), lambda, beta, w)
+  /** lowRank = Some((relativeTolerance, maxColumns)): {columns, tolerance reached, residual fraction, factor bytes} of G ~ L L^T */
+  val lowRankInfo: Array[Double] = new Array[Double](4)
+  private val h = lowRank match {
+    case Some((tol, maxColumns)) =>
+      GingrHipNative.classicCpdCreateLowRank(ctx, flat(templatePoints), flat(targetPoints), lambda, beta, w, tol, maxColumns, lowRankInfo)
+    case None => GingrHipNative.classicCpdCreate(ctx, kind, flat(templatePoints), flat(targetPoints), lambda, beta, w)
+  }
   require(h != 0L, s"gingr_classic_cpd_create failed: ${GingrHipNative.lastError(ctx)}")
+  /** the factor L, row-major M x columns (low-rank tasks) */
+  def factor(): Array[Double] = {
+    val k = new Array[Int](1)
+    require(GingrHipNative.classicCpdGetFactor(h, k, null) == 0, GingrHipNative.lastError(ctx))
+    val l = new Array[Double](templatePoints.length * k(0))
+    require(GingrHipNative.classicCpdGetFactor(h, null, l) == 0, GingrHipNative.lastError(ctx))
+    l
+  }
   private def sigma2(): Double = { val s = new Array[Double](1); GingrHipNative.classicCpdGet(h, null, s, null, null); s(0) }
 
   def Registration(max_iteration: Int, tolerance: Double = 0.001): Seq[scalismo.geometry.Point[_3D]] = {
