@@ -1,6 +1,7 @@
 """CPU side of the Bayesian coherent point drift (gingr_amd/csrc/bcpd.hip): the two routes of its numpy restatement agree on the inputs
 the GPU tests use; gingr_amd/csrc/bcpd_math.h, compiled for the host with the address and undefined-behaviour sanitizers into a
-stand-alone driver (tests/c/bcpd_math_driver.cpp), gives scipy's digamma and numpy's similarity transform; and the C ABI declares and
+stand-alone driver (tests/c/bcpd_math_driver.cpp), gives scipy's digamma and numpy's similarity transform; the restatement's helpers
+for the edge tests (chunk planner, blocked assignment, crafted inputs) and the guards those tests rely on; and the C ABI declares and
 exports the five gingr_bcpd_* functions."""
 import ctypes
 import os
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 from scipy.special import digamma
 
+from tests import bcpd_edge_cases as ec
 from tests import bcpd_restatement as br
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -119,6 +121,86 @@ def test_chunk_planner_covers_the_streamed_cloud(driver):
     for (owners, streamed), (count, length) in zip(sizes, got):
         assert length % 256 == 0 and 1 <= count <= 256
         assert count * length >= streamed > (count - 1) * length        # every chunk holds at least one point
+
+
+def edge_shapes():
+    out = []
+    for M, N in list(ec.SIZE_EDGES) + list(ec.MULTI_TILE):
+        out += [(N, M), (M, N)]                                          # column pass, row pass
+    return out
+
+
+def test_plan_chunks_restates_the_planner(driver):
+    rng = np.random.default_rng(5)
+    sizes = edge_shapes() + [(int(o), int(s)) for o, s in zip(rng.integers(1, 40000, 200), rng.integers(1, 300000, 200))]
+    sizes += [(int(o), int(s)) for o, s in zip(rng.integers(1, 600, 200), rng.integers(1, 2000, 200))]      # around the tile edges
+    got = run(driver, 2, len(sizes), np.array(sizes, float)).reshape(-1, 2)
+    for (owners, streamed), (count, length) in zip(sizes, got):
+        assert br.plan_chunks(owners, streamed) == (int(count), int(length)), (owners, streamed)
+
+
+# ------------------------------------------------------------------------------------------- helpers of the edge tests
+@pytest.mark.parametrize("g", [6, 7])
+def test_blocked_assignment_equals_the_dense_one(g):
+    """the summation order differs (slabs of columns), so 1e-13 relative, not bits"""
+    y, x = br.grid_case(g)
+    p = br.Problem(y, x, w=0.1, beta=1.5, **br.PARAMS)
+    assert p.M * p.N <= br.DENSE_LIMIT                                   # the existing cases keep the dense arithmetic
+    for it, st in p.run(10, keep=(0, 10)).items():
+        dense = p.assignment(st)
+        for pairs in (50 * p.M, 97 * p.M, br.SLAB_PAIRS):                # ragged last slab; 97 divides neither N; one slab
+            blocked = p.assignment_blocked(st, pairs=pairs)
+            assert len(p.slabs(pairs)) == -(-p.N // (pairs // p.M))
+            for name, a, b in zip(("nu", "nu_prime", "PX", "xPx"), blocked, dense):
+                assert br.rel(a, b) < 1e-13, (g, it, pairs, name)
+                assert np.abs(np.asarray(a) - np.asarray(b)).max() <= 1e-13 * np.abs(b).max(), (g, it, pairs, name)
+
+
+def test_blocked_route_is_taken_past_the_limit_and_agrees_with_the_dense_one(monkeypatch):
+    y, x = br.cloud_case(40, 1000, seed=3)
+    p = br.Problem(y, x, w=0.1, beta=1.5, **br.PARAMS)
+    st = br.crafted_state(p, seed=4)
+    dense, dense0 = p.iterate(st), p.initial()
+    monkeypatch.setattr(br, "DENSE_LIMIT", 1000)
+    monkeypatch.setattr(br, "SLAB_PAIRS", 40 * 300)                       # four slabs, the last ragged
+    monkeypatch.setattr(p, "assignment", None)                           # the dense route is not available
+    blocked = p.iterate(st)
+    for k in ("yhat", "vhat", "nu", "nu_prime", "PX", "alpha", "sig", "sigma2", "s", "R", "t"):
+        assert br.rel(getattr(blocked, k), getattr(dense, k)) < 1e-12, k
+    assert abs(p.initial().sigma2 - dense0.sigma2) < 1e-13 * dense0.sigma2
+
+
+def test_crafted_inputs_are_what_they_are_said_to_be():
+    R = br.pose_rotation()
+    assert np.abs(R @ R.T - np.eye(3)).max() < 1e-15 and abs(np.linalg.det(R) - 1.0) < 1e-15
+    assert np.arccos((np.trace(R) - 1.0) / 2.0) > 1.0 and np.abs(br.POSE_AXIS).min() > 0.3 and br.POSE_S != 1.0 and np.abs(br.POSE_T).min() >= 3.0
+    for w in (0.0, 0.1):
+        p = ec.cloud_problem(63, 300, w)
+        st = ec.cloud_state(63, 300, w, "crafted")
+        assert abs(st.alpha.sum() - 1.0) < 1e-14 and st.alpha.min() > 0.0
+        assert (st.sig > 0.0).all() and (st.sig < np.diag(p.G) / p.lam).all()
+        a = (1.0 - w) * st.alpha * np.exp(-1.5 * st.s ** 2 * st.sig / st.sigma2)
+        d2 = ((p.x[None, :, :] - st.yhat[:, None, :]) ** 2).sum(-1)
+        den = (a[:, None] * np.exp(-d2 / (2.0 * st.sigma2))).sum(0)
+        assert den.min() > 1e-12                                         # no column vanishes: w = 0 stays finite
+        assert np.isfinite(ec.cloud_reference(63, 300, w, "crafted").yhat).all()
+
+
+def test_guards_of_the_edge_tests_hold():
+    """every guard tests/test_gpu_bcpd_edges.py asserts before it uses the device, from the restatement alone"""
+    for M, N in ec.SIZE_EDGES:
+        ec.size_guard(M, N)
+    assert ec.chunks(576, 700) == {"col": (3, 256), "row": (3, 256)} and ec.chunks(1025, 300)["col"] == (5, 256)
+    for M, N in ec.MULTI_TILE:
+        ec.multi_tile_guard(M, N)
+    assert br.plan_chunks(64, 65536)[1] == br.TILE                      # one point fewer: one-tile chunks
+    assert br.plan_chunks(130816, 513) == (3, 256)                      # one target point fewer: the column pass takes three one-tile chunks
+    on = [ec.clamp_guard(which) for which in ec.CLAMP_CASES]
+    assert on[0] > br.CLAMP_AT and on[1] > br.CLAMP_AT and on[2] < br.CLAMP_AT
+    for name in ec.PARAMETER_CASES:
+        ec.parameter_guard(name)
+    p, states, refs = ec.offset_case()
+    assert np.abs(p.y).min() > 0.9 * ec.OFFSET and all(np.isfinite(r.sigma2) for r in refs.values())
 
 
 # ---------------------------------------------------------------------------------------------------------------- the ABI

@@ -54,14 +54,19 @@ def inject(reg, st):
     reg.set_state(st.yhat, st.sig, st.alpha, st.s, st.R, st.t, st.sigma2)
 
 
-def compare(got, want, p, degenerate=False, label=""):
+def figures(got, want, p):
+    """the deviation of every quantity of an iteration, on the scale `compare` holds it to"""
     kmax = float(np.diag(p.G).max() / p.lam)
-    fig = dict(yhat=br.rel(got["yhat"], want.yhat), vhat=br.rel(got["vhat"], want.vhat), alpha=br.rel(got["alpha"], want.alpha),
-               nu=br.rel(got["nu"], want.nu), nu_prime=br.rel(got["nu_prime"], want.nu_prime),
-               sigma_diag=float(np.abs(got["sigma_diag"] - want.sig).max() / kmax),
-               s=abs(got["s"] - want.s) / max(abs(want.s), 1e-300), R=float(np.abs(got["R"] - want.R).max()), t=br.rel(got["t"], want.t),
-               sigma2=abs(got["sigma2"] - want.sigma2) / max(abs(want.sigma2), 1e-300), Nhat=abs(got["Nhat"] - want.Nhat) / want.Nhat,
-               sigma_bar2=abs(got["sigma_bar2"] - want.sigma_bar2) / want.sigma_bar2)
+    return dict(yhat=br.rel(got["yhat"], want.yhat), vhat=br.rel(got["vhat"], want.vhat), alpha=br.rel(got["alpha"], want.alpha),
+                nu=br.rel(got["nu"], want.nu), nu_prime=br.rel(got["nu_prime"], want.nu_prime),
+                sigma_diag=float(np.abs(got["sigma_diag"] - want.sig).max() / kmax),
+                s=abs(got["s"] - want.s) / max(abs(want.s), 1e-300), R=float(np.abs(got["R"] - want.R).max()), t=br.rel(got["t"], want.t),
+                sigma2=abs(got["sigma2"] - want.sigma2) / max(abs(want.sigma2), 1e-300), Nhat=abs(got["Nhat"] - want.Nhat) / want.Nhat,
+                sigma_bar2=abs(got["sigma_bar2"] - want.sigma_bar2) / want.sigma_bar2)
+
+
+def compare(got, want, p, degenerate=False, label=""):
+    fig = figures(got, want, p)
     print(label, " ".join(f"{k}={v:.2e}" for k, v in fig.items()), f"min_nu={want.nu.min():.2e}")
     for k in ("yhat", "alpha", "nu", "nu_prime", "sigma_diag", "t", "Nhat"):
         assert fig[k] < 1e-9, (label, k, fig[k])
