@@ -15,7 +15,7 @@
 // partials in a fixed order: two runs give the same bits.
 #include "common.h"
 #include "bcpd_math.h"
-#include "block_sum.h"
+#include "cloud_sums.h"
 #include "dense_spd.h"
 #include "fastexp.h"
 #include "svd3.h"
@@ -28,7 +28,6 @@ namespace {
 
 constexpr int kNBc = DenseSpdWork::kBlock;
 constexpr int kRedBlocks = 64;  // workgroups of the O(M + N) reductions
-constexpr double kDblMax = 1.79769313486231570815e308;
 constexpr int kTile = (int)kBcpdTile;
 
 typedef double bcpd_v4f64 __attribute__((ext_vector_type(4)));
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(256) void bcpd_den_finalize_kernel(Cloud X, const d
         double den = 0.0;
         for (int ch = 0; ch < chunks; ++ch) den += part[(int64_t)ch * X.n + n];
         const double iv = 1.0 / (den + c), p = den * iv;
-        bad = bad || !(fabs(iv) <= kDblMax);
+        bad = bad || !finite_d(iv);
         inv[n] = iv;
         nup[n] = p;
         const double x = X.x[n], y = X.y[n], z = X.z[n];
@@ -214,25 +213,6 @@ __global__ __launch_bounds__(256) void bcpd_rows_finish_kernel(int64_t M, const 
 }
 
 // ---------------------------------------------------------------------------------------------------- the deformation
-// sum_i G_mi f_i in_d[i] for the row m of this group of 16 lanes (f == nullptr: 1); valid in every lane of the group
-__device__ __forceinline__ void g_row_dot3(const double *__restrict__ G, int64_t M, int64_t m, int lane16, const double *__restrict__ in,
-                                           int64_t stride, const double *__restrict__ f, double acc[3]) {
-    acc[0] = acc[1] = acc[2] = 0.0;
-    if (m < M)
-        for (int64_t i = lane16; i < M; i += 16) {
-            const double g = f ? G[m * M + i] * f[i] : G[m * M + i];
-            acc[0] = __builtin_fma(g, in[i], acc[0]);
-            acc[1] = __builtin_fma(g, in[stride + i], acc[1]);
-            acc[2] = __builtin_fma(g, in[2 * stride + i], acc[2]);
-        }
-    for (int q = 0; q < 3; ++q) {
-        acc[q] += __shfl_xor(acc[q], 8);
-        acc[q] += __shfl_xor(acc[q], 4);
-        acc[q] += __shfl_xor(acc[q], 2);
-        acc[q] += __shfl_xor(acc[q], 1);
-    }
-}
-
 // z = K r (K = G / lambda) and the right-hand sides b = D^1/2 z (planes of stride Mp): 16 lanes per row of G
 __global__ __launch_bounds__(256) void bcpd_kr_kernel(int64_t M, int64_t Mp, const double *__restrict__ G, double lambda,
                                                       const double *__restrict__ r, const double *__restrict__ dh, double *__restrict__ z,
@@ -240,7 +220,7 @@ __global__ __launch_bounds__(256) void bcpd_kr_kernel(int64_t M, int64_t Mp, con
     const int lane16 = threadIdx.x & 15;
     const int64_t m = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     double a[3];
-    g_row_dot3(G, M, m, lane16, r, M, nullptr, a);
+    row_dot3(G + m * M, 0, m < M ? M : 0, lane16, r, M, nullptr, a);
     if (m < M && lane16 == 0)
         for (int d = 0; d < 3; ++d) {
             const double v = a[d] / lambda;
@@ -258,7 +238,7 @@ __global__ __launch_bounds__(256) void bcpd_deform_kernel(int64_t M, int64_t Mp,
     const int lane16 = threadIdx.x & 15;
     const int64_t m = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     double a[3];
-    g_row_dot3(G, M, m, lane16, q, Mp, dh, a);
+    row_dot3(G + m * M, 0, m < M ? M : 0, lane16, q, Mp, dh, a);
     if (m < M && lane16 == 0) {
         const double c2 = params[0] * params[0] / sc[0];
         for (int d = 0; d < 3; ++d) {
@@ -306,20 +286,8 @@ __global__ __launch_bounds__(256) void bcpd_backward_kernel(int64_t Mp, const do
                                                             double *__restrict__ q) {
     const int lane16 = threadIdx.x & 15;
     const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    double a[3] = {0, 0, 0};
-    if (i < Mp)
-        for (int64_t j = i + lane16; j < Mp; j += 16) {
-            const double x = X[i * Mp + j];
-            a[0] = __builtin_fma(x, wv[j], a[0]);
-            a[1] = __builtin_fma(x, wv[Mp + j], a[1]);
-            a[2] = __builtin_fma(x, wv[2 * Mp + j], a[2]);
-        }
-    for (int d = 0; d < 3; ++d) {
-        a[d] += __shfl_xor(a[d], 8);
-        a[d] += __shfl_xor(a[d], 4);
-        a[d] += __shfl_xor(a[d], 2);
-        a[d] += __shfl_xor(a[d], 1);
-    }
+    double a[3];
+    row_dot3(X + i * Mp, i, i < Mp ? Mp : 0, lane16, wv, Mp, nullptr, a);  // (X is upper triangular: from the diagonal on)
     if (i < Mp && lane16 == 0)
         for (int d = 0; d < 3; ++d) q[d * Mp + i] = a[d];
 }
@@ -405,27 +373,19 @@ __global__ __launch_bounds__(256) void bcpd_sums_a_kernel(int64_t M, const doubl
         }
         a[7] += p * sig[m];
     }
-    for (int q = 0; q < 8; ++q) {
-        __syncthreads();  // sh is reused by every pass
-        const double t = block_sum<256>(a[q], sh);
-        if (threadIdx.x == 0) partial[blockIdx.x * 8 + q] = t;
-    }
+    block_sums<8>(a, sh, partial + blockIdx.x * 8);
 }
 
 // sc[1] = N^, sc[2] = sbar2, sc[3] = xPx; mu[0..2] = xbar, mu[3..5] = ubar, mu[6] = psi(kappa M + N^)
 __global__ void bcpd_means_finish_kernel(int64_t M, double kappa, const double *__restrict__ partial, const double *__restrict__ xpart,
                                          double *__restrict__ sc, double *__restrict__ mu) {
     if (threadIdx.x != 0) return;
-    double v[8], xpx = 0.0;
-    for (int q = 0; q < 8; ++q) {
-        v[q] = 0.0;
-        for (int b = 0; b < kRedBlocks; ++b) v[q] += partial[b * 8 + q];
-    }
-    for (int b = 0; b < kRedBlocks; ++b) xpx += xpart[b];
+    double v[8];
+    for (int q = 0; q < 8; ++q) v[q] = sum_partials(partial, kRedBlocks, 8, q);
     const double Nh = v[0];
     sc[1] = Nh;
     sc[2] = v[7] / Nh;
-    sc[3] = xpx;
+    sc[3] = sum_partials(xpart, kRedBlocks, 1, 0);
     for (int d = 0; d < 6; ++d) mu[d] = v[1 + d] / Nh;
     mu[6] = kappa > kDblMax ? 0.0 : bcpd_digamma(kappa * (double)M + Nh);
 }
@@ -452,11 +412,7 @@ __global__ __launch_bounds__(256) void bcpd_sums_b_kernel(int64_t M, const doubl
             for (int c = 0; c < 3; ++c) a[r * 3 + c] += e[r] * uc[c];
         a[9] += p * ((uc[0] * uc[0] + uc[1] * uc[1]) + uc[2] * uc[2]);
     }
-    for (int q = 0; q < 10; ++q) {
-        __syncthreads();  // sh is reused by every pass
-        const double t = block_sum<256>(a[q], sh);
-        if (threadIdx.x == 0) partial[blockIdx.x * 10 + q] = t;
-    }
+    block_sums<10>(a, sh, partial + blockIdx.x * 10);
 }
 
 // one thread of 3 x 3 algebra: S_xu, tr S_uu, the singular vectors (svd3.h), then (s, R, t) (bcpd_math.h)
@@ -464,11 +420,7 @@ __global__ void bcpd_similarity_kernel(const double *__restrict__ partial, const
                                        double *__restrict__ params) {
     if (threadIdx.x != 0) return;
     double v[10];
-    for (int q = 0; q < 10; ++q) {
-        v[q] = 0.0;
-        for (int b = 0; b < kRedBlocks; ++b) v[q] += partial[b * 10 + q];
-        v[q] /= sc[1];
-    }
+    for (int q = 0; q < 10; ++q) v[q] = sum_partials(partial, kRedBlocks, 10, q) / sc[1];
     const double tr_suu = v[9] + 3.0 * sc[2];
     double Phi[9], S[3], Psi[9], out[13];
     svd3(v, Phi, S, Psi);
@@ -481,26 +433,15 @@ __global__ __launch_bounds__(256) void bcpd_shape_kernel(int64_t M, const double
                                                          const double *__restrict__ nu, const double *__restrict__ PX, double *__restrict__ yh,
                                                          double *__restrict__ partial) {
     __shared__ double sh[256];
-    const double s = params[0], *R = params + 1, *t = params + 10;
-    double a = 0.0, b = 0.0;
+    double a[2] = {0, 0};
     for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)kRedBlocks * 256) {
-        const double ux = u[m], uy = u[M + m], uz = u[2 * M + m];
-        const double x = s * ((R[0] * ux + R[1] * uy) + R[2] * uz) + t[0];
-        const double y = s * ((R[3] * ux + R[4] * uy) + R[5] * uz) + t[1];
-        const double z = s * ((R[6] * ux + R[7] * uy) + R[8] * uz) + t[2];
-        yh[m] = x;
-        yh[M + m] = y;
-        yh[2 * M + m] = z;
-        a += (PX[m] * x + PX[M + m] * y) + PX[2 * M + m] * z;
-        b += nu[m] * ((x * x + y * y) + z * z);
+        double p[3];
+        similarity_apply(params, u[m], u[M + m], u[2 * M + m], p);
+        for (int d = 0; d < 3; ++d) yh[d * M + m] = p[d];
+        a[0] += (PX[m] * p[0] + PX[M + m] * p[1]) + PX[2 * M + m] * p[2];
+        a[1] += nu[m] * ((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
     }
-    const double ta = block_sum<256>(a, sh);
-    __syncthreads();  // sh is reused
-    const double tb = block_sum<256>(b, sh);
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x * 2] = ta;
-        partial[blockIdx.x * 2 + 1] = tb;
-    }
+    block_sums<2>(a, sh, partial + blockIdx.x * 2);
 }
 
 // sigma2 = (xPx - 2 sum PX . y^ + sum nu |y^|^2) / (3 N^) + s^2 sbar2; flags[1] (sticky until the host reads it: the first failure is
@@ -509,18 +450,13 @@ __global__ __launch_bounds__(256) void bcpd_shape_kernel(int64_t M, const double
 __global__ void bcpd_variance_kernel(const double *__restrict__ partial, const double *__restrict__ params, double *__restrict__ sc,
                                      int32_t *__restrict__ flags) {
     if (threadIdx.x != 0) return;
-    double pxy = 0.0, ypy = 0.0;
-    for (int b = 0; b < kRedBlocks; ++b) {
-        pxy += partial[b * 2];
-        ypy += partial[b * 2 + 1];
-    }
-    const double s = params[0];
+    const double pxy = sum_partials(partial, kRedBlocks, 2, 0), ypy = sum_partials(partial, kRedBlocks, 2, 1), s = params[0];
     const double ns = (sc[3] - 2.0 * pxy + ypy) / (sc[1] * 3.0) + s * s * sc[2];
     sc[0] = ns;
     if (flags[1]) return;  // (a non-finite 1 / (den_n + c) came first: the system it poisons fails its factorisation as well)
     if (flags[0])
         flags[1] = flags[0];
-    else if (!(fabs(ns) <= kDblMax) || !(fabs(s) <= kDblMax))
+    else if (!finite_d(ns) || !finite_d(s))
         flags[1] = GINGR_ERR_NONFINITE;
 }
 
@@ -584,61 +520,49 @@ int gingr_bcpd_create(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64
         gingr_bcpd_destroy(h);
         return rc;
     };
-#define BC_TRY(expr)                                                                         \
-    do {                                                                                     \
-        if ((expr) != hipSuccess) return fail(gingr_set_error(ctx, GINGR_ERR_HIP, #expr));   \
-    } while (0)
     const int64_t Mp = h->Mp, big = M > N ? M : N, nb = Mp / kNBc;
     const DenseSpdWork sys(Mp, DenseSpdWork::kIdentity);
-    BC_TRY(h->X.alloc((size_t)3 * N * sizeof(double)));
-    for (DevBuf *b : {&h->Y, &h->Yh, &h->V, &h->U, &h->PX, &h->Rr, &h->Z}) BC_TRY(b->alloc((size_t)3 * M * sizeof(double)));
-    for (DevBuf *b : {&h->B, &h->Wv, &h->Q}) BC_TRY(b->alloc((size_t)3 * Mp * sizeof(double)));
-    for (DevBuf *b : {&h->sig, &h->alpha, &h->a, &h->nu}) BC_TRY(b->alloc((size_t)M * sizeof(double)));
-    BC_TRY(h->dh.alloc((size_t)Mp * sizeof(double)));
-    BC_TRY(h->nup.alloc((size_t)N * sizeof(double)));
-    BC_TRY(h->inv.alloc((size_t)N * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->X.alloc((size_t)3 * N * sizeof(double)));
+    for (DevBuf *b : {&h->Y, &h->Yh, &h->V, &h->U, &h->PX, &h->Rr, &h->Z}) HANDLE_TRY(ctx, fail, b->alloc((size_t)3 * M * sizeof(double)));
+    for (DevBuf *b : {&h->B, &h->Wv, &h->Q}) HANDLE_TRY(ctx, fail, b->alloc((size_t)3 * Mp * sizeof(double)));
+    for (DevBuf *b : {&h->sig, &h->alpha, &h->a, &h->nu}) HANDLE_TRY(ctx, fail, b->alloc((size_t)M * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->dh.alloc((size_t)Mp * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->nup.alloc((size_t)N * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->inv.alloc((size_t)N * sizeof(double)));
     const int64_t ws = std::max(std::max(h->col.count * N, h->row.count * 4 * M), std::max(nb * Mp, sumsq_pairs_ws_doubles(M)));
-    BC_TRY(h->ws.alloc((size_t)ws * sizeof(double)));
-    BC_TRY(h->stage.alloc((size_t)3 * big * sizeof(double)));
-    BC_TRY(h->xpart.alloc(kRedBlocks * sizeof(double)));
-    BC_TRY(h->red.alloc((size_t)kRedBlocks * 10 * sizeof(double)));
-    BC_TRY(h->mu.alloc(8 * sizeof(double)));
-    BC_TRY(h->params.alloc(16 * sizeof(double)));
-    BC_TRY(h->sc.alloc(8 * sizeof(double)));
-    BC_TRY(h->aux.alloc(GINGR_AUX * sizeof(double)));
-    BC_TRY(h->flags.alloc(2 * sizeof(int32_t)));
-    BC_TRY(h->G.alloc((size_t)M * M * sizeof(double)));
-    BC_TRY(h->Aw.alloc((size_t)sys.aw_doubles() * sizeof(double)));
-    BC_TRY(h->Linv.alloc((size_t)sys.linv_doubles() * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->ws.alloc((size_t)ws * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->stage.alloc((size_t)3 * big * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->xpart.alloc(kRedBlocks * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->red.alloc((size_t)kRedBlocks * 10 * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->mu.alloc(8 * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->params.alloc(16 * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->sc.alloc(8 * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->aux.alloc(GINGR_AUX * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->flags.alloc(2 * sizeof(int32_t)));
+    HANDLE_TRY(ctx, fail, h->G.alloc((size_t)M * M * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->Aw.alloc((size_t)sys.aw_doubles() * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->Linv.alloc((size_t)sys.linv_doubles() * sizeof(double)));
     for (DevBuf *b : {&h->B, &h->Wv, &h->Q, &h->dh, &h->V, &h->nu, &h->nup, &h->sc, &h->mu, &h->aux, &h->flags})
-        BC_TRY(hipMemsetAsync(b->p, 0, b->bytes, ctx->stream));  // (the padding of the Mp-long vectors stays zero)
-    BC_TRY(hipMemcpyAsync(h->stage.p, target_xyz, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_aos_to_soa(ctx, h->stage.as<double>(), N, h->X.as<double>());
-    BC_TRY(hipStreamSynchronize(ctx->stream));  // the staging buffer is reused
-    BC_TRY(hipMemcpyAsync(h->stage.p, moving_xyz, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_aos_to_soa(ctx, h->stage.as<double>(), M, h->Y.as<double>());
-    BC_TRY(hipMemcpyAsync(h->Yh.p, h->Y.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        HANDLE_TRY(ctx, fail, hipMemsetAsync(b->p, 0, b->bytes, ctx->stream));  // (the padding of the Mp-long vectors stays zero)
+    if (int rc = upload_cloud(ctx, h->stage.as<double>(), target_xyz, N, h->X.as<double>())) return fail(rc);
+    if (int rc = upload_cloud(ctx, h->stage.as<double>(), moving_xyz, M, h->Y.as<double>())) return fail(rc);
+    HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->Yh.p, h->Y.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     const Cloud X = cloud_at(h->X.as<double>(), N), Y = cloud_at(h->Y.as<double>(), M);
     double *aux = h->aux.as<double>();
     launch_cloud_centroid(ctx, X, aux + 2);
     launch_cloud_absmax(ctx, X, aux + 2, aux);
     // sigma2_0 = gamma sum |x_n - y_m|^2 / (3 N M)
-    launch_sumsq_pairs(ctx, Y, X, h->ws.as<double>(), h->sc.as<double>() + 4);
-    double tot = 0.0;
-    BC_TRY(hipMemcpyAsync(&tot, h->sc.as<double>() + 4, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    BC_TRY(hipStreamSynchronize(ctx->stream));
-    h->sigma2_init = gamma * tot / (3.0 * (double)N * (double)M);
+    if (int rc = first_variance(ctx, Y, X, gamma, h->ws.as<double>(), h->sc.as<double>() + 4, &h->sigma2_init)) return fail(rc);
     std::vector<double> ones((size_t)M, 1.0), am((size_t)M, 1.0 / (double)M);
     const double ident[13] = {1, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    BC_TRY(hipMemcpyAsync(h->sc.p, &h->sigma2_init, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    BC_TRY(hipMemcpyAsync(h->sig.p, ones.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    BC_TRY(hipMemcpyAsync(h->alpha.p, am.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    BC_TRY(hipMemcpyAsync(h->params.p, ident, sizeof(ident), hipMemcpyHostToDevice, ctx->stream));
+    HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->sc.p, &h->sigma2_init, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->sig.p, ones.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->alpha.p, am.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->params.p, ident, sizeof(ident), hipMemcpyHostToDevice, ctx->stream));
     // G = exp(-|y_i - y_j|^2 / (2 beta^2)) over the template points (the Gaussian kernel of CPDFactory)
     launch_gauss_block(ctx, Y, Y, sqrt(2.0) * beta, 1.0, h->G.as<double>());
-    BC_TRY(hipGetLastError());
-    BC_TRY(hipStreamSynchronize(ctx->stream));
-#undef BC_TRY
+    HANDLE_TRY(ctx, fail, hipGetLastError());
+    HANDLE_TRY(ctx, fail, hipStreamSynchronize(ctx->stream));
     *out = h;
     return GINGR_OK;
 }
@@ -692,16 +616,7 @@ int gingr_bcpd_iterate(gingr_bcpd *h, int32_t n_iterations) {
         hipLaunchKernelGGL(bcpd_shape_kernel, dim3(kRedBlocks), dim3(256), 0, st, M, U, params, nu, PX, h->Yh.as<double>(), red);
         hipLaunchKernelGGL(bcpd_variance_kernel, dim3(1), dim3(64), 0, st, red, params, sc, flags);
     }
-    HIP_TRY(ctx, hipGetLastError());
-    int32_t err[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(err, flags, sizeof(err), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (err[1]) {
-        HIP_TRY(ctx, hipMemsetAsync(flags, 0, 2 * sizeof(int32_t), st));
-        return gingr_set_error(ctx, err[1], "bcpd_iterate: %s",
-                               err[1] == GINGR_ERR_NOT_SPD ? "system not positive definite" : "non-finite result");
-    }
-    return GINGR_OK;
+    return finish_iterate(ctx, flags, 2, 1, "bcpd_iterate");
 }
 
 int gingr_bcpd_get(gingr_bcpd *h, double *yhat_xyz, double *vhat_xyz, double *sigma_diag, double *alpha, double *nu, double *nu_prime,
@@ -714,11 +629,7 @@ int gingr_bcpd_get(gingr_bcpd *h, double *yhat_xyz, double *vhat_xyz, double *si
     double *const aos[2] = {yhat_xyz, vhat_xyz};
     const double *const soa[2] = {h->Yh.as<double>(), h->V.as<double>()};
     for (int q = 0; q < 2; ++q)
-        if (aos[q]) {
-            launch_soa_to_aos(ctx, soa[q], M, h->stage.as<double>());
-            HIP_TRY(ctx, hipMemcpyAsync(aos[q], h->stage.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipStreamSynchronize(st));  // the staging buffer is reused
-        }
+        if (aos[q]) GINGR_TRY(download_cloud(ctx, h->stage.as<double>(), soa[q], M, aos[q]));
     if (sigma_diag) HIP_TRY(ctx, hipMemcpyAsync(sigma_diag, h->sig.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
     if (alpha) HIP_TRY(ctx, hipMemcpyAsync(alpha, h->alpha.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
     if (nu) HIP_TRY(ctx, hipMemcpyAsync(nu, h->nu.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -736,10 +647,7 @@ int gingr_bcpd_set(gingr_bcpd *h, const double *yhat_xyz, const double *sigma_di
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t M = h->M;
     hipStream_t st = ctx->stream;
-    if (yhat_xyz) {
-        HIP_TRY(ctx, hipMemcpyAsync(h->stage.p, yhat_xyz, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, st));
-        launch_aos_to_soa(ctx, h->stage.as<double>(), M, h->Yh.as<double>());
-    }
+    if (yhat_xyz) GINGR_TRY(upload_cloud(ctx, h->stage.as<double>(), yhat_xyz, M, h->Yh.as<double>()));
     if (sigma_diag) HIP_TRY(ctx, hipMemcpyAsync(h->sig.p, sigma_diag, (size_t)M * sizeof(double), hipMemcpyHostToDevice, st));
     if (alpha) HIP_TRY(ctx, hipMemcpyAsync(h->alpha.p, alpha, (size_t)M * sizeof(double), hipMemcpyHostToDevice, st));
     if (transform13) HIP_TRY(ctx, hipMemcpyAsync(h->params.p, transform13, 13 * sizeof(double), hipMemcpyHostToDevice, st));

@@ -13,7 +13,7 @@
 // subtracted last, so that near the root (1.4616...) the error is that of one subtraction of two numbers near 1.8.
 GINGR_HD inline double bcpd_digamma(double x) {
     if (!(x > 0.0)) return NAN;
-    if (x > 1.79769313486231570815e308) return x;
+    if (x > kDblMax) return x;
     double rec[6];
     int n = 0;
     while (x < 6.0) {
@@ -40,7 +40,7 @@ GINGR_HD inline double bcpd_digamma(double x) {
 
 // <alpha_m> = exp(psi(kappa + nu_m) - psi(kappa M + N^)); kappa = +inf: 1 / M (the Dirichlet prior pins the mixing weights)
 GINGR_HD inline double bcpd_alpha(double kappa, double nu, double psi_total, double M) {
-    if (kappa > 1.79769313486231570815e308) return 1.0 / M;
+    if (kappa > kDblMax) return 1.0 / M;
     return exp(bcpd_digamma(kappa + nu) - psi_total);
 }
 
@@ -53,8 +53,7 @@ GINGR_HD inline void bcpd_similarity_finish(const double Sxu[9], const double Ph
     double W[9];
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) W[a * 3 + b] = Phi[a * 3] * Psi[b * 3] + Phi[a * 3 + 1] * Psi[b * 3 + 1] + Phi[a * 3 + 2] * Psi[b * 3 + 2];
-    const double det = W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
-    const double d = det < 0.0 ? -1.0 : 1.0;
+    const double d = det3(W) < 0.0 ? -1.0 : 1.0;
     double *R = out13 + 1, tr = 0.0;
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) {

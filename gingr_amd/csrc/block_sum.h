@@ -1,4 +1,4 @@
-// Block-wide fixed-order sum of one double per thread (the reductions of cpd_pairs.hip, cloud_ops.hip and classic_cpd.hip).
+// Block-wide fixed-order sum of one double per thread (the reductions of cpd_pairs.hip, cloud_ops.hip and cloud_sums.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -12,9 +12,10 @@
 // symmetric positive definite (the reference solves it with LU, `A \ B`); it is factored here by a blocked right-looking Cholesky
 // with 64-wide panels (dense_spd.hip: diagonal block in LDS, panel and trailing update as 64 x 64 MFMA tiles, v_mfma_f64_16x16x4,
 // over the whole chip) with the three right-hand sides riding along as extra rows of the matrix (the forward
-// substitution is a by-product), a blocked backward substitution, and TY = Y + G W as one pass over G.
+// substitution is a by-product), a blocked backward substitution, and TY = Y + G W as one pass over G.  Past dense sizes the non-rigid
+// Maximization runs over a low-rank factor of G (classic_cpd_lowrank.hip).  The reductions and the row products are cloud_sums.h's.
 #include "common.h"
-#include "block_sum.h"
+#include "cloud_sums.h"
 #include "classic_cpd_lowrank.h"
 #include "dense_spd.h"
 #include "svd3.h"
@@ -48,19 +49,13 @@ __global__ __launch_bounds__(256) void means_kernel(Cloud X, const double *__res
         a[4] += p * Y.y[i];
         a[5] += p * Y.z[i];
     }
-    for (int q = 0; q < 6; ++q) {
-        __syncthreads();  // sh is reused by every pass
-        const double t = block_sum<256>(a[q], sh);
-        if (threadIdx.x == 0) partial[blockIdx.x * 6 + q] = t;
-    }
+    block_sums<6>(a, sh, partial + blockIdx.x * 6);
 }
 
 // mu[0..2] = muX, mu[3..5] = muY   (RigidCPD.scala:117-118)
 __global__ void means_finish_kernel(const double *__restrict__ partial, const double *__restrict__ scalars, double *__restrict__ mu) {
     if (threadIdx.x >= 6) return;
-    double v = 0.0;
-    for (int b = 0; b < kRedBlocks; ++b) v += partial[b * 6 + threadIdx.x];
-    mu[threadIdx.x] = v / scalars[0];
+    mu[threadIdx.x] = sum_partials(partial, kRedBlocks, 6, threadIdx.x) / scalars[0];
 }
 
 // partial[b][0..8] = A = Xhat^T P^T Yhat (row-major; from P X: sum_i (PX_i - P1_i muX)(y_i - muY)^T), [9..17] = Yhat^T diag(P1) Yhat,
@@ -87,15 +82,7 @@ __global__ __launch_bounds__(256) void moments_kernel(Cloud X, const double *__r
         const double dx = X.x[j] - mx[0], dy = X.y[j] - mx[1], dz = X.z[j] - mx[2];
         a[18] += Pt1[j] * ((dx * dx + dy * dy) + dz * dz);
     }
-    for (int q = 0; q < 19; ++q) {
-        __syncthreads();  // sh is reused by every pass
-        const double t = block_sum<256>(a[q], sh);
-        if (threadIdx.x == 0) partial[blockIdx.x * 19 + q] = t;
-    }
-}
-
-__device__ double det3(const double *m) {
-    return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+    block_sums<19>(a, sh, partial + blockIdx.x * 19);
 }
 
 // params[0] = s (affine: 1), [1..9] = R or B (row-major), [10..12] = t; scalars[8] = the new sigma2
@@ -103,11 +90,7 @@ __global__ void transform_finish_kernel(const double *__restrict__ partial, cons
                                         int affine, double *__restrict__ params, int32_t *__restrict__ flag) {
     if (threadIdx.x != 0) return;
     double m[19];
-    for (int q = 0; q < 19; ++q) {
-        double v = 0.0;
-        for (int b = 0; b < kRedBlocks; ++b) v += partial[b * 19 + q];
-        m[q] = v;
-    }
+    for (int q = 0; q < 19; ++q) m[q] = sum_partials(partial, kRedBlocks, 19, q);
     const double *A = m, *YPY = m + 9, s1 = m[18], Np = scalars[0];
     double L[9], sc = 1.0, s2;
     if (!affine) {
@@ -136,23 +119,21 @@ __global__ void transform_finish_kernel(const double *__restrict__ partial, cons
     bool fin = true;
     for (int q = 0; q < 9; ++q) {
         params[1 + q] = L[q];
-        fin = fin && fabs(L[q]) <= 1.79769313486231570815e308;
+        fin = fin && finite_d(L[q]);
     }
     for (int r = 0; r < 3; ++r) params[10 + r] = mu[r] - sc * (L[r * 3] * mu[3] + L[r * 3 + 1] * mu[4] + L[r * 3 + 2] * mu[5]);
     const double ns = (s1 - s2) / (Np * 3.0);
     scalars[8] = ns;
-    if (!fin || !(fabs(ns) <= 1.79769313486231570815e308)) *flag = GINGR_ERR_NONFINITE;
+    if (!fin || !finite_d(ns)) *flag = GINGR_ERR_NONFINITE;
 }
 
 // TY = s Y R^T + 1 t^T  (in place)
 __global__ void apply_transform_kernel(int64_t M, double *__restrict__ ty, const double *__restrict__ params) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
-    const double s = params[0], *L = params + 1, *t = params + 10;
-    const double x = ty[i], y = ty[M + i], z = ty[2 * M + i];
-    ty[i] = s * (L[0] * x + L[1] * y + L[2] * z) + t[0];
-    ty[M + i] = s * (L[3] * x + L[4] * y + L[5] * z) + t[1];
-    ty[2 * M + i] = s * (L[6] * x + L[7] * y + L[8] * z) + t[2];
+    double p[3];
+    similarity_apply(params, ty[i], ty[M + i], ty[2 * M + i], p);
+    for (int d = 0; d < 3; ++d) ty[d * M + i] = p[d];
 }
 
 // ------------------------------------------------------------------------------------------------ non-rigid: the M x M system
@@ -182,20 +163,8 @@ __global__ __launch_bounds__(256) void deform_kernel(int64_t M, int64_t Mp, cons
                                                      double *__restrict__ ty) {
     const int lane16 = threadIdx.x & 15;
     const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    double a[3] = {0, 0, 0};
-    if (i < M)
-        for (int64_t m = lane16; m < M; m += 16) {
-            const double g = G[i * M + m];
-            a[0] = __builtin_fma(g, W[m], a[0]);
-            a[1] = __builtin_fma(g, W[Mp + m], a[1]);
-            a[2] = __builtin_fma(g, W[2 * Mp + m], a[2]);
-        }
-    for (int q = 0; q < 3; ++q) {
-        a[q] += __shfl_xor(a[q], 8);
-        a[q] += __shfl_xor(a[q], 4);
-        a[q] += __shfl_xor(a[q], 2);
-        a[q] += __shfl_xor(a[q], 1);
-    }
+    double a[3];
+    row_dot3(G + i * M, 0, i < M ? M : 0, lane16, W, Mp, nullptr, a);
     if (i < M && lane16 == 0) {
         ty[i] += a[0];
         ty[M + i] += a[1];
@@ -207,123 +176,21 @@ __global__ __launch_bounds__(256) void deform_kernel(int64_t M, int64_t Mp, cons
 __global__ __launch_bounds__(256) void nonrigid_sums_kernel(int64_t M, const double *__restrict__ ty, const double *__restrict__ P1,
                                                             const double *__restrict__ PX, double *__restrict__ partial) {
     __shared__ double sh[256];
-    double a = 0.0, b = 0.0;
+    double a[2] = {0, 0};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)kRedBlocks * 256) {
         const double x = ty[i], y = ty[M + i], z = ty[2 * M + i];
-        a += P1[i] * ((x * x + y * y) + z * z);
-        b += (x * PX[i] + y * PX[M + i]) + z * PX[2 * M + i];
+        a[0] += P1[i] * ((x * x + y * y) + z * z);
+        a[1] += (x * PX[i] + y * PX[M + i]) + z * PX[2 * M + i];
     }
-    __syncthreads();
-    const double ta = block_sum<256>(a, sh);
-    __syncthreads();  // sh is reused
-    const double tb = block_sum<256>(b, sh);
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x * 2] = ta;
-        partial[blockIdx.x * 2 + 1] = tb;
-    }
+    block_sums<2>(a, sh, partial + blockIdx.x * 2);
 }
 
 __global__ void nonrigid_finish_kernel(const double *__restrict__ partial, double *__restrict__ scalars, int32_t *__restrict__ flag) {
     if (threadIdx.x != 0) return;
-    double ypy = 0.0, tr = 0.0;
-    for (int b = 0; b < kRedBlocks; ++b) {
-        ypy += partial[b * 2];
-        tr += partial[b * 2 + 1];
-    }
+    const double ypy = sum_partials(partial, kRedBlocks, 2, 0), tr = sum_partials(partial, kRedBlocks, 2, 1);
     const double ns = (scalars[1] - 2 * tr + ypy) / (scalars[0] * 3.0);
     scalars[8] = ns;
-    if (!(fabs(ns) <= 1.79769313486231570815e308)) *flag = GINGR_ERR_NONFINITE;
-}
-
-// ------------------------------------------------------------------------------------------------ optimal-step non-rigid ICP
-// Normal equations of the stacked least-squares systems of NonRigidOptimalStepICP.scala (the reference solves `A \ B` on the sparse
-// stack; A has full column rank, so the solution is the same).  With Lg = M^T M the graph Laplacian of the template's edges:
-//   N-ICP-T (:151-190)   unknown X (n x 3):   (alpha^2 Lg + W^2 + E_L) X = W^2 (U - V) + E_L^T beta (UL - VL)
-//                        E_L: the reference's A3 has its ones at (i, i), i < L -- the first L columns, unscaled by beta
-//   N-ICP-A (:241-283)   unknown X (4n x 3):  (alpha^2 Lg (x) G^2 + D^T W^2 D + beta^2 DL^T DL) X = D^T W^2 U + beta^2 DL^T UL
-//                        D row i = [p_i, 1] in the columns 4i .. 4i+3; W zeroed at the landmark vertices; G = diag(1, 1, 1, gamma)
-// One thread per entry of the lower triangle / the border rows; the matrix is dense on the device (n of a registration template:
-// thousands) and goes through the blocked MFMA Cholesky of the non-rigid CPD.
-struct ScratchPart {  // a slice of the context's grow-only scratch
-    void *p = nullptr;
-    template <typename T>
-    T *as() const {
-        return reinterpret_cast<T *>(p);
-    }
-};
-
-struct NicpArgs {
-    int64_t n, dim, Mp, n_edges;
-    int kind;  // 0 T, 1 A
-    const double *v;        // template, SoA [3][n]
-    const double *u;        // closest points, SoA
-    const double *w;        // weights (A: already zero at the landmark vertices)
-    const int32_t *deg;     // edges per vertex
-    const int32_t *lmcount; // landmarks mapped to the vertex (A) / 1 for the first L vertices (T)
-    const double *lmsum;    // SoA [3][n]: A: sum of the landmark targets of the vertex; T: beta (UL_i - VL_i) for i < L
-    double alpha2, beta2, gamma2;
-};
-
-__global__ __launch_bounds__(256) void nicp_fill_kernel(NicpArgs a, double *__restrict__ Aw) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c >= a.Mp) return;
-    for (int64_t r = blockIdx.y; r < a.Mp + kNBc; r += gridDim.y) {
-    double val = 0.0;
-    if (r < a.dim) {
-        if (a.kind == 0) {
-            if (c == r) val = a.alpha2 * (double)a.deg[r] + a.w[r] * a.w[r] + (double)a.lmcount[r];
-        } else if (c <= r && (c >> 2) == (r >> 2)) {  // the 4 x 4 block of vertex i
-            const int64_t i = r >> 2;
-            const int ra = (int)(r & 3), ca = (int)(c & 3);
-            const double qr = ra < 3 ? a.v[ra * a.n + i] : 1.0, qc = ca < 3 ? a.v[ca * a.n + i] : 1.0;
-            val = (a.w[i] * a.w[i] + a.beta2 * (double)a.lmcount[i]) * qr * qc;
-            if (ra == ca) val += a.alpha2 * (double)a.deg[i] * (ra < 3 ? 1.0 : a.gamma2);
-        }
-    } else if (r < a.Mp) {
-        val = c == r ? 1.0 : 0.0;  // padding
-    } else if (r < a.Mp + 3 && c < a.dim) {
-        const int d = (int)(r - a.Mp);
-        if (a.kind == 0) {
-            val = a.w[c] * a.w[c] * (a.u[d * a.n + c] - a.v[d * a.n + c]) + a.lmsum[d * a.n + c];
-        } else {
-            const int64_t i = c >> 2;
-            const int ca = (int)(c & 3);
-            const double qc = ca < 3 ? a.v[ca * a.n + i] : 1.0;
-            val = qc * (a.w[i] * a.w[i] * a.u[d * a.n + i] + a.beta2 * a.lmsum[d * a.n + i]);
-        }
-    }
-    Aw[r * a.Mp + c] = val;
-    }
-}
-
-// the off-diagonal entries of alpha^2 Lg (x) G^2: -alpha^2 g_a^2 at ((p2, a), (p1, a)) for every edge p1 < p2
-__global__ __launch_bounds__(256) void nicp_edges_kernel(NicpArgs a, const int32_t *__restrict__ edges, double *__restrict__ Aw) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= a.n_edges) return;
-    const int64_t p1 = edges[2 * e], p2 = edges[2 * e + 1];
-    if (a.kind == 0) {
-        Aw[p2 * a.Mp + p1] = -a.alpha2;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) Aw[(4 * p2 + k) * a.Mp + 4 * p1 + k] = -a.alpha2 * (k < 3 ? 1.0 : a.gamma2);
-    }
-}
-
-// T: out = V + X;  A: out_i = [p_i, 1] X_i  (D X)
-__global__ __launch_bounds__(256) void nicp_apply_kernel(NicpArgs a, const double *__restrict__ W, double *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.n) return;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        double r;
-        if (a.kind == 0) {
-            r = a.v[d * a.n + i] + W[d * a.Mp + i];
-        } else {
-            const double *x = W + d * a.Mp + 4 * i;
-            r = ((a.v[i] * x[0] + a.v[a.n + i] * x[1]) + a.v[2 * a.n + i] * x[2]) + x[3];
-        }
-        out[d * a.n + i] = r;
-    }
+    if (!finite_d(ns)) *flag = GINGR_ERR_NONFINITE;
 }
 
 }  // namespace
@@ -378,51 +245,41 @@ static int classic_cpd_create_impl(gingr_ctx *ctx, int32_t kind, int64_t M, cons
         gingr_classic_cpd_destroy(h);
         return rc;
     };
-#define CC_TRY(expr)                                                                         \
-    do {                                                                                     \
-        if ((expr) != hipSuccess) return fail(gingr_set_error(ctx, GINGR_ERR_HIP, #expr));   \
-    } while (0)
     const int64_t big = M > N ? M : N;
-    CC_TRY(h->X.alloc((size_t)3 * N * sizeof(double)));
-    CC_TRY(h->TY.alloc((size_t)3 * M * sizeof(double)));
-    CC_TRY(h->stage.alloc((size_t)3 * big * sizeof(double)));
-    CC_TRY(h->den.alloc((size_t)N * sizeof(double)));
-    CC_TRY(h->inv_den.alloc((size_t)N * sizeof(double)));
-    CC_TRY(h->Pt1.alloc((size_t)N * sizeof(double)));
-    CC_TRY(h->P1.alloc((size_t)M * sizeof(double)));
-    CC_TRY(h->PX.alloc((size_t)3 * M * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->X.alloc((size_t)3 * N * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->TY.alloc((size_t)3 * M * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->stage.alloc((size_t)3 * big * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->den.alloc((size_t)N * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->inv_den.alloc((size_t)N * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->Pt1.alloc((size_t)N * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->P1.alloc((size_t)M * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->PX.alloc((size_t)3 * M * sizeof(double)));
     const int64_t ws1 = cpd_colsum_ws_doubles(M, N), ws2 = cpd_rowstats_ws_doubles(M, N);
-    CC_TRY(h->ws.alloc((size_t)std::max(std::max(ws1, ws2), sumsq_pairs_ws_doubles(M)) * sizeof(double)));
-    CC_TRY(h->part.alloc(GINGR_SCALAR_PART * sizeof(double)));
-    CC_TRY(h->sc.alloc(16 * sizeof(double)));
-    CC_TRY(h->aux.alloc(GINGR_AUX * sizeof(double)));
-    CC_TRY(h->red.alloc((size_t)kRedBlocks * 19 * sizeof(double)));
-    CC_TRY(h->mu.alloc(6 * sizeof(double)));
-    CC_TRY(h->params.alloc(16 * sizeof(double)));
-    CC_TRY(h->flag.alloc(sizeof(int32_t)));
-    CC_TRY(hipMemsetAsync(h->sc.p, 0, 16 * sizeof(double), ctx->stream));
-    CC_TRY(hipMemsetAsync(h->params.p, 0, 16 * sizeof(double), ctx->stream));
-    CC_TRY(hipMemsetAsync(h->flag.p, 0, sizeof(int32_t), ctx->stream));
-    CC_TRY(hipMemcpyAsync(h->stage.p, target_xyz, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_aos_to_soa(ctx, h->stage.as<double>(), N, h->X.as<double>());
-    CC_TRY(hipStreamSynchronize(ctx->stream));  // the staging buffer is reused
-    CC_TRY(hipMemcpyAsync(h->stage.p, template_xyz, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_aos_to_soa(ctx, h->stage.as<double>(), M, h->TY.as<double>());
+    HANDLE_TRY(ctx, fail, h->ws.alloc((size_t)std::max(std::max(ws1, ws2), sumsq_pairs_ws_doubles(M)) * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->part.alloc(GINGR_SCALAR_PART * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->sc.alloc(16 * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->aux.alloc(GINGR_AUX * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->red.alloc((size_t)kRedBlocks * 19 * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->mu.alloc(6 * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->params.alloc(16 * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->flag.alloc(sizeof(int32_t)));
+    HANDLE_TRY(ctx, fail, hipMemsetAsync(h->sc.p, 0, 16 * sizeof(double), ctx->stream));
+    HANDLE_TRY(ctx, fail, hipMemsetAsync(h->params.p, 0, 16 * sizeof(double), ctx->stream));
+    HANDLE_TRY(ctx, fail, hipMemsetAsync(h->flag.p, 0, sizeof(int32_t), ctx->stream));
+    if (int rc = upload_cloud(ctx, h->stage.as<double>(), target_xyz, N, h->X.as<double>())) return fail(rc);
+    if (int rc = upload_cloud(ctx, h->stage.as<double>(), template_xyz, M, h->TY.as<double>())) return fail(rc);
     const Cloud X = cloud_at(h->X.as<double>(), N), Y = cloud_at(h->TY.as<double>(), M);
     double *aux = h->aux.as<double>();
     launch_cloud_centroid(ctx, X, aux + 2);
     launch_cloud_absmax(ctx, X, aux + 2, aux);
     // sigma2_0 = sum |y_m - x_n|^2 / (dim N M)                                    (RigidCPD.initializeGaussianKernel, :46-57)
-    launch_sumsq_pairs(ctx, Y, X, h->ws.as<double>(), h->sc.as<double>() + 9);
-    double tot = 0.0;
-    CC_TRY(hipMemcpyAsync(&tot, h->sc.as<double>() + 9, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CC_TRY(hipStreamSynchronize(ctx->stream));
-    const double s0 = tot / (3.0 * (double)N * (double)M);
-    CC_TRY(hipMemcpyAsync(h->sc.as<double>() + 8, &s0, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    double s0 = 0.0;
+    if (int rc = first_variance(ctx, Y, X, 1.0, h->ws.as<double>(), h->sc.as<double>() + 9, &s0)) return fail(rc);
+    HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->sc.as<double>() + 8, &s0, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (lowrank) {
         h->lowrank.reset(new LowRankCpd);
-        CC_TRY(h->W.alloc((size_t)3 * h->Mp * sizeof(double)));
-        CC_TRY(hipMemsetAsync(h->W.p, 0, (size_t)3 * h->Mp * sizeof(double), ctx->stream));
+        HANDLE_TRY(ctx, fail, h->W.alloc((size_t)3 * h->Mp * sizeof(double)));
+        HANDLE_TRY(ctx, fail, hipMemsetAsync(h->W.p, 0, (size_t)3 * h->Mp * sizeof(double), ctx->stream));
         const int rc = lowrank_cpd_build(ctx, Y, beta, lowrank->relative_tolerance, lowrank->max_columns, *h->lowrank);
         if (rc != GINGR_OK) {
             (void)hipGetLastError();  // (a refused allocation must not surface again in the next call's launch check)
@@ -435,16 +292,15 @@ static int classic_cpd_create_impl(gingr_ctx *ctx, int32_t kind, int64_t M, cons
     } else if (kind == 2) {
         const int64_t Mp = h->Mp;
         const DenseSpdWork sys(Mp, DenseSpdWork::kRhsRows);
-        CC_TRY(h->G.alloc((size_t)M * M * sizeof(double)));
-        CC_TRY(h->Aw.alloc((size_t)sys.aw_doubles() * sizeof(double)));
-        CC_TRY(h->Linv.alloc((size_t)sys.linv_doubles() * sizeof(double)));
-        CC_TRY(h->W.alloc((size_t)sys.w_doubles() * sizeof(double)));
+        HANDLE_TRY(ctx, fail, h->G.alloc((size_t)M * M * sizeof(double)));
+        HANDLE_TRY(ctx, fail, h->Aw.alloc((size_t)sys.aw_doubles() * sizeof(double)));
+        HANDLE_TRY(ctx, fail, h->Linv.alloc((size_t)sys.linv_doubles() * sizeof(double)));
+        HANDLE_TRY(ctx, fail, h->W.alloc((size_t)sys.w_doubles() * sizeof(double)));
         // G = exp(-|y_i - y_j|^2 / (2 beta^2)) over the TEMPLATE points                    (CPDFactory.initializeKernelMatrixG, :54-66)
         launch_gauss_block(ctx, Y, Y, sqrt(2.0) * beta, 1.0, h->G.as<double>());
     }
-    CC_TRY(hipGetLastError());
-    CC_TRY(hipStreamSynchronize(ctx->stream));
-#undef CC_TRY
+    HANDLE_TRY(ctx, fail, hipGetLastError());
+    HANDLE_TRY(ctx, fail, hipStreamSynchronize(ctx->stream));
     *out = h;
     return GINGR_OK;
 }
@@ -519,15 +375,7 @@ int gingr_classic_cpd_iterate(gingr_classic_cpd *h, int32_t n_iterations) {
             hipLaunchKernelGGL(nonrigid_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, h->red.as<double>(), sc, flag);
         }
     }
-    HIP_TRY(ctx, hipGetLastError());
-    int32_t err = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&err, flag, sizeof(err), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (err) {
-        HIP_TRY(ctx, hipMemsetAsync(flag, 0, sizeof(int32_t), ctx->stream));
-        return gingr_set_error(ctx, err, "classic_cpd_iterate: %s", err == GINGR_ERR_NOT_SPD ? "system not positive definite" : "non-finite result");
-    }
-    return GINGR_OK;
+    return finish_iterate(ctx, flag, 1, 0, "classic_cpd_iterate");
 }
 
 int gingr_classic_cpd_get(gingr_classic_cpd *h, double *ty_xyz, double *sigma2, double *transform13, double *w_xyz) {
@@ -535,11 +383,7 @@ int gingr_classic_cpd_get(gingr_classic_cpd *h, double *ty_xyz, double *sigma2, 
     gingr_ctx *ctx = h->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t M = h->M, Mp = h->Mp;
-    if (ty_xyz) {
-        launch_soa_to_aos(ctx, h->TY.as<double>(), M, h->stage.as<double>());
-        HIP_TRY(ctx, hipMemcpyAsync(ty_xyz, h->stage.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (ty_xyz) GINGR_TRY(download_cloud(ctx, h->stage.as<double>(), h->TY.as<double>(), M, ty_xyz));
     if (sigma2) HIP_TRY(ctx, hipMemcpyAsync(sigma2, h->sc.as<double>() + 8, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (transform13) HIP_TRY(ctx, hipMemcpyAsync(transform13, h->params.p, 13 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (w_xyz) {
@@ -558,114 +402,11 @@ int gingr_classic_cpd_set(gingr_classic_cpd *h, const double *ty_xyz, double sig
     if (!h) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = h->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ty_xyz) {
-        HIP_TRY(ctx, hipMemcpyAsync(h->stage.p, ty_xyz, (size_t)3 * h->M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        launch_aos_to_soa(ctx, h->stage.as<double>(), h->M, h->TY.as<double>());
-    }
+    if (ty_xyz) GINGR_TRY(upload_cloud(ctx, h->stage.as<double>(), ty_xyz, h->M, h->TY.as<double>()));
     HIP_TRY(ctx, hipMemcpyAsync(h->sc.as<double>() + 8, &sigma2, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GINGR_OK;
 }
 
-int gingr_nicp_solve(gingr_ctx *ctx, int32_t kind, int64_t n, const double *moving_xyz, int64_t n_edges, const int32_t *edges,
-                     const double *w, const double *cp_xyz, int32_t n_lm, const int32_t *lm_ids, const double *lm_target_xyz, double alpha,
-                     double beta, double gamma, double *out_xyz, double *out_lm_xyz) {
-    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
-    if ((kind != 0 && kind != 1) || n < 1 || n_edges < 0 || n_lm < 0 || !moving_xyz || !w || !cp_xyz || !out_xyz || (n_edges > 0 && !edges) ||
-        (n_lm > 0 && (!lm_ids || !lm_target_xyz)) || !(alpha >= 0.0) || !(beta >= 0.0) || !(gamma >= 0.0) || n_lm > n)
-        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "nicp_solve: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t dim = kind == 0 ? n : 4 * n, Mp = round_up(dim, kNBc);
-    const DenseSpdWork sys(Mp, DenseSpdWork::kRhsRows);
-    // host side: SoA clouds, vertex degrees, the landmark terms per vertex
-    std::vector<double> hv((size_t)3 * n), hu((size_t)3 * n), hw((size_t)n), hs((size_t)3 * n, 0.0);
-    std::vector<int32_t> hdeg((size_t)n, 0), hcnt((size_t)n, 0);
-    for (int64_t i = 0; i < n; ++i) {
-        for (int d = 0; d < 3; ++d) {
-            hv[(size_t)(d * n + i)] = moving_xyz[3 * i + d];
-            hu[(size_t)(d * n + i)] = cp_xyz[3 * i + d];
-        }
-        hw[(size_t)i] = w[i];
-    }
-    for (int64_t e = 0; e < n_edges; ++e) {
-        const int32_t p1 = edges[2 * e], p2 = edges[2 * e + 1];
-        if (p1 < 0 || p2 <= p1 || p2 >= n) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "nicp_solve: edge %lld is not p1 < p2 < n", (long long)e);
-        ++hdeg[(size_t)p1];
-        ++hdeg[(size_t)p2];
-    }
-    for (int32_t l = 0; l < n_lm; ++l) {
-        const int32_t id = lm_ids[l];
-        if (id < 0 || id >= n) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "nicp_solve: landmark id out of range");
-        if (kind == 0) {  // row l of A3 has its one in COLUMN l; B3 row l = beta (UL_l - V[id_l])
-            hcnt[(size_t)l] = 1;
-            for (int d = 0; d < 3; ++d) hs[(size_t)(d * n + l)] = beta * (lm_target_xyz[3 * l + d] - moving_xyz[3 * (int64_t)id + d]);
-        } else {
-            hw[(size_t)id] = 0.0;  // W(i, i) = 0 at the landmark vertices (:251-253)
-            ++hcnt[(size_t)id];
-            for (int d = 0; d < 3; ++d) hs[(size_t)(d * n + id)] += lm_target_xyz[3 * l + d];
-        }
-    }
-    // one grow-only scratch of the context, carved up (an N-ICP run calls this once per iteration with the same sizes)
-    ScratchPart dv, du, dw, ds, ddeg, dcnt, dedges, Aw, Linv, W, flag, dout;
-    {
-        const size_t sizes[12] = {hv.size() * 8, hu.size() * 8, hw.size() * 8, hs.size() * 8, hdeg.size() * 4, hcnt.size() * 4,
-                                  (size_t)(n_edges > 0 ? n_edges : 1) * 8, (size_t)sys.aw_doubles() * sizeof(double),
-                                  (size_t)sys.linv_doubles() * sizeof(double), (size_t)sys.w_doubles() * sizeof(double), sizeof(int32_t),
-                                  (size_t)3 * n * sizeof(double)};
-        ScratchPart *parts[12] = {&dv, &du, &dw, &ds, &ddeg, &dcnt, &dedges, &Aw, &Linv, &W, &flag, &dout};
-        size_t total = 0;
-        for (int q = 0; q < 12; ++q) total += (sizes[q] + 255) & ~(size_t)255;
-        if (ctx->scratch_bytes < total) {
-            if (ctx->scratch) (void)hipFree(ctx->scratch);
-            ctx->scratch = nullptr;
-            ctx->scratch_bytes = 0;
-            if (hipMalloc(&ctx->scratch, total) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->scratch = nullptr;
-                return gingr_set_error(ctx, GINGR_ERR_HIP, "nicp_solve: out of device memory (the system is dense: %lld x %lld doubles)",
-                                       (long long)Mp, (long long)Mp);
-            }
-            ctx->scratch_bytes = total;
-        }
-        size_t off = 0;
-        for (int q = 0; q < 12; ++q) {
-            parts[q]->p = static_cast<char *>(ctx->scratch) + off;
-            off += (sizes[q] + 255) & ~(size_t)255;
-        }
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(dv.p, hv.data(), hv.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(du.p, hu.data(), hu.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dw.p, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ds.p, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ddeg.p, hdeg.data(), hdeg.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dcnt.p, hcnt.data(), hcnt.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (n_edges > 0) HIP_TRY(ctx, hipMemcpyAsync(dedges.p, edges, (size_t)n_edges * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(flag.p, 0, sizeof(int32_t), ctx->stream));
-    NicpArgs a{n, dim, Mp, n_edges, kind, dv.as<double>(), du.as<double>(), dw.as<double>(), ddeg.as<int32_t>(), dcnt.as<int32_t>(),
-               ds.as<double>(), alpha * alpha, beta * beta, gamma * gamma};
-    hipLaunchKernelGGL(nicp_fill_kernel, dim3((unsigned)ceil_div(Mp, 256), (unsigned)std::min<int64_t>(Mp + kNBc, 65535)), dim3(256), 0, ctx->stream, a, Aw.as<double>());
-    if (n_edges > 0)
-        hipLaunchKernelGGL(nicp_edges_kernel, dim3((unsigned)ceil_div(n_edges, 256)), dim3(256), 0, ctx->stream, a, dedges.as<int32_t>(),
-                           Aw.as<double>());
-    dense_spd_solve3(ctx, Aw.as<double>(), Mp, Linv.as<double>(), W.as<double>(), flag.as<int32_t>());
-    hipLaunchKernelGGL(nicp_apply_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, a, W.as<double>(), dout.as<double>());
-    HIP_TRY(ctx, hipGetLastError());
-    std::vector<double> ho((size_t)3 * n);
-    int32_t err = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ho.data(), dout.p, ho.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&err, flag.p, sizeof(err), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (err) return gingr_set_error(ctx, GINGR_ERR_NOT_SPD, "nicp_solve: the normal equations are not positive definite (a mesh component without any weighted vertex or landmark)");
-    for (int64_t i = 0; i < n; ++i)
-        for (int d = 0; d < 3; ++d) {
-            const double val = ho[(size_t)(d * n + i)];
-            if (!std::isfinite(val)) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "nicp_solve: non-finite result");
-            out_xyz[3 * i + d] = val;
-        }
-    if (out_lm_xyz)  // N-ICP-A: DL X = the moved landmark vertices (:278-282); N-ICP-T has no such output: the moved vertices too
-        for (int32_t l = 0; l < n_lm; ++l)
-            for (int d = 0; d < 3; ++d) out_lm_xyz[3 * l + d] = out_xyz[3 * (int64_t)lm_ids[l] + d];
-    return GINGR_OK;
-}
 
 }  // extern "C"

@@ -15,7 +15,7 @@
 //   lowrank_finish_kernel  sigma2' (the formula of nonrigid_finish_kernel over this pass's partials)
 #include "classic_cpd_lowrank.h"
 
-#include "block_sum.h"
+#include "cloud_sums.h"
 #include "dense_spd.h"
 #include "gpmm_factor.h"
 
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void lowrank_apply_kernel(const double *__rest
     __syncthreads();
     const double c = lambda * scalars[8];
     const int lane16 = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    double sa = 0.0, sb = 0.0;
+    double sums[2] = {0, 0};  // sum_i P1_i |TY_i|^2, sum_i TY_i . PX_i
     for (int64_t i = (int64_t)blockIdx.x * lowrank_plan::kApplyRows + grp; i < M; i += (int64_t)gridDim.x * lowrank_plan::kApplyRows) {
         double v[3] = {0.0, 0.0, 0.0};
         for (int b = 0; b < nb; ++b) {
@@ -201,12 +201,7 @@ __global__ __launch_bounds__(256) void lowrank_apply_kernel(const double *__rest
             }
         }
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            v[d] += __shfl_xor(v[d], 8);
-            v[d] += __shfl_xor(v[d], 4);
-            v[d] += __shfl_xor(v[d], 2);
-            v[d] += __shfl_xor(v[d], 1);
-        }
+        for (int d = 0; d < 3; ++d) v[d] = sum16(v[d]);
         if (lane16 == 0) {
             const double p = P1[i];
             double tn[3], px[3];
@@ -218,17 +213,11 @@ __global__ __launch_bounds__(256) void lowrank_apply_kernel(const double *__rest
                 ty[d * M + i] = tn[d];
                 W[d * w_stride + i] = ((px[d] - p * y) - p * v[d]) / c;
             }
-            sa += p * ((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
-            sb += (tn[0] * px[0] + tn[1] * px[1]) + tn[2] * px[2];
+            sums[0] += p * ((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
+            sums[1] += (tn[0] * px[0] + tn[1] * px[1]) + tn[2] * px[2];
         }
     }
-    const double ta = block_sum<256>(sa, sh);
-    __syncthreads();  // sh is reused
-    const double tb = block_sum<256>(sb, sh);
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x * 2] = ta;
-        partial[blockIdx.x * 2 + 1] = tb;
-    }
+    block_sums<2>(sums, sh, partial + blockIdx.x * 2);
 }
 
 // sigma2' = (xPx - 2 tr(TY^T P X) + sum P1 |TY|^2) / (3 Np)      (NonRigidCPD.scala:74-77)
@@ -246,7 +235,7 @@ __global__ __launch_bounds__(256) void lowrank_finish_kernel(const double *__res
     if (threadIdx.x != 0) return;
     const double ns = (scalars[1] - 2 * tr + ypy) / (scalars[0] * 3.0);
     scalars[8] = ns;
-    if (!(fabs(ns) <= 1.79769313486231570815e308)) *flag = GINGR_ERR_NONFINITE;
+    if (!finite_d(ns)) *flag = GINGR_ERR_NONFINITE;
     if (*sysflag) *flag = *sysflag;
 }
 

@@ -359,6 +359,39 @@ void launch_soa_to_aos(gingr_ctx *ctx, const double *soa, int64_t n, double *aos
     hipLaunchKernelGGL(soa_to_aos_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, soa, n, perm, aos);
 }
 
+int upload_cloud(gingr_ctx *ctx, double *stage, const double *xyz, int64_t n, double *soa, const int32_t *perm) {
+    HIP_TRY(ctx, hipMemcpyAsync(stage, xyz, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_aos_to_soa(ctx, stage, n, soa, perm);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffer is reused
+    return GINGR_OK;
+}
+
+int download_cloud(gingr_ctx *ctx, double *stage, const double *soa, int64_t n, double *xyz, const int32_t *perm) {
+    launch_soa_to_aos(ctx, soa, n, stage, perm);
+    HIP_TRY(ctx, hipMemcpyAsync(xyz, stage, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffer is reused
+    return GINGR_OK;
+}
+
+int first_variance(gingr_ctx *ctx, Cloud A, Cloud B, double factor, double *ws, double *slot, double *out) {
+    launch_sumsq_pairs(ctx, A, B, ws, slot);
+    double tot = 0.0;
+    HIP_TRY(ctx, hipMemcpyAsync(&tot, slot, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *out = factor * tot / (3.0 * (double)B.n * (double)A.n);
+    return GINGR_OK;
+}
+
+int finish_iterate(gingr_ctx *ctx, int32_t *flags, int words, int decides, const char *name) {
+    HIP_TRY(ctx, hipGetLastError());
+    int32_t err[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(err, flags, words * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!err[decides]) return GINGR_OK;
+    HIP_TRY(ctx, hipMemsetAsync(flags, 0, words * sizeof(int32_t), ctx->stream));
+    return gingr_set_error(ctx, err[decides], "%s: %s", name, err[decides] == GINGR_ERR_NOT_SPD ? "system not positive definite" : "non-finite result");
+}
+
 void launch_scatter(gingr_ctx *ctx, const double *in, int64_t n, const int32_t *perm, double *out) {
     if (n <= 0) return;
     hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, in, n, perm, out);

@@ -78,6 +78,16 @@ void gingr_ctx_rccl_release(gingr_ctx *ctx);  // rccl_exchange.hip: destroys the
         if (s__ != GINGR_OK) return s__; \
     } while (0)
 
+// While a handle is being built: a failed HIP call clears the runtime's sticky error (a refused allocation must not surface again in the
+// next call's launch check), leaves its text as the message and returns fail(code) -- `fail` destroys the half-built handle.
+#define HANDLE_TRY(ctx, fail, expr)                                                              \
+    do {                                                                                         \
+        if ((expr) != hipSuccess) {                                                              \
+            (void)hipGetLastError();                                                             \
+            return fail(gingr_set_error((ctx), GINGR_ERR_HIP, "%s: %s", __func__, #expr));       \
+        }                                                                                        \
+    } while (0)
+
 // did the launches so far go through?
 inline int check_launch(gingr_ctx *ctx) {
     HIP_TRY(ctx, hipGetLastError());
@@ -245,6 +255,17 @@ void launch_sumsq_pairs(gingr_ctx *ctx, Cloud A, Cloud B, double *ws, double *ou
 // soa[s] = aos[perm[s]] resp. aos[perm[s]] = soa[s]
 void launch_aos_to_soa(gingr_ctx *ctx, const double *aos, int64_t n, double *soa, const int32_t *perm = nullptr);
 void launch_soa_to_aos(gingr_ctx *ctx, const double *soa, int64_t n, double *aos, const int32_t *perm = nullptr);
+// host xyz -> stage -> SoA planes on the device, and the way back; stage: 3 n doubles on the device.  Both return a status and
+// synchronise (the staging buffer is free again, a downloaded cloud is there)
+int upload_cloud(gingr_ctx *ctx, double *stage, const double *xyz, int64_t n, double *soa, const int32_t *perm = nullptr);
+int download_cloud(gingr_ctx *ctx, double *stage, const double *soa, int64_t n, double *xyz, const int32_t *perm = nullptr);
+// *out = factor sum_ij |a_i - b_j|^2 / (3 nB nA), the first variance of the CPD family (RigidCPD.initializeGaussianKernel, :46-57;
+// BCPD: factor = gamma); ws as for launch_sumsq_pairs, slot: one double on the device, which keeps the sum.  Synchronises.
+int first_variance(gingr_ctx *ctx, Cloud A, Cloud B, double factor, double *ws, double *slot, double *out);
+// The end of an iterate call: the launch check, then the handle's `words` (<= 2) flag words come back (synchronises).  Where word
+// `decides` holds a code the words are cleared and the code is returned, with "<name>: system not positive definite" for
+// GINGR_ERR_NOT_SPD and "<name>: non-finite result" otherwise.
+int finish_iterate(gingr_ctx *ctx, int32_t *flags, int words, int decides, const char *name);
 // out[perm[s]] = in[s]  (perm nullable = copy)
 void launch_scatter(gingr_ctx *ctx, const double *in, int64_t n, const int32_t *perm, double *out);
 // spatial (balanced k-d tree, leaf = one 256-point tile) order of interleaved points: perm[s] = original index of the

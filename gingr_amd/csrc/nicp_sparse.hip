@@ -1,5 +1,5 @@
 // Optimal-step non-rigid ICP past dense sizes: the least-squares step of NonRigidOptimalStepICP.scala as a matrix-free block-Jacobi
-// preconditioned conjugate gradient on the device.  The system is the one gingr_nicp_solve (classic_cpd.hip) forms densely,
+// preconditioned conjugate gradient on the device.  The system is the one gingr_nicp_solve (nicp_dense.hip) forms densely,
 //   N-ICP-T   (alpha^2 Lg + W^2 + E_L) X = W^2 (U - V) + E_L^T beta (UL - VL)                               unknown n x 3
 //   N-ICP-A   (alpha^2 Lg (x) G^2 + D^T W^2 D + beta^2 DL^T DL) X = D^T W^2 U + beta^2 DL^T UL             unknown 4n x 3
 // with both quirks of the reference kept (N-ICP-T's landmark ones sit in the first L columns, unscaled by beta; N-ICP-A zeroes the
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void nicp_sparse_setup_kernel(SparseArgs 
 #pragma unroll
                 for (int g = 0; g < f; ++g) val -= L[e * (e + 1) / 2 + g] * L[f * (f + 1) / 2 + g];
                 if (e == f) {
-                    if (!(val > 0.0) || !(val <= 1.79769313486231570815e308)) ok = false;
+                    if (!(val > 0.0) || !(val <= kDblMax)) ok = false;
                     L[e * (e + 1) / 2 + f] = sqrt(val);
                 } else {
                     L[e * (e + 1) / 2 + f] = val / L[f * (f + 1) / 2 + f];
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void nicp_sparse_start_kernel(SparseArgs 
         a.ctl[CTL_TRUE_RR + c] = v[kSlotRR + c];
         a.ctl[CTL_FROZEN + slot + c] = frozen ? 1.0 : 0.0;
         all = all && frozen;
-        finite = finite && (v[kSlotBB + c] <= 1.79769313486231570815e308) && (v[kSlotRR + c] <= 1.79769313486231570815e308);
+        finite = finite && (v[kSlotBB + c] <= kDblMax) && (v[kSlotRR + c] <= kDblMax);
     }
     if (a.ctl[CTL_ERROR] == 0.0 && !finite) a.ctl[CTL_ERROR] = (double)GINGR_ERR_NONFINITE;
     const bool failed = a.ctl[CTL_ERROR] != 0.0;
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(kThreads) void nicp_sparse_update_kernel(SparseArgs
         if (a.ctl[CTL_FROZEN + 3 * parity + c] != 0.0) {
             step[c] = 0.0;  // a column that has met the stop rule keeps its x and r to the bit
         } else {
-            if (!(pap > 0.0) || !(pap <= 1.79769313486231570815e308)) broken = true;  // A is not positive definite along p
+            if (!(pap > 0.0) || !(pap <= kDblMax)) broken = true;  // A is not positive definite along p
             step[c] = a.ctl[CTL_RZ + 3 * parity + c] / pap;
         }
     }
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(kThreads) void nicp_sparse_direction_kernel(SparseA
         frozen[c] = was || rr[c] <= a.tol2 * a.ctl[CTL_BB + c];
         mix[c] = (was || !(before > 0.0)) ? 0.0 : rz[c] / before;
         all = all && frozen[c];
-        finite = finite && (rr[c] <= 1.79769313486231570815e308);
+        finite = finite && (rr[c] <= kDblMax);
     }
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i < a.n) {
@@ -486,43 +486,35 @@ int gingr_nicp_create(gingr_ctx *ctx, int32_t kind, int64_t n, int64_t n_edges, 
     h->hx.resize((size_t)(kind == 0 ? 3 : 12) * n);
     const size_t K = kind == 0 ? 1 : 4, planes = 3 * K * (size_t)n * sizeof(double);
     const int64_t blocks = ceil_div(n, kThreads);
-#define NS_TRY(expr)                                                                       \
-    do {                                                                                   \
-        if ((expr) != hipSuccess) {                                                        \
-            (void)hipGetLastError();                                                       \
-            return fail(gingr_set_error(ctx, GINGR_ERR_HIP, "nicp_create: %s", #expr));    \
-        }                                                                                  \
-    } while (0)
-    NS_TRY(h->row_ptr.alloc(h->graph.row_ptr.size() * sizeof(int32_t)));
-    NS_TRY(h->col.alloc(h->graph.col.size() * sizeof(int32_t)));
-    NS_TRY(h->v.alloc((size_t)3 * n * sizeof(double)));
-    NS_TRY(h->s.alloc((size_t)n * sizeof(double)));
-    NS_TRY(h->t.alloc((size_t)3 * n * sizeof(double)));
-    NS_TRY(h->x.alloc(planes));
-    NS_TRY(h->r.alloc(planes));
-    NS_TRY(h->z.alloc(planes));
-    NS_TRY(h->p.alloc(planes));
-    NS_TRY(h->ap.alloc(planes));
-    NS_TRY(h->minv.alloc((K * (K + 1) / 2) * (size_t)n * sizeof(double)));
-    NS_TRY(h->part.alloc((size_t)blocks * kSlots * sizeof(double)));
-    NS_TRY(h->ctl.alloc(CTL_DOUBLES * sizeof(double)));
-    NS_TRY(h->out.alloc((size_t)3 * n * sizeof(double)));
-    NS_TRY(h->stage.alloc((size_t)3 * n * sizeof(double)));
-    NS_TRY(h->done.alloc(sizeof(int32_t)));
+    HANDLE_TRY(ctx, fail, h->row_ptr.alloc(h->graph.row_ptr.size() * sizeof(int32_t)));
+    HANDLE_TRY(ctx, fail, h->col.alloc(h->graph.col.size() * sizeof(int32_t)));
+    HANDLE_TRY(ctx, fail, h->v.alloc((size_t)3 * n * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->s.alloc((size_t)n * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->t.alloc((size_t)3 * n * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->x.alloc(planes));
+    HANDLE_TRY(ctx, fail, h->r.alloc(planes));
+    HANDLE_TRY(ctx, fail, h->z.alloc(planes));
+    HANDLE_TRY(ctx, fail, h->p.alloc(planes));
+    HANDLE_TRY(ctx, fail, h->ap.alloc(planes));
+    HANDLE_TRY(ctx, fail, h->minv.alloc((K * (K + 1) / 2) * (size_t)n * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->part.alloc((size_t)blocks * kSlots * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->ctl.alloc(CTL_DOUBLES * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->out.alloc((size_t)3 * n * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->stage.alloc((size_t)3 * n * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->done.alloc(sizeof(int32_t)));
     h->pin.pin_doubles = CTL_DOUBLES + 1;  // the last word is the flag
-    NS_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->pin.pin), h->pin.pin_doubles * sizeof(double), hipHostMallocDefault));
+    HANDLE_TRY(ctx, fail, hipHostMalloc(reinterpret_cast<void **>(&h->pin.pin), h->pin.pin_doubles * sizeof(double), hipHostMallocDefault));
     memset(h->pin.pin, 0, h->pin.pin_doubles * sizeof(double));
     h->pin.done = h->done.as<int32_t>();
     if (hipHostGetDevicePointer(reinterpret_cast<void **>(&h->pin.pin_dev), h->pin.pin, 0) != hipSuccess) {
         (void)hipGetLastError();
         h->pin.pin_dev = nullptr;  // (pull_small then copies and synchronises)
     }
-    NS_TRY(hipMemsetAsync(h->done.p, 0, sizeof(int32_t), ctx->stream));
-    NS_TRY(hipMemcpyAsync(h->row_ptr.p, h->graph.row_ptr.data(), h->graph.row_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HANDLE_TRY(ctx, fail, hipMemsetAsync(h->done.p, 0, sizeof(int32_t), ctx->stream));
+    HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->row_ptr.p, h->graph.row_ptr.data(), h->graph.row_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     if (!h->graph.col.empty())
-        NS_TRY(hipMemcpyAsync(h->col.p, h->graph.col.data(), h->graph.col.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    NS_TRY(hipStreamSynchronize(ctx->stream));
-#undef NS_TRY
+        HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->col.p, h->graph.col.data(), h->graph.col.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HANDLE_TRY(ctx, fail, hipStreamSynchronize(ctx->stream));
     *out = h;
     return GINGR_OK;
 }
@@ -621,7 +613,6 @@ int gingr_nicp_step(gingr_nicp *h, const double *moving_xyz, const double *w, co
         first = (int)ctl[CTL_ITERATIONS];  // (the iterations behind `done` in the last chunk did nothing)
     }
     if (h->kind == 0) enqueue_moved<1>(ctx, a, h->out.as<double>()); else enqueue_moved<4>(ctx, a, h->out.as<double>());
-    launch_soa_to_aos(ctx, h->out.as<double>(), n, h->stage.as<double>());
     GINGR_TRY(check_launch(ctx));
     if (info) {
         info->iterations = (int32_t)ctl[CTL_ITERATIONS];
@@ -635,8 +626,7 @@ int gingr_nicp_step(gingr_nicp *h, const double *moving_xyz, const double *w, co
     if (err == GINGR_ERR_NOT_SPD)
         return gingr_set_error(ctx, GINGR_ERR_NOT_SPD, "nicp_step: the normal equations are not positive definite (a vertex block or a search direction)");
     if (err) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "nicp_step: non-finite residual");
-    HIP_TRY(ctx, hipMemcpyAsync(out_xyz, h->stage.p, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    GINGR_TRY(download_cloud(ctx, h->stage.as<double>(), h->out.as<double>(), n, out_xyz));
     for (int64_t i = 0; i < 3 * n; ++i)
         if (!std::isfinite(out_xyz[i])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "nicp_step: non-finite result");
     if (out_lm_xyz)  // N-ICP-A: DL X = the moved landmark vertices (:278-282); N-ICP-T has no such output: the moved vertices too

@@ -5,6 +5,7 @@
 // about the origin, with scalismo's Euler round trip of the rotation), and its application to the template.  The template stays
 // in HBM between iterations; one scalar (the mean distance) comes back per iteration for the caller's convergence test.
 #include "common.h"
+#include "cloud_sums.h"
 #include "svd3.h"
 
 #include <cmath>
@@ -49,16 +50,7 @@ __global__ __launch_bounds__(256) void icp_sums_kernel(Cloud p, Cloud t0, const 
         s[15] += x0 * x0 + x1 * x1 + x2 * x2;
         s[16] += sqrt(d2[i]);  // (pt - closestPoint).norm, RigidICP.scala:67
     }
-    for (int q = 0; q < kSums; ++q) {
-        sh[threadIdx.x] = s[q];
-        __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) part[(int64_t)blockIdx.x * kSums + q] = sh[0];
-        __syncthreads();
-    }
+    block_sums<kSums>(s, sh, part + blockIdx.x * kSums);
 }
 
 // tr[0] = scale, tr[1..9] = R (row-major, after the Euler round trip), tr[10..12] = t, tr[13] = mean distance of the pairs,
@@ -67,11 +59,7 @@ __global__ void icp_transform_kernel(const double *__restrict__ part, double n, 
                                      double *__restrict__ tr) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double s[kSums];
-    for (int q = 0; q < kSums; ++q) {
-        double a = 0.0;
-        for (int b = 0; b < kIcpBlocks; ++b) a += part[(int64_t)b * kSums + q];  // fixed order
-        s[q] = a;
-    }
+    for (int q = 0; q < kSums; ++q) s[q] = sum_partials(part, kIcpBlocks, kSums, q);
     const double c0[3] = {c0x, c0y, c0z};
     double mux[3], muy[3];
     for (int a = 0; a < 3; ++a) {
@@ -86,9 +74,7 @@ __global__ void icp_transform_kernel(const double *__restrict__ part, double n, 
     if (!polar3_rotation(Sxy, R, &trace_ds)) {
         double U[9], D[3], V[9];
         svd3(Sxy, U, D, V);
-        const double det = Sxy[0] * (Sxy[4] * Sxy[8] - Sxy[5] * Sxy[7]) - Sxy[1] * (Sxy[3] * Sxy[8] - Sxy[5] * Sxy[6]) +
-                           Sxy[2] * (Sxy[3] * Sxy[7] - Sxy[4] * Sxy[6]);
-        const double s3 = det < 0 ? -1.0 : 1.0;
+        const double s3 = det3(Sxy) < 0 ? -1.0 : 1.0;
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 3; ++b) R[a * 3 + b] = U[a * 3] * V[b * 3] + U[a * 3 + 1] * V[b * 3 + 1] + s3 * U[a * 3 + 2] * V[b * 3 + 2];
         trace_ds = D[0] + D[1] + s3 * D[2];
@@ -104,10 +90,10 @@ __global__ void icp_transform_kernel(const double *__restrict__ part, double n, 
         mya[a] = muy[a] + c0[a];
     }
     tr[0] = c;
-    bool fin = fabs(c) <= 1.79769313486231570815e308;
+    bool fin = finite_d(c);
     for (int q = 0; q < 9; ++q) {
         tr[1 + q] = Re[q];
-        fin = fin && fabs(Re[q]) <= 1.79769313486231570815e308;
+        fin = fin && finite_d(Re[q]);
     }
     for (int a = 0; a < 3; ++a) tr[10 + a] = mya[a] - c * (R[a * 3] * mxa[0] + R[a * 3 + 1] * mxa[1] + R[a * 3 + 2] * mxa[2]);
     tr[13] = s[16] / n;
@@ -119,10 +105,9 @@ __global__ __launch_bounds__(256) void icp_apply_kernel(int64_t n, double *__res
                                                         double *__restrict__ pz, const double *__restrict__ tr) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double s = tr[0], x = px[i], y = py[i], z = pz[i];
-    px[i] = s * (tr[1] * x + tr[2] * y + tr[3] * z) + tr[10];
-    py[i] = s * (tr[4] * x + tr[5] * y + tr[6] * z) + tr[11];
-    pz[i] = s * (tr[7] * x + tr[8] * y + tr[9] * z) + tr[12];
+    double q[3];
+    similarity_apply(tr, px[i], py[i], pz[i], q);
+    px[i] = q[0], py[i] = q[1], pz[i] = q[2];
 }
 
 }  // namespace
@@ -142,32 +127,30 @@ int gingr_rigid_icp_create(gingr_ctx *ctx, int32_t kind, int64_t M, const double
         delete h;
         return rc;
     };
-    const size_t big = (size_t)3 * (M > N ? M : N) * sizeof(double);
-    if (h->stage.alloc(big) != hipSuccess || h->tpl.alloc((size_t)3 * M * sizeof(double)) != hipSuccess ||
-        h->tgt.alloc((size_t)3 * N * sizeof(double)) != hipSuccess ||
-        h->torig.alloc((size_t)N * sizeof(int32_t)) != hipSuccess ||
-        h->tboxes.alloc((size_t)30 * ceil_div(N, 256) * sizeof(double)) != hipSuccess ||
-        h->ws.alloc((size_t)nn_ws_bytes(M, N)) != hipSuccess || h->idx.alloc((size_t)M * sizeof(int32_t)) != hipSuccess ||
-        h->d2.alloc((size_t)M * sizeof(double)) != hipSuccess || h->part.alloc((size_t)kIcpBlocks * kSums * sizeof(double)) != hipSuccess ||
-        h->tr.alloc(16 * sizeof(double)) != hipSuccess)
-        return fail(gingr_set_error(ctx, GINGR_ERR_HIP, "rigid_icp_create: out of device memory"));
+    HANDLE_TRY(ctx, fail, h->stage.alloc((size_t)3 * (M > N ? M : N) * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->tpl.alloc((size_t)3 * M * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->tgt.alloc((size_t)3 * N * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->torig.alloc((size_t)N * sizeof(int32_t)));
+    HANDLE_TRY(ctx, fail, h->tboxes.alloc((size_t)30 * ceil_div(N, 256) * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->ws.alloc((size_t)nn_ws_bytes(M, N)));
+    HANDLE_TRY(ctx, fail, h->idx.alloc((size_t)M * sizeof(int32_t)));
+    HANDLE_TRY(ctx, fail, h->d2.alloc((size_t)M * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->part.alloc((size_t)kIcpBlocks * kSums * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->tr.alloc(16 * sizeof(double)));
     for (int64_t i = 0; i < M; ++i)
         for (int d = 0; d < 3; ++d) h->c0[d] += moving_xyz[3 * i + d];
     for (int d = 0; d < 3; ++d) h->c0[d] /= (double)M;
     // template as an SoA cloud; the target in Morton order with its tile boxes for the nearest-first pruning of the closest-point
     // kernel (which reports POSITIONS in that order and breaks exact ties by the lowest original index)
-    (void)hipMemcpyAsync(h->stage.p, moving_xyz, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    launch_aos_to_soa(ctx, h->stage.as<double>(), M, h->tpl.as<double>());
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipMemcpyAsync(h->stage.p, target_xyz, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (int rc = upload_cloud(ctx, h->stage.as<double>(), moving_xyz, M, h->tpl.as<double>())) return fail(rc);
     std::vector<int32_t> order;
     kd_leaf_order(target_xyz, N, order);
-    (void)hipMemcpyAsync(h->torig.p, order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    launch_aos_to_soa(ctx, h->stage.as<double>(), N, h->tgt.as<double>(), h->torig.as<int32_t>());
+    HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->torig.p, order.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = upload_cloud(ctx, h->stage.as<double>(), target_xyz, N, h->tgt.as<double>(), h->torig.as<int32_t>())) return fail(rc);
     const double *t = h->tgt.as<double>();
     launch_tile_bbox(ctx, Cloud{t, t + N, t + 2 * N, N}, h->tboxes.as<double>());
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-        return fail(gingr_set_error(ctx, GINGR_ERR_HIP, "rigid_icp_create: set-up kernels failed"));
+    HANDLE_TRY(ctx, fail, hipGetLastError());
+    HANDLE_TRY(ctx, fail, hipStreamSynchronize(ctx->stream));
     if (nn_grid_build(ctx, target_xyz, N, order.data(), M, &h->tgrid) != GINGR_OK) return fail(GINGR_ERR_HIP);  // (message set)
     *out = h;
     return GINGR_OK;
@@ -222,10 +205,7 @@ int gingr_rigid_icp_get(gingr_rigid_icp *h, double *points_xyz, double *transfor
     if (!h) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = h->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (points_xyz) {
-        launch_soa_to_aos(ctx, h->tpl.as<double>(), h->M, h->stage.as<double>());
-        HIP_TRY(ctx, hipMemcpyAsync(points_xyz, h->stage.p, (size_t)3 * h->M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if (points_xyz) GINGR_TRY(download_cloud(ctx, h->stage.as<double>(), h->tpl.as<double>(), h->M, points_xyz));
     if (transform13) HIP_TRY(ctx, hipMemcpyAsync(transform13, h->tr.p, 13 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GINGR_OK;
@@ -236,10 +216,7 @@ int gingr_rigid_icp_set(gingr_rigid_icp *h, const double *points_xyz) {
     if (!h || !points_xyz) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = h->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(h->stage.p, points_xyz, (size_t)3 * h->M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_aos_to_soa(ctx, h->stage.as<double>(), h->M, h->tpl.as<double>());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GINGR_OK;
+    return upload_cloud(ctx, h->stage.as<double>(), points_xyz, h->M, h->tpl.as<double>());
 }
 
 }  // extern "C"
