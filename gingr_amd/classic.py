@@ -186,19 +186,31 @@ class BCPD:
     """Bayesian coherent point drift (Hirose 2020) over csrc/bcpd.hip -- the method of the reference's draft cpd/BCPD.scala in this
     package's definition (include/gingr_hip.h; DESIGN.md section 5 lists where it follows the paper against the draft).  The reference
     takes any PDKernel; here the kernel is the Gaussian of CPDFactory, g(a, b) = exp(-|a - b|^2 / (2 beta^2)).  `k` is the paper's
-    kappa (math.inf: constant mixing weights 1 / M).  The state (yhat, sigma_m^2, <alpha_m>, s, R, t, sigma2) lives on the device."""
+    kappa (math.inf: constant mixing weights 1 / M).  The state (yhat, sigma_m^2, <alpha_m>, s, R, t, sigma2) lives on the device.
+    lowRank: a LowRankG -- the deformation step over G ~ L L^T (csrc/bcpd_lowrank.hip: the acceleration the paper proposes), for
+    templates past the dense limit of 32 768 points; `lowRankInfo` and `factor()` are those of the classic low-rank task."""
 
     def __init__(self, ctx: Context, templatePoints, targetPoints, w: float = 0.0, lambda_: float = 2.0, gamma: float = 1.0,
-                 k: float = 1.0, beta: float = 2.0):
+                 k: float = 1.0, beta: float = 2.0, lowRank: Optional[LowRankG] = None):
         self.ctx, self._lib = ctx, ctx._lib
         self.template, self.target = f64(templatePoints), f64(targetPoints)
         self.M, self.N = self.template.shape[0], self.target.shape[0]
         self.w, self.lambda_, self.gamma, self.k, self.beta = w, lambda_, gamma, k, beta
-        self._h = None
+        self._h, self.lowRankInfo = None, None
         h = c_void_p()
-        _check(ctx.handle, self._lib.gingr_bcpd_create(ctx.handle, self.M, dptr(self.template), self.N, dptr(self.target), float(w),
-                                                       float(lambda_), float(gamma), float(k), float(beta), ctypes.byref(h)),
-               "gingr_bcpd_create")
+        if lowRank is None:
+            _check(ctx.handle, self._lib.gingr_bcpd_create(ctx.handle, self.M, dptr(self.template), self.N, dptr(self.target), float(w),
+                                                           float(lambda_), float(gamma), float(k), float(beta), ctypes.byref(h)),
+                   "gingr_bcpd_create")
+        else:
+            from ._native import ClassicCpdLowRankInfo
+            info = ClassicCpdLowRankInfo()
+            _check(ctx.handle, self._lib.gingr_bcpd_create_lowrank(
+                ctx.handle, self.M, dptr(self.template), self.N, dptr(self.target), float(w), float(lambda_), float(gamma), float(k),
+                float(beta), float(lowRank.relativeTolerance), int(lowRank.maxColumns), ctypes.byref(info), ctypes.byref(h)),
+                "gingr_bcpd_create_lowrank")
+            self.lowRankInfo = {"columns": int(info.columns), "tolerance_reached": bool(info.tolerance_reached),
+                                "residual_fraction": float(info.residual_fraction), "factor_bytes": int(info.factor_bytes)}
         self._h = h
         self._sigma2_init = self.sigma2()
 
@@ -258,6 +270,14 @@ class BCPD:
         self._get(None, None, None, None, None, None, dptr(p), None)
         return float(p[0]), p[1:10].reshape(3, 3).copy(), p[10:13].copy()
 
+    def factor(self) -> np.ndarray:
+        """L (M, k) of a low-rank task: G ~ L @ L.T"""
+        k = ctypes.c_int32()
+        _check(self.ctx.handle, self._lib.gingr_bcpd_get_factor(self._h, ctypes.byref(k), None), "gingr_bcpd_get_factor")
+        L = np.empty((self.M, k.value))
+        _check(self.ctx.handle, self._lib.gingr_bcpd_get_factor(self._h, None, dptr(L)), "gingr_bcpd_get_factor")
+        return L
+
     def correspondenceWeights(self) -> Tuple[np.ndarray, np.ndarray]:
         """(nu = P 1, nu' = P^T 1) of the last iteration: how much of the target a template point explains, and the probability that a
         target point is no outlier"""
@@ -295,12 +315,12 @@ class BCPDRegistration:
     """BCPDRegistration.scala with its defaults: register(target) returns the warped template points."""
 
     def __init__(self, ctx: Context, template, w: float = 0.0, lambda_: float = 2.0, gamma: float = 1.0, k: float = 1.0, beta: float = 2.0,
-                 max_iterations: int = 100):
-        self.ctx, self.template, self.max_iterations = ctx, f64(template), max_iterations
+                 max_iterations: int = 100, lowRank: Optional[LowRankG] = None):
+        self.ctx, self.template, self.max_iterations, self.lowRank = ctx, f64(template), max_iterations, lowRank
         self.w, self.lambda_, self.gamma, self.k, self.beta = w, lambda_, gamma, k, beta
 
     def register(self, target) -> np.ndarray:
-        task = BCPD(self.ctx, self.template, target, self.w, self.lambda_, self.gamma, self.k, self.beta)
+        task = BCPD(self.ctx, self.template, target, self.w, self.lambda_, self.gamma, self.k, self.beta, self.lowRank)
         try:
             return task.Registration(self.max_iterations)
         finally:

@@ -13,7 +13,11 @@
 //
 // Nothing divides by nu_m: a row with nu_m = 0 (a template point without counterpart) is an ordinary row.  Every reduction adds its
 // partials in a fixed order: two runs give the same bits.
+//
+// A handle of gingr_bcpd_create_lowrank holds a factor L (G ~ L L^T) in place of G and runs step 2 over it (bcpd_lowrank.hip); steps 1,
+// 3 and 4 and every M- and N-sized buffer are the same.
 #include "common.h"
+#include "bcpd_lowrank.h"
 #include "bcpd_math.h"
 #include "cloud_sums.h"
 #include "dense_spd.h"
@@ -23,6 +27,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <memory>
 
 namespace {
 
@@ -468,6 +473,14 @@ struct gingr_bcpd {
     double w = 0.0, lambda = 2.0, gamma = 1.0, kappa = 1.0, beta = 2.0, p_out = 0.0, sigma2_init = 0.0;
     BcpdChunks col{1, kBcpdTile}, row{1, kBcpdTile};
     DevBuf X, Y, Yh, V, U, PX, Rr, Z, B, Wv, Q, sig, alpha, a, nu, dh, nup, inv, ws, xpart, red, mu, params, sc, aux, flags, G, Aw, Linv, stage;
+    std::unique_ptr<BcpdLowRank> lowrank;  // gingr_bcpd_create_lowrank: G, Aw, Linv, B and Q stay empty, Z stays zero
+};
+
+// what gingr_bcpd_create_lowrank adds to the arguments of gingr_bcpd_create
+struct BcpdLowRankRequest {
+    double relative_tolerance;
+    int32_t max_columns;
+    gingr_classic_cpd_lowrank_info *info;
 };
 
 extern "C" {
@@ -478,15 +491,17 @@ void gingr_bcpd_destroy(gingr_bcpd *h) {
     delete h;
 }
 
-int gingr_bcpd_create(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, double w, double lambda,
-                      double gamma, double kappa, double beta, gingr_bcpd **out) {
+}  // extern "C"
+
+static int bcpd_create_impl(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, double w, double lambda,
+                            double gamma, double kappa, double beta, const BcpdLowRankRequest *lowrank, gingr_bcpd **out) {
     if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
     if (!out || !moving_xyz || !target_xyz) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_create: null argument");
     if (M < 1 || N < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_create: need M >= 1 and N >= 1");
     if (!(w >= 0.0 && w < 1.0)) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_create: need 0 <= w < 1");
     if (!(lambda > 0.0) || !(gamma > 0.0) || !(kappa > 0.0) || !(beta > 0.0) || !(lambda <= kDblMax) || !(gamma <= kDblMax) || !(beta <= kDblMax))
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_create: need lambda, gamma, kappa, beta > 0 (kappa alone may be +inf)");
-    if (M > 32768)
+    if (!lowrank && M > 32768)
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_create: template too large (M <= 32768: the iteration keeps M x M double buffers)");
     double p_out = 0.0;
     if (w > 0.0) {  // the outlier density 1 / V, V the volume of the target's bounding box
@@ -524,12 +539,14 @@ int gingr_bcpd_create(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64
     const DenseSpdWork sys(Mp, DenseSpdWork::kIdentity);
     HANDLE_TRY(ctx, fail, h->X.alloc((size_t)3 * N * sizeof(double)));
     for (DevBuf *b : {&h->Y, &h->Yh, &h->V, &h->U, &h->PX, &h->Rr, &h->Z}) HANDLE_TRY(ctx, fail, b->alloc((size_t)3 * M * sizeof(double)));
-    for (DevBuf *b : {&h->B, &h->Wv, &h->Q}) HANDLE_TRY(ctx, fail, b->alloc((size_t)3 * Mp * sizeof(double)));
+    HANDLE_TRY(ctx, fail, h->Wv.alloc((size_t)3 * Mp * sizeof(double)));
+    if (!lowrank)
+        for (DevBuf *b : {&h->B, &h->Q}) HANDLE_TRY(ctx, fail, b->alloc((size_t)3 * Mp * sizeof(double)));
     for (DevBuf *b : {&h->sig, &h->alpha, &h->a, &h->nu}) HANDLE_TRY(ctx, fail, b->alloc((size_t)M * sizeof(double)));
     HANDLE_TRY(ctx, fail, h->dh.alloc((size_t)Mp * sizeof(double)));
     HANDLE_TRY(ctx, fail, h->nup.alloc((size_t)N * sizeof(double)));
     HANDLE_TRY(ctx, fail, h->inv.alloc((size_t)N * sizeof(double)));
-    const int64_t ws = std::max(std::max(h->col.count * N, h->row.count * 4 * M), std::max(nb * Mp, sumsq_pairs_ws_doubles(M)));
+    const int64_t ws = std::max(std::max(h->col.count * N, h->row.count * 4 * M), std::max(lowrank ? 0 : nb * Mp, sumsq_pairs_ws_doubles(M)));
     HANDLE_TRY(ctx, fail, h->ws.alloc((size_t)ws * sizeof(double)));
     HANDLE_TRY(ctx, fail, h->stage.alloc((size_t)3 * big * sizeof(double)));
     HANDLE_TRY(ctx, fail, h->xpart.alloc(kRedBlocks * sizeof(double)));
@@ -539,11 +556,14 @@ int gingr_bcpd_create(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64
     HANDLE_TRY(ctx, fail, h->sc.alloc(8 * sizeof(double)));
     HANDLE_TRY(ctx, fail, h->aux.alloc(GINGR_AUX * sizeof(double)));
     HANDLE_TRY(ctx, fail, h->flags.alloc(2 * sizeof(int32_t)));
-    HANDLE_TRY(ctx, fail, h->G.alloc((size_t)M * M * sizeof(double)));
-    HANDLE_TRY(ctx, fail, h->Aw.alloc((size_t)sys.aw_doubles() * sizeof(double)));
-    HANDLE_TRY(ctx, fail, h->Linv.alloc((size_t)sys.linv_doubles() * sizeof(double)));
+    if (!lowrank) {
+        HANDLE_TRY(ctx, fail, h->G.alloc((size_t)M * M * sizeof(double)));
+        HANDLE_TRY(ctx, fail, h->Aw.alloc((size_t)sys.aw_doubles() * sizeof(double)));
+        HANDLE_TRY(ctx, fail, h->Linv.alloc((size_t)sys.linv_doubles() * sizeof(double)));
+    }
     for (DevBuf *b : {&h->B, &h->Wv, &h->Q, &h->dh, &h->V, &h->nu, &h->nup, &h->sc, &h->mu, &h->aux, &h->flags})
-        HANDLE_TRY(ctx, fail, hipMemsetAsync(b->p, 0, b->bytes, ctx->stream));  // (the padding of the Mp-long vectors stays zero)
+        if (b->p) HANDLE_TRY(ctx, fail, hipMemsetAsync(b->p, 0, b->bytes, ctx->stream));  // (the padding of the Mp-long vectors stays zero)
+    if (lowrank) HANDLE_TRY(ctx, fail, hipMemsetAsync(h->Z.p, 0, h->Z.bytes, ctx->stream));  // the zero `ty` of the Gram pass
     if (int rc = upload_cloud(ctx, h->stage.as<double>(), target_xyz, N, h->X.as<double>())) return fail(rc);
     if (int rc = upload_cloud(ctx, h->stage.as<double>(), moving_xyz, M, h->Y.as<double>())) return fail(rc);
     HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->Yh.p, h->Y.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -559,11 +579,56 @@ int gingr_bcpd_create(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64
     HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->sig.p, ones.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->alpha.p, am.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->params.p, ident, sizeof(ident), hipMemcpyHostToDevice, ctx->stream));
-    // G = exp(-|y_i - y_j|^2 / (2 beta^2)) over the template points (the Gaussian kernel of CPDFactory)
-    launch_gauss_block(ctx, Y, Y, sqrt(2.0) * beta, 1.0, h->G.as<double>());
+    if (lowrank) {
+        h->lowrank.reset(new BcpdLowRank);
+        const int rc = bcpd_lowrank_build(ctx, Y, beta, lowrank->relative_tolerance, lowrank->max_columns, *h->lowrank);
+        if (rc != GINGR_OK) {
+            (void)hipGetLastError();  // (a refused allocation must not surface again in the next call's launch check)
+            return fail(rc);
+        }
+        if (lowrank->info) {
+            const BcpdLowRank &lr = *h->lowrank;
+            *lowrank->info = gingr_classic_cpd_lowrank_info{lr.plan.k, lr.tolerance_reached, lr.residual_fraction, (int64_t)lr.L.bytes};
+        }
+    } else {
+        // G = exp(-|y_i - y_j|^2 / (2 beta^2)) over the template points (the Gaussian kernel of CPDFactory)
+        launch_gauss_block(ctx, Y, Y, sqrt(2.0) * beta, 1.0, h->G.as<double>());
+    }
     HANDLE_TRY(ctx, fail, hipGetLastError());
     HANDLE_TRY(ctx, fail, hipStreamSynchronize(ctx->stream));
     *out = h;
+    return GINGR_OK;
+}
+
+extern "C" {
+
+int gingr_bcpd_create(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, double w, double lambda,
+                      double gamma, double kappa, double beta, gingr_bcpd **out) {
+    return bcpd_create_impl(ctx, M, moving_xyz, N, target_xyz, w, lambda, gamma, kappa, beta, nullptr, out);
+}
+
+int gingr_bcpd_create_lowrank(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, double w,
+                              double lambda, double gamma, double kappa, double beta, double relative_tolerance, int32_t max_columns,
+                              gingr_classic_cpd_lowrank_info *info, gingr_bcpd **out) {
+    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
+    if (info) memset(info, 0, sizeof(*info));
+    if (!(relative_tolerance >= 0.0) || !(relative_tolerance < 1.0))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_create_lowrank: relative tolerance must be in [0, 1)");
+    if (max_columns > GINGR_CLASSIC_CPD_MAX_COLUMNS)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_create_lowrank: max_columns = %d is above the ceiling of %d factor columns",
+                               (int)max_columns, GINGR_CLASSIC_CPD_MAX_COLUMNS);
+    const BcpdLowRankRequest req{relative_tolerance, max_columns, info};
+    return bcpd_create_impl(ctx, M, moving_xyz, N, target_xyz, w, lambda, gamma, kappa, beta, &req, out);
+}
+
+int gingr_bcpd_get_factor(gingr_bcpd *h, int32_t *columns, double *L_rowmajor_M_by_k) {
+    if (!h) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = h->ctx;
+    if (!h->lowrank)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_get_factor: the handle holds the dense kernel matrix, not a factor");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (columns) *columns = h->lowrank->plan.k;
+    if (L_rowmajor_M_by_k) return lowrank_cpd_get_factor(ctx, *h->lowrank, L_rowmajor_M_by_k);
     return GINGR_OK;
 }
 
@@ -577,7 +642,7 @@ int gingr_bcpd_iterate(gingr_bcpd *h, int32_t n_iterations) {
     const DenseSpdWork sys(Mp, DenseSpdWork::kIdentity);
     const Cloud X = cloud_at(h->X.as<double>(), N), Yh = cloud_at(h->Yh.as<double>(), M);
     double *sc = h->sc.as<double>(), *aux = h->aux.as<double>(), *params = h->params.as<double>(), *ws = h->ws.as<double>();
-    double *G = h->G.as<double>(), *Aw = h->Aw.as<double>(), *Xt = Aw + sys.lt(), *dh = h->dh.as<double>(), *nu = h->nu.as<double>();
+    double *G = h->G.as<double>(), *Aw = h->Aw.as<double>(), *Xt = Aw ? Aw + sys.lt() : nullptr, *dh = h->dh.as<double>(), *nu = h->nu.as<double>();
     double *PX = h->PX.as<double>(), *U = h->U.as<double>(), *red = h->red.as<double>(), *mu = h->mu.as<double>();
     int32_t *flags = h->flags.as<int32_t>();
     hipStream_t st = ctx->stream;
@@ -596,16 +661,25 @@ int gingr_bcpd_iterate(gingr_bcpd *h, int32_t n_iterations) {
         hipLaunchKernelGGL(bcpd_rows_finish_kernel, dim3(gM), dim3(256), 0, st, M, ws, (int)h->row.count, h->Y.as<double>(), params, sc, nu, PX,
                            h->Rr.as<double>(), dh);
         // 2  deformation
-        hipLaunchKernelGGL(bcpd_kr_kernel, dim3(gM16), dim3(256), 0, st, M, Mp, G, h->lambda, h->Rr.as<double>(), dh, h->Z.as<double>(),
-                           h->B.as<double>());
-        launch_spd_system(st, (int)M, sys, BcpdSystemElem{G, dh, M, h->lambda}, SpdIdentityBorder{}, Aw, flags);
-        dense_spd_inverse(ctx, Aw, Mp, h->Linv.as<double>(), nullptr, flags);
-        hipLaunchKernelGGL(bcpd_forward_kernel, dim3((unsigned)(Mp / 32)), dim3(256), 0, st, Mp, Xt, h->B.as<double>(), h->Wv.as<double>());
-        hipLaunchKernelGGL(bcpd_backward_kernel, dim3((unsigned)ceil_div(Mp, 16)), dim3(256), 0, st, Mp, Xt, h->Wv.as<double>(), h->Q.as<double>());
-        hipLaunchKernelGGL(bcpd_deform_kernel, dim3(gM16), dim3(256), 0, st, M, Mp, G, h->lambda, h->Q.as<double>(), dh, h->Z.as<double>(),
-                           h->Y.as<double>(), params, sc, h->V.as<double>(), U);
-        hipLaunchKernelGGL(bcpd_sigma_tiles_kernel, dim3((unsigned)nb, (unsigned)nb), dim3(256), 0, st, Xt, Mp, G, M, dh, h->lambda, ws);
-        hipLaunchKernelGGL(bcpd_sigma_finish_kernel, dim3(gM), dim3(256), 0, st, M, Mp, G, h->lambda, ws, nb, h->sig.as<double>());
+        if (h->lowrank) {
+            BcpdLowRank &lr = *h->lowrank;
+            const double *Xl = bcpd_lowrank_system(ctx, lr, nu, h->Rr.as<double>(), h->Z.as<double>(), params, sc, h->lambda, flags);
+            hipLaunchKernelGGL(bcpd_forward_kernel, dim3((unsigned)(lr.plan.kp / 32)), dim3(256), 0, st, (int64_t)lr.plan.kp, Xl,
+                               lr.svec.as<double>(), h->Wv.as<double>());
+            bcpd_lowrank_deform(ctx, lr, Xl, h->Wv.as<double>(), h->Y.as<double>(), params, sc, h->lambda, h->V.as<double>(), U,
+                                h->sig.as<double>());
+        } else {
+            hipLaunchKernelGGL(bcpd_kr_kernel, dim3(gM16), dim3(256), 0, st, M, Mp, G, h->lambda, h->Rr.as<double>(), dh, h->Z.as<double>(),
+                               h->B.as<double>());
+            launch_spd_system(st, (int)M, sys, BcpdSystemElem{G, dh, M, h->lambda}, SpdIdentityBorder{}, Aw, flags);
+            dense_spd_inverse(ctx, Aw, Mp, h->Linv.as<double>(), nullptr, flags);
+            hipLaunchKernelGGL(bcpd_forward_kernel, dim3((unsigned)(Mp / 32)), dim3(256), 0, st, Mp, Xt, h->B.as<double>(), h->Wv.as<double>());
+            hipLaunchKernelGGL(bcpd_backward_kernel, dim3((unsigned)ceil_div(Mp, 16)), dim3(256), 0, st, Mp, Xt, h->Wv.as<double>(), h->Q.as<double>());
+            hipLaunchKernelGGL(bcpd_deform_kernel, dim3(gM16), dim3(256), 0, st, M, Mp, G, h->lambda, h->Q.as<double>(), dh, h->Z.as<double>(),
+                               h->Y.as<double>(), params, sc, h->V.as<double>(), U);
+            hipLaunchKernelGGL(bcpd_sigma_tiles_kernel, dim3((unsigned)nb, (unsigned)nb), dim3(256), 0, st, Xt, Mp, G, M, dh, h->lambda, ws);
+            hipLaunchKernelGGL(bcpd_sigma_finish_kernel, dim3(gM), dim3(256), 0, st, M, Mp, G, h->lambda, ws, nb, h->sig.as<double>());
+        }
         // 3  similarity
         hipLaunchKernelGGL(bcpd_sums_a_kernel, dim3(kRedBlocks), dim3(256), 0, st, M, nu, PX, U, h->sig.as<double>(), red);
         hipLaunchKernelGGL(bcpd_means_finish_kernel, dim3(1), dim3(64), 0, st, M, h->kappa, red, h->xpart.as<double>(), sc, mu);

@@ -241,7 +241,8 @@ __global__ __launch_bounds__(256) void lowrank_finish_kernel(const double *__res
 
 }  // namespace
 
-int lowrank_cpd_build(gingr_ctx *ctx, Cloud Y, double beta, double relative_tolerance, int32_t max_columns, LowRankCpd &lr) {
+int lowrank_factor_build(gingr_ctx *ctx, Cloud Y, double beta, double relative_tolerance, int32_t max_columns, const char *who,
+                         LowRankFactor &lr) {
     const int64_t M = Y.n;
     const int32_t cap = (int32_t)std::min<int64_t>(M, max_columns > 0 ? max_columns : lowrank_plan::kMaxColumns);
     int32_t k = 0;
@@ -250,7 +251,7 @@ int lowrank_cpd_build(gingr_ctx *ctx, Cloud Y, double beta, double relative_tole
         GINGR_TRY(fac.init(ctx, gpmm_factor::gaussian_specs(sqrt(2.0) * beta, 1.0), Y, false, cap));
         GINGR_TRY(fac.run_to_tolerance(relative_tolerance));
         k = fac.ks;
-        if (k < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "classic_cpd_create_lowrank: empty factor (tolerance too large)");
+        if (k < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: empty factor (tolerance too large)", who);
         const double residual = fac.htrace[(size_t)k], trace = fac.htrace[0];
         lr.residual_fraction = residual / trace;
         lr.tolerance_reached = (residual < relative_tolerance * trace || (int64_t)k == M) ? 1 : 0;
@@ -263,11 +264,17 @@ int lowrank_cpd_build(gingr_ctx *ctx, Cloud Y, double beta, double relative_tole
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     const lowrank_plan::Plan &p = lr.plan;
-    const DenseSpdWork sys(k, DenseSpdWork::kRhsRows);
     HIP_TRY(ctx, lr.gram_part.alloc((size_t)p.gram_partial_doubles() * sizeof(double)));
     HIP_TRY(ctx, lr.rhs_part.alloc((size_t)p.rhs_partial_doubles() * sizeof(double)));
     HIP_TRY(ctx, lr.S.alloc((size_t)p.kp * p.kp * sizeof(double)));
     HIP_TRY(ctx, lr.svec.alloc((size_t)3 * p.kp * sizeof(double)));
+    return GINGR_OK;
+}
+
+int lowrank_cpd_build(gingr_ctx *ctx, Cloud Y, double beta, double relative_tolerance, int32_t max_columns, LowRankCpd &lr) {
+    GINGR_TRY(lowrank_factor_build(ctx, Y, beta, relative_tolerance, max_columns, "classic_cpd_create_lowrank", lr));
+    const lowrank_plan::Plan &p = lr.plan;
+    const DenseSpdWork sys(p.k, DenseSpdWork::kRhsRows);
     HIP_TRY(ctx, lr.Aw.alloc((size_t)sys.aw_doubles() * sizeof(double)));
     HIP_TRY(ctx, lr.Linv.alloc((size_t)sys.linv_doubles() * sizeof(double)));
     HIP_TRY(ctx, lr.Z.alloc((size_t)sys.w_doubles() * sizeof(double)));
@@ -276,16 +283,21 @@ int lowrank_cpd_build(gingr_ctx *ctx, Cloud Y, double beta, double relative_tole
     return GINGR_OK;
 }
 
-void lowrank_cpd_mstep(gingr_ctx *ctx, LowRankCpd &lr, const double *P1, const double *PX, double *ty, double *scalars, double lambda,
-                       double *W, int64_t w_stride, int32_t *flag) {
+void lowrank_gram(gingr_ctx *ctx, LowRankFactor &lr, const double *P1, const double *PX, const double *ty) {
     const lowrank_plan::Plan &p = lr.plan;
-    const DenseSpdWork sys(p.k, DenseSpdWork::kRhsRows);  // sys.Mp == p.kp: both round k up to 64
-    int32_t *sysflag = lr.sysflag.as<int32_t>();
     hipLaunchKernelGGL(lowrank_gram_kernel, dim3((unsigned)p.nslabs, (unsigned)p.npairs), dim3(256), 0, ctx->stream, lr.L.as<double>(),
                        p.Mpad, p.M, p.nb, p.npairs, p.rows_per_slab, P1, PX, ty, lr.gram_part.as<double>(), lr.rhs_part.as<double>());
     const int64_t nred = (int64_t)p.npairs * kTile + (int64_t)p.nb * 3 * kBlock;
     hipLaunchKernelGGL(lowrank_reduce_kernel, dim3((unsigned)ceil_div(nred, 256)), dim3(256), 0, ctx->stream, lr.gram_part.as<double>(),
                        lr.rhs_part.as<double>(), p.nslabs, p.nb, p.npairs, p.kp, lr.S.as<double>(), lr.svec.as<double>());
+}
+
+void lowrank_cpd_mstep(gingr_ctx *ctx, LowRankCpd &lr, const double *P1, const double *PX, double *ty, double *scalars, double lambda,
+                       double *W, int64_t w_stride, int32_t *flag) {
+    const lowrank_plan::Plan &p = lr.plan;
+    const DenseSpdWork sys(p.k, DenseSpdWork::kRhsRows);  // sys.Mp == p.kp: both round k up to 64
+    int32_t *sysflag = lr.sysflag.as<int32_t>();
+    lowrank_gram(ctx, lr, P1, PX, ty);
     launch_spd_system(ctx->stream, p.k, sys, LowRankElem{lr.S.as<double>(), p.kp, scalars, lambda}, LowRankBorder{lr.svec.as<double>(), p.kp},
                       lr.Aw.as<double>(), sysflag);
     dense_spd_solve3(ctx, lr.Aw.as<double>(), sys.Mp, lr.Linv.as<double>(), lr.Z.as<double>(), sysflag);
@@ -295,7 +307,7 @@ void lowrank_cpd_mstep(gingr_ctx *ctx, LowRankCpd &lr, const double *P1, const d
                        flag);
 }
 
-int lowrank_cpd_get_factor(gingr_ctx *ctx, const LowRankCpd &lr, double *out) {
+int lowrank_cpd_get_factor(gingr_ctx *ctx, const LowRankFactor &lr, double *out) {
     const lowrank_plan::Plan &p = lr.plan;
     std::vector<double> hl((size_t)p.factor_doubles());
     HIP_TRY(ctx, hipMemcpyAsync(hl.data(), lr.L.p, hl.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

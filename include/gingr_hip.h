@@ -903,6 +903,23 @@ int gingr_bcpd_get(gingr_bcpd *h, double *yhat_xyz, double *vhat_xyz, double *si
 int gingr_bcpd_set(gingr_bcpd *h, const double *yhat_xyz, const double *sigma_diag, const double *alpha, const double *transform13,
                    double sigma2);
 
+/* Past dense sizes (the acceleration Hirose 2020 proposes): G ~ L L^T, the factor of gingr_classic_cpd_create_lowrank (the same
+ * pivoted Cholesky of the same Gaussian over the template, the same ceiling GINGR_CLASSIC_CPD_MAX_COLUMNS, the same rules for
+ * relative_tolerance and max_columns, the same info block).  With K = L L^T / lambda and c2 = s^2 / sigma2 the deformation step is
+ *     S = L^T diag(nu) L,  C = I + (c2 / lambda) S = R R^T,  v^ = (c2 / lambda) L C^-1 L^T r,  sigma_m^2 = |R^-1 l_m|^2 / lambda
+ * (l_m: row m of L), which is the step of gingr_bcpd_create with L L^T in place of G: a sum of squares, never negative, and nothing
+ * divides by nu_m.  Nothing of size M x M is formed, so the cap of 32768 does not apply: no limit on M but the card's memory (the factor
+ * takes 8 bytes x M rounded up to 32 x k rounded up to 64; the factorisation, at create time only, as much again for the columns it
+ * may reach; the pair passes keep up to 256 chunk partials of N doubles or of 4 M doubles).  Every other argument rule is
+ * gingr_bcpd_create's.
+ * The handle is a gingr_bcpd for iterate / get / set / destroy, with the same failures of gingr_bcpd_iterate.
+ * gingr_bcpd_get_factor: *columns (nullable) and L row-major [M][columns] (nullable); GINGR_ERR_BAD_ARGUMENT on a handle of
+ * gingr_bcpd_create. */
+int gingr_bcpd_create_lowrank(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, double w,
+                              double lambda, double gamma, double kappa, double beta, double relative_tolerance, int32_t max_columns,
+                              gingr_classic_cpd_lowrank_info *info, gingr_bcpd **out);
+int gingr_bcpd_get_factor(gingr_bcpd *h, int32_t *columns, double *L_rowmajor_M_by_k);
+
 /* ---- classic rigid / similarity ICP (the reference's other/ baseline) ------------------------------------------------
  * G/other/algorithms/icp/RigidICP.scala:24-84 (Iteration / Registration), ICPFactory.scala:28-38, RigidICPRegistration.scala:24-46
  * with the two registrators of G/other/utils/PoseRegistrator.scala:27-43: kind 0 = RigidRegistrator3D
