@@ -171,6 +171,9 @@ SIGNATURES = {
     "gingr_bcpd_create_lowrank": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_double, c_double, c_double, c_double, c_double, c_double,
                                           c_int32, POINTER(ClassicCpdLowRankInfo), POINTER(c_void_p)]),
     "gingr_bcpd_get_factor": (c_int, [c_void_p, _ip, _dp]),
+    "gingr_classic_cpd_transform_points": (c_int, [c_void_p, c_int64, _dp, _dp]),
+    "gingr_bcpd_transform_points": (c_int, [c_void_p, c_int64, _dp, _dp]),
+    "gingr_bcpd_get_coefficients": (c_int, [c_void_p, _dp]),
     "gingr_mesh_distance_stats": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_int64, POINTER(c_int32), c_int32, c_double, _dp]),
     "gingr_fitter_update_icp_surface_sample_async": (c_int, [c_void_p, POINTER(IcpParams), _dp]),
     "gingr_fitter_posterior_logpdf_icp_surface": (c_int, [c_void_p, POINTER(IcpParams), _dp, POINTER(c_double)]),

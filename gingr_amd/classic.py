@@ -20,6 +20,15 @@ from ._native import f64, dptr
 RIGID, AFFINE, NONRIGID = 0, 1, 2
 
 
+def _transform_points(ctx: Context, entry, handle, points, name: str) -> np.ndarray:
+    pts = f64(points)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points: (P, 3) expected")
+    out = np.empty_like(pts)
+    _check(ctx.handle, entry(handle, pts.shape[0], dptr(pts), dptr(out)), name)
+    return out
+
+
 class LowRankG:
     """The non-rigid kind over a low-rank factor of the kernel matrix, G ~ L L^T (Myronenko & Song 2010, "fast implementation"):
     the pivoted Cholesky of the Gaussian over the template, stopped when the residual trace falls below relativeTolerance * trace or
@@ -103,6 +112,15 @@ class RigidCPD:
         _check(self.cpd.ctx.handle, self._lib.gingr_classic_cpd_get_factor(self._h, None, dptr(L)), "gingr_classic_cpd_get_factor")
         return L
 
+    def transformPoints(self, points) -> np.ndarray:
+        """The map of the last Iteration at any points (P, 3), on the device (csrc/kernel_warp.hip).  Rigid / affine: s B z + t with
+        transform(); non-rigid: z + sum_m g(z, y_m) W_m with y the factory's template, W() and the true Gaussian -- at the template
+        points the TY of an Iteration that started from the template (low-rank: to the factor's tolerance).  As transform() and W(),
+        it is the last step alone: Registration feeds TY back into the next Iteration.  GINGR_ERR_STATE before the first Iteration
+        and after set_state."""
+        return _transform_points(self.cpd.ctx, self._lib.gingr_classic_cpd_transform_points, self._h, points,
+                                 "gingr_classic_cpd_transform_points")
+
     # -- the reference surface ------------------------------------------------------------------------------------
     def Iteration(self, Y=None, sigma2: Optional[float] = None) -> Tuple[np.ndarray, float]:
         """Iteration(X, Y, sigma2) (RigidCPD.scala:85-88) = Maximization(Expectation(...)); without arguments it advances the
@@ -155,7 +173,12 @@ class CPDFactory:
 
 class RigidCPDRegistration:
     """RigidCPDRegistration / NonRigidCPDRegistration / AffineCPDRegistration (CPDRegistration.scala:23-73): register(target)
-    returns the warped template points."""
+    returns the warped template points; register(target, points) the pair (warped template, transformPoints(points)) of the task.
+    The two do not correspond once Registration has taken more than one Iteration: the first is the whole registration, the second
+    the map of its LAST Iteration alone (the reference feeds TY back, and transform() / W() / transformPoints are one step's; close to
+    the identity at convergence).  To carry a whole classic registration to other points, take the Iterations one by one and compose
+    the rigid / affine steps, or add up the non-rigid steps' displacements transformPoints(points) - points (G is fixed over the
+    template, TY = Y + G sum_i W_i) as examples/demo_classic_cpd.py does; BCPDRegistration.register(target, points) is the whole map."""
 
     _kind = RIGID
 
@@ -165,10 +188,11 @@ class RigidCPDRegistration:
             raise ValueError("lowRank applies to the non-rigid kind only")
         self.cpd, self.max_iterations, self.lowRank = CPDFactory(ctx, template, lambda_, beta, w), max_iterations, lowRank
 
-    def register(self, target) -> np.ndarray:
+    def register(self, target, points=None):
         task = RigidCPD(self.cpd, target, self._kind, self.lowRank)
         try:
-            return task.Registration(self.max_iterations)
+            warped = task.Registration(self.max_iterations)
+            return warped if points is None else (warped, task.transformPoints(points))
         finally:
             task.close()
 
@@ -285,6 +309,19 @@ class BCPD:
         self._get(None, None, None, None, dptr(nu), dptr(nup), None, None)
         return nu, nup
 
+    def transformPoints(self, points) -> np.ndarray:
+        """The map of the last iteration at any points (P, 3), on the device (csrc/kernel_warp.hip):
+        s R (z + sum_m g(z, y_m) c_m) + t with c = deformationCoefficients() -- the Gaussian-process posterior mean of the
+        displacement field at z (the interpolation step of BCPD++, Hirose 2021), then the similarity; at the template points it is
+        points().  GINGR_ERR_STATE before the first iteration and after set_state."""
+        return _transform_points(self.ctx, self._lib.gingr_bcpd_transform_points, self._h, points, "gingr_bcpd_transform_points")
+
+    def deformationCoefficients(self) -> np.ndarray:
+        """c (M, 3) with vhat = G c (low-rank: L L^T c): (c2 / lambda) (r - nu o vhat) of the last iteration"""
+        c = np.empty((self.M, 3))
+        _check(self.ctx.handle, self._lib.gingr_bcpd_get_coefficients(self._h, dptr(c)), "gingr_bcpd_get_coefficients")
+        return c
+
     # -- the reference surface ------------------------------------------------------------------------------------
     def Iteration(self) -> Tuple[np.ndarray, float]:
         _check(self.ctx.handle, self._lib.gingr_bcpd_iterate(self._h, 1), "gingr_bcpd_iterate")
@@ -312,17 +349,21 @@ class BCPD:
 
 
 class BCPDRegistration:
-    """BCPDRegistration.scala with its defaults: register(target) returns the warped template points."""
+    """BCPDRegistration.scala with its defaults: register(target) returns the warped template points; register(target, points) the
+    pair (warped template, transformPoints(points)) of the task -- here the two correspond: y^ = s R (y + v^) + t starts from the template
+    in every iteration, so the last iteration's map is the whole registration (unlike the classic wrappers, whose second value is the
+    last step alone)."""
 
     def __init__(self, ctx: Context, template, w: float = 0.0, lambda_: float = 2.0, gamma: float = 1.0, k: float = 1.0, beta: float = 2.0,
                  max_iterations: int = 100, lowRank: Optional[LowRankG] = None):
         self.ctx, self.template, self.max_iterations, self.lowRank = ctx, f64(template), max_iterations, lowRank
         self.w, self.lambda_, self.gamma, self.k, self.beta = w, lambda_, gamma, k, beta
 
-    def register(self, target) -> np.ndarray:
+    def register(self, target, points=None):
         task = BCPD(self.ctx, self.template, target, self.w, self.lambda_, self.gamma, self.k, self.beta, self.lowRank)
         try:
-            return task.Registration(self.max_iterations)
+            warped = task.Registration(self.max_iterations)
+            return warped if points is None else (warped, task.transformPoints(points))
         finally:
             task.close()
 

@@ -22,6 +22,7 @@
 #include "cloud_sums.h"
 #include "dense_spd.h"
 #include "fastexp.h"
+#include "kernel_warp.h"
 #include "svd3.h"
 
 #include <algorithm>
@@ -39,7 +40,7 @@ typedef double bcpd_v4f64 __attribute__((ext_vector_type(4)));
 
 Cloud cloud_at(const double *soa, int64_t n) { return Cloud{soa, soa + n, soa + 2 * n, n}; }
 
-// device scalars: sc[0] sigma2, [1] N^, [2] sbar2, [3] xPx;  params: s, R row-major, t;  mu: xbar, ubar, [6] psi(kappa M + N^)
+// device scalars: sc[0] sigma2, [1] N^, [2] sbar2, [3] xPx, [5] the c2 = s^2 / sigma2 that went into the last iteration;  params: s, R row-major, t;  mu: xbar, ubar, [6] psi(kappa M + N^)
 
 // a_m = (1 - w) <alpha_m> exp(-1.5 s^2 sigma_m^2 / sigma2)
 __global__ __launch_bounds__(256) void bcpd_weights_kernel(int64_t M, double w, const double *__restrict__ alpha, const double *__restrict__ sig,
@@ -195,13 +196,15 @@ __global__ __launch_bounds__(256) void bcpd_rowstats_kernel(Cloud Yh, Cloud X, c
     }
 }
 
-// nu_m, PX_m from the chunk partials; r_m = (1 / s) R^T (PX_m - nu_m t) - nu_m y_m; dh_m = (c2 nu_m)^1/2
+// nu_m, PX_m from the chunk partials; r_m = (1 / s) R^T (PX_m - nu_m t) - nu_m y_m; dh_m = (c2 nu_m)^1/2; *c2_keep = c2 (the end of the
+// iteration overwrites s and sigma2: the coefficients of the kernel warp need the c2 that went in)
 __global__ __launch_bounds__(256) void bcpd_rows_finish_kernel(int64_t M, const double *__restrict__ part, int chunks, const double *__restrict__ y,
                                                                const double *__restrict__ params, const double *__restrict__ sc,
                                                                double *__restrict__ nu, double *__restrict__ PX, double *__restrict__ r,
-                                                               double *__restrict__ dh) {
+                                                               double *__restrict__ dh, double *c2_keep) {  // (c2_keep points into sc's buffer)
     const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
+    if (m == 0) *c2_keep = params[0] * params[0] / sc[0];
     double v[4] = {0, 0, 0, 0};
     for (int ch = 0; ch < chunks; ++ch)
 #pragma unroll
@@ -252,6 +255,17 @@ __global__ __launch_bounds__(256) void bcpd_deform_kernel(int64_t M, int64_t Mp,
             u[d * M + m] = y[d * M + m] + v;
         }
     }
+}
+
+// The coefficients of the kernel warp: c = (c2 / lambda) (r - nu o v^), so that v^ = G c (Sigma^-1 v^ = c2 r with
+// Sigma^-1 = lambda G^-1 + c2 diag nu; L L^T in place of G on the low-rank route) -- no inverse of G, no division by nu_m
+__global__ __launch_bounds__(256) void bcpd_coefficients_kernel(int64_t M, double lambda, const double *__restrict__ sc,
+                                                                const double *__restrict__ r, const double *__restrict__ nu,
+                                                                const double *__restrict__ vhat, double *__restrict__ c) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    const double f = sc[5] / lambda, p = nu[m];
+    for (int d = 0; d < 3; ++d) c[d * M + m] = f * (r[d * M + m] - p * vhat[d * M + m]);
 }
 
 struct BcpdSystemElem {  // I + D^1/2 K D^1/2
@@ -474,6 +488,11 @@ struct gingr_bcpd {
     BcpdChunks col{1, kBcpdTile}, row{1, kBcpdTile};
     DevBuf X, Y, Yh, V, U, PX, Rr, Z, B, Wv, Q, sig, alpha, a, nu, dh, nup, inv, ws, xpart, red, mu, params, sc, aux, flags, G, Aw, Linv, stage;
     std::unique_ptr<BcpdLowRank> lowrank;  // gingr_bcpd_create_lowrank: G, Aw, Linv, B and Q stay empty, Z stays zero
+    // the kernel warp (gingr_bcpd_transform_points): the map belongs to the last successful iteration; C, its coefficients, is formed on
+    // the first query after it
+    bool map_valid = false, coeff_ready = false;
+    DevBuf C;
+    KernelWarpWork warp;
 };
 
 // what gingr_bcpd_create_lowrank adds to the arguments of gingr_bcpd_create
@@ -647,6 +666,7 @@ int gingr_bcpd_iterate(gingr_bcpd *h, int32_t n_iterations) {
     int32_t *flags = h->flags.as<int32_t>();
     hipStream_t st = ctx->stream;
     const unsigned gM = (unsigned)ceil_div(M, 256), gM16 = (unsigned)ceil_div(M, 16);
+    if (n_iterations > 0) h->map_valid = h->coeff_ready = false;
     for (int32_t it = 0; it < n_iterations; ++it) {
         // 1  soft assignment
         launch_cloud_absmax(ctx, Yh, aux + 2, aux + 1);
@@ -659,7 +679,7 @@ int gingr_bcpd_iterate(gingr_bcpd *h, int32_t n_iterations) {
         hipLaunchKernelGGL(bcpd_rowstats_kernel, dim3((unsigned)ceil_div(M, kBcpdTile), (unsigned)h->row.count), dim3(256), 0, st, Yh, X,
                            h->a.as<double>(), h->inv.as<double>(), sc, aux, h->row.length, ws);
         hipLaunchKernelGGL(bcpd_rows_finish_kernel, dim3(gM), dim3(256), 0, st, M, ws, (int)h->row.count, h->Y.as<double>(), params, sc, nu, PX,
-                           h->Rr.as<double>(), dh);
+                           h->Rr.as<double>(), dh, sc + 5);
         // 2  deformation
         if (h->lowrank) {
             BcpdLowRank &lr = *h->lowrank;
@@ -690,7 +710,49 @@ int gingr_bcpd_iterate(gingr_bcpd *h, int32_t n_iterations) {
         hipLaunchKernelGGL(bcpd_shape_kernel, dim3(kRedBlocks), dim3(256), 0, st, M, U, params, nu, PX, h->Yh.as<double>(), red);
         hipLaunchKernelGGL(bcpd_variance_kernel, dim3(1), dim3(64), 0, st, red, params, sc, flags);
     }
-    return finish_iterate(ctx, flags, 2, 1, "bcpd_iterate");
+    const int rc = finish_iterate(ctx, flags, 2, 1, "bcpd_iterate");
+    if (rc == GINGR_OK && n_iterations > 0) h->map_valid = true;
+    return rc;
+}
+
+// the coefficients of the last iteration in h->C (three planes of stride M), formed once
+static int bcpd_coefficients(gingr_bcpd *h, const char *name) {
+    gingr_ctx *ctx = h->ctx;
+    if (!h->map_valid) return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: no successful iteration since the state was created or set", name);
+    if (h->coeff_ready) return GINGR_OK;
+    const int64_t M = h->M;
+    if (!h->C.p && h->C.alloc((size_t)3 * M * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        h->C.release();
+        return gingr_set_error(ctx, GINGR_ERR_HIP, "%s: out of device memory", name);
+    }
+    hipLaunchKernelGGL(bcpd_coefficients_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, h->lambda, h->sc.as<double>(),
+                       h->Rr.as<double>(), h->nu.as<double>(), h->V.as<double>(), h->C.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    h->coeff_ready = true;
+    return GINGR_OK;
+}
+
+int gingr_bcpd_get_coefficients(gingr_bcpd *h, double *c_xyz) {
+    if (!h) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = h->ctx;
+    if (!c_xyz) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_get_coefficients: null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    GINGR_TRY(bcpd_coefficients(h, "bcpd_get_coefficients"));
+    return download_cloud(ctx, h->stage.as<double>(), h->C.as<double>(), h->M, c_xyz);
+}
+
+int gingr_bcpd_transform_points(gingr_bcpd *h, int64_t P, const double *points_xyz, double *out_xyz) {
+    if (!h) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = h->ctx;
+    if (P < 0 || (P > 0 && (!points_xyz || !out_xyz))) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "bcpd_transform_points: bad argument");
+    if (P == 0) return GINGR_OK;  // (whatever the state: nothing is asked for)
+    if (!h->map_valid)
+        return gingr_set_error(ctx, GINGR_ERR_STATE, "bcpd_transform_points: no successful iteration since the state was created or set");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    GINGR_TRY(bcpd_coefficients(h, "bcpd_transform_points"));
+    return kernel_warp_points(ctx, h->warp, cloud_at(h->Y.as<double>(), h->M), h->C.as<double>(), h->M, h->beta, h->params.as<double>(), false, P,
+                              points_xyz, out_xyz);
 }
 
 int gingr_bcpd_get(gingr_bcpd *h, double *yhat_xyz, double *vhat_xyz, double *sigma_diag, double *alpha, double *nu, double *nu_prime,
@@ -721,6 +783,7 @@ int gingr_bcpd_set(gingr_bcpd *h, const double *yhat_xyz, const double *sigma_di
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t M = h->M;
     hipStream_t st = ctx->stream;
+    h->map_valid = h->coeff_ready = false;
     if (yhat_xyz) GINGR_TRY(upload_cloud(ctx, h->stage.as<double>(), yhat_xyz, M, h->Yh.as<double>()));
     if (sigma_diag) HIP_TRY(ctx, hipMemcpyAsync(h->sig.p, sigma_diag, (size_t)M * sizeof(double), hipMemcpyHostToDevice, st));
     if (alpha) HIP_TRY(ctx, hipMemcpyAsync(h->alpha.p, alpha, (size_t)M * sizeof(double), hipMemcpyHostToDevice, st));

@@ -18,6 +18,7 @@
 #include "cloud_sums.h"
 #include "classic_cpd_lowrank.h"
 #include "dense_spd.h"
+#include "kernel_warp.h"
 #include "svd3.h"
 
 #include <algorithm>
@@ -202,6 +203,11 @@ struct gingr_classic_cpd {
     double lambda = 2.0, beta = 2.0, w = 0.0;
     DevBuf X, TY, den, inv_den, Pt1, P1, PX, ws, part, sc, aux, red, mu, params, flag, G, Aw, Linv, W, stage;
     std::unique_ptr<LowRankCpd> lowrank;  // gingr_classic_cpd_create_lowrank: G, Aw and Linv stay empty
+    // the kernel warp (gingr_classic_cpd_transform_points): the map belongs to the last successful iteration; Y0 (non-rigid kind): the
+    // template as it was given, the centres of the Gaussian -- TY moves
+    bool map_valid = false;
+    DevBuf Y0;
+    KernelWarpWork warp;
 };
 
 static_assert(GINGR_CLASSIC_CPD_MAX_COLUMNS == lowrank_plan::kMaxColumns, "the header's ceiling is the plan's");
@@ -268,6 +274,10 @@ static int classic_cpd_create_impl(gingr_ctx *ctx, int32_t kind, int64_t M, cons
     HANDLE_TRY(ctx, fail, hipMemsetAsync(h->flag.p, 0, sizeof(int32_t), ctx->stream));
     if (int rc = upload_cloud(ctx, h->stage.as<double>(), target_xyz, N, h->X.as<double>())) return fail(rc);
     if (int rc = upload_cloud(ctx, h->stage.as<double>(), template_xyz, M, h->TY.as<double>())) return fail(rc);
+    if (kind == 2) {
+        HANDLE_TRY(ctx, fail, h->Y0.alloc((size_t)3 * M * sizeof(double)));
+        HANDLE_TRY(ctx, fail, hipMemcpyAsync(h->Y0.p, h->TY.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
     const Cloud X = cloud_at(h->X.as<double>(), N), Y = cloud_at(h->TY.as<double>(), M);
     double *aux = h->aux.as<double>();
     launch_cloud_centroid(ctx, X, aux + 2);
@@ -343,6 +353,7 @@ int gingr_classic_cpd_iterate(gingr_classic_cpd *h, int32_t n_iterations) {
     const Cloud X = cloud_at(h->X.as<double>(), N), Y = cloud_at(h->TY.as<double>(), M);
     double *sc = h->sc.as<double>(), *s2 = sc + 8, *aux = h->aux.as<double>(), *ty = h->TY.as<double>();
     int32_t *flag = h->flag.as<int32_t>();
+    if (n_iterations > 0) h->map_valid = false;
     for (int32_t it = 0; it < n_iterations; ++it) {
         // Expectation (RigidCPD.scala:90-105) as streaming statistics: P1, Pt1, P X, Np, xPx
         launch_cloud_absmax(ctx, Y, aux + 2, aux + 1);
@@ -375,7 +386,26 @@ int gingr_classic_cpd_iterate(gingr_classic_cpd *h, int32_t n_iterations) {
             hipLaunchKernelGGL(nonrigid_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, h->red.as<double>(), sc, flag);
         }
     }
-    return finish_iterate(ctx, flag, 1, 0, "classic_cpd_iterate");
+    const int rc = finish_iterate(ctx, flag, 1, 0, "classic_cpd_iterate");
+    if (rc == GINGR_OK && n_iterations > 0) h->map_valid = true;
+    return rc;
+}
+
+int gingr_classic_cpd_transform_points(gingr_classic_cpd *h, int64_t P, const double *points_xyz, double *out_xyz) {
+    if (!h) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = h->ctx;
+    if (P < 0 || (P > 0 && (!points_xyz || !out_xyz)))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "classic_cpd_transform_points: bad argument");
+    if (P == 0) return GINGR_OK;  // (whatever the state: nothing is asked for)
+    if (!h->map_valid)
+        return gingr_set_error(ctx, GINGR_ERR_STATE, "classic_cpd_transform_points: no successful iteration since the state was created or set");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (h->kind != 2)  // T(z) = s B z + t
+        return kernel_warp_points(ctx, h->warp, Cloud{nullptr, nullptr, nullptr, 0}, nullptr, 0, h->beta, h->params.as<double>(), true, P,
+                                  points_xyz, out_xyz);
+    // T(z) = z + sum_m g(z, y_m) W_m
+    return kernel_warp_points(ctx, h->warp, cloud_at(h->Y0.as<double>(), h->M), h->W.as<double>(), h->Mp, h->beta, nullptr, false, P, points_xyz,
+                              out_xyz);
 }
 
 int gingr_classic_cpd_get(gingr_classic_cpd *h, double *ty_xyz, double *sigma2, double *transform13, double *w_xyz) {
@@ -402,6 +432,7 @@ int gingr_classic_cpd_set(gingr_classic_cpd *h, const double *ty_xyz, double sig
     if (!h) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = h->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    h->map_valid = false;
     if (ty_xyz) GINGR_TRY(upload_cloud(ctx, h->stage.as<double>(), ty_xyz, h->M, h->TY.as<double>()));
     HIP_TRY(ctx, hipMemcpyAsync(h->sc.as<double>() + 8, &sigma2, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -920,6 +920,32 @@ int gingr_bcpd_create_lowrank(gingr_ctx *ctx, int64_t M, const double *moving_xy
                               gingr_classic_cpd_lowrank_info *info, gingr_bcpd **out);
 int gingr_bcpd_get_factor(gingr_bcpd *h, int32_t *columns, double *L_rowmajor_M_by_k);
 
+/* ---- the fitted map at points off the template (kernel_warp.hip; BCPD++'s interpolation step, pycpd's transform_point_cloud) ----
+ * With Y the task's original template (moving_xyz), g(a, b) = exp(-|a - b|^2 / (2 beta^2)) the task's Gaussian and z any point:
+ *   rigid / affine CPD (kinds 0, 1)   T(z) = s B z + t, (s, B, t) the transform13 of the last Maximization;
+ *   non-rigid CPD, dense and low-rank T(z) = z + sum_m g(z, y_m) W_m, W the w_xyz of gingr_classic_cpd_get (low-rank: the W of the
+ *                                     comment above).  The sum uses the true Gaussian, not L L^T: on the dense route T(y_m) is the
+ *                                     TY_m of a Maximization that started at Y, to rounding; on the low-rank route
+ *                                     T(y_m) - TY_m = ((G - L L^T) W)_m, which follows the factor's tolerance;
+ *   BCPD, dense and low-rank          T(z) = s R (z + sum_m g(z, y_m) c_m) + t, (s, R, t) of the state after the iteration and
+ *                                     c = (c2 / lambda) (r - nu o v^), c2 = s^2 / sigma2 and r those that went into the iteration:
+ *                                     Sigma^-1 v^ = c2 r with Sigma^-1 = lambda G^-1 + c2 diag nu gives v^ = G c (L L^T in place
+ *                                     of G on the low-rank route), so c needs no inverse of G and no division by nu_m, and
+ *                                     g(z, Y) c is the Gaussian-process posterior mean of the displacement at z; T(y_m) = y^_m.
+ * As transform13 and w_xyz, the map is the LAST iteration's: the classic kinds feed TY back into the next iteration, so after
+ * several iterations their T is the last step of the composition, not the whole of it.
+ * The entries return GINGR_ERR_STATE before any iteration, after gingr_*_set with no iteration since, and after an iteration that
+ * failed.  points_xyz, out_xyz: [3 P] interleaved host arrays, P limited by memory alone; they may be the same array.  P = 0 succeeds
+ * and touches nothing, in any state; P < 0 or a NULL pointer with P > 0: GINGR_ERR_BAD_ARGUMENT.  A point's image depends on that point and the
+ * handle's state alone -- not on P or on the other points of the call -- and two calls give the same bits: the sum over the centres
+ * is taken in chunks whose boundaries depend on M alone, added in chunk order.  A kernel entry g(z, y_m) has the bits of the dense
+ * route's G where z = y_m'.  The points pass through the device in slabs of at most 2^20; the handle keeps the buffers of its largest
+ * call (two slabs of points and the chunk partials, at most 128 MiB unless 256 points need more) until it is destroyed.
+ * gingr_bcpd_get_coefficients: c [3 M] interleaved, formed on the first query after an iteration. */
+int gingr_classic_cpd_transform_points(gingr_classic_cpd *h, int64_t P, const double *points_xyz, double *out_xyz);
+int gingr_bcpd_transform_points(gingr_bcpd *h, int64_t P, const double *points_xyz, double *out_xyz);
+int gingr_bcpd_get_coefficients(gingr_bcpd *h, double *c_xyz);
+
 /* ---- classic rigid / similarity ICP (the reference's other/ baseline) ------------------------------------------------
  * G/other/algorithms/icp/RigidICP.scala:24-84 (Iteration / Registration), ICPFactory.scala:28-38, RigidICPRegistration.scala:24-46
  * with the two registrators of G/other/utils/PoseRegistrator.scala:27-43: kind 0 = RigidRegistrator3D
