@@ -21,7 +21,14 @@ NUM_PHASES = 3
 NUM_SEGMENTS = 2
 SEGMENT_FULLFIT = 2   # the gather of a sharded surface update (gingr_hip.h)
 SEGMENT_REVSUM = 3    # per-template-vertex sums of the sharded reversed correspondence direction
-FLAVOUR_CPD, FLAVOUR_ICP, FLAVOUR_ICP_SURFACE = 0, 1, 2
+FLAVOUR_CPD, FLAVOUR_ICP, FLAVOUR_ICP_SURFACE, FLAVOUR_PAIRS = 0, 1, 2, 3   # enum Flavour of gingr_amd/csrc/correspondence.h
+# flavour -> the entry points named after it, indexed by OP_*; each takes (fitter, [the flavour's parameter struct,] the operation's own)
+OP_UPDATE, OP_UPDATE_SAMPLE, OP_LOGPDF, OP_POSTERIOR_COVARIANCE, OP_POSTERIOR_MODEL = range(5)
+FITTER_OPS = {
+    flavour: tuple("gingr_fitter_" + op.format(name) for op in
+                   ("update_{}_async", "update_{}_sample_async", "posterior_logpdf_{}", "posterior_covariance_{}", "posterior_model_{}"))
+    for flavour, name in ((FLAVOUR_CPD, "cpd"), (FLAVOUR_ICP, "icp"), (FLAVOUR_ICP_SURFACE, "icp_surface"), (FLAVOUR_PAIRS, "pairs"))
+}
 RCCL_UNIQUE_ID_BYTES = 128
 
 _STATUS_NAMES = {

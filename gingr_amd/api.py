@@ -1191,6 +1191,7 @@ class GingrAlgorithm:
         self._device_state = None         # the python state currently mirrored on the device (strong reference, compared with `is`)
         self._mh = None                   # fused Metropolis-Hastings steps: {"sdev", "points"} of the likelihood evaluated with them
         self._mh_last = None              # what the last fused step measured: {"from", "to", "stats", "fw", "bw"}
+        self._plan_memo = None            # (config object, what _correspondence said about it + the argument its entry points take)
         self._mh_plan_memo = None         # (config object, what _mh_flavour said about it + ctypes pointers)
         self._mh_req = None               # the request / result structs of the fused step, reused (the call is synchronous)
         self._sel = {}                    # selections already made on the current fitter (options, direction, surface method): set again only when they change
@@ -1291,14 +1292,48 @@ class GingrAlgorithm:
         return dataclasses.replace(general, modelParameters=mp, fit=fit, sigma2=s.sigma2, iteration=s.iteration,
                                    status=s.status, generatedBy=self.name)
 
-    def _native_update(self, current, n: int):
+    # -- the correspondence flavour: what a sub-class says once, and the five operations named after it ------------------------------
+    def _correspondence(self, state):
+        """(flavour, its parameter struct or None): enum Flavour of gingr_amd/csrc/correspondence.h"""
         raise NotImplementedError
+
+    def _prepare_native(self, state):
+        """selections on the fitter that the flavour's entry points read (direction, surface method, the caller's pairs)"""
+
+    def _plan(self, state):
+        """_correspondence(state) and the parameter argument of its entry points, remembered for the configuration OBJECT (frozen
+        dataclasses shared by all the states of a run)"""
+        c = state.config
+        memo = self._plan_memo
+        if memo is not None and memo[0] is c:
+            return memo[1]
+        flavour, p = self._correspondence(state)
+        plan = (flavour, p, () if p is None else (ctypes.byref(p),))
+        self._plan_memo = (c, plan)
+        return plan
+
+    def _native(self, state, op: int, *args):
+        self._prepare_native(state)
+        flavour, _, p = self._plan(state)
+        name = nat.FITTER_OPS[flavour][op]
+        _check(self.ctx.handle, getattr(self._lib, name)(self._fitter, *p, *args), name)
+
+    def _native_update(self, current, n: int):
+        self._native(current, nat.OP_UPDATE, n)
+
+    def _native_update_sample(self, current, z: np.ndarray):
+        self._native(current, nat.OP_UPDATE_SAMPLE, dptr(z))
+
+    def _native_logpdf(self, state, mesh: np.ndarray) -> float:
+        out = ctypes.c_double()
+        self._native(state, nat.OP_LOGPDF, dptr(mesh), ctypes.byref(out))
+        return out.value
 
     def _native_posterior_covariance(self, state, out: np.ndarray):
-        raise NotImplementedError
+        self._native(state, nat.OP_POSTERIOR_COVARIANCE, dptr(out))
 
     def _native_posterior_model(self, state, out):
-        raise NotImplementedError
+        self._native(state, nat.OP_POSTERIOR_MODEL, ctypes.byref(out))
 
     # -- the reference surface ----------------------------------------------------------------
     def initializeState(self, general: GeneralRegistrationState, config):
@@ -1343,11 +1378,12 @@ class GingrAlgorithm:
         self._mh = self._mh_last = None
 
     def _mh_flavour(self, state):
-        """(flavour, CpdParams | None, IcpParams | None) of gingr_mh_request; None when this configuration has no fused step"""
-        return None
-
-    def _mh_prepare(self, state):
-        pass
+        """(flavour, CpdParams | None, IcpParams | None) of gingr_mh_request, a view of _correspondence; None when this configuration has
+        no fused step: the pairs come from the host, and the reversed direction keeps the call-by-call path"""
+        flavour, p, _ = self._plan(state)
+        if flavour == nat.FLAVOUR_PAIRS or getattr(state.config, "reverseCorrespondenceDirection", False):
+            return None
+        return (flavour, p, None) if flavour == nat.FLAVOUR_CPD else (flavour, None, p)
 
     def _mh_plan(self, state):
         """_mh_flavour(state) with its ctypes pointers, remembered for the configuration OBJECT (frozen dataclasses shared by all the
@@ -1386,7 +1422,7 @@ class GingrAlgorithm:
             else:
                 self._push_state(g)
             self._device_state = current
-        self._mh_prepare(current)
+        self._prepare_native(current)
         flavour, _, _, cpp, ipp = self._mh_plan(current)
         if self._mh_req is None:
             self._mh_req = (nat.MhRequest(), nat.MhResult())
@@ -1647,35 +1683,8 @@ class CpdRegistration(GingrAlgorithm):
             s2 = self.ctx.cpd_initial_sigma2(mean_pts, general.target)
         return CpdRegistrationState(general.updateSigma2(s2), config)
 
-    def _native_update(self, current: CpdRegistrationState, n: int):
-        p = nat.CpdParams(current.config.w, current.config.lambda_)
-        _check(self.ctx.handle, self._lib.gingr_fitter_update_cpd_async(self._fitter, ctypes.byref(p), n),
-               "gingr_fitter_update_cpd_async")
-
-    def _mh_flavour(self, state: CpdRegistrationState):
-        return 0, nat.CpdParams(state.config.w, state.config.lambda_), None
-
-    def _native_update_sample(self, current: CpdRegistrationState, z: np.ndarray):
-        p = nat.CpdParams(current.config.w, current.config.lambda_)
-        _check(self.ctx.handle, self._lib.gingr_fitter_update_cpd_sample_async(self._fitter, ctypes.byref(p), dptr(z)),
-               "gingr_fitter_update_cpd_sample_async")
-
-    def _native_logpdf(self, state: CpdRegistrationState, mesh: np.ndarray) -> float:
-        p = nat.CpdParams(state.config.w, state.config.lambda_)
-        out = ctypes.c_double()
-        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_logpdf_cpd(self._fitter, ctypes.byref(p), dptr(mesh),
-                                                                             ctypes.byref(out)), "gingr_fitter_posterior_logpdf_cpd")
-        return out.value
-
-    def _native_posterior_covariance(self, state: CpdRegistrationState, out: np.ndarray):
-        p = nat.CpdParams(state.config.w, state.config.lambda_)
-        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_covariance_cpd(self._fitter, ctypes.byref(p), dptr(out)),
-               "gingr_fitter_posterior_covariance_cpd")
-
-    def _native_posterior_model(self, state: CpdRegistrationState, out):
-        p = nat.CpdParams(state.config.w, state.config.lambda_)
-        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_model_cpd(self._fitter, ctypes.byref(p), ctypes.byref(out)),
-               "gingr_fitter_posterior_model_cpd")
+    def _correspondence(self, state: CpdRegistrationState):
+        return nat.FLAVOUR_CPD, nat.CpdParams(state.config.w, state.config.lambda_)
 
     # plugin accessors served from one streaming evaluation (the reference recomputes P for each of them)
     def _stats(self, state: CpdRegistrationState) -> dict:
@@ -1727,14 +1736,10 @@ class IcpRegistration(GingrAlgorithm):
         self._bind(g, c.useLandmarkCorrespondence)
         self._push_state(g)
         self._device_state = None
-        self._select_direction(c)
-        p = nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
-        if self._surface(c):
-            self._select_surface_method(c)
-            _check(self.ctx.handle, self._lib.gingr_fitter_icp_surface_phase_async(self._fitter, ctypes.byref(p), 0),
-                   "gingr_fitter_icp_surface_phase_async")
-        else:
-            _check(self.ctx.handle, self._lib.gingr_fitter_icp_phase_async(self._fitter, ctypes.byref(p), 0), "gingr_fitter_icp_phase_async")
+        self._prepare_native(state)
+        flavour, _, p = self._plan(state)
+        name = "gingr_fitter_icp_surface_phase_async" if flavour == nat.FLAVOUR_ICP_SURFACE else "gingr_fitter_icp_phase_async"
+        _check(self.ctx.handle, getattr(self._lib, name)(self._fitter, *p, 0), name)
 
     def reversedCorrespondence(self, state: "IcpRegistrationState") -> Tuple[np.ndarray, np.ndarray]:
         """closestPointCorrespondenceReversal (ClosestPointRegistrator.scala:34-49) for the state's fit: per TARGET vertex the
@@ -1763,17 +1768,14 @@ class IcpRegistration(GingrAlgorithm):
                              "clouds choose correspondenceMethod=\"PointcloudClosestPoint\"")
         return IcpRegistrationState(general.updateSigma2(float(config.initialSigma)), config)   # ICP.scala:73-85
 
-    def _native_update(self, current: IcpRegistrationState, n: int):
-        c = current.config
-        p = nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
-        self._select_direction(c)
-        if self._surface(c):
-            self._select_surface_method(c)
-            _check(self.ctx.handle, self._lib.gingr_fitter_update_icp_surface_async(self._fitter, ctypes.byref(p), n),
-                   "gingr_fitter_update_icp_surface_async")
-        else:
-            _check(self.ctx.handle, self._lib.gingr_fitter_update_icp_async(self._fitter, ctypes.byref(p), n),
-                   "gingr_fitter_update_icp_async")
+    def _correspondence(self, state: IcpRegistrationState):
+        c = state.config
+        return (nat.FLAVOUR_ICP_SURFACE if self._surface(c) else nat.FLAVOUR_ICP), nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
+
+    def _prepare_native(self, state: IcpRegistrationState):
+        self._select_direction(state.config)
+        if self._surface(state.config):
+            self._select_surface_method(state.config)
 
     def surfaceCorrespondence(self, state: IcpRegistrationState) -> Tuple[np.ndarray, np.ndarray]:
         """ClosestPointTriangleMesh3D.closestPointCorrespondence(fit, target) (ClosestPointRegistrator.scala:75-100) for the
@@ -1789,58 +1791,6 @@ class IcpRegistration(GingrAlgorithm):
         _check(self.ctx.handle, self._lib.gingr_fitter_get_surface_correspondence(self._fitter, dptr(cp), dptr(w)),
                "gingr_fitter_get_surface_correspondence")
         return cp, w
-
-    def _mh_flavour(self, state: IcpRegistrationState):
-        c = state.config
-        if c.reverseCorrespondenceDirection:
-            return None
-        return (2 if self._surface(c) else 1), None, nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
-
-    def _mh_prepare(self, state: IcpRegistrationState):
-        self._select_direction(state.config)
-        if self._surface(state.config):
-            self._select_surface_method(state.config)
-
-    def _native_update_sample(self, current: IcpRegistrationState, z: np.ndarray):
-        c = current.config
-        p = nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
-        self._select_direction(c)
-        if self._surface(c):
-            self._select_surface_method(c)
-            _check(self.ctx.handle, self._lib.gingr_fitter_update_icp_surface_sample_async(self._fitter, ctypes.byref(p), dptr(z)),
-                   "gingr_fitter_update_icp_surface_sample_async")
-        else:
-            _check(self.ctx.handle, self._lib.gingr_fitter_update_icp_sample_async(self._fitter, ctypes.byref(p), dptr(z)),
-                   "gingr_fitter_update_icp_sample_async")
-
-    def _native_logpdf(self, state: IcpRegistrationState, mesh: np.ndarray) -> float:
-        c = state.config
-        p = nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
-        out = ctypes.c_double()
-        self._select_direction(c)
-        if self._surface(c):
-            self._select_surface_method(c)
-        fn = self._lib.gingr_fitter_posterior_logpdf_icp_surface if self._surface(c) else self._lib.gingr_fitter_posterior_logpdf_icp
-        _check(self.ctx.handle, fn(self._fitter, ctypes.byref(p), dptr(mesh), ctypes.byref(out)), "gingr_fitter_posterior_logpdf_icp")
-        return out.value
-
-    def _native_posterior_covariance(self, state: IcpRegistrationState, out: np.ndarray):
-        c = state.config
-        p = nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
-        self._select_direction(c)
-        if self._surface(c):
-            self._select_surface_method(c)
-        fn = self._lib.gingr_fitter_posterior_covariance_icp_surface if self._surface(c) else self._lib.gingr_fitter_posterior_covariance_icp
-        _check(self.ctx.handle, fn(self._fitter, ctypes.byref(p), dptr(out)), "gingr_fitter_posterior_covariance_icp")
-
-    def _native_posterior_model(self, state: IcpRegistrationState, out):
-        c = state.config
-        p = nat.IcpParams(c.initialSigma, c.endSigma, c.maxIterations)
-        self._select_direction(c)
-        if self._surface(c):
-            self._select_surface_method(c)
-        fn = self._lib.gingr_fitter_posterior_model_icp_surface if self._surface(c) else self._lib.gingr_fitter_posterior_model_icp
-        _check(self.ctx.handle, fn(self._fitter, ctypes.byref(p), ctypes.byref(out)), "gingr_fitter_posterior_model_icp")
 
     def getCorrespondence(self, state: IcpRegistrationState) -> CorrespondencePairs:
         if state.config.reverseCorrespondenceDirection:                               # ICP.scala:46-50
@@ -2009,32 +1959,16 @@ class TemplateRegistration(GingrAlgorithm):
         # the callbacks run on the host every iteration: the generic loop of `run`, never a block of updates enqueued at once
         return GingrAlgorithm.run(self, state, callBackLogger=lambda s: None)
 
+    def _correspondence(self, state: TemplateRegistrationState):
+        return nat.FLAVOUR_PAIRS, None
+
+    def _prepare_native(self, state: TemplateRegistrationState):
+        self._push_pairs(state)
+
     def _native_update(self, current: TemplateRegistrationState, n: int):
         if n != 1:
             raise ValueError("Template: one update per call (the correspondences of the next one come from the host)")
-        self._push_pairs(current)
-        _check(self.ctx.handle, self._lib.gingr_fitter_update_pairs_async(self._fitter, 1), "gingr_fitter_update_pairs_async")
-
-    def _native_update_sample(self, current: TemplateRegistrationState, z: np.ndarray):
-        self._push_pairs(current)
-        _check(self.ctx.handle, self._lib.gingr_fitter_update_pairs_sample_async(self._fitter, dptr(z)), "gingr_fitter_update_pairs_sample_async")
-
-    def _native_logpdf(self, state: TemplateRegistrationState, mesh: np.ndarray) -> float:
-        self._push_pairs(state)
-        out = ctypes.c_double()
-        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_logpdf_pairs(self._fitter, dptr(mesh), ctypes.byref(out)),
-               "gingr_fitter_posterior_logpdf_pairs")
-        return out.value
-
-    def _native_posterior_covariance(self, state: TemplateRegistrationState, out: np.ndarray):
-        self._push_pairs(state)
-        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_covariance_pairs(self._fitter, dptr(out)),
-               "gingr_fitter_posterior_covariance_pairs")
-
-    def _native_posterior_model(self, state: TemplateRegistrationState, out):
-        self._push_pairs(state)
-        _check(self.ctx.handle, self._lib.gingr_fitter_posterior_model_pairs(self._fitter, ctypes.byref(out)),
-               "gingr_fitter_posterior_model_pairs")
+        super()._native_update(current, n)
 
     def pairObservations(self, state) -> Tuple[np.ndarray, np.ndarray]:
         """The isotropic pairs of `state` as the device consolidated them: (observed point (M, 3), weight (M,)) per vertex -- the

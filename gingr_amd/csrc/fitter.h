@@ -76,7 +76,6 @@ struct gingr_fitter {
     int32_t last_err = 0;          // DevState::pad (error code of the last update, 0: it committed) as of the last gingr_fitter_get_state
     bool has_state = false;
     // ---- ICP surface correspondence (surface.h, surface*.hip): triangles in device vertex positions and a spatial triangle order
-    bool icp_surface = false;                      // correspondence flavour of the ICP phases
     int32_t surface_method = 0;                    // 0 TriangularClosestPoint, 1 AlongNormalClosestPoint (ICP.scala:32-34)
     // reversed correspondence direction (ICP.scala:46-48): per TARGET vertex buffers, then one observation per model vertex
     bool reversed = false;
@@ -128,7 +127,7 @@ struct gingr_fitter {
     // state up to three times (proposal, both transition densities); single shard only (a sharded run all-reduces the buffer).
     struct Key {
         std::vector<double> v;  // alpha[r], euler, center, translation, scale, sigma2
-        int flavour = -1;       // 0 CPD, 1 ICP point cloud, 2 ICP surface; + method / direction bits
+        int flavour = -1;       // memo_flavour_key (correspondence.h)
         double p0 = 0, p1 = 0;  // CPD: w, lambda
         bool same(const Key &o) const { return flavour == o.flavour && p0 == o.p0 && p1 == o.p1 && v == o.v; }
     };
@@ -219,7 +218,6 @@ struct gingr_fitter {
     // ---- correspondences given by the caller, flavour 3 (fitter_pairs.hip).  Isotropic pairs: the list as uploaded (ppid global ids,
     // pxyz interleaved, pvar), the sort buffers, and the per-vertex planes they are consolidated into once per gingr_fitter_set_pairs
     // -- pobs [3][M] / pwin [M], what launch_obs_points reads every iteration.  All sized for pairs_cap pairs, grown only.
-    bool pairs = false;  // correspondence flavour of the ICP phases: the pairs as they stand (set by the phase entry points)
     int64_t n_pairs = 0, pairs_cap = -1;
     int32_t *ppid = nullptr, *pkeys = nullptr, *pvals = nullptr, *pskeys = nullptr, *psvals = nullptr;
     double *pxyz = nullptr, *pvar = nullptr, *pobs = nullptr, *pwin = nullptr;
@@ -266,6 +264,7 @@ inline hipError_t ensure(DevBuf &b, size_t bytes) { return b.p && b.bytes >= byt
 
 // ---- fitter.hip
 int check_ready(gingr_fitter *f);  // target and state set; makes the context's device current
+int check_parameters(gingr_fitter *f, const Correspondence &c);  // check_ready, then the parameters of the flavour
 SweepArgs base_args(const gingr_fitter *f);
 void refresh_fit(gingr_fitter *f);    // fit = modelInstanceShapePoseScale(model, state)
 void fit_boxes_now(gingr_fitter *f);  // boxes + |coordinate - centre| maximum of a fit that refresh_fit did not write
@@ -305,8 +304,8 @@ struct Rot3 {
 };
 void launch_basis_rotate(gingr_ctx *ctx, const gingr_model *src, const double *T, const Rot3 &rot, gingr_model *dst);
 // ---- fitter_phases.hip
-int gather_fit(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, gingr_allreduce_fn reduce, void *user,
-               fitter_gather_fn gather, const char *who);
+int gather_fit(gingr_fitter *f, const Correspondence &c, gingr_allreduce_fn reduce, void *user, fitter_gather_fn gather, const char *who);
+int fitter_posterior_inputs(gingr_fitter *f, const Correspondence &c);  // phases 0 and 1 of the current state for a query (allow_alt)
 // ---- fitter_surface.hip
 void free_meshes(gingr_fitter *f);
 // ---- fitter_pairs.hip

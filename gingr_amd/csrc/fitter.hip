@@ -96,6 +96,26 @@ int check_ready(gingr_fitter *f) {
     return GINGR_OK;
 }
 
+// ready, then the parameter rules of correspondence.h with the texts the entry points have always answered with
+int check_parameters(gingr_fitter *f, const Correspondence &c) {
+    GINGR_TRY(check_ready(f));
+    switch (correspondence_error(c)) {
+        case CorrespondenceError::None: return GINGR_OK;
+        case CorrespondenceError::CpdParams: return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "cpd params: need 0 <= w < 1 and lambda > 0");
+        case CorrespondenceError::IcpParams: return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
+        case CorrespondenceError::BadFlavour: break;
+    }
+    return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "correspondence flavour %d out of range", (int)c.kind);
+}
+
+// ... then what the flavour needs of the fitter (the order of correspondence.h)
+int check_correspondence(gingr_fitter *f, const Correspondence &c) {
+    GINGR_TRY(check_parameters(f, c));
+    if (needs_meshes(c) && (!f->Tm || !f->Tt)) return gingr_set_error(f->ctx, GINGR_ERR_STATE, "icp surface: no meshes set (gingr_fitter_set_meshes)");
+    if (c.kind == Flavour::Pairs) GINGR_TRY(pairs_ensure_planes(f));  // (no gingr_fitter_set_pairs yet: no pairs)
+    return GINGR_OK;
+}
+
 std::vector<double> state_key_values(int32_t r, const double *alpha, const double euler[3], const double center[3], const double t[3],
                                      double scale, double sigma2) {
     std::vector<double> v(alpha, alpha + r);

@@ -50,12 +50,9 @@ __global__ void pose_of_state_kernel(const DevState *__restrict__ st, DevPose *_
 
 }  // namespace
 
-extern "C" {
-
 // ------------------------------------------------------------------------------------------ probabilistic proposal
-// correspondence flavour of a probabilistic query: 0 CPD, 1 ICP point cloud, 2 ICP surface
-static int sample_update(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, const double *z) {
-    GINGR_TRY(check_ready(f));
+int fitter_sample_update(gingr_fitter *f, const Correspondence &c, const double *z) {
+    GINGR_TRY(check_correspondence(f, c));
     gingr_ctx *ctx = f->ctx;
     if (!z) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "update_sample: z is null");
     if (f->m->M != f->m->M_total) return gingr_set_error(ctx, GINGR_ERR_STATE, "update_sample: single shard only");
@@ -65,29 +62,14 @@ static int sample_update(gingr_fitter *f, int flavour, const gingr_cpd_params *c
     f->zrand_active = true;
     int rc = GINGR_OK;
     f->allow_alt = true;
-    for (int ph = 0; ph < GINGR_NUM_PHASES && rc == GINGR_OK; ++ph) rc = fitter_run_phase(f, flavour, cp, ip, ph);
+    for (int ph = 0; ph < GINGR_NUM_PHASES && rc == GINGR_OK; ++ph) rc = fitter_run_phase(f, c, ph);
     f->allow_alt = false;
     f->zrand_active = false;
     return rc;
 }
 
-int gingr_fitter_update_cpd_sample_async(gingr_fitter *f, const gingr_cpd_params *p, const double *z) {
-    return sample_update(f, 0, p, nullptr, z);
-}
-
-int gingr_fitter_update_icp_sample_async(gingr_fitter *f, const gingr_icp_params *p, const double *z) {
-    return sample_update(f, 1, nullptr, p, z);
-}
-
-int gingr_fitter_update_icp_surface_sample_async(gingr_fitter *f, const gingr_icp_params *p, const double *z) {
-    return sample_update(f, 2, nullptr, p, z);
-}
-
-int gingr_fitter_update_pairs_sample_async(gingr_fitter *f, const double *z) { return sample_update(f, 3, nullptr, nullptr, z); }
-
-static int posterior_logpdf(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip,
-                            const double *mesh_xyz, double *logpdf) {
-    GINGR_TRY(check_ready(f));
+int fitter_posterior_logpdf(gingr_fitter *f, const Correspondence &c, const double *mesh_xyz, double *logpdf) {
+    GINGR_TRY(check_correspondence(f, c));
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
     if (!mesh_xyz || !logpdf) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "posterior_logpdf: null argument");
@@ -95,11 +77,7 @@ static int posterior_logpdf(gingr_fitter *f, int flavour, const gingr_cpd_params
     const int64_t M = m->M;
     const int32_t r = m->r, rp = m->rp;
     // posterior of the current state: correspondences, Gram, right-hand side (phases 0 and 1 do not touch the state)
-    f->allow_alt = true;
-    int prc = GINGR_OK;
-    for (int ph = 0; ph < 2 && prc == GINGR_OK; ++ph) prc = fitter_run_phase(f, flavour, cp, ip, ph);
-    f->allow_alt = false;
-    GINGR_TRY(prc);
+    GINGR_TRY(fitter_posterior_inputs(f, c));
     if (f->lp_epoch == 0) HIP_TRY(ctx, hipMemsetAsync(f->lp_sync, 0, 2 * sizeof(unsigned), ctx->stream));  // before the first hand-over
     const bool cached = f->fx_valid[f->live];  // this state's factors are on the device: only the mesh-dependent part is left
     double *G = f->seg1_live();
@@ -128,28 +106,32 @@ static int posterior_logpdf(gingr_fitter *f, int flavour, const gingr_cpd_params
     return GINGR_OK;
 }
 
+extern "C" {
+
+int gingr_fitter_update_cpd_sample_async(gingr_fitter *f, const gingr_cpd_params *p, const double *z) {
+    return fitter_sample_update(f, abi_correspondence(0, p, nullptr), z);
+}
+int gingr_fitter_update_icp_sample_async(gingr_fitter *f, const gingr_icp_params *p, const double *z) {
+    return fitter_sample_update(f, abi_correspondence(1, nullptr, p), z);
+}
+int gingr_fitter_update_icp_surface_sample_async(gingr_fitter *f, const gingr_icp_params *p, const double *z) {
+    return fitter_sample_update(f, abi_correspondence(2, nullptr, p), z);
+}
+int gingr_fitter_update_pairs_sample_async(gingr_fitter *f, const double *z) {
+    return fitter_sample_update(f, abi_correspondence(3, nullptr, nullptr), z);
+}
+
 int gingr_fitter_posterior_logpdf_cpd(gingr_fitter *f, const gingr_cpd_params *p, const double *mesh_xyz, double *logpdf) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    if (!p || !(p->w >= 0.0 && p->w < 1.0) || !(p->lambda > 0.0))
-        return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "cpd params: need 0 <= w < 1 and lambda > 0");
-    return posterior_logpdf(f, 0, p, nullptr, mesh_xyz, logpdf);
+    return fitter_posterior_logpdf(f, abi_correspondence(0, p, nullptr), mesh_xyz, logpdf);
 }
-
 int gingr_fitter_posterior_logpdf_icp(gingr_fitter *f, const gingr_icp_params *p, const double *mesh_xyz, double *logpdf) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
-    return posterior_logpdf(f, 1, nullptr, p, mesh_xyz, logpdf);
+    return fitter_posterior_logpdf(f, abi_correspondence(1, nullptr, p), mesh_xyz, logpdf);
 }
-
 int gingr_fitter_posterior_logpdf_icp_surface(gingr_fitter *f, const gingr_icp_params *p, const double *mesh_xyz, double *logpdf) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
-    return posterior_logpdf(f, 2, nullptr, p, mesh_xyz, logpdf);
+    return fitter_posterior_logpdf(f, abi_correspondence(2, nullptr, p), mesh_xyz, logpdf);
 }
-
 int gingr_fitter_posterior_logpdf_pairs(gingr_fitter *f, const double *mesh_xyz, double *logpdf) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    return posterior_logpdf(f, 3, nullptr, nullptr, mesh_xyz, logpdf);
+    return fitter_posterior_logpdf(f, abi_correspondence(3, nullptr, nullptr), mesh_xyz, logpdf);
 }
 
 }  // extern "C"
@@ -205,20 +187,21 @@ int fitter_logpdf_finish(gingr_fitter *f, double *logpdf) {
 
 // posterior(of the current state).gp.logpdf(posterior.coefficients(mesh)) on a row shard (GeneratorWrapperStochastic.scala:42-63):
 // phases 0 and 1 with their exchanges; Q0^T e rides in segment 1; the log-density kernel is replicated.
-int fitter_sharded_logpdf(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, const double *mesh_xyz_full,
-                          gingr_allreduce_fn reduce, void *user, double *logpdf, fitter_gather_fn gather) {
+int fitter_sharded_logpdf(gingr_fitter *f, const Correspondence &c, const double *mesh_xyz_full, gingr_allreduce_fn reduce, void *user,
+                          double *logpdf, fitter_gather_fn gather) {
     GINGR_TRY(check_ready(f));
     gingr_ctx *ctx = f->ctx;
-    if (!mesh_xyz_full || !logpdf || !reduce || flavour < 0 || flavour > 3)
+    if (!mesh_xyz_full || !logpdf || !reduce || correspondence_error(c) == CorrespondenceError::BadFlavour)
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sharded posterior_logpdf: bad arguments");
+    GINGR_TRY(check_correspondence(f, c));
     if (f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded posterior_logpdf: this fitter belongs to a device group");
-    if ((flavour == 2 || (flavour == 1 && f->reversed)) && f->sharded()) GINGR_TRY(gather_fit(f, flavour, cp, ip, reduce, user, gather, "sharded posterior_logpdf"));
-    GINGR_TRY(fitter_run_phase(f, flavour, cp, ip, 0));
-    if (flavour == 0 && reduce(user, 0, f->xch + f->off[0], f->cnt[0]) != 0)
+    if (needs_gathered_fit(c, f->reversed) && f->sharded()) GINGR_TRY(gather_fit(f, c, reduce, user, gather, "sharded posterior_logpdf"));
+    GINGR_TRY(fitter_run_phase(f, c, 0));
+    if (exchanges_segment0(c) && reduce(user, 0, f->xch + f->off[0], f->cnt[0]) != 0)
         return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded posterior_logpdf: the all-reduce callback failed (segment 0)");
-    if ((flavour == 1 || flavour == 2) && f->reversed && f->sharded() && reduce(user, GINGR_SEGMENT_REVSUM, f->revsum, 4 * f->m->M_total) != 0)
+    if (exchanges_reversal_sums(c, f->reversed) && f->sharded() && reduce(user, GINGR_SEGMENT_REVSUM, f->revsum, 4 * f->m->M_total) != 0)
         return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded posterior_logpdf: the all-reduce callback failed (reversal sums)");
-    GINGR_TRY(fitter_run_phase(f, flavour, cp, ip, 1));
+    GINGR_TRY(fitter_run_phase(f, c, 1));
     GINGR_TRY(fitter_logpdf_prepare(f, mesh_xyz_full));
     if (reduce(user, 1, f->xch + f->off[1], f->cnt[1]) != 0)
         return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded posterior_logpdf: the all-reduce callback failed (segment 1)");
@@ -229,8 +212,7 @@ extern "C" {
 
 int gingr_fitter_posterior_logpdf_sharded(gingr_fitter *f, int32_t flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip,
                                           const double *mesh_xyz_full, gingr_allreduce_fn reduce, void *user, double *logpdf) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    return fitter_sharded_logpdf(f, flavour, cp, ip, mesh_xyz_full, reduce, user, logpdf, nullptr);
+    return fitter_sharded_logpdf(f, abi_correspondence(flavour, cp, ip), mesh_xyz_full, reduce, user, logpdf);
 }
 
 // ------------------------------------------------------------------------------------------ one Metropolis-Hastings step
@@ -305,10 +287,11 @@ int gingr_fitter_mh_step(gingr_fitter *f, const gingr_mh_request *q, double *alp
     if (!q || !res || !alpha_out || q->flavour < 0 || q->flavour > 2 || (q->kind != 0 && q->kind != 1) || !(q->eval_sdev > 0.0) ||
         q->eval_points < 0 || q->eval_points > m->M || (q->flavour == 0 ? !q->cpd : !q->icp) || (q->kind == 0 ? !q->z : (!q->alpha || !q->scalars)))
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "mh_step: bad request");
-    if (q->flavour == 0 && (!(q->cpd->w >= 0.0 && q->cpd->w < 1.0) || !(q->cpd->lambda > 0.0)))
-        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "cpd params: need 0 <= w < 1 and lambda > 0");
-    if (q->flavour != 0 && q->icp->max_iterations < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
+    const Correspondence c = abi_correspondence(q->flavour, q->cpd, q->icp);
+    GINGR_TRY(check_parameters(f, c));
     if (m->M != m->M_total || f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "mh_step: single shard only");
+    // (the likelihood of a step is measured on the surfaces, whatever the flavour: the surface flavour's precondition with this entry
+    // point's own text; there is no step for the pairs flavour)
     if (!f->Tm || !f->Tt) return gingr_set_error(ctx, GINGR_ERR_STATE, "mh_step: no meshes set (gingr_fitter_set_meshes)");
     if (f->step_length != 1.0) return gingr_set_error(ctx, GINGR_ERR_STATE, "mh_step: step length 1 only (the transition density projects from.fit)");
     if (!f->state_key_valid)
@@ -316,7 +299,6 @@ int gingr_fitter_mh_step(gingr_fitter *f, const gingr_mh_request *q, double *alp
     const int64_t M = m->M;
     const int32_t r = m->r, rp = m->rp;
     const size_t head = (size_t)rp + kScalarsDoubles + kDevStateDoubles;
-    const int flavour = q->flavour;
     int rc = GINGR_OK;
     f->allow_alt = true;
     struct Restore {  // whatever happens below, the entry-point-scoped switches go back
@@ -324,7 +306,7 @@ int gingr_fitter_mh_step(gingr_fitter *f, const gingr_mh_request *q, double *alp
         ~Restore() { f->allow_alt = false, f->zrand_active = false; }
     } restore{f};
     // (1) the posterior inputs of x (memo: they exist unless x is the first state of the chain)
-    for (int ph = 0; ph < 2 && rc == GINGR_OK; ++ph) rc = fitter_run_phase(f, flavour, q->cpd, q->icp, ph);
+    for (int ph = 0; ph < 2 && rc == GINGR_OK; ++ph) rc = fitter_run_phase(f, c, ph);
     GINGR_TRY(rc);
     // (2) x stays: parameters + device state in mh_save (parked by the launch that also brings the proposal's draws / parameters, or
     // by a copy where those do not fit a kernel argument), the fit by exchanging the two fit buffers
@@ -360,7 +342,7 @@ int gingr_fitter_mh_step(gingr_fitter *f, const gingr_mh_request *q, double *alp
             HIP_TRY(ctx, hipMemcpyAsync(f->zrand, f->pin, (size_t)rp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         }
         f->zrand_active = true;
-        rc = fitter_run_phase(f, flavour, q->cpd, q->icp, 2);
+        rc = fitter_run_phase(f, c, 2);
         f->zrand_active = false;
         GINGR_TRY(rc);
         mh_tag_state(f);
@@ -386,16 +368,16 @@ int gingr_fitter_mh_step(gingr_fitter *f, const gingr_mh_request *q, double *alp
     const int slot_fw = f->live;
     if (q->need_forward) GINGR_TRY(mh_logpdf_enqueue(f, x_state, f->fit_alt, f->small, true));
     // (5) the posterior inputs of x' (x's are parked in the second slot)
-    rc = fitter_run_phase(f, flavour, q->cpd, q->icp, 0);
+    rc = fitter_run_phase(f, c, 0);
     const bool memo_hit = f->skip_phase1;
-    if (rc == GINGR_OK) rc = fitter_run_phase(f, flavour, q->cpd, q->icp, 1);
+    if (rc == GINGR_OK) rc = fitter_run_phase(f, c, 1);
     GINGR_TRY(rc);
     // (6) the likelihood of x'
     if (!f->stat_scratch) f->stat_scratch = new StatScratch;
     StatScratch &sc = *f->stat_scratch;
     HIP_TRY(ctx, ensure(sc.part, (size_t)distance_stats_ws_doubles() * sizeof(double)));
     const double *d2 = f->surf_d2;
-    if (!(flavour == 2 && !memo_hit && !f->reversed && f->surface_method == 0)) {  // no fresh closest-point scan of x' to share
+    if (!(c.kind == Flavour::IcpSurface && !memo_hit && !f->reversed && f->surface_method == 0)) {  // no fresh closest-point scan of x' to share
         const Cloud fit = cloud_of(f->fit, M), tgt = cloud_of(f->target, f->N);
         HIP_TRY(ctx, ensure(sc.cp, (size_t)3 * M * sizeof(double)));
         HIP_TRY(ctx, ensure(sc.d2, (size_t)M * sizeof(double)));

@@ -126,17 +126,14 @@ struct Segments {
 //            fx_valid / nf_valid of the live slot; corr_stale
 //   phase 1  skip_phase1; post_stage 1 -> 2
 //   phase 2  state_key_valid, mh_saved
-bool memo_enter(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, int phase) {
+bool memo_enter(gingr_fitter *f, const Correspondence &c, int phase) {
     const gingr_model *m = f->m;
     if (phase == 0) {
         f->skip_phase1 = false;
         gingr_fitter::Key k;
-        // (3: the pairs as they stand -- gingr_fitter_set_pairs / _set_pairs_cov forget the memo, so the key need not describe them)
-        k.flavour = !icp ? 0 : f->pairs ? 3 : ((f->icp_surface ? 2 : 1) + 4 * f->surface_method + 16 * (f->reversed ? 1 : 0));
-        if (!icp) {
-            k.p0 = cp->w;
-            k.p1 = cp->lambda;
-        }
+        k.flavour = memo_flavour_key(c, f->surface_method, f->reversed);
+        k.p0 = c.cpd.w;  // (zero for every flavour but CPD)
+        k.p1 = c.cpd.lambda;
         const bool single = m->M == m->M_total;
         if (single && f->state_key_valid) {
             k.v = f->state_key.v;
@@ -331,7 +328,7 @@ void nearest_template_vertex(gingr_fitter *f, const ReversedSide &s, Cloud q) {
 // original id and ties go to the lowest id as on a single shard), for THIS shard's range of the target queries only; what leaves the
 // phase is the per-template-vertex sums of the range (see gingr_fitter::revsum).  The tests that involve the target mesh itself
 // (self-intersection) see the whole target.
-int phase0_reversed(gingr_fitter *f, Cloud fit, Cloud tgt, Cloud meshc) {
+int phase0_reversed(gingr_fitter *f, const Correspondence &c, Cloud fit, Cloud tgt, Cloud meshc) {
     gingr_ctx *ctx = f->ctx;
     ReversedSide s;
     if (f->sharded()) {
@@ -348,7 +345,7 @@ int phase0_reversed(gingr_fitter *f, Cloud fit, Cloud tgt, Cloud meshc) {
         s = ReversedSide{fit, f->madj_ptr, f->madj_tri, f->mvn, f->mboundary, tgt, 0, f->tvn, nullptr, nullptr};
     }
     const int64_t Mv = s.mesh.n;
-    const bool surface = f->icp_surface, along = f->surface_method == 1;
+    const bool surface = c.kind == Flavour::IcpSurface, along = f->surface_method == 1;
     if (surface) {
         launch_cell_normals(ctx, s.mesh, f->mtri, f->Tm, f->mcn);
         launch_vertex_normals(ctx, s.adj_ptr, s.adj_tri, f->mcn, f->Tm, Mv, s.vn);
@@ -382,26 +379,26 @@ int phase0_reversed(gingr_fitter *f, Cloud fit, Cloud tgt, Cloud meshc) {
 // ---- phase 1
 // The observations (correspondence point, uncertainty) of the local rows -> weight, evec; CPD: also den and the row statistics.
 // Fills the scalar-sum fields of `fa`.
-void phase1_observations(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const Segments &s, Cloud fit, Cloud tgt, Phase1FinalizeArgs &fa) {
+void phase1_observations(gingr_fitter *f, const Correspondence &c, const Segments &s, Cloud fit, Cloud tgt, Phase1FinalizeArgs &fa) {
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
     const int64_t M = m->M;
-    if (icp && f->pairs) {  // the caller's pairs, consolidated per vertex by gingr_fitter_set_pairs; weight 0: no pair
+    if (c.kind == Flavour::Pairs) {  // the caller's pairs, consolidated per vertex by gingr_fitter_set_pairs; weight 0: no pair
         launch_obs_points(ctx, m, f->st, f->pobs, f->pwin, f->weight, f->evec, f->lm_mask);
         fa.scalar_mode = 0;
-    } else if (icp) {
+    } else if (c.kind != Flavour::Cpd) {
         if (f->reversed && f->sharded())  // the totals over all shards' query ranges are in place: this shard's rows of them
             hipLaunchKernelGGL(reversal_local_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, m->row_begin, m->perm,
                                m->M_total, f->revsum, &f->st->sigma2, f->robs, f->rwin);
         if (f->reversed)  // one observation per template vertex: mean of its accepted targets, weight count / sigma2
             launch_obs_points(ctx, m, f->st, f->robs, f->rwin, f->weight, f->evec, f->lm_mask);
-        else if (f->icp_surface)  // only the weight-1 pairs are observed (ICP.scala:50): weight 0 drops the row
+        else if (c.kind == Flavour::IcpSurface)  // only the weight-1 pairs are observed (ICP.scala:50): weight 0 drops the row
             launch_obs_points(ctx, m, f->st, f->surf_cp, f->surf_win, f->weight, f->evec, f->lm_mask, f->zero_counts);
         else if (f->n_lm != 0)  // (without landmarks the observation is formed inside the right-hand-side pass of run_phase)
             launch_obs_icp(ctx, m, f->st, tgt, f->nn_idx, f->lm_mask, f->weight, f->evec);
         fa.scalar_mode = 0;
     } else {
-        launch_cpd_den_finalize(ctx, tgt, &f->st->sigma2, cp->w, m->M_total, s.seg0, f->inv_den, f->Pt1, f->tile_bad, f->part,
+        launch_cpd_den_finalize(ctx, tgt, &f->st->sigma2, c.cpd.w, m->M_total, s.seg0, f->inv_den, f->Pt1, f->tile_bad, f->part,
                                 f->scalars, f->colsum_chunks > 0 ? f->ws : nullptr, f->colsum_chunks);
         f->colsum_chunks = 0;
         // observations (correspondence point, uncertainty) come out of the row-statistics reduction; the scalar sums are
@@ -414,7 +411,7 @@ void phase1_observations(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, 
         ob.R = f->st->R;
         ob.center = f->st->center;
         ob.t = f->st->t;
-        ob.lambda = cp->lambda;
+        ob.lambda = c.cpd.lambda;
         ob.lm_mask = f->lm_mask;
         ob.weight = f->weight;
         ob.evec = f->evec;
@@ -445,19 +442,19 @@ struct GramOutcome {
 //                    The gate sums THIS shard's zero_counts against THIS shard's M: the shards of one update may decide differently.
 //   weighted pass    everything else -- always for the pairs flavour, whose weights are the caller's: each shard contributes the pass over its own rows; the pass may leave the right-hand-side
 //                    partials as well (rhs_done).
-GramOutcome phase1_gram(gingr_fitter *f, bool icp, double *gram_ws, double *sweep_ws, Phase1FinalizeArgs &fa) {
+GramOutcome phase1_gram(gingr_fitter *f, const Correspondence &c, double *gram_ws, double *sweep_ws, Phase1FinalizeArgs &fa) {
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
     const int64_t M = m->M;
     const int32_t rp = m->rp;
     GramOutcome out{false, ZeroGate{}};
-    if (icp && !f->pairs && !f->icp_surface && !f->reversed && f->n_lm == 0) {
+    if (uniform_weights(c, f->reversed, f->n_lm)) {
         // (ICP.scala:90-92; written by the phase-1 finalize kernel: one launch less than a copy kernel of its own)
         fa.nslabs = 0;
         fa.scaled_src = m->mom + MomentLayout{rp}.stot();
         fa.sigma2 = &f->st->sigma2;
         fa.scaled_contribute = m->row_begin == 0 ? 1 : 0;
-    } else if (icp && !f->pairs && f->icp_surface && !f->reversed &&
+    } else if (zero_one_weights(c, f->reversed) &&
                (ctx->gram_downdate == 1 || (ctx->gram_downdate < 0 && M >= kGramDowndateMinRows))) {
         // surface correspondence: an accepted pair has the weight 1 / sigma2, a rejected one (and a vertex a landmark overrides) 0
         // (ICP.scala:50,90-92) -- the weighted Gram is the model's moment minus the rows of the zero-weight vertices, scaled.
@@ -487,13 +484,13 @@ GramOutcome phase1_gram(gingr_fitter *f, bool icp, double *gram_ws, double *swee
 }
 
 // ---- phase 2: the replicated algebra -- posterior solve, post-solve (commit or failure status) -- and the new fit of the local rows
-void phase2_solve_and_commit(gingr_fitter *f, bool icp, const gingr_icp_params *ip, const Segments &s) {
+void phase2_solve_and_commit(gingr_fitter *f, const Correspondence &c, const Segments &s) {
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
     const int32_t r = m->r, rp = m->rp;
     // the posterior mean of the uniform-weight case comes from the model's eigen-decomposition (no factorisation); a sampled
     // proposal needs the Cholesky factor itself (its square root of the covariance is part of the parity contract)
-    const bool eig = icp && !f->pairs && !f->icp_surface && !f->reversed && f->n_lm == 0 && !f->zrand_active && m->eig_ready;
+    const bool eig = uniform_weights(c, f->reversed, f->n_lm) && !f->zrand_active && m->eig_ready;
     if (eig)
         launch_posterior_solve_eig(ctx, r, rp, m->eigV, m->eigL, &f->st->sigma2, s.rhs, f->acoef, f->st);
     else if (f->zrand_active && f->allow_alt && f->post_stage == 2 && f->nf_valid[f->live] && m->M == m->M_total && !f->partial_out)
@@ -510,10 +507,10 @@ void phase2_solve_and_commit(gingr_fitter *f, bool icp, const gingr_icp_params *
     a.zbuf = f->zbuf;
     a.alpha = f->alpha;
     a.scalars = s.sc8;
-    a.is_icp = !icp ? 0 : f->pairs ? 2 : 1;  // sigma2 of the next state: CPD's sums / ICP's schedule / kept (the caller's updateSigma2)
-    if (icp && !f->pairs) {
-        a.icp_step = (ip->initial_sigma - ip->end_sigma) / (double)ip->max_iterations;  // ICP.scala:65
-        a.icp_end = ip->end_sigma;
+    a.is_icp = post_solve_sigma2_rule(c);  // sigma2 of the next state: CPD's sums / ICP's schedule / kept (the caller's updateSigma2)
+    if (is_icp_schedule(c)) {
+        a.icp_step = (c.icp.initial_sigma - c.icp.end_sigma) / (double)c.icp.max_iterations;  // ICP.scala:65
+        a.icp_end = c.icp.end_sigma;
     }
     a.step = f->step_length;
     a.global_transform = f->global_transform;
@@ -526,7 +523,7 @@ void phase2_solve_and_commit(gingr_fitter *f, bool icp, const gingr_icp_params *
     refresh_fit(f);
 }
 
-int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr_icp_params *ip, int phase) {
+int run_phase(gingr_fitter *f, const Correspondence &c, int phase) {
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
     const int64_t M = m->M;
@@ -560,16 +557,16 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
     }
     // the template mesh of the surface tests: the fit itself, or -- on a row shard -- the gathered fit of all shards (original order)
     const Cloud meshc = f->sharded() && f->fullfit ? cloud_of(f->fullfit, m->M_total) : fit;
-    if (memo_enter(f, icp, cp, phase)) return GINGR_OK;
+    if (memo_enter(f, c, phase)) return GINGR_OK;
     switch (phase) {
         case 0:
-            if (icp && f->pairs)
+            if (c.kind == Flavour::Pairs)
                 break;  // the correspondences are the caller's: nothing to compute, nothing to exchange
-            if (icp && f->reversed)
-                GINGR_TRY(phase0_reversed(f, fit, tgt, meshc));
-            else if (icp && f->icp_surface)
+            if (reversed_icp(c, f->reversed))
+                GINGR_TRY(phase0_reversed(f, c, fit, tgt, meshc));
+            else if (c.kind == Flavour::IcpSurface)
                 phase0_surface(f, fit, tgt, meshc);
-            else if (icp)
+            else if (c.kind == Flavour::IcpCloud)
                 phase0_nearest_vertex(f, fit, tgt);
             else
                 phase0_cpd_colsums(f, s, fit, tgt);
@@ -581,9 +578,9 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
             fa.G = s.Gw;
             fa.rhs = s.rhsw;
             fa.sc8 = s.sc8w;
-            phase1_observations(f, icp, cp, s, fit, tgt, fa);
+            phase1_observations(f, c, s, fit, tgt, fa);
             double *gram_ws = f->ws, *sweep_ws = f->ws + gram_ws_doubles(M, rp);
-            const GramOutcome gram = phase1_gram(f, icp, gram_ws, sweep_ws, fa);
+            const GramOutcome gram = phase1_gram(f, c, gram_ws, sweep_ws, fa);
             fa.sweep_partial = sweep_ws;
             if (gram.rhs_done) {  // the Gram pass left the right-hand-side partials, one row per slab
                 fa.sweep_blocks = fa.nslabs;
@@ -593,7 +590,7 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
                 a.partial = sweep_ws;
                 a.no_reduce = 1;
                 a.gate = gram.rhs_gate;
-                if (icp && !f->pairs && !f->icp_surface && !f->reversed && f->n_lm == 0) {  // point-cloud ICP: observation + Q^T e in one pass
+                if (uniform_weights(c, f->reversed, f->n_lm)) {  // point-cloud ICP: observation + Q^T e in one pass
                     a.state = f->st;
                     a.icp_idx = f->nn_idx;
                     a.tx = tgt.x, a.ty = tgt.y, a.tz = tgt.z;
@@ -607,7 +604,7 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
                 fa.sweep_blocks = sweep_num_blocks(M);
             }
             launch_phase1_finalize(ctx, fa);
-            if (icp && f->pairs && f->n_pc > 0)  // one launch over [covariance pairs | landmarks]: a defined summation order
+            if (c.kind == Flavour::Pairs && f->n_pc > 0)  // one launch over [covariance pairs | landmarks]: a defined summation order
                 launch_landmarks(ctx, m, f->st, f->n_cat, f->cat_pid.as<int32_t>(), f->cat_xyz.as<double>(), f->cat_cov.as<double>(),
                                  s.Gw, s.rhsw);
             else
@@ -615,7 +612,7 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
             break;
         }
         case 2:
-            phase2_solve_and_commit(f, icp, ip, s);
+            phase2_solve_and_commit(f, c, s);
             break;
         default:
             return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "phase %d out of range", phase);
@@ -625,82 +622,65 @@ int run_phase(gingr_fitter *f, bool icp, const gingr_cpd_params *cp, const gingr
 
 }  // namespace
 
-// One phase of flavour 0 CPD / 1 ICP point cloud / 2 ICP surface / 3 pairs given (GINGR_PHASE_GATHER included)
-int fitter_run_phase(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int phase) {
-    if (flavour == 0) return gingr_fitter_cpd_phase_async(f, cp, phase);
-    if (flavour == 1) return gingr_fitter_icp_phase_async(f, ip, phase);
-    if (flavour == 3) return gingr_fitter_pairs_phase_async(f, phase);
-    return gingr_fitter_icp_surface_phase_async(f, ip, phase);
+// One phase of one flavour (GINGR_PHASE_GATHER included); the caller has checked the descriptor (check_correspondence)
+int fitter_run_phase(gingr_fitter *f, const Correspondence &c, int phase) { return run_phase(f, c, phase); }
+
+// The posterior inputs of the current state -- correspondences, Gram, right-hand side -- for a query that leaves the state as it is:
+// phases 0 and 1, which may bring a parked memo slot back (allow_alt)
+int fitter_posterior_inputs(gingr_fitter *f, const Correspondence &c) {
+    f->allow_alt = true;
+    int rc = GINGR_OK;
+    for (int ph = 0; ph < 2 && rc == GINGR_OK; ++ph) rc = run_phase(f, c, ph);
+    f->allow_alt = false;
+    return rc;
 }
 
 // n_iterations single-shard updates of one flavour, each timed as one step
-static int update_loop(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int32_t n_iterations) {
+int fitter_update(gingr_fitter *f, const Correspondence &c, int32_t n_iterations) {
+    GINGR_TRY(check_correspondence(f, c));
+    if (f->sharded()) {
+        static const char *const text[4] = {
+            "update_cpd_async: sharded model needs the phase API + exchange", "update_icp_async: sharded model needs the phase API + exchange",
+            "update_icp_surface_async: a row shard needs the sharded update (gingr_fitter_update_sharded_async / _rccl_async / the device group)",
+            "update_pairs_async: a row shard needs the sharded update (gingr_fitter_update_sharded_async)"};
+        return gingr_set_error(f->ctx, GINGR_ERR_STATE, "%s", text[(int)c.kind]);
+    }
     for (int32_t it = 0; it < n_iterations; ++it) {
         TimerScope ts(f->ctx, 3);
-        for (int ph = 0; ph < GINGR_NUM_PHASES; ++ph) GINGR_TRY(fitter_run_phase(f, flavour, cp, ip, ph));
+        for (int ph = 0; ph < GINGR_NUM_PHASES; ++ph) GINGR_TRY(run_phase(f, c, ph));
     }
     return GINGR_OK;
+}
+
+static int checked_phase(gingr_fitter *f, const Correspondence &c, int32_t phase) {
+    GINGR_TRY(check_correspondence(f, c));
+    return run_phase(f, c, phase);
 }
 
 extern "C" {
 
 int gingr_fitter_cpd_phase_async(gingr_fitter *f, const gingr_cpd_params *p, int32_t phase) {
-    GINGR_TRY(check_ready(f));
-    if (!p || !(p->w >= 0.0 && p->w < 1.0) || !(p->lambda > 0.0))
-        return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "cpd params: need 0 <= w < 1 and lambda > 0");
-    return run_phase(f, false, p, nullptr, phase);
+    return checked_phase(f, abi_correspondence(0, p, nullptr), phase);
 }
-
 int gingr_fitter_icp_phase_async(gingr_fitter *f, const gingr_icp_params *p, int32_t phase) {
-    GINGR_TRY(check_ready(f));
-    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
-    f->icp_surface = false;
-    f->pairs = false;
-    return run_phase(f, true, nullptr, p, phase);
+    return checked_phase(f, abi_correspondence(1, nullptr, p), phase);
 }
-
-int gingr_fitter_pairs_phase_async(gingr_fitter *f, int32_t phase) {
-    GINGR_TRY(check_ready(f));
-    GINGR_TRY(pairs_ensure_planes(f));  // (no gingr_fitter_set_pairs yet: no pairs)
-    f->pairs = true;
-    return run_phase(f, true, nullptr, nullptr, phase);
+int gingr_fitter_icp_surface_phase_async(gingr_fitter *f, const gingr_icp_params *p, int32_t phase) {
+    return checked_phase(f, abi_correspondence(2, nullptr, p), phase);
 }
-
-int gingr_fitter_update_pairs_async(gingr_fitter *f, int32_t n_iterations) {
-    GINGR_TRY(check_ready(f));
-    if (f->m->M != f->m->M_total)
-        return gingr_set_error(f->ctx, GINGR_ERR_STATE, "update_pairs_async: a row shard needs the sharded update (gingr_fitter_update_sharded_async)");
-    return update_loop(f, 3, nullptr, nullptr, n_iterations);
-}
+int gingr_fitter_pairs_phase_async(gingr_fitter *f, int32_t phase) { return checked_phase(f, abi_correspondence(3, nullptr, nullptr), phase); }
 
 int gingr_fitter_update_cpd_async(gingr_fitter *f, const gingr_cpd_params *p, int32_t n_iterations) {
-    GINGR_TRY(check_ready(f));
-    if (f->m->M != f->m->M_total)
-        return gingr_set_error(f->ctx, GINGR_ERR_STATE, "update_cpd_async: sharded model needs the phase API + exchange");
-    return update_loop(f, 0, p, nullptr, n_iterations);
+    return fitter_update(f, abi_correspondence(0, p, nullptr), n_iterations);
 }
-
 int gingr_fitter_update_icp_async(gingr_fitter *f, const gingr_icp_params *p, int32_t n_iterations) {
-    GINGR_TRY(check_ready(f));
-    if (f->m->M != f->m->M_total)
-        return gingr_set_error(f->ctx, GINGR_ERR_STATE, "update_icp_async: sharded model needs the phase API + exchange");
-    return update_loop(f, 1, nullptr, p, n_iterations);
+    return fitter_update(f, abi_correspondence(1, nullptr, p), n_iterations);
 }
-
-int gingr_fitter_icp_surface_phase_async(gingr_fitter *f, const gingr_icp_params *p, int32_t phase) {
-    GINGR_TRY(check_ready(f));
-    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
-    if (!f->Tm || !f->Tt) return gingr_set_error(f->ctx, GINGR_ERR_STATE, "icp surface: no meshes set (gingr_fitter_set_meshes)");
-    f->icp_surface = true;
-    f->pairs = false;
-    return run_phase(f, true, nullptr, p, phase);
-}
-
 int gingr_fitter_update_icp_surface_async(gingr_fitter *f, const gingr_icp_params *p, int32_t n_iterations) {
-    GINGR_TRY(check_ready(f));
-    if (f->sharded())
-        return gingr_set_error(f->ctx, GINGR_ERR_STATE, "update_icp_surface_async: a row shard needs the sharded update (gingr_fitter_update_sharded_async / _rccl_async / the device group)");
-    return update_loop(f, 2, nullptr, p, n_iterations);
+    return fitter_update(f, abi_correspondence(2, nullptr, p), n_iterations);
+}
+int gingr_fitter_update_pairs_async(gingr_fitter *f, int32_t n_iterations) {
+    return fitter_update(f, abi_correspondence(3, nullptr, nullptr), n_iterations);
 }
 
 }  // extern "C"
@@ -711,25 +691,26 @@ int gingr_fitter_update_icp_surface_async(gingr_fitter *f, const gingr_icp_param
 // replicated r x r algebra, so z is the same on every shard and nothing else is exchanged.
 // gather (nullable): does the whole gather of the fit itself (stage, all-gather, unpack: rccl_exchange.hip) and returns 0; a positive
 // value means "not possible here" and the zero-padded all-reduce through `reduce` is used instead
-int gather_fit(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, gingr_allreduce_fn reduce, void *user,
-                      fitter_gather_fn gather, const char *who) {
+int gather_fit(gingr_fitter *f, const Correspondence &c, gingr_allreduce_fn reduce, void *user, fitter_gather_fn gather, const char *who) {
     gingr_ctx *ctx = f->ctx;
     if (gather) {
         const int g = gather(user, f);
         if (g == 0) return GINGR_OK;
         if (g < 0) return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: the all-gather of the fit failed", who);
     }
-    GINGR_TRY(fitter_run_phase(f, flavour, cp, ip, GINGR_PHASE_GATHER));
+    GINGR_TRY(run_phase(f, c, GINGR_PHASE_GATHER));
     if (reduce(user, GINGR_SEGMENT_FULLFIT, f->fullfit, 3 * f->m->M_total) != 0)
         return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: the all-reduce callback failed (full fit)", who);
     return GINGR_OK;
 }
 
-int fitter_sharded_update(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int32_t n_iterations,
-                          const double *z, gingr_allreduce_fn reduce, void *user, fitter_gather_fn gather, bool split_native) {
+int fitter_sharded_update(gingr_fitter *f, const Correspondence &c, int32_t n_iterations, const double *z, gingr_allreduce_fn reduce,
+                          void *user, fitter_gather_fn gather, bool split_native) {
     GINGR_TRY(check_ready(f));
     gingr_ctx *ctx = f->ctx;
-    if (n_iterations < 0 || !reduce || flavour < 0 || flavour > 3) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sharded update: bad arguments");
+    if (n_iterations < 0 || !reduce || correspondence_error(c) == CorrespondenceError::BadFlavour)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sharded update: bad arguments");
+    GINGR_TRY(check_correspondence(f, c));
     if (f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "sharded update: this fitter belongs to a device group");
     if (z && n_iterations != 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sharded update: a sampled proposal is one iteration");
     if (z) GINGR_TRY(fitter_upload_zrand(f, z));
@@ -737,7 +718,7 @@ int fitter_sharded_update(gingr_fitter *f, int flavour, const gingr_cpd_params *
     int rc = GINGR_OK;
     // GINGR_OPT_SPLIT_EXCHANGE: pass 1 in two halves of the target tiles; the all-reduce of the first half runs on the context's second
     // stream (ordered by events, same communicator) while the second half computes, so only the second half's all-reduce is exposed
-    bool split = split_native && flavour == 0 && f->sharded() && f->N >= 8192;
+    bool split = split_native && c.kind == Flavour::Cpd && f->sharded() && f->N >= 8192;
     // (the halves take twice the chunks of the whole pass)
     if (split && (int64_t)2 * cpd_colsum_chunks(f->m->M, f->N) * f->N > f->ws_doubles) split = false;
     if (split && !ctx->side_stream) {
@@ -750,13 +731,13 @@ int fitter_sharded_update(gingr_fitter *f, int flavour, const gingr_cpd_params *
     }
     for (int32_t it = 0; it < n_iterations && rc == GINGR_OK; ++it) {
         TimerScope ts(ctx, 3);
-        if ((flavour == 2 || (flavour == 1 && f->reversed)) && f->sharded()) rc = gather_fit(f, flavour, cp, ip, reduce, user, gather, "sharded update");
+        if (needs_gathered_fit(c, f->reversed) && f->sharded()) rc = gather_fit(f, c, reduce, user, gather, "sharded update");
         for (int ph = 0; ph < GINGR_NUM_PHASES && rc == GINGR_OK; ++ph) {
             if (ph == 0 && split) {
                 const int64_t NA = split_cut(f->N);
                 double *seg0 = f->xch + f->off[0];
                 f->split_half = 1;
-                rc = fitter_run_phase(f, flavour, cp, ip, 0);
+                rc = run_phase(f, c, 0);
                 {
                     TimerScope tx(ctx, 6);
                     if (!rc && (hipEventRecord(ctx->split_ev[0], ctx->stream) != hipSuccess ||
@@ -772,7 +753,7 @@ int fitter_sharded_update(gingr_fitter *f, int flavour, const gingr_cpd_params *
                         rc = gingr_set_error(ctx, GINGR_ERR_HIP, "sharded update: event ordering of the split exchange failed");
                 }
                 f->split_half = 2;
-                if (!rc) rc = fitter_run_phase(f, flavour, cp, ip, 0);
+                if (!rc) rc = run_phase(f, c, 0);
                 f->split_half = 0;
                 {
                     TimerScope tx(ctx, 6);
@@ -783,13 +764,13 @@ int fitter_sharded_update(gingr_fitter *f, int flavour, const gingr_cpd_params *
                 }
                 continue;
             }
-            rc = fitter_run_phase(f, flavour, cp, ip, ph);
-            if (!rc && ph < GINGR_NUM_SEGMENTS && !(flavour != 0 && ph == 0)) {
+            rc = run_phase(f, c, ph);
+            if (!rc && ph < GINGR_NUM_SEGMENTS && (ph != 0 || exchanges_segment0(c))) {
                 TimerScope tx(ctx, 6 + ph);  // the exchange of segment ph as this shard sees it (includes waiting for the peers)
                 if (reduce(user, ph, f->xch + f->off[ph], f->cnt[ph]) != 0)
                     rc = gingr_set_error(ctx, GINGR_ERR_STATE, "sharded update: the all-reduce callback failed (segment %d)", ph);
             }
-            if (!rc && ph == 0 && (flavour == 1 || flavour == 2) && f->reversed && f->sharded() &&
+            if (!rc && ph == 0 && exchanges_reversal_sums(c, f->reversed) && f->sharded() &&
                 reduce(user, GINGR_SEGMENT_REVSUM, f->revsum, 4 * f->m->M_total) != 0)
                 rc = gingr_set_error(ctx, GINGR_ERR_STATE, "sharded update: the all-reduce callback failed (reversal sums)");
         }
@@ -802,20 +783,17 @@ extern "C" {
 
 int gingr_fitter_update_cpd_sharded_async(gingr_fitter *f, const gingr_cpd_params *p, int32_t n_iterations, gingr_allreduce_fn reduce,
                                           void *user) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    return fitter_sharded_update(f, 0, p, nullptr, n_iterations, nullptr, reduce, user, nullptr, false);
+    return fitter_sharded_update(f, abi_correspondence(0, p, nullptr), n_iterations, nullptr, reduce, user);
 }
 
 int gingr_fitter_update_icp_sharded_async(gingr_fitter *f, const gingr_icp_params *p, int32_t n_iterations, gingr_allreduce_fn reduce,
                                           void *user) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    return fitter_sharded_update(f, 1, nullptr, p, n_iterations, nullptr, reduce, user, nullptr, false);
+    return fitter_sharded_update(f, abi_correspondence(1, nullptr, p), n_iterations, nullptr, reduce, user);
 }
 
 int gingr_fitter_update_sharded_async(gingr_fitter *f, int32_t flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip,
                                       int32_t n_iterations, const double *z, gingr_allreduce_fn reduce, void *user) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    return fitter_sharded_update(f, flavour, cp, ip, n_iterations, z, reduce, user, nullptr, false);
+    return fitter_sharded_update(f, abi_correspondence(flavour, cp, ip), n_iterations, z, reduce, user);
 }
 
 int gingr_fitter_gather_stage(gingr_fitter *f, int32_t world, int32_t rank, void **send_ptr, void **recv_ptr, int64_t *count_per_rank) {

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.h"
+#include "correspondence.h"
 #include "svd3.h"
 
 #include <functional>
@@ -142,16 +143,22 @@ int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const doubl
 // the gather step of a sharded surface update writes the shard's contribution to the full fit (nullptr: in place)
 void fitter_set_partial_output(gingr_fitter *f, double *base);
 void fitter_set_partial_fullfit(gingr_fitter *f, double *base);
-// the sharded update (fitter_phases.hip) for the other translation units: flavour 0 CPD, 1 ICP point cloud, 2 ICP surface; z nullable (sampled proposal)
+// fitter.hip: ready, parameters and what the flavour needs of the fitter -- once per ABI call, in front of everything below
+int check_correspondence(gingr_fitter *f, const Correspondence &c);
+// the sharded update (fitter_phases.hip) for the other translation units; z nullable (sampled proposal)
 // gather (nullable): the host's own all-gather of the fit -- 0 done, > 0 not possible here (fall back to the zero-padded all-reduce), < 0 failed
 typedef int (*fitter_gather_fn)(void *user, gingr_fitter *f);
 // split_native: the caller's `reduce` is the library's own RCCL all-reduce (user = the context) and honours ctx->exchange_stream:
 // GINGR_OPT_SPLIT_EXCHANGE may then run the CPD column-sum exchange in two halves
-int fitter_sharded_update(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int32_t n_iterations,
-                          const double *z, gingr_allreduce_fn reduce, void *user, fitter_gather_fn gather = nullptr, bool split_native = false);
-int fitter_sharded_logpdf(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, const double *mesh_xyz_full,
-                          gingr_allreduce_fn reduce, void *user, double *logpdf, fitter_gather_fn gather = nullptr);
-int fitter_run_phase(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int phase);
+int fitter_sharded_update(gingr_fitter *f, const Correspondence &c, int32_t n_iterations, const double *z, gingr_allreduce_fn reduce,
+                          void *user, fitter_gather_fn gather = nullptr, bool split_native = false);
+int fitter_sharded_logpdf(gingr_fitter *f, const Correspondence &c, const double *mesh_xyz_full, gingr_allreduce_fn reduce, void *user,
+                          double *logpdf, fitter_gather_fn gather = nullptr);
+int fitter_run_phase(gingr_fitter *f, const Correspondence &c, int phase);  // one phase; the caller has checked the descriptor
+// the single shard's operations behind the entry points named after a flavour (they check the descriptor themselves)
+int fitter_update(gingr_fitter *f, const Correspondence &c, int32_t n_iterations);
+int fitter_sample_update(gingr_fitter *f, const Correspondence &c, const double *z);
+int fitter_posterior_logpdf(gingr_fitter *f, const Correspondence &c, const double *mesh_xyz, double *logpdf);
 int fitter_logpdf_prepare(gingr_fitter *f, const double *mesh_xyz_full);  // before the exchange of segment 1
 int fitter_logpdf_finish(gingr_fitter *f, double *logpdf);                // behind it
 int fitter_set_zrand(gingr_fitter *f, const double *z);                    // nullable: the next phase 2 draws a sample (device group)

@@ -382,48 +382,44 @@ int exchange_revsum(gingr_group *g, int r, int parity, bool ok) {
     return exchange_buffers(g, r, g->readyrev[parity], g->sendrev[parity], 0, fitter_revsum(g->fit[(size_t)r]), 4 * g->M_total, ok);
 }
 
-// flavour 0 CPD, 1 ICP point cloud, 2 ICP surface; z (nullable): the draws of a sampled proposal (one iteration)
-int group_update(gingr_group *g, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int32_t n_iterations, const double *z) {
-    if (!g || n_iterations < 0 || flavour < 0 || flavour > 2) return GINGR_ERR_BAD_ARGUMENT;
+// the flavours a group runs: CPD and the two of ICP (the pairs come from a host that talks to one fitter)
+bool group_flavour(const Correspondence &c) { return correspondence_error(c) != CorrespondenceError::BadFlavour && c.kind != Flavour::Pairs; }
+
+// z (nullable): the draws of a sampled proposal (one iteration)
+int group_update(gingr_group *g, const Correspondence &c, int32_t n_iterations, const double *z) {
+    if (!g || n_iterations < 0 || !group_flavour(c)) return GINGR_ERR_BAD_ARGUMENT;
     if (g->fit.empty() || !g->fit[0] || g->xch.empty()) return group_fail(g, GINGR_ERR_STATE, "group update: no model / target set");
-    const bool gather = flavour == 2 || (flavour == 1 && g->reversed);  // the tests against the template need all of it
+    const bool gather = needs_gathered_fit(c, g->reversed);  // the tests against the template need all of it
     if (gather && !g->meshes) return group_fail(g, GINGR_ERR_STATE, "group update: no meshes set (gingr_group_set_meshes)");
     if (z && n_iterations != 1) return group_fail(g, GINGR_ERR_BAD_ARGUMENT, "group update: a sampled proposal is one iteration");
     if (g->n == 1)
-        return g->run([&](int) {
-            gingr_fitter *f = g->fit[0];
-            if (z) {
-                if (flavour == 0) return gingr_fitter_update_cpd_sample_async(f, cp, z);
-                return flavour == 1 ? gingr_fitter_update_icp_sample_async(f, ip, z) : gingr_fitter_update_icp_surface_sample_async(f, ip, z);
-            }
-            if (flavour == 0) return gingr_fitter_update_cpd_async(f, cp, n_iterations);
-            return flavour == 1 ? gingr_fitter_update_icp_async(f, ip, n_iterations) : gingr_fitter_update_icp_surface_async(f, ip, n_iterations);
-        });
+        return g->run([&](int) { return z ? fitter_sample_update(g->fit[0], c, z) : fitter_update(g->fit[0], c, n_iterations); });
     const int64_t it0 = g->iteration;
     g->iteration += n_iterations;
     return g->run([&](int r) {
         gingr_fitter *f = g->fit[(size_t)r];
         int rc = fitter_set_zrand(f, z);  // (a shard that failed here still takes part in every exchange below, flagged not-ok)
+        if (!rc) rc = check_correspondence(f, c);
         for (int32_t it = 0; it < n_iterations; ++it) {
             const int parity = (int)((it0 + it) & 1);
             if (!rc) fitter_set_partial_output(f, g->send[parity][(size_t)r]);
             TimerScope ts(g->ctx[(size_t)r], 3);
             if (gather) {  // the whole posed template for the tests against it: gather the shards' rows of the fit
                 if (!rc) fitter_set_partial_fullfit(f, g->sendfit[parity][(size_t)r]);
-                if (!rc) rc = fitter_run_phase(f, flavour, cp, ip, GINGR_PHASE_GATHER);
+                if (!rc) rc = fitter_run_phase(f, c, GINGR_PHASE_GATHER);
                 const int xrc = exchange_fullfit(g, r, parity, rc == GINGR_OK);
                 if (!rc) rc = xrc;
             }
-            if (!rc && g->reversed && flavour != 0) fitter_set_partial_revsum(f, g->sendrev[parity][(size_t)r]);
+            if (!rc && exchanges_reversal_sums(c, g->reversed)) fitter_set_partial_revsum(f, g->sendrev[parity][(size_t)r]);
             for (int ph = 0; ph < GINGR_NUM_PHASES; ++ph) {
-                if (!rc) rc = fitter_run_phase(f, flavour, cp, ip, ph);
+                if (!rc) rc = fitter_run_phase(f, c, ph);
                 // ICP: the correspondence phase has nothing to exchange (rows are independent) ...
-                if (ph < GINGR_NUM_SEGMENTS && !(flavour != 0 && ph == 0)) {
+                if (ph < GINGR_NUM_SEGMENTS && (ph != 0 || exchanges_segment0(c))) {
                     const int xrc = timed_exchange_segment(g, r, ph, parity, rc == GINGR_OK);
                     if (!rc) rc = xrc;
                 }
                 // ... except in the reversed direction: every shard scanned its range of the target queries, the sums are totalled
-                if (ph == 0 && flavour != 0 && g->reversed) {
+                if (ph == 0 && exchanges_reversal_sums(c, g->reversed)) {
                     const int xrc = exchange_revsum(g, r, parity, rc == GINGR_OK);
                     if (!rc) rc = xrc;
                 }
@@ -436,42 +432,36 @@ int group_update(gingr_group *g, int flavour, const gingr_cpd_params *cp, const 
 
 // posterior(state).gp.logpdf(posterior.coefficients(mesh)): phases 0 and 1 with their exchanges, Q0^T e in the tail of segment 1, the
 // log-density kernel replicated on every shard (shard 0's value is returned; they are bit-identical)
-int group_logpdf(gingr_group *g, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, const double *mesh_xyz_full,
-                 double *logpdf) {
-    if (!g || !mesh_xyz_full || !logpdf || flavour < 0 || flavour > 2) return GINGR_ERR_BAD_ARGUMENT;
+int group_logpdf(gingr_group *g, const Correspondence &c, const double *mesh_xyz_full, double *logpdf) {
+    if (!g || !mesh_xyz_full || !logpdf || !group_flavour(c)) return GINGR_ERR_BAD_ARGUMENT;
     if (g->fit.empty() || !g->fit[0] || g->xch.empty()) return group_fail(g, GINGR_ERR_STATE, "group posterior_logpdf: no model / target set");
-    const bool gather = flavour == 2 || (flavour == 1 && g->reversed);
+    const bool gather = needs_gathered_fit(c, g->reversed);
     if (gather && !g->meshes) return group_fail(g, GINGR_ERR_STATE, "group posterior_logpdf: no meshes set (gingr_group_set_meshes)");
     if (g->n == 1)
-        return g->run([&](int) {
-            gingr_fitter *f = g->fit[0];
-            if (flavour == 0) return gingr_fitter_posterior_logpdf_cpd(f, cp, mesh_xyz_full, logpdf);
-            return flavour == 1 ? gingr_fitter_posterior_logpdf_icp(f, ip, mesh_xyz_full, logpdf)
-                                : gingr_fitter_posterior_logpdf_icp_surface(f, ip, mesh_xyz_full, logpdf);
-        });
+        return g->run([&](int) { return fitter_posterior_logpdf(g->fit[0], c, mesh_xyz_full, logpdf); });
     const int parity = (int)(g->iteration & 1);
     g->iteration += 1;
     std::vector<double> out((size_t)g->n, 0.0);
     GINGR_TRY(g->run([&](int r) {
-        int rc = GINGR_OK;
         gingr_fitter *f = g->fit[(size_t)r];
+        int rc = check_correspondence(f, c);
         fitter_set_partial_output(f, g->send[parity][(size_t)r]);
         if (gather) {
             fitter_set_partial_fullfit(f, g->sendfit[parity][(size_t)r]);
-            rc = fitter_run_phase(f, flavour, cp, ip, GINGR_PHASE_GATHER);
+            if (!rc) rc = fitter_run_phase(f, c, GINGR_PHASE_GATHER);
             const int xrc = exchange_fullfit(g, r, parity, rc == GINGR_OK);
             if (!rc) rc = xrc;
         }
-        if (!rc && g->reversed && flavour != 0) fitter_set_partial_revsum(f, g->sendrev[parity][(size_t)r]);
-        if (!rc) rc = fitter_run_phase(f, flavour, cp, ip, 0);
-        if (flavour == 0) {
+        if (!rc && exchanges_reversal_sums(c, g->reversed)) fitter_set_partial_revsum(f, g->sendrev[parity][(size_t)r]);
+        if (!rc) rc = fitter_run_phase(f, c, 0);
+        if (exchanges_segment0(c)) {
             const int xrc = exchange_segment(g, r, 0, parity, rc == GINGR_OK);
             if (!rc) rc = xrc;
-        } else if (g->reversed) {
+        } else if (exchanges_reversal_sums(c, g->reversed)) {
             const int xrc = exchange_revsum(g, r, parity, rc == GINGR_OK);
             if (!rc) rc = xrc;
         }
-        if (!rc) rc = fitter_run_phase(f, flavour, cp, ip, 1);
+        if (!rc) rc = fitter_run_phase(f, c, 1);
         if (!rc) rc = fitter_logpdf_prepare(f, mesh_xyz_full);
         const int xrc = exchange_segment(g, r, 1, parity, rc == GINGR_OK);
         if (!rc) rc = xrc;
@@ -766,12 +756,12 @@ int gingr_group_set_correspondence_direction(gingr_group *g, int32_t reversed) {
 
 int gingr_group_update_async(gingr_group *g, int32_t flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int32_t n_iterations,
                              const double *z) {
-    return group_update(g, flavour, cp, ip, n_iterations, z);
+    return group_update(g, abi_correspondence(flavour, cp, ip), n_iterations, z);
 }
 
 int gingr_group_posterior_logpdf(gingr_group *g, int32_t flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip,
                                  const double *mesh_xyz_full, double *logpdf) {
-    return group_logpdf(g, flavour, cp, ip, mesh_xyz_full, logpdf);
+    return group_logpdf(g, abi_correspondence(flavour, cp, ip), mesh_xyz_full, logpdf);
 }
 
 int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, int32_t *fine_grained) {
@@ -811,12 +801,12 @@ int gingr_group_get_state(gingr_group *g, double *alpha, gingr_state_scalars *s,
 
 int gingr_group_update_cpd_async(gingr_group *g, const gingr_cpd_params *p, int32_t n_iterations) {
     if (!g || !p) return GINGR_ERR_BAD_ARGUMENT;
-    return group_update(g, 0, p, nullptr, n_iterations, nullptr);
+    return group_update(g, abi_correspondence(0, p, nullptr), n_iterations, nullptr);
 }
 
 int gingr_group_update_icp_async(gingr_group *g, const gingr_icp_params *p, int32_t n_iterations) {
     if (!g || !p) return GINGR_ERR_BAD_ARGUMENT;
-    return group_update(g, 1, nullptr, p, n_iterations, nullptr);
+    return group_update(g, abi_correspondence(1, nullptr, p), n_iterations, nullptr);
 }
 
 int gingr_group_synchronize(gingr_group *g) {

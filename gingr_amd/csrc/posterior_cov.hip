@@ -315,18 +315,14 @@ int gingr_model_cross_covariance(gingr_ctx *ctx, const gingr_model *model, const
 // posterior(of the current state).gp.cov(pid, pid) for every vertex: built like posterior_logpdf (fitter_mh.hip) -- phases 0 and 1
 // of the state (they do not touch it; landmarks are in G already), the factor of I + G, one pass over the basis with the state's
 // rotation.  The posterior is that of model.transform(rigid) (GingrAlgorithm.scala:297-301): no scale.
-static int posterior_covariance(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, double *cov6_out) {
-    GINGR_TRY(check_ready(f));
+static int posterior_covariance(gingr_fitter *f, const Correspondence &c, double *cov6_out) {
+    GINGR_TRY(check_correspondence(f, c));
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
     if (!cov6_out) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "posterior_covariance: null argument");
     if (m->M != m->M_total || f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "posterior_covariance: single shard only");
     const int64_t M = m->M;
-    f->allow_alt = true;
-    int prc = GINGR_OK;
-    for (int ph = 0; ph < 2 && prc == GINGR_OK; ++ph) prc = fitter_run_phase(f, flavour, cp, ip, ph);
-    f->allow_alt = false;
-    GINGR_TRY(prc);
+    GINGR_TRY(fitter_posterior_inputs(f, c));
     HIP_TRY(ctx, ensure(f->cov_work, (size_t)posterior_factor_work_doubles(m->rp) * sizeof(double)));
     HIP_TRY(ctx, ensure(f->cov_out, (size_t)6 * M * sizeof(double)));
     int64_t ldw = 0;
@@ -345,27 +341,16 @@ static int posterior_covariance(gingr_fitter *f, int flavour, const gingr_cpd_pa
 }
 
 int gingr_fitter_posterior_covariance_cpd(gingr_fitter *f, const gingr_cpd_params *p, double *cov6_out) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    if (!p || !(p->w >= 0.0 && p->w < 1.0) || !(p->lambda > 0.0))
-        return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "cpd params: need 0 <= w < 1 and lambda > 0");
-    return posterior_covariance(f, 0, p, nullptr, cov6_out);
+    return posterior_covariance(f, abi_correspondence(0, p, nullptr), cov6_out);
 }
-
 int gingr_fitter_posterior_covariance_icp(gingr_fitter *f, const gingr_icp_params *p, double *cov6_out) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
-    return posterior_covariance(f, 1, nullptr, p, cov6_out);
+    return posterior_covariance(f, abi_correspondence(1, nullptr, p), cov6_out);
 }
-
 int gingr_fitter_posterior_covariance_icp_surface(gingr_fitter *f, const gingr_icp_params *p, double *cov6_out) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
-    return posterior_covariance(f, 2, nullptr, p, cov6_out);
+    return posterior_covariance(f, abi_correspondence(2, nullptr, p), cov6_out);
 }
-
 int gingr_fitter_posterior_covariance_pairs(gingr_fitter *f, double *cov6_out) {
-    if (!f) return GINGR_ERR_BAD_ARGUMENT;
-    return posterior_covariance(f, 3, nullptr, nullptr, cov6_out);
+    return posterior_covariance(f, abi_correspondence(3, nullptr, nullptr), cov6_out);
 }
 
 }  // extern "C"

@@ -176,16 +176,14 @@ static int posterior_model_build(gingr_fitter *f, const double *G, const double 
 
 // posterior model of the fitter's current state: built like posterior_covariance (posterior_cov.hip) -- phases 0 and 1 of the state
 // (they do not touch it; landmarks are in G already), then the common part
-static int fitter_posterior_model(gingr_fitter *f, int flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, gingr_model **out) {
-    GINGR_TRY(check_ready(f));
+static int fitter_posterior_model(gingr_fitter *f, const Correspondence &c, gingr_model **out) {
+    if (!out) return GINGR_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    GINGR_TRY(check_correspondence(f, c));
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
     if (m->M != m->M_total || f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "posterior_model: single shard only");
-    f->allow_alt = true;
-    int prc = GINGR_OK;
-    for (int ph = 0; ph < 2 && prc == GINGR_OK; ++ph) prc = fitter_run_phase(f, flavour, cp, ip, ph);
-    f->allow_alt = false;
-    GINGR_TRY(prc);
+    GINGR_TRY(fitter_posterior_inputs(f, c));
     const double *G = f->seg1_live();
     return posterior_model_build(f, G, G + (int64_t)m->rp * m->rp, "posterior_model", out);
 }
@@ -210,31 +208,16 @@ int gingr_model_posterior(gingr_ctx *ctx, const gingr_model *model, const double
 }
 
 int gingr_fitter_posterior_model_cpd(gingr_fitter *f, const gingr_cpd_params *p, gingr_model **out) {
-    if (!f || !out) return GINGR_ERR_BAD_ARGUMENT;
-    *out = nullptr;
-    if (!p || !(p->w >= 0.0 && p->w < 1.0) || !(p->lambda > 0.0))
-        return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "cpd params: need 0 <= w < 1 and lambda > 0");
-    return fitter_posterior_model(f, 0, p, nullptr, out);
+    return fitter_posterior_model(f, abi_correspondence(0, p, nullptr), out);
 }
-
 int gingr_fitter_posterior_model_icp(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out) {
-    if (!f || !out) return GINGR_ERR_BAD_ARGUMENT;
-    *out = nullptr;
-    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
-    return fitter_posterior_model(f, 1, nullptr, p, out);
+    return fitter_posterior_model(f, abi_correspondence(1, nullptr, p), out);
 }
-
 int gingr_fitter_posterior_model_icp_surface(gingr_fitter *f, const gingr_icp_params *p, gingr_model **out) {
-    if (!f || !out) return GINGR_ERR_BAD_ARGUMENT;
-    *out = nullptr;
-    if (!p || p->max_iterations < 1) return gingr_set_error(f->ctx, GINGR_ERR_BAD_ARGUMENT, "icp params: max_iterations < 1");
-    return fitter_posterior_model(f, 2, nullptr, p, out);
+    return fitter_posterior_model(f, abi_correspondence(2, nullptr, p), out);
 }
-
 int gingr_fitter_posterior_model_pairs(gingr_fitter *f, gingr_model **out) {
-    if (!f || !out) return GINGR_ERR_BAD_ARGUMENT;
-    *out = nullptr;
-    return fitter_posterior_model(f, 3, nullptr, nullptr, out);
+    return fitter_posterior_model(f, abi_correspondence(3, nullptr, nullptr), out);
 }
 
 }  // extern "C"

@@ -202,14 +202,14 @@ int gingr_fitter_update_cpd_rccl_async(gingr_fitter *f, const gingr_cpd_params *
     if (!f) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = fitter_ctx(f);
     if (!ctx->rccl_comm) return gingr_set_error(ctx, GINGR_ERR_STATE, "update_cpd_rccl: no communicator (gingr_ctx_rccl_init)");
-    return fitter_sharded_update(f, 0, p, nullptr, n_iterations, nullptr, native_allreduce, ctx, nullptr, ctx->split_exchange != 0);
+    return fitter_sharded_update(f, abi_correspondence(0, p, nullptr), n_iterations, nullptr, native_allreduce, ctx, nullptr, ctx->split_exchange != 0);
 }
 
 int gingr_fitter_update_icp_rccl_async(gingr_fitter *f, const gingr_icp_params *p, int32_t n_iterations) {
     if (!f) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = fitter_ctx(f);
     if (!ctx->rccl_comm) return gingr_set_error(ctx, GINGR_ERR_STATE, "update_icp_rccl: no communicator (gingr_ctx_rccl_init)");
-    return gingr_fitter_update_icp_sharded_async(f, p, n_iterations, native_allreduce, ctx);
+    return fitter_sharded_update(f, abi_correspondence(1, nullptr, p), n_iterations, nullptr, native_allreduce, ctx);
 }
 
 int gingr_fitter_update_rccl_async(gingr_fitter *f, int32_t flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip, int32_t n_iterations,
@@ -217,7 +217,7 @@ int gingr_fitter_update_rccl_async(gingr_fitter *f, int32_t flavour, const gingr
     if (!f) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = fitter_ctx(f);
     if (!ctx->rccl_comm) return gingr_set_error(ctx, GINGR_ERR_STATE, "update_rccl: no communicator (gingr_ctx_rccl_init)");
-    return fitter_sharded_update(f, flavour, cp, ip, n_iterations, z, native_allreduce, ctx, native_gather, ctx->split_exchange != 0);
+    return fitter_sharded_update(f, abi_correspondence(flavour, cp, ip), n_iterations, z, native_allreduce, ctx, native_gather, ctx->split_exchange != 0);
 }
 
 int gingr_fitter_posterior_logpdf_rccl(gingr_fitter *f, int32_t flavour, const gingr_cpd_params *cp, const gingr_icp_params *ip,
@@ -225,7 +225,7 @@ int gingr_fitter_posterior_logpdf_rccl(gingr_fitter *f, int32_t flavour, const g
     if (!f) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = fitter_ctx(f);
     if (!ctx->rccl_comm) return gingr_set_error(ctx, GINGR_ERR_STATE, "posterior_logpdf_rccl: no communicator (gingr_ctx_rccl_init)");
-    return fitter_sharded_logpdf(f, flavour, cp, ip, mesh_xyz_full, native_allreduce, ctx, logpdf, native_gather);
+    return fitter_sharded_logpdf(f, abi_correspondence(flavour, cp, ip), mesh_xyz_full, native_allreduce, ctx, logpdf, native_gather);
 }
 
 }  // extern "C"

@@ -122,11 +122,11 @@ class DeviceGroup:
     @staticmethod
     def _params(flavour: int, params):
         cp = nat.CpdParams(*params) if flavour == nat.FLAVOUR_CPD else None
-        ip = nat.IcpParams(*params) if flavour != nat.FLAVOUR_CPD else None
+        ip = nat.IcpParams(*params) if flavour in (nat.FLAVOUR_ICP, nat.FLAVOUR_ICP_SURFACE) else None
         return cp, ip
 
     def update(self, flavour: int, params, n_iterations: int = 1, z=None):
-        """flavour 0 CPD (params = (w, lambda)), 1 ICP point cloud, 2 ICP surface (params = (initialSigma, endSigma, maxIterations));
+        """flavour FLAVOUR_CPD (params = (w, lambda)), FLAVOUR_ICP, FLAVOUR_ICP_SURFACE (params = (initialSigma, endSigma, maxIterations));
         z: rank standard normals = the sampled proposal (one iteration)."""
         cp, ip = self._params(flavour, params)
         zz = None if z is None else f64(z)

@@ -46,18 +46,20 @@ SEGMENT_REVSUM = nat.SEGMENT_REVSUM
 
 
 def drive_update(run_phase: Callable[[int], None], all_reduce_segment: Callable[[int], None], world: int,
-                 skip_segment0: bool = False, flavour: int = 0, reversed_direction: bool = False) -> None:
-    """One iteration in the order of fitter_sharded_update (gingr_amd/csrc/fitter_phases.hip): for the surface correspondence (flavour 2)
-    the gather of the fit first; then phase p followed (for p < 2) by the all-reduce of exchange segment p -- the ICP flavours
-    exchange nothing after phase 0 (their closest-point search is local to the shard's rows)."""
-    if (flavour == 2 or (flavour == 1 and reversed_direction)) and world > 1:   # (the reversed direction works on the gathered template)
+                 skip_segment0: bool = False, flavour: int = nat.FLAVOUR_CPD, reversed_direction: bool = False) -> None:
+    """One iteration in the order of fitter_sharded_update (gingr_amd/csrc/fitter_phases.hip; the rules are those of
+    gingr_amd/csrc/correspondence.h): for the surface correspondence the gather of the fit first; then phase p followed (for p < 2) by
+    the all-reduce of exchange segment p -- only CPD exchanges something after phase 0 (the others' correspondences are local to the
+    shard's rows)."""
+    icp = flavour in (nat.FLAVOUR_ICP, nat.FLAVOUR_ICP_SURFACE)
+    if (flavour == nat.FLAVOUR_ICP_SURFACE or (icp and reversed_direction)) and world > 1:   # (the reversed direction works on the gathered template)
         run_phase(PHASE_GATHER)
         all_reduce_segment(SEGMENT_FULLFIT)
     for ph in range(NUM_PHASES):
         run_phase(ph)
-        if world > 1 and ph < 2 and not ((skip_segment0 or flavour != 0) and ph == 0):
+        if world > 1 and ph < 2 and not ((skip_segment0 or flavour != nat.FLAVOUR_CPD) and ph == 0):
             all_reduce_segment(ph)
-        if world > 1 and ph == 0 and flavour != 0 and reversed_direction:
+        if world > 1 and ph == 0 and icp and reversed_direction:
             # every shard scanned its index range of the target queries: the per-template-vertex sums are totalled
             all_reduce_segment(SEGMENT_REVSUM)
 
@@ -272,11 +274,11 @@ class ShardedFitter:
     @staticmethod
     def _params(flavour: int, params):
         cp = nat.CpdParams(*params) if flavour == nat.FLAVOUR_CPD else None
-        ip = nat.IcpParams(*params) if flavour != nat.FLAVOUR_CPD else None
+        ip = nat.IcpParams(*params) if flavour in (nat.FLAVOUR_ICP, nat.FLAVOUR_ICP_SURFACE) else None
         return (ctypes.byref(cp) if cp else None), (ctypes.byref(ip) if ip else None), (cp, ip)
 
     def update(self, flavour: int, params, n_iterations: int = 1, z=None):
-        """flavour 0 CPD (params = (w, lambda)), 1 ICP point cloud, 2 ICP surface (params = (initialSigma, endSigma, maxIterations));
+        """flavour FLAVOUR_CPD (params = (w, lambda)), FLAVOUR_ICP, FLAVOUR_ICP_SURFACE (params = (initialSigma, endSigma, maxIterations));
         z: rank standard normals = update(current, probabilistic = true), one iteration, the same on every rank."""
         cpp, ipp, _keep = self._params(flavour, params)
         zz = None if z is None else f64(z)
