@@ -1,7 +1,9 @@
 """gingr_amd -- MI355X (gfx950) implementation of GiNGR's per-iteration GP-regression update.
 
-Only what the hot path needs: `csrc/` (HIP kernels + the C ABI of include/gingr_hip.h), `_native` (ctypes binding) and
-`api` (host-side mirror of the reference's GingrConfig / GingrRegistrationState / GingrAlgorithm plugin surface).
+Only what the hot path needs: `csrc/` (HIP kernels + the C ABI of include/gingr_hip.h), `_native` (ctypes binding) and the
+host-side mirror of the reference's GingrConfig / GingrRegistrationState / GingrAlgorithm plugin surface: `context` (Context),
+`models` (point distribution models, host and resident), `states` (configuration and state records), `registration`
+(GingrAlgorithm and its CPD / ICP / Template flavours), with `api` as the one place all their names can be imported from.
 There is no CPU implementation in this package.
 """
 from .api import (  # noqa: F401

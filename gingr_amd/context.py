@@ -1,0 +1,191 @@
+"""The context wrapper: `Context` (gingr_ctx: one device, one stream, the stateless all-pairs and mesh operators) and `_check`, which
+turns a native error code into a GingrNativeError.  Everything else in the package is built on these two."""
+from __future__ import annotations
+
+import ctypes
+from ctypes import c_int64, c_void_p
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _native as nat
+from ._native import GingrNativeError, f64, dptr, iptr
+
+
+def _check(ctx_handle, code: int, where: str):
+    if code != nat.GINGR_OK:
+        text = ""
+        if ctx_handle:
+            text = (nat.load().gingr_last_error(ctx_handle) or b"").decode("utf-8", "replace")
+        raise GingrNativeError(code, where, text)
+
+
+# ----------------------------------------------------------------------------- context + operators
+class Context:
+    """One device + one stream (gingr_ctx).  Not thread-safe; one per chain / per GPU."""
+
+    def __init__(self, device: int = 0):
+        self._lib = nat.load()
+        h = c_void_p()
+        code = self._lib.gingr_ctx_create(int(device), ctypes.byref(h))
+        if code != nat.GINGR_OK:
+            raise GingrNativeError(code, "gingr_ctx_create", "(no usable GPU: this package has no CPU path)")
+        self.handle = h
+        self.device = device
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.gingr_ctx_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def synchronize(self):
+        _check(self.handle, self._lib.gingr_ctx_synchronize(self.handle), "gingr_ctx_synchronize")
+
+    def set_stream(self, hip_stream: Optional[int]):
+        _check(self.handle, self._lib.gingr_ctx_set_stream(self.handle, c_void_p(hip_stream or 0)), "gingr_ctx_set_stream")
+
+    # timing hooks (bench.py roofline)
+    def get_stream(self) -> int:
+        """The hipStream_t (as an integer) the context's kernels are enqueued on."""
+        return int(self._lib.gingr_ctx_get_stream(self.handle) or 0)
+
+    def timing_enable(self, on: bool = True):
+        _check(self.handle, self._lib.gingr_ctx_timing_enable(self.handle, 1 if on else 0), "timing_enable")
+
+    def timing_reset(self):
+        _check(self.handle, self._lib.gingr_ctx_timing_reset(self.handle), "timing_reset")
+
+    def timing_read(self, which: int) -> Tuple[float, int]:
+        ms = ctypes.c_double()
+        n = c_int64()
+        _check(self.handle, self._lib.gingr_ctx_timing_read(self.handle, which, ctypes.byref(ms), ctypes.byref(n)), "timing_read")
+        return ms.value, n.value
+
+    def set_option(self, option: int, value: int):
+        """gingr_ctx_set_option: nat.OPT_CULL / OPT_FINE_CULL / OPT_NN_GRID -- code paths with identical results (tests, A/B timing)."""
+        _check(self.handle, self._lib.gingr_ctx_set_option(self.handle, int(option), int(value)), "gingr_ctx_set_option")
+
+    def get_option(self, option: int) -> int:
+        v = ctypes.c_int32()
+        _check(self.handle, self._lib.gingr_ctx_get_option(self.handle, int(option), ctypes.byref(v)), "gingr_ctx_get_option")
+        return int(v.value)
+
+    # ---- native RCCL exchange (one process per GPU; the library enqueues ncclAllReduce on this context's stream)
+    def rccl_load(self, path: Optional[str] = None):
+        """Bind a specific librccl (default: the copy already loaded in the process, e.g. torch's, else the loader's search path)."""
+        _check(self.handle, self._lib.gingr_rccl_load(self.handle, path.encode() if path else None), "gingr_rccl_load")
+
+    def rccl_unique_id(self) -> bytes:
+        """ncclGetUniqueId: rank 0 creates it, the host distributes the 128 bytes to every rank."""
+        buf = ctypes.create_string_buffer(nat.RCCL_UNIQUE_ID_BYTES)
+        _check(self.handle, self._lib.gingr_rccl_unique_id(self.handle, buf), "gingr_rccl_unique_id")
+        return bytes(buf.raw)
+
+    def rccl_init(self, unique_id: bytes, world: int, rank: int):
+        """ncclCommInitRank on this context's device (collective over the `world` ranks); the communicator dies with the context."""
+        assert len(unique_id) == nat.RCCL_UNIQUE_ID_BYTES
+        buf = ctypes.create_string_buffer(unique_id, nat.RCCL_UNIQUE_ID_BYTES)
+        _check(self.handle, self._lib.gingr_ctx_rccl_init(self.handle, buf, int(world), int(rank)), "gingr_ctx_rccl_init")
+
+    def rccl_info(self) -> dict:
+        w, r, v = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        path = ctypes.create_string_buffer(512)
+        _check(self.handle, self._lib.gingr_ctx_rccl_info(self.handle, ctypes.byref(w), ctypes.byref(r), ctypes.byref(v), path, 512),
+               "gingr_ctx_rccl_info")
+        return {"world": int(w.value), "rank": int(r.value), "version": int(v.value), "library": path.value.decode()}
+
+    def rccl_allreduce(self, device_ptr: int, count: int):
+        """In-place float64 sum all-reduce of `count` elements at `device_ptr`, enqueued on this context's stream."""
+        _check(self.handle, self._lib.gingr_ctx_rccl_allreduce_async(self.handle, c_void_p(int(device_ptr)), int(count)),
+               "gingr_ctx_rccl_allreduce_async")
+
+    def nn_counting(self, on: bool = True):
+        """Diagnostics: count the distance tests the nearest-neighbour launches of this context really execute (clears the counter)."""
+        _check(self.handle, self._lib.gingr_ctx_nn_counting(self.handle, 1 if on else 0), "nn_counting")
+
+    def nn_tests(self) -> int:
+        n = c_int64()
+        _check(self.handle, self._lib.gingr_ctx_nn_tests(self.handle, ctypes.byref(n)), "nn_tests")
+        return int(n.value)
+
+    # ---- stateless all-pairs operators -------------------------------------------------
+    def cpd_stats(self, fit, target, sigma2: float, w: float = 0.0) -> dict:
+        """CPD statistics of one affinity evaluation (CPD.scala:54-75,36,133-147), P never materialised."""
+        y, x = f64(fit), f64(target)
+        M, N = y.shape[0], x.shape[0]
+        den, Pt1 = np.empty(N), np.empty(N)
+        P1, PX, sc = np.empty(M), np.empty((M, 3)), np.empty(6)
+        _check(self.handle, self._lib.gingr_cpd_stats(self.handle, M, dptr(y), N, dptr(x), float(sigma2), float(w),
+                                                      dptr(den), dptr(P1), dptr(PX), dptr(Pt1), dptr(sc)), "gingr_cpd_stats")
+        return dict(den=den, P1=P1, PX=PX, Pt1=Pt1, Np=float(sc[0]), xPx=float(sc[1]), trPXY=float(sc[2]),
+                    yPy=float(sc[3]), sigma2_next=float(sc[4]), c=float(sc[5]))
+
+    def cpd_initial_sigma2(self, reference, target) -> float:
+        y, x = f64(reference), f64(target)
+        out = ctypes.c_double()
+        _check(self.handle, self._lib.gingr_cpd_initial_sigma2(self.handle, y.shape[0], dptr(y), x.shape[0], dptr(x),
+                                                               ctypes.byref(out)), "gingr_cpd_initial_sigma2")
+        return out.value
+
+    def nn(self, query, target) -> Tuple[np.ndarray, np.ndarray, float]:
+        """Exact nearest neighbour, lowest index on ties (ClosestPointRegistrator.scala:133-148)."""
+        y, x = f64(query), f64(target)
+        idx = np.empty(y.shape[0], dtype=np.int32)
+        d2 = np.empty(y.shape[0])
+        md = ctypes.c_double()
+        _check(self.handle, self._lib.gingr_nn(self.handle, y.shape[0], dptr(y), x.shape[0], dptr(x), iptr(idx), dptr(d2),
+                                               ctypes.byref(md)), "gingr_nn")
+        return idx, d2, md.value
+
+    def gauss_block(self, A, B, sigma: float, scaling: float) -> np.ndarray:
+        """scaling * exp(-|a-b|^2 / sigma^2)  (GPMMHelper.scala:99-102)."""
+        A, B = f64(A), f64(B)
+        out = np.empty((A.shape[0], B.shape[0]))
+        _check(self.handle, self._lib.gingr_gauss_block(self.handle, A.shape[0], dptr(A), B.shape[0], dptr(B), float(sigma),
+                                                        float(scaling), dptr(out)), "gingr_gauss_block")
+        return out
+
+    def mesh_distance_stats(self, points, vertices, cells, boundary_aware: bool = False, sdev: float = 0.0
+                            ) -> Tuple[float, float, int, float]:
+        """(sum, max, count, sum of log N(d; 0, sdev)) of d = |p - closestPointOnSurface(p)| for the rows of `points` against
+        the triangle mesh (vertices, cells); boundary_aware as RegistrationComparison.avgDistanceBoundaryAware (:63-73)."""
+        p, v = f64(points), f64(vertices)
+        c = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros(4)
+        _check(self.handle, self._lib.gingr_mesh_distance_stats(self.handle, p.shape[0], dptr(p), v.shape[0], dptr(v), c.shape[0],
+                                                                iptr(c), int(bool(boundary_aware)), float(sdev), dptr(out)),
+               "gingr_mesh_distance_stats")
+        return float(out[0]), float(out[1]), int(out[2]), float(out[3])
+
+    def mesh_closest_points(self, points, vertices, cells) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """mesh.operations.closestPointOnSurface for every row of `points`: (closest points (n,3), squared distances (n,), triangle
+        ids (n,), barycentric weights of that triangle's corners (n,3)) -- gingr_mesh_closest_points."""
+        p, v = f64(points).reshape(-1, 3), f64(vertices).reshape(-1, 3)
+        c = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = p.shape[0]
+        cp, d2, tid, bary = np.empty((n, 3)), np.empty(n), np.empty(n, dtype=np.int32), np.empty((n, 3))
+        _check(self.handle, self._lib.gingr_mesh_closest_points(self.handle, n, dptr(p), v.shape[0], dptr(v), c.shape[0], iptr(c),
+                                                                dptr(cp), dptr(d2), iptr(tid), dptr(bary)),
+               "gingr_mesh_closest_points")
+        return cp, d2, tid, bary
+
+    def mesh_decimate(self, vertices, cells, n_target: int) -> Tuple[np.ndarray, Optional[np.ndarray], float]:
+        """Vertex clustering to about `n_target` vertices on the device -- gingr_mesh_decimate, the result of
+        `gingr_amd.simple.cluster_decimate` bit for bit: (kept vertex ids, ascending (k,) int32; the re-indexed triangles (t,3) int32,
+        or None for a point cloud (cells=None); the chosen cube size, 0.0 when nothing was decimated)."""
+        v = f64(vertices).reshape(-1, 3)
+        c = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n, t = v.shape[0], 0 if c is None else c.shape[0]
+        kept = np.empty(max(n, 1), dtype=np.int32)
+        out = None if c is None else np.empty((max(t, 1), 3), dtype=np.int32)
+        nk, nt, h = c_int64(), c_int64(), ctypes.c_double()
+        _check(self.handle, self._lib.gingr_mesh_decimate(self.handle, n, dptr(v), t, iptr(c), int(n_target), ctypes.byref(nk), iptr(kept),
+                                                          ctypes.byref(nt), iptr(out), ctypes.byref(h)), "gingr_mesh_decimate")
+        return kept[:nk.value].copy(), None if c is None else out[:nt.value].copy(), h.value
+

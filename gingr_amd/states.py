@@ -1,0 +1,194 @@
+"""The records a registration is described by -- the enums, the fitting parameters, the correspondence lists, the general state and the
+configuration / state pair of each algorithm -- with the reference's names and field order.  Plain data: nothing here calls into the
+library, and the model and algorithm modules are only named in annotations.
+
+  GeneralRegistrationState, ModelFittingParameters              G/api/GeneralRegistrationState.scala:28-41,
+                                                                G/api/ModelFittingParameters.scala:31-57
+  CpdConfiguration / CpdRegistrationState                       G/api/registration/config/CPD.scala:52-155
+  IcpConfiguration / IcpRegistrationState                       G/api/registration/config/ICP.scala:54-107
+  TemplateConfiguration / TemplateRegistrationState             G/api/registration/config/Template.scala:24-60
+  GlobalTranformationType, FittingStatuses                      G/api/GlobalTranformationType.scala:20-24,
+                                                                G/api/FittingStatuses.scala:22
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import TYPE_CHECKING, Callable, Optional, Tuple
+
+import numpy as np
+
+if TYPE_CHECKING:
+    from .models import PointDistributionModel
+
+
+# ----------------------------------------------------------------------------- enums
+class GlobalTranformationType:  # sic: the reference spells it this way
+    NoTransforms = 0
+    RigidTransforms = 1
+    SimilarityTransforms = 2
+
+
+class FittingStatuses:
+    None_ = 0
+    Converged = 1
+    MaxIteration = 2
+    ModelFlexibilityError = 3
+
+
+# ----------------------------------------------------------------------------- state records
+@dataclasses.dataclass(frozen=True)
+class EulerAngles:
+    phi: float = 0.0
+    theta: float = 0.0
+    psi: float = 0.0
+
+
+@dataclasses.dataclass(frozen=True)
+class ModelFittingParameters:
+    """scale, pose = (translation, Euler rotation about a centre), shape  (ModelFittingParameters.scala:31-57)."""
+    scale: float
+    translation: Tuple[float, float, float]
+    rotation: EulerAngles
+    center: Tuple[float, float, float]
+    shape: np.ndarray
+
+    @staticmethod
+    def zero(rank: int) -> "ModelFittingParameters":
+        return ModelFittingParameters(1.0, (0.0, 0.0, 0.0), EulerAngles(), (0.0, 0.0, 0.0), np.zeros(rank))
+
+
+@dataclasses.dataclass
+class LandmarkCorrespondences:
+    """(pid, target point, 3x3 covariance) triples (GeneralRegistrationState.scala:43-62)."""
+    pids: np.ndarray
+    points: np.ndarray
+    covs: np.ndarray
+
+
+@dataclasses.dataclass(frozen=True)
+class CorrespondencePairs:
+    """(PointId, Point) pairs (G/api/CorrespondencePairs.scala:23)."""
+    pids: np.ndarray
+    points: np.ndarray
+
+
+@dataclasses.dataclass(frozen=True)
+class GeneralRegistrationState:
+    model: PointDistributionModel
+    modelParameters: ModelFittingParameters
+    target: np.ndarray
+    fit: np.ndarray
+    sigma2: float = 1.0
+    globalTransformation: int = GlobalTranformationType.RigidTransforms
+    stepLength: float = 1.0
+    generatedBy: str = ""
+    iteration: int = 0
+    status: int = FittingStatuses.None_
+    landmarkCorrespondences: Optional[LandmarkCorrespondences] = None
+    targetCells: Optional[np.ndarray] = None   # (T,3) int: triangulation of the target mesh (surface ICP only)
+
+    def updateStatus(self, status: int) -> "GeneralRegistrationState":
+        return dataclasses.replace(self, status=status)
+
+    def updateSigma2(self, s2: float) -> "GeneralRegistrationState":
+        return dataclasses.replace(self, sigma2=s2)
+
+    def statusText(self) -> str:
+        """GeneralRegistrationState.printStatus (GeneralRegistrationState.scala:103-114)"""
+        n = self.iteration + 1
+        return {FittingStatuses.None_: "Initial state - no iterations performed!",
+                FittingStatuses.Converged: f"Fitting converged after {n} accepted iterations!",
+                FittingStatuses.MaxIteration: f"Fitting finished the MaxIterations with ({n}) accepted iterations!",
+                FittingStatuses.ModelFlexibilityError:
+                    f"Model not flexible enough to compute posterior model - finished after {n} accepted iterations!"}[self.status]
+
+    def printStatus(self) -> None:
+        print(self.statusText())
+
+
+# ----------------------------------------------------------------------------- configs
+def _cpd_converged(last: GeneralRegistrationState, current: GeneralRegistrationState, threshold: float) -> bool:
+    return abs(last.sigma2 - current.sigma2) < threshold          # CPD.scala:108-110
+
+
+def _never_converged(last, current, threshold) -> bool:
+    return False                                                   # ICP.scala:57-58
+
+
+@dataclasses.dataclass(frozen=True)
+class CpdConfiguration:
+    maxIterations: int = 100
+    threshold: float = 1e-10
+    converged: Callable = _cpd_converged
+    useLandmarkCorrespondence: bool = True
+    initialSigma: Optional[float] = None
+    w: float = 0.0
+    lambda_: float = 1.0
+
+
+@dataclasses.dataclass(frozen=True)
+class IcpConfiguration:
+    maxIterations: int = 100
+    threshold: float = 1e-10
+    converged: Callable = _never_converged
+    useLandmarkCorrespondence: bool = True
+    initialSigma: float = 100.0
+    endSigma: float = 1.0
+    reverseCorrespondenceDirection: bool = False
+    correspondenceMethod: str = "TriangularClosestPoint"    # the reference's default (ICP.scala:63); needs both triangulations
+
+    @property
+    def sigmaStep(self) -> float:
+        return (self.initialSigma - self.endSigma) / float(self.maxIterations)
+
+
+@dataclasses.dataclass(frozen=True)
+class CpdRegistrationState:
+    general: GeneralRegistrationState
+    config: CpdConfiguration
+
+    def updateGeneral(self, update: GeneralRegistrationState) -> "CpdRegistrationState":
+        return dataclasses.replace(self, general=update)
+
+
+@dataclasses.dataclass(frozen=True)
+class IcpRegistrationState:
+    general: GeneralRegistrationState
+    config: IcpConfiguration
+
+    def updateGeneral(self, update: GeneralRegistrationState) -> "IcpRegistrationState":
+        return dataclasses.replace(self, general=update)
+
+
+def _with_fields(obj, **changes):
+    """dataclasses.replace for the plain frozen dataclasses above (no __post_init__, no slots), without its per-field machinery: 1 us
+    instead of 7 for a GeneralRegistrationState -- the fused Metropolis-Hastings step builds two objects per step."""
+    new = object.__new__(type(obj))
+    d = new.__dict__
+    d.update(obj.__dict__)
+    d.update(changes)
+    return new
+
+
+# ----------------------------------------------------------------------------- Template: correspondence and uncertainty from the host
+@dataclasses.dataclass(frozen=True)
+class TemplateConfiguration:
+    """TemplateConfiguration (G/api/registration/config/Template.scala:24-29)."""
+    maxIterations: int = 1
+    threshold: float = 1e-5
+    converged: Callable = _never_converged
+    useLandmarkCorrespondence: bool = True
+
+
+@dataclasses.dataclass(frozen=True)
+class TemplateRegistrationState:
+    general: GeneralRegistrationState
+    config: TemplateConfiguration
+
+    def updateGeneral(self, update: GeneralRegistrationState) -> "TemplateRegistrationState":
+        return dataclasses.replace(self, general=update)
+
+
+def _empty_pairs() -> CorrespondencePairs:
+    return CorrespondencePairs(np.empty(0, dtype=np.int64), np.empty((0, 3)))
+

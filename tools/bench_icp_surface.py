@@ -68,7 +68,7 @@ for _ in range(n):
     state = algo.update(state)      # host-boundary call per iteration (push state, update, pull the fit)
 ctx.synchronize()
 dt = time.perf_counter() - t0
-# the same iterations the way GingrAlgorithm.run takes them when nobody watches the intermediate states (api.py: _run_resident): the
+# the same iterations the way GingrAlgorithm.run takes them when nobody watches the intermediate states (registration.py: _run_resident): the
 # state stays on the device, an iteration reads back its scalars only, coefficients and fit come back once at the end
 nres = int(OPTS.get("resident", 50))
 cfg_run = ga.IcpConfiguration(maxIterations=nres + 1, initialSigma=10.0, endSigma=1.0, correspondenceMethod=METHOD)
