@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void bcpd_colsum_kernel(Cloud X, Cloud Yh, con
 #pragma unroll 4
             for (int k = 0; k < cnt; ++k) {
                 const double dx = px - rec[4 * k], dy = py - rec[4 * k + 1], dz = pz - rec[4 * k + 2];
-                const double d2 = fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), ps.lim);
+                const double d2 = fastexp_clamp_d2(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), ps.lim);
                 acc = __builtin_fma(rec[4 * k + 3], fastexp2_scaled<3>(d2, ps.c, T), acc);
             }
         } else {
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void bcpd_rowstats_kernel(Cloud Yh, Cloud X, c
             for (int k = 0; k < cnt; ++k) {
                 const double qx = rec[4 * k], qy = rec[4 * k + 1], qz = rec[4 * k + 2];
                 const double dx = qx - px, dy = qy - py, dz = qz - pz;
-                const double d2 = fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), ps.lim);
+                const double d2 = fastexp_clamp_d2(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), ps.lim);
                 const double t = fastexp2_scaled<3>(d2, ps.c, T) * rec[4 * k + 3];
                 s0 += t;
                 sx = __builtin_fma(t, qx, sx);

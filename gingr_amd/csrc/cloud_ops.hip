@@ -140,7 +140,7 @@ __global__ __launch_bounds__(kBlock) void gauss_block_kernel(Cloud A, Cloud B, d
     const int64_t i = blockIdx.y;
     if (j >= B.n) return;
     const double dx = A.x[i] - B.x[j], dy = A.y[i] - B.y[j], dz = A.z[i] - B.z[j];
-    const double d2 = fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), fastexp_d2_limit(c));
+    const double d2 = fastexp_clamp_d2(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), fastexp_d2_limit(c));
     out[i * B.n + j] = scaling * fastexp2_scaled(d2, c, T);
 }
 

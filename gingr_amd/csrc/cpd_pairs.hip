@@ -246,7 +246,7 @@ __device__ __forceinline__ void colsum_tile(const P4 *tile, int j0, int j1, unsi
             if (MASKED && !((mask >> t) & 1u)) continue;
             const double dx = x[t] - p.x, dy = y[t] - p.y, dz = z[t] - p.z;
             double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
-            if (CLAMP) d2 = fmin(d2, lim);
+            if (CLAMP) d2 = fastexp_clamp_d2(d2, lim);
             acc[t] += fastexp2_floor_scaled(d2, c, T);
         }
     }
@@ -539,7 +539,7 @@ __device__ __forceinline__ void rowstats_tile(const P4 *tile, const P4 *tw, int 
             if (MASKED && !((mask >> t) & 1u)) continue;
             const double dx = p.x - x[t], dy = p.y - y[t], dz = p.z - z[t];
             double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx));
-            if (CLAMP) d2 = fmin(d2, lim);
+            if (CLAMP) d2 = fastexp_clamp_d2(d2, lim);
             const double k = fastexp2_floor_scaled(d2, c, T);
             a1[t] = __builtin_fma(k, p.w, a1[t]);
             ax[t] = __builtin_fma(k, q.x, ax[t]);

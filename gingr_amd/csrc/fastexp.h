@@ -18,7 +18,8 @@
 // against the 1e-5 bar on vertex positions.  Zero / subnormal / NaN behaviour is identical (it comes from v_ldexp_f64).
 //
 // Accuracy (DEG = 3): <= 1 ulp of the correctly rounded result of its argument; v_ldexp_f64 gives gradual underflow and flushes
-// to +0 below 2^-1075 like Math.exp in the reference (CPD.scala:56).  NaN propagates (tm = NaN -> f = NaN).
+// to +0 below 2^-1075 like Math.exp in the reference (CPD.scala:56).  NaN propagates (tm = NaN -> f = NaN), through the callers'
+// clamp as well (fastexp_clamp_d2).
 // Range: e is taken from mantissa bits 11..42 of tm, valid for |d2*c| < 2^42 (= 1.5e9 in units of d2/(2 sigma2));
 // callers clamp d2 when the inputs could exceed that (fastexp_needs_clamp).
 #pragma once
@@ -86,8 +87,9 @@ __device__ __forceinline__ double fastexp2_scaled(double d2, double c, const dou
 // With the wave's float64 rounding mode set to round-toward-minus-infinity (fastexp_round_down()), tm = u + MAGIC holds
 // floor(u) in its low mantissa bits and v_fract_f64 gives f = u - floor(u) in [0, 1) EXACTLY -- one add and
 // one fract instead of add, subtract, subtract.  The polynomial is the economised degree-2 one of ExpTab<11> re-centred on
-// [0, 1):  2^((j + f)/2048) = T'[j] (1 + f (Q0 + Q1 f)),  T'[j] = T[j] * S,  S = 2^(1/4096) (1 - C1_D2/2 + C2/4); same
-// 2.02e-13 bound (tools/gen_exp_table.py floor).  Everything a wave computes while the mode is set rounds down: sums of n
+// [0, 1):  2^((j + f)/2048) = T'[j] (1 + f (Q0 + Q1 f)),  T'[j] = T[j] * S,  S = 2^(1/4096) (1 - C1_D2/2 + C2/4); relative
+// error <= 2.0203e-13 on [0, 1) (the nearest form's 2.0194e-13 on |f| <= 1/2; tests/test_fastexp_host.py measures both).
+// Everything a wave computes while the mode is set rounds down: sums of n
 // terms carry a bias of at most n 2^-53 relative (1e-13 over a 512-point chunk), inside the same budget.  Zero / subnormal /
 // NaN behaviour is unchanged (v_ldexp_f64; v_fract_f64 of NaN is NaN, of +-inf NaN as well -- callers clamp beforehand).
 struct ExpFloor11 {
@@ -165,6 +167,15 @@ __device__ __forceinline__ double fastexp_scale_for_variance(double two_sigma2) 
 template <int TB = 11>
 __device__ __forceinline__ double fastexp_d2_limit(double c) {
     return -1100.0 * (double)(1 << TB) / c;
+}
+
+// d2 clamped to fastexp_d2_limit.  fmin alone returns its other operand for a NaN: a NaN squared distance (a NaN coordinate, inf - inf)
+// would come out as the kernel value +0 instead of NaN, so the NaN is put back behind it.  +inf (an infinite coordinate) is clamped:
+// K = +0, as exp(-inf).  (v_min_f64 plus a compare and a select; written as `d2 > lim ? lim : d2` it changed the register allocation of
+// the CPD pair kernels' other arithmetic forms, which share a kernel with the CLAMP loops.)
+__device__ __forceinline__ double fastexp_clamp_d2(double d2, double lim) {
+    const double m = fmin(d2, lim);
+    return d2 == d2 ? m : d2;
 }
 
 // true when an upper bound on d2 could push |d2*c| past 2^41 (a factor 2 of margin to the 2^42 limit)

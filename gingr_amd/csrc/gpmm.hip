@@ -44,7 +44,7 @@ constexpr int kPcBlock = 256;
 __device__ __forceinline__ double mixture_value(const Mixture &mix, double d2, const double *T) {
     double v = 0.0;
     for (int i = 0; i < mix.n; ++i) {
-        const double e = mix.s[i] * fastexp2_scaled<3>(fmin(d2, fastexp_d2_limit(mix.c[i])), mix.c[i], T);
+        const double e = mix.s[i] * fastexp2_scaled<3>(fastexp_clamp_d2(d2, fastexp_d2_limit(mix.c[i])), mix.c[i], T);
         v = i == 0 ? e : v + e;
     }
     return v;

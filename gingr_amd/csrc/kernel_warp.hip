@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void kernel_warp_kernel(Cloud Z, Cloud Y, cons
 #pragma unroll 4
             for (int k = 0; k < cnt; ++k) {
                 const double dx = px - rec[6 * k], dy = py - rec[6 * k + 1], dz = pz - rec[6 * k + 2];
-                const double d2 = fmin(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), lim);
+                const double d2 = fastexp_clamp_d2(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), lim);
                 const double e = fastexp2_scaled<3>(d2, c, T);
                 ax = __builtin_fma(rec[6 * k + 3], e, ax);
                 ay = __builtin_fma(rec[6 * k + 4], e, ay);

@@ -106,7 +106,12 @@ def regime_of(fit, target, sigma2):
     # coordinate, and on every axis the points sit either near 0 or near SEP: the smallest per-axis gap bounds every gap
     # between boxes of different clusters from below; 3 am^2 bounds every squared distance from above.
     pts = np.concatenate([fit, target])
-    gap = min(float(pts[:, d][pts[:, d] > SEP / 2].min() - pts[:, d][pts[:, d] < SEP / 2].max()) for d in range(3))
+
+    def side_gap(d):    # (a cloud that is no clustered one -- tests/test_gpu_fastexp.py -- has no two sides: no gap, nothing is culled)
+        far, near = pts[:, d][pts[:, d] > SEP / 2], pts[:, d][pts[:, d] < SEP / 2]
+        return float(far.min() - near.max()) if far.size and near.size else 0.0
+
+    gap = min(side_gap(d) for d in range(3))
     culls_clusters = gap * gap * negc > 1084.0 * 2048.0
     culls_nothing = not (3.0 * am * am * negc > 1084.0 * 2048.0)
     return {"expand": expand, "clamp": clamp, "culls_clusters": culls_clusters, "culls_nothing": culls_nothing}
