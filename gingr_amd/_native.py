@@ -83,6 +83,7 @@ _ip = POINTER(c_int32)
 
 KERNEL_GAUSSIAN_MIXTURE, KERNEL_DOT, KERNEL_LOOKUP = 0, 1, 2
 OPT_CULL, OPT_FINE_CULL, OPT_NN_GRID, OPT_TRI_GRID, OPT_SPLIT_EXCHANGE, OPT_GRAM_DOWNDATE, OPT_DECIMATE_BATCH = 0, 1, 2, 3, 4, 5, 6  # gingr_ctx_option
+OPT_SEPARABLE = 7
 
 
 class ScalarKernel(ctypes.Structure):
@@ -210,6 +211,7 @@ SIGNATURES = {
     "gingr_model_download": (c_int, [c_void_p, c_void_p, _dp, _dp, _dp, _dp]),
     "gingr_model_num_points": (c_int64, [c_void_p]),
     "gingr_model_rank": (c_int32, [c_void_p]),
+    "gingr_model_separable": (c_int, [c_void_p, _ip, _ip, _ip]),
     "gingr_model_instance": (c_int, [c_void_p, c_void_p, _dp, _dp, _dp, _dp, c_double, _dp]),
     "gingr_model_coefficients": (c_int, [c_void_p, c_void_p, _dp, _dp, _dp, _dp, _dp]),
     "gingr_model_posterior_mean": (c_int, [c_void_p, c_void_p, _dp, _dp, _dp, _dp, _dp, c_int32, _ip, _dp, _dp, _dp, _dp]),

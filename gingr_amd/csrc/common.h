@@ -53,6 +53,7 @@ struct gingr_ctx {
     // where the native all-reduce is enqueued right now (nullptr = the context's stream).
     int split_exchange = 0;
     int gram_downdate = -1;  // GINGR_OPT_GRAM_DOWNDATE: 0 / 1 weights of the surface ICP -> the model's moment minus the rejected rows (fitter_phases.hip: phase1_gram); -1: by size
+    int separable = -1;  // GINGR_OPT_SEPARABLE: -1 the compact passes of a coordinate-separable model where they apply (fitter_phases.hip: use_compact); 0 never
     int decimate_batch = 16;  // GINGR_OPT_DECIMATE_BATCH: bisection steps of gingr_mesh_decimate enqueued per read-back of its control block
     hipStream_t side_stream = nullptr, exchange_stream = nullptr;
     hipEvent_t split_ev[2] = {nullptr, nullptr};

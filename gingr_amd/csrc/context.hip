@@ -156,6 +156,7 @@ int gingr_ctx_set_option(gingr_ctx *ctx, int32_t option, int32_t value) {
         case GINGR_OPT_SPLIT_EXCHANGE: ctx->split_exchange = value != 0; return GINGR_OK;
         case GINGR_OPT_GRAM_DOWNDATE: ctx->gram_downdate = value < 0 ? -1 : (value != 0); return GINGR_OK;
         case GINGR_OPT_DECIMATE_BATCH: ctx->decimate_batch = value < 1 ? 1 : (value > 60 ? 60 : value); return GINGR_OK;
+        case GINGR_OPT_SEPARABLE: ctx->separable = value < 0 ? -1 : 0; return GINGR_OK;
         default: return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "ctx_set_option: unknown option %d", option);
     }
 }
@@ -170,6 +171,7 @@ int gingr_ctx_get_option(gingr_ctx *ctx, int32_t option, int32_t *value) {
         case GINGR_OPT_SPLIT_EXCHANGE: *value = ctx->split_exchange; return GINGR_OK;
         case GINGR_OPT_GRAM_DOWNDATE: *value = ctx->gram_downdate; return GINGR_OK;
         case GINGR_OPT_DECIMATE_BATCH: *value = ctx->decimate_batch; return GINGR_OK;
+        case GINGR_OPT_SEPARABLE: *value = ctx->separable; return GINGR_OK;
         default: return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "ctx_get_option: unknown option %d", option);
     }
 }

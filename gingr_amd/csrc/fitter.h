@@ -129,7 +129,8 @@ struct gingr_fitter {
         std::vector<double> v;  // alpha[r], euler, center, translation, scale, sigma2
         int flavour = -1;       // memo_flavour_key (correspondence.h)
         double p0 = 0, p1 = 0;  // CPD: w, lambda
-        bool same(const Key &o) const { return flavour == o.flavour && p0 == o.p0 && p1 == o.p1 && v == o.v; }
+        bool compact = false;   // phase 1 ran the compact Gram pass of a coordinate-separable model (fitter_phases.hip: use_compact)
+        bool same(const Key &o) const { return flavour == o.flavour && p0 == o.p0 && p1 == o.p1 && compact == o.compact && v == o.v; }
     };
     Key state_key, post_key;
     bool state_key_valid = false;
@@ -180,6 +181,7 @@ struct gingr_fitter {
     // host that all-reduces xch in place -- torch.distributed).  The device group (group.hip) points it at the shard's send
     // buffer: peers read that while the summed result lands in xch, so nobody overwrites what a peer may still be reading.
     double *partial_out = nullptr;
+    bool group_member = false;  // created by a device group (group.hip), of one device or more: the dense passes only (use_compact)
     // Row-sharded surface ICP: the tests against the template itself (vertex normals, self-intersection) need the WHOLE posed template,
     // so every iteration starts with a gather -- each shard contributes its rows of the fit to a [3][M_total] buffer in ORIGINAL
     // point order (zeros elsewhere), the buffers are summed across the shards (exchange segment 2: an all-gather spelled as the
@@ -266,7 +268,8 @@ inline hipError_t ensure(DevBuf &b, size_t bytes) { return b.p && b.bytes >= byt
 int check_ready(gingr_fitter *f);  // target and state set; makes the context's device current
 int check_parameters(gingr_fitter *f, const Correspondence &c);  // check_ready, then the parameters of the flavour
 SweepArgs base_args(const gingr_fitter *f);
-void refresh_fit(gingr_fitter *f);    // fit = modelInstanceShapePoseScale(model, state)
+// fit = modelInstanceShapePoseScale(model, state); compact: through the model's compact basis (the caller has checked that it exists)
+void refresh_fit(gingr_fitter *f, bool compact = false);
 void fit_boxes_now(gingr_fitter *f);  // boxes + |coordinate - centre| maximum of a fit that refresh_fit did not write
 // Key::v of a state the host knows by value: alpha[r], euler, center, translation, scale, sigma2
 std::vector<double> state_key_values(int32_t r, const double *alpha, const double euler[3], const double center[3], const double t[3],

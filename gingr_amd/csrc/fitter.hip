@@ -71,11 +71,12 @@ void fit_boxes_now(gingr_fitter *f) {
 }
 
 // fit = modelInstanceShapePoseScale(model, state)
-void refresh_fit(gingr_fitter *f) {
+void refresh_fit(gingr_fitter *f, bool compact) {
     SweepArgs a = base_args(f);
     a.coef0 = f->alpha;
     a.shape_out = f->fit;
     if (f->fboxes && f->m->rp <= 512 && f->cpd_seen) {  // the pass also leaves the quarter boxes and the |coordinate - centre| maximum
+        if (compact) a.Qc = f->m->Qc, a.sep_map = f->m->sep_map;  // (only the quarter-box form has a compact instance)
         a.qboxes = f->fboxes + 6 * ceil_div(f->m->M, 256);
         a.box_centre = f->absmax + 2;
         a.absmax_slot = f->absmax + 1;
@@ -317,6 +318,7 @@ int gingr_fitter_set_target(gingr_fitter *f, int64_t N, const double *target_xyz
     mx(ceil_div(nn_ws_bytes(M, N), 8));
     mx(ceil_div(nn_ws_bytes(N, M), 8));  // reversed correspondence direction: the targets query the model vertices
     mx(gram_ws_doubles(M, rp) + sweep_ws_doubles(M, rp));  // phase 1 keeps both sets of partials until its finalize kernel
+    if (f->m->Qc) mx(gram_compact_ws_doubles(M));           // (the compact pass: Gram and right-hand-side partials in one block)
     f->ws_doubles = w;
     GINGR_TRY(dev_alloc(ctx, &f->ws, (size_t)w));
     const int64_t big = M > N ? M : N;
@@ -601,6 +603,7 @@ int gingr_fitter_exchange(gingr_fitter *f, void **dev_ptr, int64_t offsets[GINGR
 
 // --------------------------------------------------------------------------------------------------- internal hooks (group.hip)
 void fitter_set_partial_output(gingr_fitter *f, double *base) { f->partial_out = base; }
+void fitter_set_group_member(gingr_fitter *f) { f->group_member = true; }
 void fitter_set_partial_fullfit(gingr_fitter *f, double *base) { f->partial_fullfit = base; }
 double *fitter_fullfit(gingr_fitter *f) { return f->fullfit; }
 void fitter_set_partial_revsum(gingr_fitter *f, double *base) { f->partial_revsum = base; }

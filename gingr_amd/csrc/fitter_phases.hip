@@ -120,6 +120,19 @@ struct Segments {
     double *seg0w, *Gw, *rhsw, *sc8w;
 };
 
+// Whether this update runs the compact passes of a coordinate-separable model (gp.h: gingr_model::Qc) in place of the weighted Gram pass
+// and the fit pass: a single shard, the flavours that take the weighted pass with nothing added to G behind it (CPD; the caller's pairs
+// without covariances), no landmarks, no sampled proposal, no query that leaves the state as it is, no device group (whatever its size).  A fixed rule:
+// the two forms add in different orders -- which is also why the answer is part of the posterior memo's key (memo_enter): phase-1 results
+// are reused only by a caller that would have computed them the same way.
+bool use_compact(const gingr_fitter *f, const Correspondence &c) {
+    const gingr_model *m = f->m;
+    if (!m->Qc || f->ctx->separable == 0) return false;
+    if (m->M != m->M_total || f->partial_out || f->group_member) return false;
+    if (!(c.kind == Flavour::Cpd || (c.kind == Flavour::Pairs && f->n_pc == 0))) return false;
+    return f->n_lm == 0 && !f->zrand_active && !f->allow_alt;
+}
+
 // Posterior memo (see gingr_fitter::Key): phases 0 and 1 are skipped when their results for exactly this state are still in place.
 // Returns whether `phase` is already satisfied.  The state it mutates:
 //   phase 0  skip_phase1; post_key, post_stage; alt_key, alt_stage; seg_swapped and live (the two slots exchange roles);
@@ -134,6 +147,7 @@ bool memo_enter(gingr_fitter *f, const Correspondence &c, int phase) {
         k.flavour = memo_flavour_key(c, f->surface_method, f->reversed);
         k.p0 = c.cpd.w;  // (zero for every flavour but CPD)
         k.p1 = c.cpd.lambda;
+        k.compact = use_compact(f, c);
         const bool single = m->M == m->M_total;
         if (single && f->state_key_valid) {
             k.v = f->state_key.v;
@@ -442,6 +456,8 @@ struct GramOutcome {
 //                    The gate sums THIS shard's zero_counts against THIS shard's M: the shards of one update may decide differently.
 //   weighted pass    everything else -- always for the pairs flavour, whose weights are the caller's: each shard contributes the pass over its own rows; the pass may leave the right-hand-side
 //                    partials as well (rhs_done).
+//   compact pass     the weighted pass of a coordinate-separable model (use_compact): the three Gram blocks and right-hand sides from the
+//                    compact basis, scattered into the same dense G / rhs by the finalize kernel (rhs_done).
 GramOutcome phase1_gram(gingr_fitter *f, const Correspondence &c, double *gram_ws, double *sweep_ws, Phase1FinalizeArgs &fa) {
     gingr_ctx *ctx = f->ctx;
     const gingr_model *m = f->m;
@@ -476,6 +492,11 @@ GramOutcome phase1_gram(gingr_fitter *f, const Correspondence &c, double *gram_w
             fa.gate = many;
             out.rhs_gate = few;
         }
+    } else if (use_compact(f, c)) {
+        fa.gram_partial = gram_ws;
+        fa.nslabs = launch_gram_compact(ctx, m->Qc, M, f->weight, f->evec, gram_ws);
+        fa.sep_map = m->sep_map;
+        out.rhs_done = true;
     } else {
         fa.gram_partial = gram_ws;
         fa.nslabs = launch_gram(ctx, m->Q0, M, rp, f->weight, gram_ws, nullptr, f->evec, sweep_ws, &out.rhs_done);
@@ -496,6 +517,8 @@ void phase2_solve_and_commit(gingr_fitter *f, const Correspondence &c, const Seg
     else if (f->zrand_active && f->allow_alt && f->post_stage == 2 && f->nf_valid[f->live] && m->M == m->M_total && !f->partial_out)
         // the log-density query that first met this state left the factor of I + G and the posterior coefficients behind
         launch_posterior_sample_cached(ctx, r, rp, f->nfac[f->live], f->fxbuf[f->live] + (int64_t)rp * rp, f->zrand, f->acoef, f->st);
+    else if (use_compact(f, c))
+        launch_posterior_solve_separable(ctx, m, s.G, s.rhs, f->acoef, f->st);
     else
         launch_posterior_solve(ctx, r, rp, s.G, s.rhs, f->zrand_active ? f->zrand : nullptr, f->work, f->acoef, f->st);
     launch_post_matvecs(ctx, m, f->alpha, f->acoef, f->zbuf);
@@ -520,7 +543,7 @@ void phase2_solve_and_commit(gingr_fitter *f, const Correspondence &c, const Seg
     a.probabilistic = f->zrand_active ? 1 : 0;
     a.stop_threshold = f->stop_threshold;
     launch_post_solve(ctx, a);
-    refresh_fit(f);
+    refresh_fit(f, use_compact(f, c));
 }
 
 int run_phase(gingr_fitter *f, const Correspondence &c, int phase) {

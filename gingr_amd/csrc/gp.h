@@ -126,7 +126,30 @@ struct gingr_model {
     double Ps[3] = {0};        // sum_i p~_i
     std::vector<double> variance;  // host copy of lambda (gingr_model_download)
     bool finalized = false;
+    // ---- coordinate-separable basis, decided once by model_finalize_impl from the local Q0.  Column k is of
+    // class d when only the rows 3i + d of it hold anything but +-0.0 (an all-zero column: class 0); separable = every column has a class.
+    bool separable = false;
+    std::vector<int32_t> col_class;      // [r]
+    std::vector<int32_t> class_cols[3];  // the columns of each class, in model order
+    int32_t rc[3] = {0, 0, 0};           // their counts
+    // Qc [3][M + kCompactRowSlack][kCompactCols]: plane d = row 3i + d of every point restricted to class_cols[d], zero padded.  Kept
+    // (non-null) only for a separable single-shard model with rp <= 112 and every rc[d] <= kCompactCols; Q0 stays what everything else reads.
+    double *Qc = nullptr;
+    int32_t *sep_map = nullptr;  // SepMap, on the device; non-null exactly when Qc is
 };
+
+constexpr int kCompactCols = 48;      // width of a plane of Qc: three 16-column tiles
+constexpr int kCompactRowSlack = 48;  // zero rows behind each plane
+// gingr_model::sep_map ([2 rp + 3 kCompactCols] int32): the class of a dense column (-1: padding), its position within the class, and the
+// three class lists (dense column of compact column p of class d; -1 behind the class's last)
+struct SepMap {
+    int32_t rp;
+    __host__ __device__ int cls(int k) const { return k; }
+    __host__ __device__ int pos(int k) const { return rp + k; }
+    __host__ __device__ int col(int d, int p) const { return 2 * rp + d * kCompactCols + p; }
+    __host__ __device__ int total() const { return 2 * rp + 3 * kCompactCols; }
+};
+__host__ __device__ inline int64_t compact_plane_doubles(int64_t M) { return (M + kCompactRowSlack) * kCompactCols; }
 
 // gp_sweep.hip: basis rows of a model on a new reference as fixed convex combinations of three source rows (gingr_model_new_reference)
 void launch_interp_pack(gingr_ctx *ctx, const double *Qs, int32_t rp, const int32_t *inv_src, const int32_t *ids, const double *w,
@@ -142,6 +165,7 @@ int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const doubl
 // fitter.hip hooks for the device group (group.hip): where phases 0 / 1 write this shard's partial exchange segments, and where
 // the gather step of a sharded surface update writes the shard's contribution to the full fit (nullptr: in place)
 void fitter_set_partial_output(gingr_fitter *f, double *base);
+void fitter_set_group_member(gingr_fitter *f);  // this fitter belongs to a device group
 void fitter_set_partial_fullfit(gingr_fitter *f, double *base);
 // fitter.hip: ready, parameters and what the flavour needs of the fitter -- once per ABI call, in front of everything below
 int check_correspondence(gingr_fitter *f, const Correspondence &c);
@@ -245,6 +269,9 @@ struct SweepArgs {
     double *weight_out, *evec_out;
     const DevState *frame;  // SWEEP_PROJ2 (nullable): project in the rigid frame of this state instead of `pose`
     ZeroGate gate;          // SWEEP_RHS: the pass leaves at once when the gate says so (memset-zeroed args: no gate)
+    // SWEEP_FIT with qboxes, nullable: the pass reads the three planes of the model's compact basis (gingr_model::Qc, sep_map) instead of Q0
+    const double *Qc;
+    const int32_t *sep_map;
 };
 
 int sweep_num_blocks(int64_t M);
@@ -295,8 +322,17 @@ struct Phase1FinalizeArgs {
     // alt_nslabs slab partials hold the weighted Gram itself (no scaled_src), the right-hand-side partials are alt_nslabs rows
     ZeroGate gate;
     int32_t alt_nslabs;
+    // sep_map != nullptr: gram_partial holds the slab partials of launch_gram_compact ([nslabs][3][kCompactCols^2 + kCompactCols], the
+    // right-hand side behind each Gram block; sweep_partial is not read).  They are summed in the same fixed order and scattered into the
+    // dense G / rhs through the map; entries between two classes and the padding are written as +0.0.
+    const int32_t *sep_map;
 };
 void launch_phase1_finalize(gingr_ctx *ctx, const Phase1FinalizeArgs &a);
+// The weighted Gram blocks and right-hand sides of a coordinate-separable model from its compact basis Qc (gp.h: gingr_model): the
+// triangle kernel at three tiles, one row per point, the three planes as gridDim.z of one launch.  ws: gram_compact_ws_doubles(M)
+// doubles of slab partials (Phase1FinalizeArgs::sep_map).  Returns the slab count.
+int64_t gram_compact_ws_doubles(int64_t M);
+int launch_gram_compact(gingr_ctx *ctx, const double *Qc, int64_t M, const double *weight, const double *evec, double *ws);
 // partial[b] = sum over the vertices i of slab b with weight[i] == 0 of Q0_i^T Q0_i (full rp x rp, zeros when the slab has none);
 // returns the slab count (<= 256: the workspace of launch_gram is large enough).  Any rp (112-column patches above 112).
 int launch_gram_downdate(gingr_ctx *ctx, const double *Q0, int64_t M, int32_t rp, const double *weight, double *ws,
@@ -323,6 +359,8 @@ void launch_landmarks(gingr_ctx *ctx, const gingr_model *m, const DevState *st, 
 // zrand (nullable, [r] on the device): standard-normal draws; the result is then a posterior SAMPLE a + L^-T z
 void launch_posterior_solve(gingr_ctx *ctx, int32_t r, int32_t rp, const double *G, const double *rhs, const double *zrand,
                             double *work, double *a, DevState *st);
+// the same for a model that keeps its compact basis (gingr_model::Qc): three workgroups, one per coordinate class, on the dense G / rhs
+void launch_posterior_solve_separable(gingr_ctx *ctx, const gingr_model *m, const double *G, const double *rhs, double *a, DevState *st);
 // out2[0] = posterior.gp.logpdf(posterior.coefficients(mesh)), out2[1] != 0: the posterior failed; qte = Q0^T e (model-frame
 // residual).  fx ([rp*rp + 2*rp], nullable): receives the state-only part of the computation (cached == false) or provides it
 // (cached == true: only the mesh-dependent part runs).  sync (2 zero-initialised words on the device) + a launch number `epoch`

@@ -22,10 +22,12 @@ namespace {
 // time every access was a FLAT instruction: ~3x the latency of the LDS path, 64-bit address arithmetic, SGPR spills.)
 // The solve on a workspace `sm` (LDS or global, see below); all kSolveThreads threads.  bad_spd / bad: two ints of LDS.
 // FAST (LDS-resident, rp <= 112: sixteen more rows fit into the 160 KB): the identity rows of lds_cholesky / lds_backward_w.
+// cols != nullptr (FAST, no zrand): the system is one class of a coordinate-separable model -- rows / columns cols[0 .. r) of the dense G
+// (row stride ldg) and rhs, padded to n = rp; the coefficients go back to a[cols[k]] (posterior_solve_lds_kernel<2>).
 template <bool FAST, typename PtrD>
 __device__ __forceinline__ void posterior_solve_body(PtrD sm, int r, int rp, const double *__restrict__ G, const double *__restrict__ rhs,
                                                      const double *__restrict__ zrand, double *__restrict__ a, DevState *__restrict__ st,
-                                                     int *bad_spd, int *bad) {
+                                                     int *bad_spd, int *bad, const int32_t *__restrict__ cols = nullptr, int ldg = 0) {
     const int n = rp, ld = solve_ld(n);
     constexpr int XR = FAST ? 2 * kNB : kNB;
     auto A = sm;
@@ -37,7 +39,7 @@ __device__ __forceinline__ void posterior_solve_body(PtrD sm, int r, int rp, con
         *bad_spd = 0;
         *bad = 0;
     }
-    for (int k = tid; k < kNB * ld; k += kSolveThreads) y[k] = k < r ? rhs[k] : 0.0;
+    for (int k = tid; k < kNB * ld; k += kSolveThreads) y[k] = k < r ? rhs[cols ? cols[k] : k] : 0.0;
     for (int k = tid; k < n; k += kSolveThreads) y2[k] = (zrand && k < r) ? zrand[k] : 0.0;
     if (FAST)  // rows n+16 .. n+31: the tiled identity
         for (int k = tid; k < kNB * ld; k += kSolveThreads) {
@@ -46,7 +48,10 @@ __device__ __forceinline__ void posterior_solve_body(PtrD sm, int r, int rp, con
         }
     // Mm = QtL Q + I     (scalismo genericRegressionComputations)
     GINGR_STAGE_CLOCK(7)
-    lds_load_spd<kSolveThreads>(A, ld, r, n, G, 1.0, nullptr, 0.0, 1.0);
+    if (cols)
+        lds_load_spd<kSolveThreads, false, kCompactCols / 16>(A, ld, r, n, G, 1.0, nullptr, 0.0, 1.0, cols, ldg);
+    else
+        lds_load_spd<kSolveThreads>(A, ld, r, n, G, 1.0, nullptr, 0.0, 1.0);
     GINGR_STAGE_CLOCK(0)
     lds_cholesky<kSolveThreads>(A, ld, n, rd, bad_spd, kNB, FAST ? kNB : 0);  // y <- L^-1 y on the way
     GINGR_STAGE_CLOCK(4)
@@ -68,7 +73,10 @@ __device__ __forceinline__ void posterior_solve_body(PtrD sm, int r, int rp, con
     GINGR_STAGE_CLOCK(6)
     for (int k = tid; k < rp; k += kSolveThreads) {
         const double v = k < r ? y[k] + y2[k] : 0.0;
-        a[k] = v;
+        if (!cols)
+            a[k] = v;
+        else if (k < r)
+            a[cols[k]] = v;
         if (!finite_d(v)) *bad = 1;
     }
     __syncthreads();
@@ -81,13 +89,28 @@ __device__ __forceinline__ void posterior_solve_body(PtrD sm, int r, int rp, con
 }
 
 // MODE 0: LDS, identity rows (rp <= 112); 1: LDS (rp = 128)
+// MODE 2: a coordinate-separable model (gp.h: SepMap): I + G is three uncoupled systems, one per coordinate class.  Workgroup d gathers
+// class d's rows and columns of the dense G / rhs, solves the kCompactCols-padded system as MODE 0 does and writes its coefficients to
+// their dense positions; the padding of a is cleared by every workgroup.  Each workgroup stores the error code ITS system gives into
+// st->err (plain stores, no hand-over): a non-finite weight or observation enters all three blocks, which then store the same code.
+struct SepCounts {
+    int32_t rc[3];
+};
 template <int MODE>
 __global__ __launch_bounds__(kSolveThreads) void posterior_solve_lds_kernel(int r, int rp, const double *__restrict__ G,
                                                                   const double *__restrict__ rhs,
                                                                   const double *__restrict__ zrand, double *__restrict__ a,
-                                                                  DevState *__restrict__ st) {
+                                                                  DevState *__restrict__ st, const int32_t *__restrict__ sep_map = nullptr,
+                                                                  SepCounts sc = SepCounts{}) {
     extern __shared__ double lds_sm[];
     __shared__ int bad_spd, bad;
+    if constexpr (MODE == 2) {
+        const int d = blockIdx.x;
+        for (int k = r + (int)threadIdx.x; k < rp; k += kSolveThreads) a[k] = 0.0;
+        if (sc.rc[d] == 0) return;  // (workgroup-uniform) a coordinate without columns: nothing to solve, nothing to write
+        posterior_solve_body<true>(lds_sm, sc.rc[d], kCompactCols, G, rhs, nullptr, a, st, &bad_spd, &bad, sep_map + SepMap{rp}.col(d, 0), rp);
+        return;
+    }
 #ifdef GINGR_SOLVE_TWICE  // tools/ubench_solve.hip only: the second pass runs with the kernel's code in the instruction cache
     for (int pass = 0; pass < 2; ++pass) {
         __syncthreads();
@@ -1034,6 +1057,13 @@ __global__ __launch_bounds__(512) void logpdf_finish_kernel(int r, int n, int64_
 }
 }  // namespace
 
+void launch_posterior_solve_separable(gingr_ctx *ctx, const gingr_model *m, const double *G, const double *rhs, double *a, DevState *st) {
+    TimerScope ts(ctx, 5);
+    const size_t lds = lds_solve_doubles(kCompactCols, 2 * kNB) * sizeof(double);  // (32 KB: below the limit that needs the attribute)
+    hipLaunchKernelGGL(posterior_solve_lds_kernel<2>, dim3(3), dim3(kSolveThreads), lds, ctx->stream, (int)m->r, (int)m->rp, G, rhs,
+                       (const double *)nullptr, a, st, (const int32_t *)m->sep_map, SepCounts{{m->rc[0], m->rc[1], m->rc[2]}});
+}
+
 void launch_posterior_solve(gingr_ctx *ctx, int32_t r, int32_t rp, const double *G, const double *rhs, const double *zrand,
                             double *work, double *a, DevState *st) {
     TimerScope ts(ctx, 5);
@@ -1052,7 +1082,8 @@ void launch_posterior_solve(gingr_ctx *ctx, int32_t r, int32_t rp, const double 
         auto go = [&](auto kern) {
             if (lds > 48 * 1024)  // per function and per device: set whenever needed
                 set_dynamic_lds(kern, (size_t)(lds));
-            hipLaunchKernelGGL(kern, dim3(1), dim3(kSolveThreads), lds, ctx->stream, (int)r, (int)rp, G, rhs, zrand, a, st);
+            hipLaunchKernelGGL(kern, dim3(1), dim3(kSolveThreads), lds, ctx->stream, (int)r, (int)rp, G, rhs, zrand, a, st,
+                               (const int32_t *)nullptr, SepCounts{});
         };
         if (fast)
             go(posterior_solve_lds_kernel<0>);

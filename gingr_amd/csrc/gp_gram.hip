@@ -150,7 +150,9 @@ __host__ __device__ constexpr int tri_col(int q) {
     return t + q;
 }
 
-template <int NT, int HALF, bool FULL>
+// RPP: basis rows per point -- 3 (Q0: the weight / evec index of a row is row / 3, the plane row % 3) or 1 (a plane of the compact basis
+// Qc, gp.h: one row per point, weight and evec indexed by the row itself; evec points at the plane's own part)
+template <int NT, int HALF, bool FULL, int RPP>
 __device__ __forceinline__ void gram_tri_half(const double *__restrict__ Q0, int rp, const double *__restrict__ weight, int64_t r0,
                                               int64_t r1, int kgroup, int kq, int cl, int lane, double *red, double *xchg,
                                               double *__restrict__ out, const double *__restrict__ evec, int64_t npts,
@@ -194,12 +196,12 @@ __device__ __forceinline__ void gram_tri_half(const double *__restrict__ Q0, int
     // row -> (point, coordinate) = (row / 3, row % 3); 16 rows further: (point + 5, coordinate + 1) or (point + 6, coordinate - 2).
     // `third` = coordinate * ceil(2^32 / 3): adding ceil(2^32 / 3) carries exactly when the coordinate wraps (the excess of 2 per
     // wrap stays below the margin for 7e8 wraps).  evec is SoA [3][npts]: entry (coordinate, point).
-    const int64_t pt_first = first / 3;
-    const int rem_first = (int)(first - 3 * pt_first);
+    const int64_t pt_first = first / RPP;
+    const int rem_first = (int)(first - RPP * pt_first);
     constexpr unsigned kThird = 0x55555556u;
     unsigned third = (unsigned)rem_first * kThird;
-    const double *wclamp = with_w ? weight + r0 / 3 : pclamp;
-    const double *eclamp = with_rhs ? evec + r0 / 3 : pclamp;
+    const double *wclamp = with_w ? weight + r0 / RPP : pclamp;
+    const double *eclamp = with_rhs ? evec + r0 / RPP : pclamp;
     const double *wp = with_w ? weight + pt_first : pclamp;  // without weights / evec: any readable address, the value is not used
     const double *ep = with_rhs ? evec + rem_first * npts + pt_first : pclamp;
     const int64_t estep = with_rhs ? 5 + npts : 0, ewrap = with_rhs ? 6 - 2 * npts : 0;
@@ -226,11 +228,16 @@ __device__ __forceinline__ void gram_tri_half(const double *__restrict__ Q0, int
         }
         left_u -= 16;
         pnext += pstep;
-        const unsigned t2 = third + kThird;
-        const bool wrap = t2 < third;
-        third = t2;
-        wp += wrap ? 6 : 5;
-        ep += wrap ? ewrap : estep;
+        if constexpr (RPP == 1) {
+            wp += 16;
+            ep += 16;
+        } else {
+            const unsigned t2 = third + kThird;
+            const bool wrap = t2 < third;
+            third = t2;
+            wp += wrap ? 6 : 5;
+            ep += wrap ? ewrap : estep;
+        }
     };
     double racc[kO];
 #pragma unroll
@@ -368,7 +375,7 @@ __device__ __forceinline__ void gram_tri_half(const double *__restrict__ Q0, int
 }
 
 // FULL: weight and evec are both given (the per-iteration call) -- their loads are unconditional
-template <int NT, bool FULL>
+template <int NT, bool FULL, int RPP = 3>
 __global__ __launch_bounds__(512) void gram_tri_kernel(const double *__restrict__ Q0, int64_t rows, int rp,
                                                        const double *__restrict__ weight, int64_t rows_per_slab,
                                                        double *__restrict__ partial, const double *__restrict__ evec, int64_t npts,
@@ -383,10 +390,17 @@ __global__ __launch_bounds__(512) void gram_tri_kernel(const double *__restrict_
     const int64_t r1 = min(rows, r0 + rows_per_slab);
     double *out = partial + (int64_t)blockIdx.x * rp * rp;
     double *rhs_out = rhs_partial ? rhs_partial + (int64_t)blockIdx.x * rp : nullptr;  // one row of right-hand-side partials per slab
+    if constexpr (RPP == 1) {  // plane blockIdx.z of the compact basis; partials [slab][plane][rp * rp + rp], the right-hand side last
+        const int d = blockIdx.z;
+        Q0 += (int64_t)d * (rows + kCompactRowSlack) * rp;
+        evec += (int64_t)d * npts;
+        out = partial + ((int64_t)blockIdx.x * 3 + d) * (rp * rp + rp);
+        rhs_out = out + rp * rp;
+    }
     if ((wave >> 2) == 0)
-        gram_tri_half<NT, 0, FULL>(Q0, rp, weight, r0, r1, wave & 3, kq, cl, lane, red, xchg, out, evec, npts, rhs_out, rsh);
+        gram_tri_half<NT, 0, FULL, RPP>(Q0, rp, weight, r0, r1, wave & 3, kq, cl, lane, red, xchg, out, evec, npts, rhs_out, rsh);
     else
-        gram_tri_half<NT, 1, FULL>(Q0, rp, weight, r0, r1, wave & 3, kq, cl, lane, red, xchg, out, evec, npts, rhs_out, rsh);
+        gram_tri_half<NT, 1, FULL, RPP>(Q0, rp, weight, r0, r1, wave & 3, kq, cl, lane, red, xchg, out, evec, npts, rhs_out, rsh);
 }
 
 // G[i][j] = sum over slabs (fixed order): 32 consecutive elements x 8 slab groups per workgroup, so every load instruction
@@ -441,7 +455,16 @@ __global__ __launch_bounds__(256) void phase1_finalize_kernel(Phase1FinalizeArgs
         const int i = idx / rp, j = idx - i * rp;
         const bool need = idx < rr && !(i > j);
         double s = 0.0;
-        if (need) {
+        if (A.sep_map) {  // compact partials: entry (i, j) of the dense G is entry (pos i, pos j) of its class's block, or +0.0
+            constexpr int64_t kBlock = kCompactCols * kCompactCols + kCompactCols;
+            const SepMap sm{rp};
+            const int ci = need ? A.sep_map[sm.cls(i)] : -1, cj = need ? A.sep_map[sm.cls(j)] : -1;
+            if (ci >= 0 && ci == cj) {  // (class lists are in model order: i <= j gives pos i <= pos j, the upper tiles the pass wrote)
+                const double *p = A.gram_partial + ci * kBlock + A.sep_map[sm.pos(i)] * kCompactCols + A.sep_map[sm.pos(j)];
+#pragma unroll 8
+                for (int q = g; q < A.nslabs; q += 8) s += p[(int64_t)q * 3 * kBlock];
+            }
+        } else if (need) {
             const double *p = A.gram_partial + idx;
 #pragma unroll 8
             for (int q = g; q < A.nslabs; q += 8) s += p[(int64_t)q * rr];
@@ -460,7 +483,17 @@ __global__ __launch_bounds__(256) void phase1_finalize_kernel(Phase1FinalizeArgs
     if (b < nG + rp) {
         const int k = b - nG;
         double s = 0.0;
-        for (int q = threadIdx.x; q < A.sweep_blocks; q += 256) s += A.sweep_partial[(int64_t)q * rp + k];
+        if (A.sep_map) {  // behind the Gram block of column k's class, at its position there; padding columns: +0.0
+            constexpr int64_t kBlock = kCompactCols * kCompactCols + kCompactCols;
+            const SepMap sm{rp};
+            const int c = A.sep_map[sm.cls(k)];
+            if (c >= 0) {
+                const double *p = A.gram_partial + c * kBlock + kCompactCols * kCompactCols + A.sep_map[sm.pos(k)];
+                for (int q = threadIdx.x; q < A.nslabs; q += 256) s += p[(int64_t)q * 3 * kBlock];
+            }
+        } else {
+            for (int q = threadIdx.x; q < A.sweep_blocks; q += 256) s += A.sweep_partial[(int64_t)q * rp + k];
+        }
         sv[threadIdx.x] = s;
         __syncthreads();
 #pragma unroll
@@ -683,6 +716,31 @@ int launch_gram(gingr_ctx *ctx, const double *Q0, int64_t M, int32_t rp, const d
     if (G)  // nullptr: the caller reduces the slab partials itself (launch_phase1_finalize with the returned slab count)
         hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)ceil_div((int64_t)rp * rp, 32)), dim3(256), 0, ctx->stream, ws,
                            nslabs, (int)rp, 1, G);
+    return nslabs;
+}
+
+// slabs of the compact pass, per plane: two workgroups per CU over the three planes (a wave has three tiles of work per step, far less
+// than the seven-tile pass, so one workgroup per CU would leave the memory system idle); small models keep at least 64 rows per slab
+static void gram_compact_plan(int64_t M, int *nslabs, int64_t *rows_per_slab) {
+    const int64_t want = std::min<int64_t>(170, std::max<int64_t>(1, ceil_div(M, 64)));
+    *rows_per_slab = round_up(ceil_div(M, want), 16);
+    *nslabs = (int)ceil_div(M, *rows_per_slab);
+}
+
+int64_t gram_compact_ws_doubles(int64_t M) {
+    int nslabs;
+    int64_t rps;
+    gram_compact_plan(M, &nslabs, &rps);
+    return (int64_t)nslabs * 3 * (kCompactCols * kCompactCols + kCompactCols);
+}
+
+int launch_gram_compact(gingr_ctx *ctx, const double *Qc, int64_t M, const double *weight, const double *evec, double *ws) {
+    int nslabs;
+    int64_t rps;
+    gram_compact_plan(M, &nslabs, &rps);
+    TimerScope ts(ctx, 2);
+    hipLaunchKernelGGL((gram_tri_kernel<kCompactCols / 16, true, 1>), dim3(nslabs, 1, 3), dim3(512), 0, ctx->stream, Qc, M, (int)kCompactCols,
+                       weight, rps, ws, evec, M, (double *)nullptr, ZeroGate{});
     return nslabs;
 }
 

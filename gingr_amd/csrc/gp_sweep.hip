@@ -273,14 +273,19 @@ __global__ __launch_bounds__(256) void block_partials_reduce_kernel(const double
 // S points per 16-lane group in flight (4 for KM <= 8: the whole quarter at once; 1 above: the basis rows of a point are 3 KM values
 // per lane, requested eight column blocks at a time -- ranks above 128 keep the quarter-box form with the registers of three waves per
 // SIMD instead of falling back to the generic pass + a box launch of its own).
-template <int KM, int S>
+// SEP: the compact basis of a coordinate-separable model (gp.h: gingr_model::Qc) -- coordinate d of a point is the product of its
+// kCompactCols-wide row in plane d with the coefficients of class d's columns (KM = kCompactCols / 16)
+template <int KM, int S, bool SEP = false>
 __global__ __launch_bounds__(kSweepThreads) void sweep_fit_boxes_kernel(SweepArgs a) {
     constexpr int CH = KM < 8 ? KM : 8;  // column blocks per request
+    constexpr int ND = SEP ? 3 : 1;      // coefficient sets: one per coordinate class, or the one vector
     static_assert(4 % S == 0, "points per group and round");
     extern __shared__ double lds[];  // [rp] coefficients, then [16][8] box scratch + 8
     const int tid = threadIdx.x, lane16 = tid & 15, grp = tid >> 4;
-    const int rp = a.rp, km = rp >> 4;
+    const int rp = a.rp, km = SEP ? KM : rp >> 4;
     const int64_t M = a.M;
+    const int64_t qstride = SEP ? kCompactCols : rp, dstride = SEP ? compact_plane_doubles(M) : rp;  // point to point, coordinate to coordinate
+    const double *basis = SEP ? a.Qc : a.Q0;
     double *coef = lds, *red = lds + rp;
     for (int k = tid; k < rp; k += kSweepThreads) coef[k] = a.coef0[k];
     double R[9], tr[3], cen[3];
@@ -290,10 +295,19 @@ __global__ __launch_bounds__(kSweepThreads) void sweep_fit_boxes_kernel(SweepArg
         cen[q] = a.state->center[q];
     }
     const double scale = a.state->scale;
-    double cf[KM];
+    double cf[ND][KM];
     __syncthreads();
 #pragma unroll
-    for (int m = 0; m < KM; ++m) cf[m] = m < km ? coef[m * 16 + lane16] : 0.0;
+    for (int e = 0; e < ND; ++e)
+#pragma unroll
+        for (int m = 0; m < KM; ++m) {
+            if constexpr (SEP) {
+                const int col = a.sep_map[SepMap{rp}.col(e, m * 16 + lane16)];
+                cf[e][m] = col >= 0 ? coef[col] : 0.0;
+            } else {
+                cf[e][m] = m < km ? coef[m * 16 + lane16] : 0.0;
+            }
+        }
     double amax = 0.0;
     for (int64_t qd = blockIdx.x; qd * 64 < M; qd += gridDim.x) {
         double lo[3] = {__builtin_huge_val(), __builtin_huge_val(), __builtin_huge_val()};
@@ -312,11 +326,11 @@ __global__ __launch_bounds__(kSweepThreads) void sweep_fit_boxes_kernel(SweepArg
                 for (int s = 0; s < S; ++s) {  // every load of the round's column blocks in flight
                     const int64_t p = qd * 64 + (s0 + s) * kGroups + grp;
                     const int64_t pc = p < M ? p : 0;
-                    const double *q0 = a.Q0 + (3 * pc) * rp + lane16;
+                    const double *q0 = basis + (SEP ? pc : 3 * pc) * qstride + lane16;
 #pragma unroll
                     for (int d = 0; d < 3; ++d) {
 #pragma unroll
-                        for (int m = 0; m < CH; ++m) u[s][d][m] = (mc + m < KM && mc + m < km) ? q0[d * rp + (mc + m) * 16] : 0.0;
+                        for (int m = 0; m < CH; ++m) u[s][d][m] = (mc + m < KM && mc + m < km) ? q0[d * dstride + (mc + m) * 16] : 0.0;
                         if (mc == 0) rm[s][d] = a.ref[d * M + pc] + a.mean[d * M + pc];
                     }
                 }
@@ -326,7 +340,7 @@ __global__ __launch_bounds__(kSweepThreads) void sweep_fit_boxes_kernel(SweepArg
                     for (int d = 0; d < 3; ++d)
 #pragma unroll
                         for (int m = 0; m < CH; ++m)
-                            if (mc + m < KM) facc[s][d] = __builtin_fma(u[s][d][m], cf[mc + m], facc[s][d]);  // (m >= km: 0 * 0)
+                            if (mc + m < KM) facc[s][d] = __builtin_fma(u[s][d][m], cf[SEP ? d : 0][mc + m], facc[s][d]);  // (m >= km: 0 * 0)
             }
 #pragma unroll
             for (int s = 0; s < S; ++s) {
@@ -398,7 +412,9 @@ static void launch_sweep_mode(gingr_ctx *ctx, const SweepArgs &a, int width) {
         const int nq = (int)std::min<int64_t>(4096, ceil_div(a.M, 64));
         const size_t l2 = (size_t)(a.rp + kGroups * 8 + 8) * sizeof(double);
         TimerScope ts(ctx, 4);
-        if (a.rp <= 64)
+        if (a.Qc && a.sep_map)  // (rp <= 112: three kCompactCols-wide rows per point, 36 basis values per thread in flight)
+            hipLaunchKernelGGL((sweep_fit_boxes_kernel<kCompactCols / 16, 4, true>), dim3(nq), dim3(kSweepThreads), l2, ctx->stream, a);
+        else if (a.rp <= 64)
             hipLaunchKernelGGL((sweep_fit_boxes_kernel<4, 4>), dim3(nq), dim3(kSweepThreads), l2, ctx->stream, a);
         else if (a.rp <= 112)  // (rank 100: 84 basis values per thread in flight; eight column blocks would spill into AGPRs)
             hipLaunchKernelGGL((sweep_fit_boxes_kernel<7, 4>), dim3(nq), dim3(kSweepThreads), l2, ctx->stream, a);

@@ -333,7 +333,11 @@ int finish_models(gingr_group *g) {
     g->rank = gingr_model_rank(g->model[0]);
     // one fitter per shard
     g->fit.assign((size_t)n, nullptr);
-    return g->run([&](int r) { return gingr_fitter_create(g->ctx[(size_t)r], g->model[(size_t)r], &g->fit[(size_t)r]); });
+    return g->run([&](int r) {
+        const int rc = gingr_fitter_create(g->ctx[(size_t)r], g->model[(size_t)r], &g->fit[(size_t)r]);
+        if (rc == GINGR_OK) fitter_set_group_member(g->fit[(size_t)r]);
+        return rc;
+    });
 }
 
 // One-shot all-reduce over peer pointers, called by every worker: the shard has written its contribution to src[r]; it records

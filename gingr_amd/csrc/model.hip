@@ -31,7 +31,102 @@ __global__ __launch_bounds__(256) void truncate_basis_kernel(const double *__res
     Q[idx] = q < k ? Qs[row * rps + q] : 0.0;
 }
 
+// ---- coordinate-separable bases (gp.h: gingr_model::separable) ----------------------------------------------------------------------
+// partial[b][d * rp + k] = 1 when any entry of column k in the rows 3i + d of workgroup b's share is not +-0.0 (a NaN counts), else 0.
+// Every thread owns the columns k = tid, tid + 256, ... and walks its workgroup's rows: whole 2 KB runs per load instruction, no atomics.
+constexpr int kSepBlocks = 256;
+__global__ __launch_bounds__(256) void sep_flags_kernel(const double *__restrict__ Q0, int64_t rows, int32_t rp, int32_t *__restrict__ partial) {
+    const int64_t per = (rows + gridDim.x - 1) / gridDim.x;
+    const int64_t r0 = (int64_t)blockIdx.x * per, r1 = r0 + per < rows ? r0 + per : rows;
+    for (int k = threadIdx.x; k < rp; k += 256) {
+        int32_t fl[3] = {0, 0, 0};
+        for (int64_t row = r0; row < r1; ++row)
+            if (Q0[row * rp + k] != 0.0) fl[row % 3] = 1;
+        for (int d = 0; d < 3; ++d) partial[(int64_t)blockIdx.x * 3 * rp + d * rp + k] = fl[d];
+    }
+}
+// flags[q] = OR over the workgroups' partials, q < 3 rp
+__global__ __launch_bounds__(256) void sep_flags_reduce_kernel(const int32_t *__restrict__ partial, int nblocks, int32_t n, int32_t *__restrict__ flags) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    int32_t f = 0;
+    for (int b = 0; b < nblocks; ++b) f |= partial[(int64_t)b * n + q];
+    flags[q] = f;
+}
+// Qc[d][p][k] = Q0[3p + d][col(d, k)], zero behind the class's last column (the slack rows are cleared by the caller)
+__global__ __launch_bounds__(256) void compact_basis_kernel(const double *__restrict__ Q0, int64_t M, int32_t rp, const int32_t *__restrict__ sep_map,
+                                                            double *__restrict__ Qc) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 3 * M * kCompactCols) return;
+    const int k = (int)(idx % kCompactCols);
+    const int64_t pd = idx / kCompactCols;
+    const int64_t p = pd % M;
+    const int d = (int)(pd / M);
+    const int col = sep_map[SepMap{rp}.col(d, k)];
+    Qc[d * compact_plane_doubles(M) + p * kCompactCols + k] = col >= 0 ? Q0[(3 * p + d) * rp + col] : 0.0;
+}
+
+// Decides gingr_model::separable from the local Q0 and, where the compact passes can use it, builds Qc and sep_map.
+int model_detect_separable(gingr_ctx *ctx, gingr_model *m) {
+    const int32_t r = m->r, rp = m->rp;
+    const int64_t rows = 3 * m->M;
+    dev_free(m->Qc), dev_free(m->sep_map);
+    m->Qc = nullptr, m->sep_map = nullptr;
+    m->separable = false;
+    const int nb = (int)std::min<int64_t>(kSepBlocks, (rows + 63) / 64);
+    DevBuf part, flags;
+    HIP_TRY(ctx, part.alloc((size_t)nb * 3 * rp * sizeof(int32_t)));
+    HIP_TRY(ctx, flags.alloc((size_t)3 * rp * sizeof(int32_t)));
+    hipLaunchKernelGGL(sep_flags_kernel, dim3(nb), dim3(256), 0, ctx->stream, m->Q0, rows, rp, part.as<int32_t>());
+    hipLaunchKernelGGL(sep_flags_reduce_kernel, dim3((unsigned)ceil_div(3 * rp, 256)), dim3(256), 0, ctx->stream, part.as<int32_t>(), nb, 3 * rp,
+                       flags.as<int32_t>());
+    GINGR_TRY(check_launch(ctx));
+    std::vector<int32_t> hf((size_t)3 * rp);
+    HIP_TRY(ctx, hipMemcpyAsync(hf.data(), flags.p, hf.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    m->col_class.assign((size_t)r, 0);
+    for (int d = 0; d < 3; ++d) m->class_cols[d].clear();
+    bool sep = true;
+    for (int32_t k = 0; k < r; ++k) {
+        const int n = hf[(size_t)k] + hf[(size_t)rp + k] + hf[(size_t)2 * rp + k];
+        if (n > 1) sep = false;
+        const int cls = hf[(size_t)k] ? 0 : hf[(size_t)rp + k] ? 1 : hf[(size_t)2 * rp + k] ? 2 : 0;  // an all-zero column joins class x
+        m->col_class[(size_t)k] = cls;
+        m->class_cols[cls].push_back(k);
+    }
+    for (int d = 0; d < 3; ++d) m->rc[d] = (int32_t)m->class_cols[d].size();
+    if (!sep) {
+        m->col_class.clear();
+        for (int d = 0; d < 3; ++d) m->class_cols[d].clear(), m->rc[d] = 0;
+        return GINGR_OK;
+    }
+    m->separable = true;
+    // the compact passes: one shard, the ranks of the triangle kernel, and every class inside a plane's width
+    if (m->M != m->M_total || rp > 112 || std::max(m->rc[0], std::max(m->rc[1], m->rc[2])) > kCompactCols) return GINGR_OK;
+    const SepMap sm{rp};
+    std::vector<int32_t> map((size_t)sm.total(), -1);
+    for (int d = 0; d < 3; ++d)
+        for (int32_t p = 0; p < m->rc[d]; ++p) {
+            const int32_t k = m->class_cols[d][(size_t)p];
+            map[(size_t)sm.cls(k)] = d;
+            map[(size_t)sm.pos(k)] = p;
+            map[(size_t)sm.col(d, p)] = k;
+        }
+    GINGR_TRY(dev_alloc(ctx, &m->sep_map, map.size()));
+    GINGR_TRY(dev_alloc(ctx, &m->Qc, (size_t)3 * compact_plane_doubles(m->M)));
+    HIP_TRY(ctx, hipMemcpyAsync(m->sep_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    for (int d = 0; d < 3; ++d)
+        HIP_TRY(ctx, hipMemsetAsync(m->Qc + d * compact_plane_doubles(m->M) + m->M * kCompactCols, 0,
+                                    (size_t)kCompactRowSlack * kCompactCols * sizeof(double), ctx->stream));
+    hipLaunchKernelGGL(compact_basis_kernel, dim3((unsigned)ceil_div(3 * m->M * kCompactCols, 256)), dim3(256), 0, ctx->stream, m->Q0, m->M, rp,
+                       m->sep_map, m->Qc);
+    GINGR_TRY(check_launch(ctx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // map leaves scope
+    return GINGR_OK;
+}
+
 int model_finalize_impl(gingr_ctx *ctx, gingr_model *m) {
+    GINGR_TRY(model_detect_separable(ctx, m));
     DevBuf work, flag;
     HIP_TRY(ctx, work.alloc((size_t)binv_work_doubles(m->rp) * sizeof(double)));
     HIP_TRY(ctx, flag.alloc(sizeof(int32_t)));
@@ -244,9 +339,18 @@ int gingr_model_upload(gingr_ctx *ctx, int64_t M_total, int32_t rank, const doub
 void gingr_model_destroy(gingr_model *m) {
     if (!m) return;
     if (m->ctx) (void)hipSetDevice(m->ctx->device);
-    void *ptrs[] = {m->Q0, m->ref, m->mean, m->mom, m->Binv, m->eigV, m->eigL, m->cmat, m->pvec, m->perm, m->iperm};
+    void *ptrs[] = {m->Q0, m->ref, m->mean, m->mom, m->Binv, m->eigV, m->eigL, m->cmat, m->pvec, m->perm, m->iperm, m->Qc, m->sep_map};
     for (void *p : ptrs) dev_free(p);
     delete m;
+}
+
+int gingr_model_separable(const gingr_model *m, int32_t *separable, int32_t class_counts[3], int32_t *compact) {
+    if (!m || !separable) return GINGR_ERR_BAD_ARGUMENT;
+    *separable = m->separable ? 1 : 0;
+    if (class_counts)
+        for (int d = 0; d < 3; ++d) class_counts[d] = m->rc[d];
+    if (compact) *compact = m->Qc ? 1 : 0;
+    return GINGR_OK;
 }
 
 int64_t gingr_model_num_points(const gingr_model *m) { return m ? m->M : 0; }

@@ -97,28 +97,32 @@ __host__ __device__ inline size_t lds_solve_doubles(int rp, int xr) { return (si
 // HAS_S (round 6): whether the second matrix is there is known at every call site -- as a run-time test of the pointer it sat between
 // the loads of the two matrices for each of the 36 blocks, and the request of the next block waited for the previous block's value
 // (one memory round trip per block: 19k cycles of the transition-density kernel's 93k, tools/ubench_logpdf_split.hip).
-template <int NT, bool HAS_S = false>
+// cols != nullptr (the LDS-resident case only): row / column i of the system is row / column cols[i] of G, whose row stride is ldg --
+// one class of a coordinate-separable model out of the dense matrix (gp.h: SepMap); MAXB bounds n / 16 (blocks requested).
+template <int NT, bool HAS_S = false, int MAXB = 8>
 __device__ __forceinline__ void lds_load_spd(double *A, int ld, int r, int n, const double *__restrict__ G, double ca,
-                                             const double *__restrict__ S, double cs, double ci) {
+                                             const double *__restrict__ S, double cs, double ci, const int32_t *__restrict__ cols = nullptr,
+                                             int ldg = 0) {
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     constexpr int RB = NT / 16;  // rows per block of 16 columns: one element per thread and block
-    if (RB == 16 && n <= 128) {
+    if (RB == 16 && n <= 16 * MAXB) {
         // The LDS-resident case: all (at most 36) lower blocks are requested before the first value is used.  A lone workgroup
         // sees the full memory latency per dependent batch; with batches of eight blocks this stage was four round trips.
-        double v[36], vs[HAS_S ? 36 : 1];
+        double v[MAXB * (MAXB + 1) / 2], vs[HAS_S ? MAXB * (MAXB + 1) / 2 : 1];
         int idx = 0;
 #pragma unroll
-        for (int bi = 0; bi < 8; ++bi)
+        for (int bi = 0; bi < MAXB; ++bi)
 #pragma unroll
             for (int bj = 0; bj <= bi; ++bj, ++idx) {
                 const int i = bi * 16 + ty, j = bj * 16 + tx;
-                const int g = min(min(i, r - 1), n - 1) * n + min(j, r - 1);  // the global matrices have row stride rp == n
+                int g = min(min(i, r - 1), n - 1) * n + min(j, r - 1);  // the global matrices have row stride rp == n
+                if (cols) g = cols[min(min(i, r - 1), n - 1)] * ldg + cols[min(j, r - 1)];
                 v[idx] = G[g];  // (blocks past n: a clamped, valid address; the value is not stored)
                 if (HAS_S) vs[idx] = S[g];
             }
         idx = 0;
 #pragma unroll
-        for (int bi = 0; bi < 8; ++bi)
+        for (int bi = 0; bi < MAXB; ++bi)
 #pragma unroll
             for (int bj = 0; bj <= bi; ++bj, ++idx) {
                 double t = ca * v[idx];
@@ -127,7 +131,7 @@ __device__ __forceinline__ void lds_load_spd(double *A, int ld, int r, int n, co
             }
         idx = 0;
 #pragma unroll
-        for (int bi = 0; bi < 8; ++bi)
+        for (int bi = 0; bi < MAXB; ++bi)
 #pragma unroll
             for (int bj = 0; bj <= bi; ++bj, ++idx) {
                 const int i = bi * 16 + ty, j = bj * 16 + tx;

@@ -703,6 +703,13 @@ class DeviceModel:
     def finalize(self):
         _check(self.ctx.handle, self._lib.gingr_model_finalize(self.ctx.handle, self.handle), "gingr_model_finalize")
 
+    def separable(self) -> Tuple[bool, Tuple[int, int, int], bool]:
+        """gingr_model_separable: (every basis column lives on one coordinate, columns per coordinate, the compact basis is kept)"""
+        sep, compact, counts = ctypes.c_int32(), ctypes.c_int32(), (ctypes.c_int32 * 3)()
+        _check(self.ctx.handle, self._lib.gingr_model_separable(self.handle, ctypes.byref(sep), counts, ctypes.byref(compact)),
+               "gingr_model_separable")
+        return bool(sep.value), tuple(counts), bool(compact.value)
+
     def close(self):
         if getattr(self, "handle", None):
             # (a model that outlives its context -- e.g. collected after Context.close() -- must not call into the freed context: its

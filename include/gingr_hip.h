@@ -97,6 +97,11 @@ const char *gingr_build_info(void);
  *                        accept / reject decision in the next iteration.
  *   GINGR_OPT_DECIMATE_BATCH  16 (default), 1 .. 60: gingr_mesh_decimate enqueues this many steps of its cube-size bisection before it reads
  *                        the control block back; the steps behind the deciding one return at once.  1 = one read-back per step.
+ *   GINGR_OPT_SEPARABLE  -1 (default) / 0: a model whose basis columns each live on one coordinate (every model built from a diagonal
+ *                        kernel; gingr_model_separable) keeps a compact copy of its basis, and a single-shard CPD or isotropic-pairs
+ *                        update without landmarks or a sampled proposal forms the weighted Gram matrix, solves the posterior and
+ *                        writes the fit as three scalar-valued problems over it / 0: the dense passes.  Same results up to the
+ *                        summation order.
  * No reference counterpart (the reference has one code path per operation). */
 typedef enum gingr_ctx_option {
     GINGR_OPT_CULL = 0,
@@ -105,7 +110,8 @@ typedef enum gingr_ctx_option {
     GINGR_OPT_TRI_GRID = 3,
     GINGR_OPT_SPLIT_EXCHANGE = 4,
     GINGR_OPT_GRAM_DOWNDATE = 5,
-    GINGR_OPT_DECIMATE_BATCH = 6
+    GINGR_OPT_DECIMATE_BATCH = 6,
+    GINGR_OPT_SEPARABLE = 7
 } gingr_ctx_option;
 int gingr_ctx_set_option(gingr_ctx *ctx, int32_t option, int32_t value);
 int gingr_ctx_get_option(gingr_ctx *ctx, int32_t option, int32_t *value);
@@ -244,6 +250,10 @@ int gingr_model_download(gingr_ctx *ctx, const gingr_model *model, double *ref, 
                          double *variance);
 int64_t gingr_model_num_points(const gingr_model *model); /* local rows */
 int32_t gingr_model_rank(const gingr_model *model);
+/* Whether every basis column of the (finalised) model is supported on one coordinate only -- decided on the device from the local basis,
+ * entries of +-0.0 counting as absent -- the number of columns per coordinate (class_counts, nullable; zeros when not separable), and
+ * whether the model keeps the compact basis the separable passes read (compact, nullable; GINGR_OPT_SEPARABLE). */
+int gingr_model_separable(const gingr_model *model, int32_t *separable, int32_t class_counts[3], int32_t *compact);
 
 /* PointDistributionModel.instance(alpha) posed and scaled:  s * (R (ref + mean + U sqrt(lam) alpha - c) + c + t)
  * (G/api/ModelFittingParameters.scala:130-143).  out_xyz[3*M_local]. */

@@ -67,7 +67,8 @@ int main() {
         hipMemcpyToSymbol(HIP_SYMBOL(g_stage), zero, sizeof(zero));
         hipEventRecord(a);
         for (int i = 0; i < reps; ++i)
-            hipLaunchKernelGGL(posterior_solve_lds_kernel<0>, dim3(1), dim3(kSolveThreads), lds, 0, r, rp, dG, drhs, (const double *)nullptr, da, st);
+            hipLaunchKernelGGL(posterior_solve_lds_kernel<0>, dim3(1), dim3(kSolveThreads), lds, 0, r, rp, dG, drhs, (const double *)nullptr, da, st,
+                               (const int32_t *)nullptr, SepCounts{});
         hipEventRecord(b);
         hipDeviceSynchronize();
     }
