@@ -50,14 +50,42 @@ def have_extended():
 
 
 # ------------------------------------------------------------------------------------------------ dispatch restatement
-def route_of(r, sampled, factor_cached=False, eig=False):
-    """launch_posterior_solve / phase2_solve_and_commit.  eig: point-cloud ICP without landmarks, deterministic."""
+COMPACT_COLS = 48  # kCompactCols (gp.h)
+
+
+def keeps_compact_basis(r, class_counts, shards=1):
+    """model_detect_separable: a separable model (class_counts: columns per coordinate, None when some column has no class) keeps
+    its compact basis on one shard, at the ranks of the triangle kernel, with every class inside a plane's width."""
+    return class_counts is not None and shards == 1 and rp_of(r) <= 112 and max(class_counts) <= COMPACT_COLS
+
+
+def uses_compact(r, class_counts, flavour="cpd", sampled=False, landmarks=False, covariance_pairs=False, query=False, shards=1,
+                 device_group=False, option=-1):
+    """use_compact (fitter_phases.hip): flavour 'cpd', 'pairs', 'icp' or 'icp_surface'; query: a log-density, covariance or
+    posterior-model query, or a Metropolis-Hastings step (allow_alt); option: GINGR_OPT_SEPARABLE."""
+    if not keeps_compact_basis(r, class_counts, shards) or option == 0 or device_group:
+        return False
+    if not (flavour == "cpd" or (flavour == "pairs" and not covariance_pairs)):
+        return False
+    return not landmarks and not sampled and not query
+
+
+def even_classes(r):
+    return tuple((r + 2 - d) // 3 for d in range(3))
+
+
+def route_of(r, sampled, factor_cached=False, eig=False, compact=False):
+    """launch_posterior_solve / phase2_solve_and_commit.  eig: point-cloud ICP without landmarks, deterministic.  compact: uses_compact
+    of the update (never together with eig, sampled or factor_cached: those are flavours and callers it excludes)."""
     rp = rp_of(r)
     if eig and not sampled and r <= EIG_MAX_RANK:  # (eig_ready: model.hip decomposes S_tot only up to kSymEigColsMaxN columns)
         return "posterior_solve_eig_kernel"
     if sampled and factor_cached:  # nf_valid: only the split density kernel (rp <= 112, through gingr_fitter_mh_step) leaves the factor
         assert rp <= 112
         return "posterior_sample_cached_kernel"
+    if compact:
+        assert rp <= 112 and not sampled
+        return "posterior_solve_lds_kernel<2>"
     if rp > 240 and not sampled:
         return "dense_spd_solve3"
     if r <= 128:
@@ -89,6 +117,8 @@ def density_route_of(r, route_kind):
 EXPECTED = {
     "posterior_solve_lds_kernel<0>": (lambda r: route_of(r, False), 1, 112),
     "posterior_solve_lds_kernel<1>": (lambda r: route_of(r, False), 113, 128),
+    # a separable model with its columns dealt evenly to the coordinates (a Gaussian kernel's): CPD or isotropic pairs, nothing excluded
+    "posterior_solve_lds_kernel<2>": (lambda r: route_of(r, False, compact=uses_compact(r, even_classes(r))), 1, 112),
     "posterior_solve_wide_kernel<64>": (lambda r: route_of(r, False), 129, 240),
     "posterior_solve_wide_kernel<64> (sampled)": (lambda r: route_of(r, True) + " (sampled)", 129, 256),
     "posterior_solve_wide_kernel<32> (sampled)": (lambda r: route_of(r, True) + " (sampled)", 257, 512),

@@ -13,6 +13,8 @@ Which instance a rank reaches is the restatement route_of / density_route_of (as
     deterministic update   posterior_solve_lds_kernel<0>, <1>, posterior_solve_wide_kernel<64>, dense_spd_solve3
     sampled update         the same LDS kernels, posterior_solve_wide_kernel<64> up to rp 256, <32> above
     density (row shard)    posterior_logpdf_lds_kernel<false>, posterior_logpdf_wide_kernel<64>, <32>, two dense solves
+posterior_solve_lds_kernel<2> (the three-block solve of a coordinate-separable model, uses_compact) takes the same injection with a
+separable model in `parts`: tests/test_gpu_separable_edges.py.
 Layer B (test_real_state_readback) reaches what injection cannot -- posterior_logpdf_split_kernel and the two
 posterior_logpdf_cached_kernel instances, plus the wide / dense density once more: a real CPD state whose model's lam spans
 [1e-3, 1e6], G / rhs / Q0^T e copied OUT of segment 1 by a read-only callback of the row-shard density, then the same state asked

@@ -23,7 +23,27 @@ def test_route_table_names_every_instance_at_both_edges():
     for lo, hi in ((15, 17), (31, 33)):
         assert lo in pc.RANKS and hi in pc.RANKS and 16 in pc.RANKS
     named = {n.replace(" (sampled)", "") for n in pc.EXPECTED}
-    assert len(named) + len(pc.UNREACHABLE) == 15  # every instance behind the three launchers (the dense routes and the eigen route included)
+    assert len(named) + len(pc.UNREACHABLE) == 16  # every instance behind the four launchers (the dense routes and the eigen route included)
+
+
+def test_three_block_solve_is_selected_by_use_compact_alone():
+    """posterior_solve_lds_kernel<2>: a deterministic CPD or isotropic-pairs update of a single-shard separable model that keeps its
+    compact basis (rp <= 112, at most 48 columns per coordinate), without landmarks and not behind a query -- and nothing else."""
+    name = "posterior_solve_lds_kernel<2>"
+
+    def route(r, counts, **kw):
+        return pc.route_of(r, kw.get("sampled", False), compact=pc.uses_compact(r, counts, **kw))
+
+    assert route(49, (48, 1, 0)) == name and route(96, (0, 48, 48)) == name and route(112, (48, 47, 17)) == name
+    assert route(100, (34, 33, 33), flavour="pairs") == name
+    assert pc.even_classes(112) == (38, 37, 37) and pc.even_classes(1) == (1, 0, 0) and pc.even_classes(113) == (38, 38, 37)
+    dense = "posterior_solve_lds_kernel<0>"
+    assert route(51, (49, 1, 1)) == dense          # a class past the plane's width
+    assert route(30, None) == dense                 # not separable
+    assert route(113, (38, 38, 37)) == "posterior_solve_lds_kernel<1>"  # rp = 128: no compact basis is kept
+    for kw in ({"landmarks": True}, {"sampled": True}, {"query": True}, {"shards": 2}, {"device_group": True}, {"option": 0},
+               {"flavour": "icp"}, {"flavour": "icp_surface"}, {"flavour": "pairs", "covariance_pairs": True}):
+        assert route(100, (34, 33, 33), **kw) == dense, kw
 
 
 def test_global_workspace_density_kernel_has_no_caller():
