@@ -69,5 +69,41 @@ for name, prior in (("kernel GPMM     ", gpmm), ("PCA model       ", pca), ("PCA
     print(f"CPD of the femur pair from the {name} (rank {prior.rank}): {best.general.iteration} iterations, "
           f"mean vertex distance {mean_distance(best.general.fit, target):.3f} mm")
     cpd.close()
+
+# ---- how good are the three models?  ModelMetrics: generalization on fits the PCA model was not built from, specificity against
+# the fits it was built from.  Distances are vertex to corresponding vertex (scalismo's ModelMetrics measures to the closest surface
+# point); there is no pose in either measure, so every shape is first moved rigidly onto the model's own mean shape.
+
+
+def onto_mean(model, shapes):
+    """Kabsch, vertex for vertex: every shape rotated and translated onto model.reference + model.mean"""
+    h = model.device().download(basis=False)
+    tgt = np.asarray(h.reference) + np.asarray(h.mean)
+    out = []
+    for x in shapes:
+        cx, ct = x.mean(axis=0), tgt.mean(axis=0)
+        u, _, vt = np.linalg.svd((tgt - ct).T @ (x - cx))
+        R = u @ np.diag([1.0, 1.0, np.sign(np.linalg.det(u @ vt))]) @ vt
+        out.append((x - cx) @ R.T + ct)
+    return np.stack(out)
+
+
+held_out = []
+for i in range(3):
+    sample = gpmm.device().instance(rng.normal(0, 0.7, gpmm.rank), euler=rng.normal(0, 0.05, 3), center=ref.mean(axis=0),
+                                    translation=rng.normal(0, 3, 3))
+    cpd = ga.CpdRegistration(ctx)
+    best = cpd.run(cpd.createInitialState(gpmm, sample + rng.normal(0, 0.2, sample.shape), cfg, transform=ga.GlobalTranformationType.RigidTransforms))
+    cpd.close()
+    held_out.append(best.general.fit)
+for name, prior in (("kernel GPMM     ", gpmm), ("PCA model       ", pca), ("PCA + kernel    ", augmented)):
+    t0 = time.perf_counter()
+    ranks = sorted({1, max(1, prior.rank // 2), prior.rank})
+    gen = ga.ModelMetrics.generalization(ctx, prior, onto_mean(prior, held_out), ranks=ranks)
+    spec = ga.ModelMetrics.specificity(ctx, prior, onto_mean(prior, fits), 200, seed=2)
+    compact = ga.ModelMetrics.compactness(prior.device().download(basis=False), ranks=ranks)
+    print(f"{name} (rank {prior.rank}): generalization on {len(held_out)} held-out fits at ranks {ranks}: "
+          + ", ".join(f"{v:.3f}" for v in gen.curve()) + " mm (compactness " +", ".join(f"{v:.2f}" for v in compact)
+          + f"); specificity of 200 samples against the {len(fits)} fits: {spec.curve()[0]:.3f} mm; {1e3 * (time.perf_counter() - t0):.0f} ms")
 augmented.device().close()
 pca.device().close()

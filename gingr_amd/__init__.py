@@ -13,8 +13,9 @@ from .api import (  # noqa: F401
     DevicePointDistributionModel, GaussianKernelParameters, GPMMTriangleMesh3D, PointSetHelper, automaticGPMMfromTemplate,
     GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo,
     AugmentedDevicePointDistributionModel, AugmentInfo, LaplacianDevicePointDistributionModel, LaplacianInfo,
-    TemplateConfiguration, TemplateRegistration, TemplateRegistrationState,
+    TemplateConfiguration, TemplateRegistration, TemplateRegistrationState, ModelMetrics,
 )
+from . import metrics  # noqa: F401  (generalization, specificity, compactness of a shape model)
 from ._native import GingrNativeError  # noqa: F401
 from .group import DeviceGroup  # noqa: F401  (in-library multi-GPU group: gingr_group_*)
 from . import io  # noqa: F401  (file / wire formats shared with the Scala host)

@@ -191,6 +191,9 @@ __global__ __launch_bounds__(256) void augment_factor_kernel(const double *__res
     T[e] = (i < rs && j < k) ? V[(int64_t)(row0 + i) * n + j] : 0.0;
 }
 
+}  // namespace
+
+// (declared in basis_rotate.h: model_metrics.hip takes Q0^T D through the same pass, D a block of columns in the model's row order)
 void cross_gram_plan(int64_t M, int32_t rpa, int32_t rpb, int *npa, int *npb, int *nslabs, int64_t *verts_per_slab) {
     *npa = (rpa + 63) / 64;
     *npb = (rpb + 63) / 64;
@@ -214,6 +217,8 @@ void launch_cross_gram(gingr_ctx *ctx, const gingr_model *a, const gingr_model *
     }
     hipLaunchKernelGGL(cross_gram_reduce_kernel, dim3((unsigned)ceil_div(n, 32)), dim3(256), 0, ctx->stream, ws, nslabs, n, C);
 }
+
+namespace {
 
 void launch_basis_rotate2(gingr_ctx *ctx, const gingr_model *a, const double *Ta, const gingr_model *b, const double *Tb, gingr_model *dst) {
     const int nchunks = (int)ceil_div(dst->rp / 16, kRotChunkTiles);

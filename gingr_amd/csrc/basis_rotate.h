@@ -6,6 +6,11 @@
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
+// augment_model.hip: C [a->rp][b->rp] = Q_a^T Q_b on ctx->stream, slab partials added in a fixed order.  Of a and b it reads M, Q0, rp
+// and a->perm, b->iperm (the vertex at row s of a sits at row b->iperm[a->perm[s]] of b); ws: nslabs a->rp b->rp doubles (cross_gram_plan)
+void cross_gram_plan(int64_t M, int32_t rpa, int32_t rpb, int *npa, int *npb, int *nslabs, int64_t *verts_per_slab);
+void launch_cross_gram(gingr_ctx *ctx, const gingr_model *a, const gingr_model *b, double *ws, double *C);
+
 constexpr int kRotWaves = 8;       // waves per workgroup, each with 16 vertices of its own (no LDS, no barrier); two per SIMD keep the
                                    // 96 accumulator registers in VGPRs (marginal_cov_kernel, posterior_cov.hip)
 constexpr int kRotVerts = 16;      // vertices per wave = rows of one MFMA tile

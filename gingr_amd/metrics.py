@@ -1,0 +1,91 @@
+"""Model metrics: how good is a shape model?  The three measures of the shape-model literature (and of scalismo's ModelMetrics), with the
+two expensive ones batched on the device:
+
+  generalization   how closely the model, cut to its k leading components, reproduces shapes it has not seen
+  specificity      how far random samples of the model lie from the nearest real shape
+  compactness      the share of the variance the k leading components keep (host only)
+
+What is not scalismo's is this package's definition -- scalismo's own source is not in reach.  scalismo measures against the closest
+surface point; here every distance is vertex to corresponding vertex: the shapes must be in correspondence with the model's reference,
+as the shapes of PointDistributionModel.createUsingPCA are.  The projection of a shape onto k components is the existing rule,
+model.truncate(k).coefficients(shape) followed by .instance: the regression with noise 1e-5 at the identity pose.
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import Optional
+
+import numpy as np
+
+from ._native import f64, dptr, iptr
+from .context import Context, _check
+from .models import _resident
+
+
+@dataclasses.dataclass
+class GeneralizationResult:
+    ranks: np.ndarray          # [n_ranks]
+    avg: np.ndarray            # [n_ranks, n] mean vertex distance between shape and projection
+    max: np.ndarray            # [n_ranks, n] largest vertex distance
+    coefficients: np.ndarray   # [n_ranks, n, rank], zero from entry k on
+
+    def curve(self) -> np.ndarray:
+        """the mean over the shapes of the mean distance, per rank"""
+        return self.avg.mean(axis=1)
+
+
+@dataclasses.dataclass
+class SpecificityResult:
+    ranks: np.ndarray          # [n_ranks]
+    min_avg: np.ndarray        # [n_ranks, nSamples] mean vertex distance to the nearest training shape
+    argmin: np.ndarray         # [n_ranks, nSamples] that shape's index (the lowest on an exact tie)
+    alphas: np.ndarray         # [nSamples, rank] the coefficient vectors of the samples
+
+    def curve(self) -> np.ndarray:
+        """the mean over the samples, per rank"""
+        return self.min_avg.mean(axis=1)
+
+
+class ModelMetrics:
+    """model: a device-built model, a DeviceModel, or a host PointDistributionModel (uploaded for the call)."""
+
+    @staticmethod
+    def generalization(ctx: Context, model, shapes, ranks=None) -> GeneralizationResult:
+        """shapes: n x M x 3 in correspondence with the model's reference, n <= 512 per call.  ranks=None: the full rank only."""
+        dm, own = _resident(ctx, model)
+        try:
+            coef, avg, mx = dm.project(shapes, ranks)
+            return GeneralizationResult(dm._ranks(ranks).astype(np.int64), avg, mx, coef)
+        finally:
+            if own:
+                dm.close()
+
+    @staticmethod
+    def specificity(ctx: Context, model, shapes, nSamples: int, ranks=None, seed: int = 0, alphas=None) -> SpecificityResult:
+        """shapes: the n <= 512 training shapes.  The samples are the instances of `alphas` (nSamples x rank), drawn here with
+        numpy.random.default_rng(seed).standard_normal unless given -- the library draws nothing; for rank k the entries from k on
+        count as zero."""
+        dm, own = _resident(ctx, model)
+        try:
+            X, k = dm._shapes(shapes), dm._ranks(ranks)
+            A = np.random.default_rng(seed).standard_normal((int(nSamples), dm.rank)) if alphas is None else f64(alphas)
+            if A.ndim != 2 or A.shape != (int(nSamples), dm.rank):
+                raise ValueError(f"alphas: expected ({int(nSamples)}, {dm.rank}), got {A.shape}")
+            A = f64(A)
+            S = A.shape[0]
+            mn, am = np.empty((k.size, S)), np.empty((k.size, S), dtype=np.int32)
+            _check(ctx.handle, ctx._lib.gingr_model_specificity(ctx.handle, dm.handle, X.shape[0], dptr(X), S, dptr(A), k.size, iptr(k),
+                                                                dptr(mn), iptr(am)), "gingr_model_specificity")
+            return SpecificityResult(k.astype(np.int64), mn, am.astype(np.int64), A)
+        finally:
+            if own:
+                dm.close()
+
+    @staticmethod
+    def compactness(model, ranks: Optional[np.ndarray] = None) -> np.ndarray:
+        """Host only: the cumulative fraction of the model's variance that the k leading components keep -- for every k = 1 .. rank,
+        or for the k in ranks."""
+        host = getattr(model, "host", model)
+        var = np.asarray(host.variance, dtype=np.float64)
+        frac = np.cumsum(var) / var.sum()
+        return frac if ranks is None else frac[np.atleast_1d(np.asarray(ranks, dtype=np.int64)) - 1]

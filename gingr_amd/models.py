@@ -739,6 +739,43 @@ class DeviceModel:
                                                                    dptr(m), dptr(out)), "gingr_model_coefficients")
         return out
 
+    def _ranks(self, ranks) -> np.ndarray:
+        """ranks=None: the full rank only"""
+        return np.ascontiguousarray([self.rank] if ranks is None else np.atleast_1d(ranks), dtype=np.int32)
+
+    def _shapes(self, shapes) -> np.ndarray:
+        X = f64(shapes)
+        if X.ndim == 2:
+            X = X[None]
+        if X.ndim != 3 or X.shape[1:] != (self.M_local, 3):
+            raise ValueError(f"shapes: expected (n, {self.M_local}, 3), got {X.shape}")
+        return X
+
+    def instances(self, alphas) -> np.ndarray:
+        """ref + mean + Q0 alpha_i for every row of alphas (n x rank), n x M x 3, no pose (gingr_model_instances): one pass over the
+        basis per 512 coefficient vectors instead of a fitter and a pass per vector."""
+        A = f64(alphas)
+        if A.ndim == 1:
+            A = A[None]
+        if A.ndim != 2 or A.shape[1] != self.rank:
+            raise ValueError(f"alphas: expected (n, {self.rank}), got {A.shape}")
+        out = np.empty((A.shape[0], self.M_local, 3))
+        _check(self.ctx.handle, self._lib.gingr_model_instances(self.ctx.handle, self.handle, A.shape[0], dptr(A), dptr(out)),
+               "gingr_model_instances")
+        return out
+
+    def project(self, shapes, ranks=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The shapes (n x M x 3, n <= 512) projected onto the k leading components for every k in ranks (gingr_model_generalization):
+        (coefficients [n_ranks, n, rank], zero from entry k on; mean vertex distance [n_ranks, n]; largest vertex distance
+        [n_ranks, n]) between each shape and its projection -- what truncate(k).coefficients(shape) and .instance give, shape by
+        shape.  Vertex to corresponding vertex."""
+        X, k = self._shapes(shapes), self._ranks(ranks)
+        n = X.shape[0]
+        coef, avg, mx = np.empty((k.size, n, self.rank)), np.empty((k.size, n)), np.empty((k.size, n))
+        _check(self.ctx.handle, self._lib.gingr_model_generalization(self.ctx.handle, self.handle, n, dptr(X), k.size, iptr(k), dptr(coef),
+                                                                     dptr(avg), dptr(mx)), "gingr_model_generalization")
+        return coef, avg, mx
+
     def posterior_mean(self, obs_points, weights, euler=(0, 0, 0), center=(0, 0, 0), translation=(0, 0, 0),
                        landmarks: Optional["LandmarkCorrespondences"] = None) -> Tuple[np.ndarray, np.ndarray]:
         o, w, e, c, t = f64(obs_points), f64(weights), f64(euler), f64(center), f64(translation)

@@ -573,6 +573,35 @@ typedef struct gingr_augment_info {
 int gingr_model_augment(gingr_ctx *ctx, const gingr_model *a, const gingr_model *b, double relative_tolerance,
                         int32_t max_rank, gingr_model **out, gingr_augment_info *info /* may be NULL */);
 
+/* ---- model metrics: many instances, many projections, many samples against many shapes ------------------------------------------
+ * What the shape-model literature (and scalismo's ModelMetrics) measures a model by, batched on the device.  What is not scalismo's is
+ * this library's definition: nothing in reach pins scalismo's own, and scalismo measures against the closest surface point, whereas
+ * every distance here is vertex to corresponding vertex.  model: a complete (single-shard), finalized model of this context -- a row
+ * shard or a model that is not finalized is GINGR_ERR_STATE.  Shapes are host arrays of 3 M doubles each, one after the other,
+ * interleaved xyz in the caller's point order (the layout of gingr_model_from_shapes).  ranks: n_ranks <= 16 strictly increasing values
+ * 1 <= k <= rank.  Bad counts or ranks and null arguments are GINGR_ERR_BAD_ARGUMENT (the text names the cause); a non-finite
+ * coordinate or coefficient is GINGR_ERR_NONFINITE (the text names the shape or vector) and nothing is computed.  Single precision
+ * nowhere; every sum in a fixed order, no float atomics: two calls with the same input give the same bits.  All three synchronise.
+ *
+ * gingr_model_instances: out_xyz [n][3 M] = ref + mean + Q0 alpha_i for the n >= 1 coefficient vectors alphas [n][rank], no pose: one
+ *   pass over the basis on the matrix pipe per block of 512 vectors.
+ * gingr_model_generalization: for the 1 <= n <= 512 shapes and every k in ranks, avg [n_ranks][n] the mean and max [n_ranks][n] the
+ *   largest vertex distance between the shape and its projection onto the k leading components; coeffs (may be NULL)
+ *   [n_ranks][n][rank] the projection's coefficients, zero from entry k on.  The projection is the existing rule: what
+ *   gingr_model_truncate(k), gingr_model_coefficients and gingr_model_instance return at the identity pose -- the regression with
+ *   noise 1e-5, alpha_k = (S_k / 1e-5 + I)^-1 Q_k^T (x - ref - mean) / 1e-5 with Q_k the k leading columns of U sqrt(lambda) and
+ *   S_k = Q_k^T Q_k.  A shape that is an instance of the model therefore comes back at a distance of the order of that ridge's bias,
+ *   not 0.  GINGR_ERR_NOT_SPD: S / 1e-5 + I could not be factored.
+ * gingr_model_specificity: the sample (i, k) is the instance of alphas [n_samples][rank] row i with the entries from k on set to
+ *   zero; min_avg [n_ranks][n_samples] is its smallest mean vertex distance to one of the 1 <= n_train <= 512 training shapes and
+ *   argmin [n_ranks][n_samples] that shape's index, the lowest index on an exact tie.  The coefficients are the caller's: the library
+ *   draws nothing.  n_samples >= 1, in blocks of 512. */
+int gingr_model_instances(gingr_ctx *ctx, const gingr_model *model, int64_t n, const double *alphas, double *out_xyz);
+int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t n, const double *shapes_xyz, int32_t n_ranks,
+                               const int32_t *ranks, double *coeffs /* may be NULL */, double *avg, double *max);
+int gingr_model_specificity(gingr_ctx *ctx, const gingr_model *model, int32_t n_train, const double *train_xyz, int64_t n_samples,
+                            const double *alphas, int32_t n_ranks, const int32_t *ranks, double *min_avg, int32_t *argmin);
+
 /* ---- the inverse-Laplacian model from the sparse Laplacian's own eigenpairs -------------------------------------------------
  * The model of DiagonalKernel(LookupKernel(pinv(L)) * scaling) (GPMMHelper.scala:132-136, InvLapKernel) without the n x n
  * pseudo-inverse: a new, finalized, single-shard model on this context.  Everything is host memory: ref_xyz [3 M] the reference,
@@ -832,7 +861,8 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * 11 / 12 = the cross Gram pass / the two-source basis pass of gingr_model_augment alone, 13 .. 16 = the stages of gingr_mesh_decimate:
  * bounding box, bisection (every enqueued step, the ones that return at once included), clusters and representatives (insertion at
  * the chosen size, sort, means, argmin), compaction of vertices and triangles, 17 = the Chebyshev step of gingr_model_from_laplacian
- * (lap_cheb_kernel) alone.  Returns accumulated ms and launches since
+ * (lap_cheb_kernel) alone, 18 / 19 / 20 = the passes of the model metrics alone: reconstruct and measure (gingr_model_generalization), samples
+ * against training shapes (gingr_model_specificity), the stored basis x factor product (gingr_model_instances, gingr_model_specificity).  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
