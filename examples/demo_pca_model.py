@@ -6,7 +6,9 @@ fits are point for point on the reference's vertices, so they go straight into P
 generalised Procrustes alignment (DataCollection.gpa + createUsingPCA of scalismo, on the device).  The PCA model is saved as a
 statismo .h5.json file and is then the prior of one more CPD registration.  A model of eight fits has rank 7 at most and is far too
 stiff to reach a new femur, so a third prior is the PCA model augmented with a Gaussian kernel model on its own reference
-(PointDistributionModel.augmentModel: the covariances are added and re-diagonalised on the device)."""
+(PointDistributionModel.augmentModel: the covariances are added and re-diagonalised on the device), and a fourth is the PCA model
+localized (PointDistributionModel.localizeModel: the sample covariance under a Gaussian taper of the distance on the reference --
+every vertex keeps its variance, the long-range correlations eight fits cannot support are removed, nothing generic is added)."""
 import os
 import sys
 import tempfile
@@ -63,14 +65,21 @@ ainfo = augmented.augmentInfo
 print(f"PCA model + Gaussian kernel (sigma 70, scaling 20): {ainfo.columns} columns, rank {ainfo.rank}, variance kept {ainfo.kept_variance:.1f} of "
       f"{ainfo.total_variance:.1f} mm^2, built in {1e3 * (time.perf_counter() - t0):.1f} ms")
 
-for name, prior in (("kernel GPMM     ", gpmm), ("PCA model       ", pca), ("PCA + kernel    ", augmented)):
+t0 = time.perf_counter()
+localized = ga.PointDistributionModel.localizeModel(ctx, pca, sigma=70.0, relativeTolerance=0.01)
+linfo = localized.localizeInfo
+print(f"PCA model localized (sigma 70): {linfo.columns} factor columns, rank {linfo.rank}, residual {linfo.residual_fraction:.2e} of the trace, variance "
+      f"kept {linfo.kept_variance:.1f} of {linfo.total_variance:.1f} mm^2, built in {1e3 * (time.perf_counter() - t0):.1f} ms")
+
+PRIORS = (("kernel GPMM     ", gpmm), ("PCA model       ", pca), ("PCA + kernel    ", augmented), ("PCA localized   ", localized))
+for name, prior in PRIORS:
     cpd = ga.CpdRegistration(ctx)
     best = cpd.run(cpd.createInitialState(prior, target, cfg, transform=ga.GlobalTranformationType.RigidTransforms))
     print(f"CPD of the femur pair from the {name} (rank {prior.rank}): {best.general.iteration} iterations, "
           f"mean vertex distance {mean_distance(best.general.fit, target):.3f} mm")
     cpd.close()
 
-# ---- how good are the three models?  ModelMetrics: generalization on fits the PCA model was not built from, specificity against
+# ---- how good are the four models?  ModelMetrics: generalization on fits the PCA model was not built from, specificity against
 # the fits it was built from.  Distances are vertex to corresponding vertex (scalismo's ModelMetrics measures to the closest surface
 # point); there is no pose in either measure, so every shape is first moved rigidly onto the model's own mean shape.
 
@@ -96,7 +105,7 @@ for i in range(3):
     best = cpd.run(cpd.createInitialState(gpmm, sample + rng.normal(0, 0.2, sample.shape), cfg, transform=ga.GlobalTranformationType.RigidTransforms))
     cpd.close()
     held_out.append(best.general.fit)
-for name, prior in (("kernel GPMM     ", gpmm), ("PCA model       ", pca), ("PCA + kernel    ", augmented)):
+for name, prior in PRIORS:
     t0 = time.perf_counter()
     ranks = sorted({1, max(1, prior.rank // 2), prior.rank})
     gen = ga.ModelMetrics.generalization(ctx, prior, onto_mean(prior, held_out), ranks=ranks)
@@ -105,5 +114,6 @@ for name, prior in (("kernel GPMM     ", gpmm), ("PCA model       ", pca), ("PCA
     print(f"{name} (rank {prior.rank}): generalization on {len(held_out)} held-out fits at ranks {ranks}: "
           + ", ".join(f"{v:.3f}" for v in gen.curve()) + " mm (compactness " +", ".join(f"{v:.2f}" for v in compact)
           + f"); specificity of 200 samples against the {len(fits)} fits: {spec.curve()[0]:.3f} mm; {1e3 * (time.perf_counter() - t0):.0f} ms")
+localized.device().close()
 augmented.device().close()
 pca.device().close()

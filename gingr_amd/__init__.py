@@ -13,6 +13,7 @@ from .api import (  # noqa: F401
     DevicePointDistributionModel, GaussianKernelParameters, GPMMTriangleMesh3D, PointSetHelper, automaticGPMMfromTemplate,
     GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo,
     AugmentedDevicePointDistributionModel, AugmentInfo, LaplacianDevicePointDistributionModel, LaplacianInfo,
+    LocalizedDevicePointDistributionModel, LocalizeInfo,
     TemplateConfiguration, TemplateRegistration, TemplateRegistrationState, ModelMetrics,
 )
 from . import metrics  # noqa: F401  (generalization, specificity, compactness of a shape model)

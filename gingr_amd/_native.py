@@ -120,6 +120,12 @@ class AugmentInfo(ctypes.Structure):
     _fields_ = [("columns", c_int32), ("rank", c_int32), ("total_variance", c_double), ("kept_variance", c_double)]
 
 
+class LocalizeInfo(ctypes.Structure):
+    """gingr_localize_info"""
+    _fields_ = [("columns", c_int32), ("rank", c_int32), ("tolerance_reached", c_int32), ("residual_fraction", c_double),
+                ("total_variance", c_double), ("kept_variance", c_double)]
+
+
 class LaplacianInfo(ctypes.Structure):
     """gingr_laplacian_info"""
     _fields_ = [("n_components", c_int32), ("n_dropped", c_int32), ("block_columns", c_int32), ("outer_iterations", c_int32),
@@ -254,6 +260,7 @@ SIGNATURES = {
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),
+    "gingr_model_localize": (c_int, [c_void_p, c_void_p, c_double, c_double, c_int32, POINTER(c_void_p), POINTER(LocalizeInfo)]),
     "gingr_model_instances": (c_int, [c_void_p, c_void_p, c_int64, _dp, _dp]),
     "gingr_model_generalization": (c_int, [c_void_p, c_void_p, c_int32, _dp, c_int32, _ip, _dp, _dp, _dp]),
     "gingr_model_specificity": (c_int, [c_void_p, c_void_p, c_int32, _dp, c_int64, _dp, c_int32, _ip, _dp, _ip]),

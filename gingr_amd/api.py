@@ -28,7 +28,7 @@ from .context import Context, _check  # noqa: F401
 from .models import (  # noqa: F401
     AugmentInfo, AugmentedDevicePointDistributionModel, DeviceModel, DevicePointDistributionModel, GPMMTriangleMesh3D,
     GaussianKernelParameters, GpmmBuildInfo, InterpolatedDevicePointDistributionModel, LaplacianDevicePointDistributionModel,
-    LaplacianHelper, LaplacianInfo, PcaDevicePointDistributionModel, PcaInfo, PointDistributionModel, PointSetHelper,
+    LaplacianHelper, LaplacianInfo, LocalizeInfo, LocalizedDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo, PointDistributionModel, PointSetHelper,
     PosteriorDevicePointDistributionModel, ScalarKernelSpec, TruncatedDevicePointDistributionModel, _cells_of, _resident,
     automaticGPMMfromTemplate,
 )

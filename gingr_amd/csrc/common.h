@@ -14,7 +14,7 @@
 #include "../../include/gingr_hip.h"
 #include "host_device.h"
 
-#define GINGR_TIMERS 21
+#define GINGR_TIMERS 22
 
 struct gingr_ctx {
     int device = 0;

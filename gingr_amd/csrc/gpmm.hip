@@ -16,7 +16,7 @@
 //
 // The other kernels of GPMMTriangleMesh3D (GPMMHelper.scala:103-142) go through gingr_gpmm_build_diagonal: one scalar kernel per
 // coordinate (Gaussian mixture with an optional x-mirrored copy, linear, lookup table).  Three equal kernels take the scalar route
-// above; different kernels (GaussianSymmetry) run the generic factorisation over the 3M entries themselves (pc_*_kernel<true>).
+// above; different kernels (GaussianSymmetry) run the generic factorisation over the 3M entries themselves (pc_*_kernel<Diagonal>).
 // Exact ties between residuals follow scalismo's rule -- the first maximum in the permuted index order -- through a log of the
 // swaps that is replayed for tied candidates (PosLog).
 //
@@ -34,6 +34,8 @@
 namespace {
 
 using gpmm_factor::Factor;
+using gpmm_factor::FactorKind;
+using gpmm_factor::TaperBasis;
 using gpmm_factor::kMaxMix;
 using gpmm_factor::KSpec;
 using gpmm_factor::KSpec3;
@@ -89,7 +91,7 @@ struct PosLog {
 // slot" -- only depends on the step that pivoted e (at most one, and e never moves after it) and otherwise on the LAST step that displaced
 // it, so the loop carries two selects and no branch: its reads do not depend on one another and run pipelined (as a literal replay with
 // an early return every logged step was a dependent round trip, and a mirrored kernel's structural ties replay the log dozens of times
-// per step: pc_step_kernel<true> 131 -> 113 us on average with the log in LDS, -> see profiles/r06_gpmm_build_ab_blocked_kernels.txt).
+// per step: pc_step_kernel<Diagonal> (then <true>) 131 -> 113 us on average with the log in LDS, -> see profiles/r06_gpmm_build_ab_blocked_kernels.txt).
 __device__ __forceinline__ int32_t log_position(const PosLog &lg, int32_t e) {
     int32_t sp = -1, sl = -1;
     for (int32_t s = 0; s < lg.n; ++s) {
@@ -138,17 +140,21 @@ __device__ __forceinline__ void block_best_sum(Best &b, double &sum, Best *shb, 
     __syncthreads();
 }
 
-// GEN = false: one scalar kernel, entries = points.  GEN = true: the generic factorisation over the 3M (point, coordinate) entries
+// KIND = Scalar: one scalar kernel, entries = points.  KIND = Diagonal: the generic factorisation over the 3M (point, coordinate) entries
 // of a DiagonalKernel(k_x, k_y, k_z) whose coordinates have DIFFERENT kernels (entry e = 3 point + coordinate; entries of
-// different coordinates never interact: their column values are exact zeros).
-template <bool GEN>
-__global__ __launch_bounds__(kPcBlock) void pc_init_kernel(Cloud pts, KSpec3 specs, double *__restrict__ diag,
+// different coordinates never interact: their column values are exact zeros).  KIND = Tapered: the same 3M entries under the full
+// block kernel g(x_i, x_j) <Q[3i+a,:], Q[3j+b,:]> of gingr_model_localize (g = specs.k[0], one Gaussian of scaling 1; Q^T = basis.qt):
+// every entry interacts with every other.  g(x, x) = 1, so an entry's own value is its row's dot product with itself, summed as the
+// step kernel sums it (multiply, then add, ascending columns).
+template <FactorKind KIND>
+__global__ __launch_bounds__(kPcBlock) void pc_init_kernel(Cloud pts, KSpec3 specs, TaperBasis basis, double *__restrict__ diag,
                                                            int32_t *__restrict__ pivoted, double *__restrict__ pmax,
                                                            int32_t *__restrict__ pidx, double *__restrict__ ptr,
                                                            int32_t *__restrict__ ctl) {
     __shared__ double T[GINGR_EXP_TABLE];
     __shared__ Best shb[kPcBlock];
     __shared__ double shs[kPcBlock];
+    constexpr bool GEN = KIND != FactorKind::Scalar, TAP = KIND == FactorKind::Tapered;
     fastexp_table_init(T);
     __syncthreads();
     const int64_t n = GEN ? 3 * pts.n : pts.n;
@@ -159,7 +165,13 @@ __global__ __launch_bounds__(kPcBlock) void pc_init_kernel(Cloud pts, KSpec3 spe
         const int64_t pc = GEN ? c / 3 : c;
         const KSpec &spec = specs.k[GEN ? (int)(c - 3 * pc) : 0];
         double d0;
-        if (spec.kind == 0 && spec.mirror == 0.0) {
+        if (TAP) {
+            d0 = 0.0;
+            for (int q = 0; q < basis.r; ++q) {
+                const double v = basis.qt[(int64_t)q * n + c];
+                d0 = __dadd_rn(d0, __dmul_rn(v, v));
+            }
+        } else if (spec.kind == 0 && spec.mirror == 0.0) {
             d0 = 0.0;
             for (int i = 0; i < spec.mix.n; ++i) d0 = i == 0 ? spec.mix.s[i] : d0 + spec.mix.s[i];  // k(x,x) = sum scaling_i * exp(0)
         } else {
@@ -182,8 +194,12 @@ __global__ __launch_bounds__(kPcBlock) void pc_init_kernel(Cloud pts, KSpec3 spe
 
 // One pivot step.  Every workgroup first reduces the previous step's block partials (same data, same tree => same pivot
 // everywhere, no grid synchronisation), then fills its rows of column k.
-template <bool GEN>
-__global__ __launch_bounds__(kPcBlock) void pc_step_kernel(Cloud pts, KSpec3 specs, int32_t k, int32_t kmax, double rel_tol,
+// KIND = Tapered: the kernel value is itself a dot product, of the entry's and the pivot's rows of the source basis.  basis.qt holds
+// the basis transposed ([r][n], entry order) exactly as L holds the factor ([k][n]): both sums run with the lanes along the entries --
+// every load of a wave is one contiguous line -- over a fixed ascending column order, against the pivot's row in LDS (Qp next to Lp).
+// A step reads (r + k) n doubles; that traffic is its bound.
+template <FactorKind KIND>
+__global__ __launch_bounds__(kPcBlock) void pc_step_kernel(Cloud pts, KSpec3 specs, TaperBasis basis, int32_t k, int32_t kmax, double rel_tol,
                                                            int32_t nblocks, double *__restrict__ L /* [kmax][n] */,
                                                            double *__restrict__ diag, int32_t *__restrict__ pivoted,
                                                            const double *__restrict__ pmax_in,
@@ -199,6 +215,8 @@ __global__ __launch_bounds__(kPcBlock) void pc_step_kernel(Cloud pts, KSpec3 spe
     __shared__ double Lp[512];
     __shared__ int32_t s_piv[512], s_dis[512], s_old[512];
     __shared__ int32_t finished, sh_dis, sh_old;
+    constexpr bool GEN = KIND != FactorKind::Scalar, TAP = KIND == FactorKind::Tapered;
+    __shared__ double Qp[TAP ? 512 : 1];  // the pivot's row of the basis (a model holds at most 512 columns)
     const int t = threadIdx.x;
     if (t == 0) finished = ctl[1];  // set by an earlier launch (or, harmlessly, by workgroup 0 of this one)
     __syncthreads();
@@ -248,6 +266,8 @@ __global__ __launch_bounds__(kPcBlock) void pc_step_kernel(Cloud pts, KSpec3 spe
     const KSpec &spec = specs.k[pd];
     const double lpk = sqrt(g.v);
     for (int r = t; r < k; r += kPcBlock) Lp[r] = L[(int64_t)r * n + p];
+    if (TAP)
+        for (int q = t; q < basis.r; q += kPcBlock) Qp[q] = basis.qt[(int64_t)q * n + p];
     __syncthreads();
     lg.vp = (int32_t)p, lg.vd = sh_dis, lg.vo = sh_old;  // the candidates of the NEXT step compete in the order after this swap
     const double px = pts.x[pp], py = pts.y[pp], pz = pts.z[pp];
@@ -262,14 +282,20 @@ __global__ __launch_bounds__(kPcBlock) void pc_step_kernel(Cloud pts, KSpec3 spe
             pivoted[c] = 1;
         } else if (pivoted[c]) {
             l = 0.0;
-        } else if (GEN && (int)(c - 3 * pc) != pd) {
+        } else if (KIND == FactorKind::Diagonal && (int)(c - 3 * pc) != pd) {
             l = 0.0;  // another coordinate: exact zero, the residual is untouched
             b = Best{diag[c], (int32_t)c};
             tr = b.v;
         } else {
             double S = 0.0;
             for (int r = 0; r < k; ++r) S = __dadd_rn(S, __dmul_rn(L[(int64_t)r * n + c], Lp[r]));
-            l = (kspec_value(spec, pts, pc, pp, px, py, pz, T) - S) / lpk;
+            double kv = kspec_value(spec, pts, pc, pp, px, py, pz, T);
+            if (TAP) {  // the taper times <Q[c,:], Q[p,:]>
+                double A = 0.0;
+                for (int q = 0; q < basis.r; ++q) A = __dadd_rn(A, __dmul_rn(basis.qt[(int64_t)q * n + c], Qp[q]));
+                kv = __dmul_rn(kv, A);
+            }
+            l = (kv - S) / lpk;
             const double dc = __dadd_rn(diag[c], -__dmul_rn(l, l));
             diag[c] = dc;
             b = Best{dc, (int32_t)c};
@@ -400,8 +426,20 @@ __global__ __launch_bounds__(256) void gpmm_pack_generic_kernel(const double *__
 namespace gpmm_factor {
 
 int Factor::init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap) {
+    return init_kind(c, k, p, gen ? FactorKind::Diagonal : FactorKind::Scalar, cap);
+}
+
+int Factor::init_tapered(gingr_ctx *c, const KSpec3 &taper, const Cloud &p, const TaperBasis &qb, int32_t cap, int timer_hook) {
+    basis = qb, timer = timer_hook;
+    return init_kind(c, taper, p, FactorKind::Tapered, cap);
+}
+
+int Factor::init_kind(gingr_ctx *c, const KSpec3 &k, const Cloud &p, FactorKind kind, int32_t cap) {
+    const bool gen = kind != FactorKind::Scalar;
     ctx = c, specs = k, pts = p, n = gen ? 3 * p.n : p.n, kcap = cap;
-    step_kernel = gen ? pc_step_kernel<true> : pc_step_kernel<false>;
+    step_kernel = kind == FactorKind::Tapered    ? pc_step_kernel<FactorKind::Tapered>
+                  : kind == FactorKind::Diagonal ? pc_step_kernel<FactorKind::Diagonal>
+                                                 : pc_step_kernel<FactorKind::Scalar>;
     nb = (int)ceil_div(n, kPcBlock);
     HIP_TRY(ctx, Lb.alloc((size_t)kcap * n * sizeof(double)));
     HIP_TRY(ctx, diag.alloc((size_t)n * sizeof(double)));
@@ -415,16 +453,24 @@ int Factor::init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_
     pmaxv[0] = part.as<double>(), pmaxv[1] = part.as<double>() + nb;
     ptrv[0] = part.as<double>() + 2 * nb, ptrv[1] = part.as<double>() + 3 * nb;
     pidxv[0] = reinterpret_cast<int32_t *>(part.as<double>() + 4 * nb), pidxv[1] = pidxv[0] + nb;
-    hipLaunchKernelGGL(gen ? pc_init_kernel<true> : pc_init_kernel<false>, dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs,
-                       diag.as<double>(), piv.as<int32_t>(), pmaxv[0], pidxv[0], ptrv[0], ctl.as<int32_t>());
+    hipLaunchKernelGGL(kind == FactorKind::Tapered    ? pc_init_kernel<FactorKind::Tapered>
+                       : kind == FactorKind::Diagonal ? pc_init_kernel<FactorKind::Diagonal>
+                                                      : pc_init_kernel<FactorKind::Scalar>,
+                       dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs, basis, diag.as<double>(), piv.as<int32_t>(), pmaxv[0], pidxv[0],
+                       ptrv[0], ctl.as<int32_t>());
     return check_launch(ctx);
 }
 
 void Factor::launch(int32_t k, double rel_tol) {
     const int in = k & 1, o = in ^ 1;
-    hipLaunchKernelGGL(step_kernel, dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs, k, kcap, rel_tol, nb, Lb.as<double>(),
-                       diag.as<double>(), piv.as<int32_t>(), pmaxv[in], pidxv[in], ptrv[in], pmaxv[o], pidxv[o], ptrv[o],
-                       ctl.as<int32_t>(), trace.as<double>(), pivots.as<int32_t>(), swd.as<int32_t>(), swo.as<int32_t>());
+    auto step = [&] {
+        hipLaunchKernelGGL(step_kernel, dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs, basis, k, kcap, rel_tol, nb, Lb.as<double>(),
+                           diag.as<double>(), piv.as<int32_t>(), pmaxv[in], pidxv[in], ptrv[in], pmaxv[o], pidxv[o], ptrv[o],
+                           ctl.as<int32_t>(), trace.as<double>(), pivots.as<int32_t>(), swd.as<int32_t>(), swo.as<int32_t>());
+    };
+    if (timer < 0) return step();
+    TimerScope ts(ctx, timer);
+    step();
 }
 
 int Factor::run_to_tolerance(double rel_tol) {
@@ -444,6 +490,34 @@ int Factor::run_to_tolerance(double rel_tol) {
     HIP_TRY(ctx, hipMemcpyAsync(htrace.data(), trace.p, htrace.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GINGR_OK;
+}
+
+// G = L^T L of the n columns, its eigenpairs, the caller's choice of the leading `keep`, U sqrt(lambda) = L V for those, the model
+int generic_tail(gingr_ctx *ctx, Factor &fg, int64_t M, const double *ref, const double *mean, int64_t row_begin, int64_t row_end,
+                 std::vector<double> &hev, const std::function<int(std::vector<double> &, int32_t *)> &choose, gingr_model **out) {
+    const int32_t n = fg.ks;
+    DevBuf G, ev, V, B;
+    HIP_TRY(ctx, G.alloc((size_t)n * n * sizeof(double)));
+    HIP_TRY(ctx, ev.alloc((size_t)(n + 1) * sizeof(double)));
+    HIP_TRY(ctx, V.alloc((size_t)(n * n + 1) * sizeof(double)));
+    HIP_TRY(ctx, B.alloc((size_t)n * 3 * M * sizeof(double)));
+    hipLaunchKernelGGL(pc_gram_kernel, dim3((unsigned)ceil_div(n, kPcGramTile), (unsigned)ceil_div(n, kPcGramTile)), dim3(kPcBlock), 0, ctx->stream, fg.Lb.as<double>(), 3 * M, n, G.as<double>());
+    GINGR_TRY(launch_jacobi_eig(ctx, G.as<double>(), n, n, ev.as<double>(), V.as<double>()));
+    hev.assign((size_t)n, 0.0);
+    HIP_TRY(ctx, hipMemcpyAsync(hev.data(), ev.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    int32_t keep = n;
+    GINGR_TRY(choose(hev, &keep));
+    hipLaunchKernelGGL(lv_kernel, dim3((unsigned)ceil_div(3 * M, 256), (unsigned)ceil_div(keep, kLvCols)), dim3(256), 0, ctx->stream, fg.Lb.as<double>(), 3 * M, n,
+                       keep, V.as<double>(), B.as<double>());
+    GINGR_TRY(check_launch(ctx));
+    auto fill = [&](gingr_model *m) -> int {
+        const int64_t total = 3 * m->M * m->rp;
+        hipLaunchKernelGGL(gpmm_pack_generic_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, B.as<double>(),
+                           M, m->row_begin, m->M, m->r, m->rp, m->perm, m->Q0);
+        return check_launch(ctx);
+    };
+    return model_create_impl(ctx, M, keep, ref, mean, hev.data(), row_begin, row_end, fill, out);
 }
 
 }  // namespace gpmm_factor
@@ -553,30 +627,13 @@ int build_generic(const Build &b) {
     }
     if (gpmm_plan::unfinished(b.to_tolerance, n, reached, fraction, pi) != gpmm_plan::Refusal::None)
         return report(b, gpmm_plan::Refusal::CeilingBeforeTolerance, pi);
-    DevBuf G, ev, V, B;
-    HIP_TRY(ctx, G.alloc((size_t)n * n * sizeof(double)));
-    HIP_TRY(ctx, ev.alloc((size_t)(n + 1) * sizeof(double)));
-    HIP_TRY(ctx, V.alloc((size_t)(n * n + 1) * sizeof(double)));
-    HIP_TRY(ctx, B.alloc((size_t)n * 3 * M * sizeof(double)));
-    hipLaunchKernelGGL(pc_gram_kernel, dim3((unsigned)ceil_div(n, kPcGramTile), (unsigned)ceil_div(n, kPcGramTile)), dim3(kPcBlock), 0, ctx->stream, fg.Lb.as<double>(), 3 * M, n, G.as<double>());
-    GINGR_TRY(launch_jacobi_eig(ctx, G.as<double>(), n, n, ev.as<double>(), V.as<double>()));
-    std::vector<double> hev((size_t)n);
-    HIP_TRY(ctx, hipMemcpyAsync(hev.data(), ev.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (auto &v : hev) v = v > 0.0 ? v : 0.0;
-    int32_t keep = n;
-    const gpmm_plan::Refusal refusal = gpmm_plan::conclude(b.ex, b.keep_rank, n, reached, fraction, hev, keep, pi);
-    GINGR_TRY(report(b, refusal, pi));
-    hipLaunchKernelGGL(lv_kernel, dim3((unsigned)ceil_div(3 * M, 256), (unsigned)ceil_div(keep, kLvCols)), dim3(256), 0, ctx->stream, fg.Lb.as<double>(), 3 * M, n,
-                       keep, V.as<double>(), B.as<double>());
-    GINGR_TRY(check_launch(ctx));
-    auto fill = [&](gingr_model *m) -> int {
-        const int64_t total = 3 * m->M * m->rp;
-        hipLaunchKernelGGL(gpmm_pack_generic_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, B.as<double>(),
-                           M, m->row_begin, m->M, m->r, m->rp, m->perm, m->Q0);
-        return check_launch(ctx);
+    std::vector<double> hev;
+    const std::vector<double> zero_mean((size_t)3 * M, 0.0);
+    auto choose = [&](std::vector<double> &lam, int32_t *keep) -> int {
+        for (auto &v : lam) v = v > 0.0 ? v : 0.0;
+        return report(b, gpmm_plan::conclude(b.ex, b.keep_rank, n, reached, fraction, lam, *keep, pi), pi);
     };
-    return create_model(b, keep, hev.data(), fill);
+    return gpmm_factor::generic_tail(ctx, fg, M, b.ref, zero_mean.data(), b.row_begin, b.row_end, hev, choose, b.out);
 }
 
 // One kernel for all coordinates: the scalar factorisation (M x k_s), the generic column count from its traces (gpmm_plan.h:

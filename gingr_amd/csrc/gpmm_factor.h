@@ -5,6 +5,9 @@
 #include "common.h"
 #include "fastexp.h"
 
+#include <functional>
+#include <vector>
+
 namespace gpmm_factor {
 
 constexpr int kMaxMix = 8;
@@ -46,17 +49,30 @@ inline KSpec3 gaussian_specs(double sigma, double scaling) {
     return s;
 }
 
-// pc_step_kernel<gen> of gpmm.hip
-using StepKernel = void (*)(Cloud, KSpec3, int32_t, int32_t, double, int32_t, double *, double *, int32_t *, const double *,
+// The basis a tapered kernel takes its entries from (gingr_model_localize): Qt [r][n], row q = column q of the source's
+// Q = U sqrt(lambda) over the n = 3M (point, coordinate) entries in the caller's order.  qt == nullptr: none (every other build).
+struct TaperBasis {
+    const double *qt;
+    int32_t r;
+};
+
+// What the pivoted Cholesky factors: one scalar kernel over the points; a DiagonalKernel with different kernels per coordinate over the
+// 3M (point, coordinate) entries; or the full 3 x 3 block kernel g(x_i, x_j) (Q Q^T)[(i,a),(j,b)] over the same entries, g = specs.k[0]
+enum class FactorKind { Scalar = 0, Diagonal = 1, Tapered = 2 };
+
+// pc_step_kernel<kind> of gpmm.hip
+using StepKernel = void (*)(Cloud, KSpec3, TaperBasis, int32_t, int32_t, double, int32_t, double *, double *, int32_t *, const double *,
                             const int32_t *, const double *, double *, int32_t *, double *, int32_t *, double *, int32_t *, int32_t *,
                             int32_t *);
 
 // The pivoted Cholesky factorisation on the device: over the M points for one scalar kernel, or (gen) over the 3M (point,
-// coordinate) entries of a DiagonalKernel whose coordinates have different kernels.
+// coordinate) entries of a DiagonalKernel whose coordinates have different kernels, or (init_tapered) of a tapered basis kernel.
 struct Factor {
     gingr_ctx *ctx = nullptr;
     KSpec3 specs{};
     Cloud pts{};
+    TaperBasis basis{nullptr, 0};
+    int timer = -1;    // timing hook of the pivot step (-1: none)
     StepKernel step_kernel = nullptr;
     int64_t n = 0;     // entries
     int nb = 0;
@@ -68,9 +84,19 @@ struct Factor {
     int32_t *pidxv[2]{};
 
     int init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap);
+    // the tapered kernel of `taper` (one Gaussian, all three coordinates) and the basis qb over the 3 p.n entries
+    int init_tapered(gingr_ctx *c, const KSpec3 &taper, const Cloud &p, const TaperBasis &qb, int32_t cap, int timer_hook);
+    int init_kind(gingr_ctx *c, const KSpec3 &k, const Cloud &p, FactorKind kind, int32_t cap);  // what the two above share
     void launch(int32_t k, double rel_tol);
     // the whole factorisation under the device's stopping rule (residual trace below rel_tol * trace, capacity, exhaustion)
     int run_to_tolerance(double rel_tol);
 };
+
+// The tail of a generic build (gpmm.hip), shared by the GPMM of coordinate-wise different kernels and gingr_model_localize: from the
+// fg.ks columns of a factor over the 3M entries, G = L^T L and its eigenpairs (descending, as the solver leaves them, in lam); `choose`
+// clamps or refuses them and names the leading columns to keep (or returns an error code, which ends the build); then the model of
+// U sqrt(lambda) = L V for those columns on ref with `mean` ([3M] interleaved).
+int generic_tail(gingr_ctx *ctx, Factor &fg, int64_t M, const double *ref, const double *mean, int64_t row_begin, int64_t row_end,
+                 std::vector<double> &lam, const std::function<int(std::vector<double> &, int32_t *)> &choose, gingr_model **out);
 
 }  // namespace gpmm_factor

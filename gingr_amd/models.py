@@ -69,6 +69,17 @@ class PointDistributionModel:
         package's definition; scalismo's own are not pinned by anything in reach."""
         return AugmentedDevicePointDistributionModel(ctx, model, bias, relativeTolerance, maxRank, biasTolerance, cells)
 
+    @staticmethod
+    def localizeModel(ctx: "Context", model, sigma: float, relativeTolerance: float = 0.01, maxRank: int = 0,
+                      cells=None) -> "LocalizedDevicePointDistributionModel":
+        """The localized model of Luethi et al. (Gaussian Process Morphable Models) on the device (gingr_model_localize): `model`'s
+        covariance multiplied element-wise by the Gaussian taper exp(-|x - y|^2 / sigma^2) over its reference, factored to
+        relativeTolerance by the pivoted Cholesky of the GPMM builder (at most 512 columns; `localizeInfo` says whether the tolerance was
+        reached) and re-diagonalised, resident in HBM.  Every vertex keeps its variance, nearby correlations survive, far ones go; the
+        mean is the model's.  model: a device-built model, a DeviceModel or a host PointDistributionModel (uploaded for the call).  At
+        most maxRank components are kept (0: no limit besides 512)."""
+        return LocalizedDevicePointDistributionModel(ctx, model, sigma, relativeTolerance, maxRank, cells)
+
 
 @dataclasses.dataclass(frozen=True)
 class AugmentInfo:
@@ -77,6 +88,17 @@ class AugmentInfo:
     rank: int                # rank of the model
     total_variance: float    # sum of all eigenvalues of the summed covariance (= the two models' total variances)
     kept_variance: float     # sum of the kept ones
+
+
+@dataclasses.dataclass(frozen=True)
+class LocalizeInfo:
+    """gingr_localize_info: what the build behind PointDistributionModel.localizeModel / DeviceModel.localize did."""
+    columns: int               # factor columns of the pivoted Cholesky
+    rank: int                  # rank of the model
+    tolerance_reached: bool    # False: stopped at the ceiling of 512 columns above the tolerance
+    residual_fraction: float   # residual trace / trace of the tapered covariance after the last column
+    total_variance: float      # trace of the tapered covariance (= the source's total variance)
+    kept_variance: float       # sum of the kept eigenvalues
 
 
 @dataclasses.dataclass(frozen=True)
@@ -444,6 +466,28 @@ class AugmentedDevicePointDistributionModel(_DerivedDevicePointDistributionModel
         self._adopt(ctx, _handle, cells)
 
 
+class LocalizedDevicePointDistributionModel(_DerivedDevicePointDistributionModel):
+    """PointDistributionModel.localizeModel: a resident model's covariance under a Gaussian taper (gingr_model_localize), built in HBM
+    and adopted like a PCA model.  `localizeInfo` carries gingr_localize_info; reference and mean are read back once, basis and
+    variance only if somebody asks.  cells: the argument's, else the model's."""
+
+    _ELSEWHERE = "a localized model lives whole on the context it was built on; download it (to_host) for anything else"
+
+    def __init__(self, ctx: Context, model, sigma: float, relativeTolerance: float = 0.01, maxRank: int = 0, cells=None, _handle=None,
+                 _info=None):
+        if _handle is None:
+            if cells is None:
+                cells = _cells_of(model)
+            d, own = _resident(ctx, model)
+            try:
+                _handle, _info = d._localize_native(sigma, relativeTolerance, maxRank)
+            finally:
+                if own:
+                    d.close()
+        self.localizeInfo = _info
+        self._adopt(ctx, _handle, cells)
+
+
 def _cells_of(model):
     return getattr(model.host if isinstance(model, DeviceModel) else model, "cells", None)
 
@@ -684,6 +728,21 @@ class DeviceModel:
         cells = _cells_of(self)
         return AugmentedDevicePointDistributionModel(self.ctx, None, None, cells=cells if cells is not None else _cells_of(other), _handle=h,
                                                      _info=info).device()
+
+    def _localize_native(self, sigma: float, relativeTolerance: float, maxRank: int):
+        h, info = c_void_p(), nat.LocalizeInfo()
+        _check(self.ctx.handle, self._lib.gingr_model_localize(self.ctx.handle, self.handle, float(sigma), float(relativeTolerance), int(maxRank),
+                                                               ctypes.byref(h), ctypes.byref(info)), "gingr_model_localize")
+        return h, LocalizeInfo(int(info.columns), int(info.rank), bool(info.tolerance_reached), float(info.residual_fraction),
+                               float(info.total_variance), float(info.kept_variance))
+
+    def localize(self, sigma: float, relativeTolerance: float = 0.01, maxRank: int = 0) -> "DeviceModel":
+        """This model localized as a new resident model (gingr_model_localize): the covariance multiplied element-wise by the Gaussian
+        taper exp(-|x - y|^2 / sigma^2) over the reference, factored to relativeTolerance (at most 512 columns) and re-diagonalised; the
+        same reference and mean.  A complete model of this context.  The result is an ordinary DeviceModel, independent of this one;
+        its host (a LocalizedDevicePointDistributionModel) carries `localizeInfo`; cells are carried over."""
+        h, info = self._localize_native(sigma, relativeTolerance, maxRank)
+        return LocalizedDevicePointDistributionModel(self.ctx, None, 0.0, cells=_cells_of(self), _handle=h, _info=info).device()
 
     def download(self, basis: bool = True) -> "PointDistributionModel":
         """Local rows back on the host in gingr_model_upload's layout (gingr_model_download)."""

@@ -573,6 +573,35 @@ typedef struct gingr_augment_info {
 int gingr_model_augment(gingr_ctx *ctx, const gingr_model *a, const gingr_model *b, double relative_tolerance,
                         int32_t max_rank, gingr_model **out, gingr_augment_info *info /* may be NULL */);
 
+/* ---- a model localized: its covariance tapered by a Gaussian of the distance on the reference --------------------------------------
+ * The localized statistical shape model of Luethi et al. (Gaussian Process Morphable Models): with Q = U sqrt(lambda) of the source
+ * (3M x r, rows 3i + d) and x_1 .. x_M its reference,
+ *     K[(i,a),(j,b)] = g(x_i, x_j) sum_k Q[3i+a, k] Q[3j+b, k],    g(x, y) = exp(-|x - y|^2 / sigma^2)
+ * -- every vertex keeps its own variance (g(x, x) = 1), correlations survive nearby and are removed far away; the rank rises from r to
+ * hundreds.  g is taken over the reference (not reference + mean) and is the GPMM builder's Gaussian of scaling 1, bit for bit.  K is
+ * positive semi-definite (Schur product) with trace K = trace Q Q^T.  K ~ L L^T by the builder's pivoted Cholesky over the 3M (point,
+ * coordinate) entries (its pivot, tie and stop rules) until the residual trace is below relative_tolerance trace K, or 512 columns
+ * are computed (the generic factor's ceiling), or no positive residual is left; reaching the ceiling first is not an error, info says
+ * so.  Then L^T L = V diag(lambda') V^T, basis L V; the leading components with lambda'_j > 1e-12 lambda'_1 and > 0 are kept, at most
+ * max_rank (0: 512) and at most 512.  The 1e-12 is the noise floor of the Gram route, not a modelling knob: relative_tolerance and
+ * max_rank are.  The result is a new, independent, finalized model on the same reference with the same mean; the source is not
+ * changed.  Only reference and mean pass through the host.  Float64, a complete (single-shard) model.  Every sum has a fixed order: two
+ * calls with the same input give the same bits.  Synchronises.
+ * GINGR_ERR_BAD_ARGUMENT (the text contains "model_localize" and names the cause): a null argument, a model of another context, a row
+ * shard or a model that is not finalized, sigma not positive and finite, relative_tolerance outside [0, 1) or NaN, a negative
+ * max_rank, rank 0 after the cutoff; GINGR_ERR_NONFINITE: a non-finite trace or eigenvalue.  On any error *out is NULL, *info is
+ * zeroed and the context stays usable. */
+typedef struct gingr_localize_info {
+    int32_t columns;            /* factor columns computed */
+    int32_t rank;               /* rank of the returned model */
+    int32_t tolerance_reached;  /* 0: stopped at the 512-column ceiling above the tolerance */
+    double residual_fraction;   /* residual trace / trace K after the last column */
+    double total_variance;      /* trace K */
+    double kept_variance;       /* sum of the kept eigenvalues */
+} gingr_localize_info;
+int gingr_model_localize(gingr_ctx *ctx, const gingr_model *model, double sigma, double relative_tolerance,
+                         int32_t max_rank, gingr_model **out, gingr_localize_info *info /* may be NULL */);
+
 /* ---- model metrics: many instances, many projections, many samples against many shapes ------------------------------------------
  * What the shape-model literature (and scalismo's ModelMetrics) measures a model by, batched on the device.  What is not scalismo's is
  * this library's definition: nothing in reach pins scalismo's own, and scalismo measures against the closest surface point, whereas
@@ -862,7 +891,8 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * bounding box, bisection (every enqueued step, the ones that return at once included), clusters and representatives (insertion at
  * the chosen size, sort, means, argmin), compaction of vertices and triangles, 17 = the Chebyshev step of gingr_model_from_laplacian
  * (lap_cheb_kernel) alone, 18 / 19 / 20 = the passes of the model metrics alone: reconstruct and measure (gingr_model_generalization), samples
- * against training shapes (gingr_model_specificity), the stored basis x factor product (gingr_model_instances, gingr_model_specificity).  Returns accumulated ms and launches since
+ * against training shapes (gingr_model_specificity), the stored basis x factor product (gingr_model_instances, gingr_model_specificity),
+ * 21 = the pivot step of gingr_model_localize alone.  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
