@@ -14,7 +14,7 @@ from .api import (  # noqa: F401
     GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo,
     AugmentedDevicePointDistributionModel, AugmentInfo, LaplacianDevicePointDistributionModel, LaplacianInfo,
     LocalizedDevicePointDistributionModel, LocalizeInfo,
-    TemplateConfiguration, TemplateRegistration, TemplateRegistrationState, ModelMetrics,
+    TemplateConfiguration, TemplateRegistration, TemplateRegistrationState, ModelMetrics, normalTangentCovariances,
 )
 from . import metrics  # noqa: F401  (generalization, specificity, compactness of a shape model)
 from ._native import GingrNativeError  # noqa: F401

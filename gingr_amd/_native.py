@@ -248,7 +248,9 @@ SIGNATURES = {
     # correspondences given by the caller (flavour 3, fitter_pairs.hip)
     "gingr_fitter_set_pairs": (c_int, [c_void_p, c_int64, _ip, _dp, _dp]),
     "gingr_fitter_set_pairs_cov": (c_int, [c_void_p, c_int64, _ip, _dp, _dp]),
+    "gingr_fitter_set_pairs_cov_dense": (c_int, [c_void_p, c_int64, _ip, _dp, _dp]),
     "gingr_fitter_get_pair_observations": (c_int, [c_void_p, _dp, _dp]),
+    "gingr_fitter_get_pair_precisions": (c_int, [c_void_p, _dp, _dp]),
     "gingr_fitter_set_sigma2": (c_int, [c_void_p, c_double]),
     "gingr_fitter_last_update_error": (c_int, [c_void_p, POINTER(c_int32)]),
     "gingr_fitter_update_pairs_async": (c_int, [c_void_p, c_int32]),

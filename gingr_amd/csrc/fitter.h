@@ -231,6 +231,16 @@ struct gingr_fitter {
     std::vector<int32_t> h_pc_row, h_lm_row, h_lm_mask;
     std::vector<double> h_pc_xyz, h_pc_cov, h_lm_xyz, h_lm_cov;
     DevBuf cat_pid, cat_xyz, cat_cov;
+    // The dense covariance list (gingr_fitter_set_pairs_cov_dense): a third, independent list for one pair per vertex.  The list as
+    // uploaded (dpid global ids, dxyz, dcov [9 K]) and its sort buffers, sized for dense_cap pairs and grown only; the per-vertex planes
+    // it is consolidated into once per call -- dobs [3][M] / dprec [6][M], what launch_gram_cov reads every iteration -- and that
+    // pass's workspace (gram_cov_ws_doubles).  n_dense = 0: no list, nothing of this is launched or read.
+    int64_t n_dense = 0, dense_cap = -1;
+    int32_t *dpid = nullptr, *dkeys = nullptr, *dvals = nullptr, *dskeys = nullptr, *dsvals = nullptr;
+    double *dxyz = nullptr, *dcov = nullptr, *dobs = nullptr, *dprec = nullptr;
+    void *dsort = nullptr;
+    size_t dsort_bytes = 0;
+    DevBuf dense_ws;
 };
 
 // GINGR_OPT_GRAM_DOWNDATE by default: from this many local rows on.  The downdate pays while fewer than ~20 % of the rows have weight 0

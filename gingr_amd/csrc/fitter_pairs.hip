@@ -4,8 +4,12 @@
 //                     keys kernel (global pid -> device row, or the sentinel M for another shard's rows), stable radix sort over the
 //                     bits a key can have, one gather thread per local vertex that walks its run in ascending pair position.
 //   covariance pairs  (pid, point, 3 x 3)          ->  in front of the landmarks in the list the landmark pass sums (gp_obs.hip)
+//   dense covariance pairs (pid, point, 3 x 3) x K ->  one precision and one precision-weighted point per vertex, once per
+//                     gingr_fitter_set_pairs_cov_dense: the same keys kernel and sort, a gather thread that adds the inverses;
+//                     summed every iteration by the 3 x 3-weighted Gram pass (gp_gram_cov.hip)
 // The phases themselves are in fitter_phases.hip (run_phase), the probabilistic queries next to their siblings.
 #include "fitter.h"
+#include "svd3.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -59,6 +63,53 @@ __global__ __launch_bounds__(256) void pairs_gather_kernel(int64_t M, int64_t K,
     weight_in[i] = sw;
 }
 
+// The dense covariance list, per local vertex i (device row), over the same kind of sorted run:
+//   prec6[.][i] = Lambda_i = sum_k Sigma_k^-1 (planes xx, xy, xz, yy, yz, zz),   obs[.][i] = Lambda_i^-1 sum_k Sigma_k^-1 x_k
+// -- k observations of one point with their own covariances are one observation of their precision-weighted mean.  Both sums in
+// ascending pair position; a single pair keeps its point bit for bit; no pair: all zero.  spd3_inverse (svd3.h) makes NaN of a matrix
+// that is no covariance, which is passed on: it fails the posterior.
+__global__ __launch_bounds__(256) void pairs_gather_cov_kernel(int64_t M, int64_t K, const int32_t *__restrict__ skeys,
+                                                               const int32_t *__restrict__ svals, const double *__restrict__ xyz,
+                                                               const double *__restrict__ cov, double *__restrict__ obs,
+                                                               double *__restrict__ prec6) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    int64_t lo = 0, hi = K;  // first position with key >= i
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (skeys[mid] < (int32_t)i)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    double L[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0}, x1[3] = {0, 0, 0};
+    int64_t n = 0;
+    for (int64_t p = lo; p < K && skeys[p] == (int32_t)i; ++p, ++n) {
+        const int64_t k = svals[p];
+        double Ci[9];
+        spd3_inverse(cov + 9 * k, Ci);
+        const double x = xyz[3 * k], y = xyz[3 * k + 1], z = xyz[3 * k + 2];
+        L[0] += Ci[0], L[1] += Ci[1], L[2] += Ci[2], L[3] += Ci[4], L[4] += Ci[5], L[5] += Ci[8];
+        b[0] += Ci[0] * x + Ci[1] * y + Ci[2] * z;
+        b[1] += Ci[3] * x + Ci[4] * y + Ci[5] * z;
+        b[2] += Ci[6] * x + Ci[7] * y + Ci[8] * z;
+        x1[0] = x, x1[1] = y, x1[2] = z;
+    }
+    if (n > 1) {
+        const double Lf[9] = {L[0], L[1], L[2], L[1], L[3], L[4], L[2], L[4], L[5]};
+        double Li[9];
+        spd3_inverse(Lf, Li);
+        x1[0] = Li[0] * b[0] + Li[1] * b[1] + Li[2] * b[2];
+        x1[1] = Li[3] * b[0] + Li[4] * b[1] + Li[5] * b[2];
+        x1[2] = Li[6] * b[0] + Li[7] * b[1] + Li[8] * b[2];
+    }
+    obs[i] = x1[0];
+    obs[M + i] = x1[1];
+    obs[2 * M + i] = x1[2];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) prec6[q * M + i] = L[q];
+}
+
 // sigma2 of the device state and of the scalars it was initialised from (one thread)
 __global__ void set_sigma2_kernel(DevState *st, gingr_state_scalars *hs, double sigma2) {
     st->sigma2 = sigma2;
@@ -109,6 +160,52 @@ int reserve_pairs(gingr_fitter *f, int64_t K) {
     return GINGR_OK;
 }
 
+void free_dense_list(gingr_fitter *f) {
+    void *ptrs[] = {f->dpid, f->dkeys, f->dvals, f->dskeys, f->dsvals, f->dxyz, f->dcov, f->dsort};
+    for (void *q : ptrs) dev_free(q);
+    f->dpid = f->dkeys = f->dvals = f->dskeys = f->dsvals = nullptr;
+    f->dxyz = f->dcov = nullptr;
+    f->dsort = nullptr;
+    f->dsort_bytes = 0;
+    f->dense_cap = -1;
+}
+
+// room for K dense covariance pairs (grow only), as reserve_pairs
+int reserve_dense(gingr_fitter *f, int64_t K) {
+    if (K <= f->dense_cap) return GINGR_OK;
+    gingr_ctx *ctx = f->ctx;
+    free_dense_list(f);
+    f->n_dense = 0;
+    const size_t n = (size_t)K;
+    GINGR_TRY(dev_alloc(ctx, &f->dpid, n));
+    GINGR_TRY(dev_alloc(ctx, &f->dkeys, n));
+    GINGR_TRY(dev_alloc(ctx, &f->dvals, n));
+    GINGR_TRY(dev_alloc(ctx, &f->dskeys, n));
+    GINGR_TRY(dev_alloc(ctx, &f->dsvals, n));
+    GINGR_TRY(dev_alloc(ctx, &f->dxyz, 3 * n));
+    GINGR_TRY(dev_alloc(ctx, &f->dcov, 9 * n));
+    f->dsort_bytes = pair_sort_temp_bytes(K);
+    HIP_TRY(ctx, hipMalloc(&f->dsort, f->dsort_bytes ? f->dsort_bytes : 8));
+    f->dense_cap = K;
+    return GINGR_OK;
+}
+
+// dobs / dprec and the pass's workspace exist (the planes all zero before the first list)
+int dense_ensure_planes(gingr_fitter *f) {
+    gingr_ctx *ctx = f->ctx;
+    const int64_t M = f->m->M;
+    if (!f->dobs) {
+        GINGR_TRY(dev_alloc(ctx, &f->dobs, (size_t)3 * M));
+        HIP_TRY(ctx, hipMemsetAsync(f->dobs, 0, (size_t)3 * M * sizeof(double), ctx->stream));
+    }
+    if (!f->dprec) {
+        GINGR_TRY(dev_alloc(ctx, &f->dprec, (size_t)6 * M));
+        HIP_TRY(ctx, hipMemsetAsync(f->dprec, 0, (size_t)6 * M * sizeof(double), ctx->stream));
+    }
+    HIP_TRY(ctx, ensure(f->dense_ws, (size_t)gram_cov_ws_doubles(M, f->m->rp) * sizeof(double)));
+    return GINGR_OK;
+}
+
 }  // namespace
 
 int pairs_ensure_planes(gingr_fitter *f) {
@@ -156,6 +253,11 @@ void free_pairs(gingr_fitter *f) {
     f->pobs = f->pwin = nullptr;
     f->n_pairs = 0;
     f->n_pc = 0;
+    free_dense_list(f);
+    dev_free(f->dobs), dev_free(f->dprec);
+    f->dobs = f->dprec = nullptr;
+    f->dense_ws.release();
+    f->n_dense = 0;
 }
 
 extern "C" {
@@ -217,6 +319,77 @@ int gingr_fitter_set_pairs_cov(gingr_fitter *f, int64_t K, const int32_t *pid, c
     }
     f->n_pc = (int32_t)K;
     return pairs_rebuild_cov_list(f);
+}
+
+int gingr_fitter_set_pairs_cov_dense(gingr_fitter *f, int64_t K, const int32_t *pid, const double *xyz, const double *cov) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    const gingr_model *m = f->m;
+    if (K < 0 || K > (1 << 24) || (K > 0 && (!pid || !xyz || !cov)))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_pairs_cov_dense: bad argument");
+    for (int64_t k = 0; k < K; ++k)
+        if (pid[k] < 0 || pid[k] >= m->M_total)
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_pairs_cov_dense: point id %d of pair %lld outside the model's %lld points",
+                                   pid[k], (long long)k, (long long)m->M_total);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    f->forget_posteriors();  // the same state with other pairs is another posterior
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (an update in flight reads the planes)
+    const int64_t M = m->M;
+    if (K == 0) {  // no list: nothing of it is launched again; the planes, where they exist, read as "no pair"
+        f->n_dense = 0;
+        if (f->dobs) HIP_TRY(ctx, hipMemsetAsync(f->dobs, 0, (size_t)3 * M * sizeof(double), ctx->stream));
+        if (f->dprec) HIP_TRY(ctx, hipMemsetAsync(f->dprec, 0, (size_t)6 * M * sizeof(double), ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return GINGR_OK;
+    }
+    f->n_dense = 0;  // (until everything below is in place)
+    GINGR_TRY(dense_ensure_planes(f));
+    GINGR_TRY(reserve_dense(f, K));
+    HIP_TRY(ctx, hipMemcpyAsync(f->dpid, pid, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(f->dxyz, xyz, (size_t)3 * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(f->dcov, cov, (size_t)9 * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(pairs_keys_kernel, dim3((unsigned)ceil_div(K, 256)), dim3(256), 0, ctx->stream, K, f->dpid, m->row_begin, M, m->iperm,
+                       f->dkeys, f->dvals);
+    // the stable sort of gingr_fitter_set_pairs: equal keys keep ascending pair positions
+    HIP_TRY(ctx, hipcub::DeviceRadixSort::SortPairs(f->dsort, f->dsort_bytes, f->dkeys, f->dskeys, f->dvals, f->dsvals, (int)K, 0,
+                                                    pair_key_bits(M), ctx->stream));
+    hipLaunchKernelGGL(pairs_gather_cov_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, K, f->dskeys, f->dsvals, f->dxyz,
+                       f->dcov, f->dobs, f->dprec);
+    GINGR_TRY(check_launch(ctx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the caller's arrays are free again
+    f->n_dense = K;
+    return GINGR_OK;
+}
+
+int gingr_fitter_get_pair_precisions(gingr_fitter *f, double *obs_xyz, double *prec6) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t M = f->m->M;
+    if (!f->dobs || !f->dprec) {  // never set: no pair anywhere
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (obs_xyz) std::fill(obs_xyz, obs_xyz + 3 * M, 0.0);
+        if (prec6) std::fill(prec6, prec6 + 6 * M, 0.0);
+        return GINGR_OK;
+    }
+    DevBuf tmp;
+    HIP_TRY(ctx, tmp.alloc((size_t)6 * M * sizeof(double)));
+    if (obs_xyz) {  // back to the caller's point order
+        launch_soa_to_aos(ctx, f->dobs, M, tmp.as<double>(), f->m->perm);
+        HIP_TRY(ctx, hipMemcpyAsync(obs_xyz, tmp.p, (size_t)3 * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (prec6) {  // planes in the caller's order on the device, interleaved per vertex here
+        for (int q = 0; q < 6; ++q) launch_scatter(ctx, f->dprec + (int64_t)q * M, M, f->m->perm, tmp.as<double>() + (int64_t)q * M);
+        std::vector<double> planes((size_t)6 * M);
+        HIP_TRY(ctx, hipMemcpyAsync(planes.data(), tmp.p, (size_t)6 * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t i = 0; i < M; ++i)
+            for (int q = 0; q < 6; ++q) prec6[6 * i + q] = planes[(size_t)q * M + i];
+    }
+    GINGR_TRY(check_launch(ctx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GINGR_OK;
 }
 
 int gingr_fitter_get_pair_observations(gingr_fitter *f, double *obs_xyz, double *weight) {

@@ -129,7 +129,7 @@ bool use_compact(const gingr_fitter *f, const Correspondence &c) {
     const gingr_model *m = f->m;
     if (!m->Qc || f->ctx->separable == 0) return false;
     if (m->M != m->M_total || f->partial_out || f->group_member) return false;
-    if (!(c.kind == Flavour::Cpd || (c.kind == Flavour::Pairs && f->n_pc == 0))) return false;
+    if (!(c.kind == Flavour::Cpd || (c.kind == Flavour::Pairs && f->n_pc == 0 && f->n_dense == 0))) return false;
     return f->n_lm == 0 && !f->zrand_active && !f->allow_alt;
 }
 
@@ -627,6 +627,8 @@ int run_phase(gingr_fitter *f, const Correspondence &c, int phase) {
                 fa.sweep_blocks = sweep_num_blocks(M);
             }
             launch_phase1_finalize(ctx, fa);
+            if (c.kind == Flavour::Pairs && f->n_dense > 0)  // the dense covariance list: its own pass, added before the segment is handed out
+                launch_gram_cov(ctx, m, f->st, f->dobs, f->dprec, f->lm_mask, f->dense_ws.as<double>(), s.Gw, s.rhsw);
             if (c.kind == Flavour::Pairs && f->n_pc > 0)  // one launch over [covariance pairs | landmarks]: a defined summation order
                 launch_landmarks(ctx, m, f->st, f->n_cat, f->cat_pid.as<int32_t>(), f->cat_xyz.as<double>(), f->cat_cov.as<double>(),
                                  s.Gw, s.rhsw);

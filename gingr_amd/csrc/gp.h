@@ -353,6 +353,14 @@ void launch_obs_points(gingr_ctx *ctx, const gingr_model *m, const DevState *st,
 // landmarks with full 3x3 covariance added into G and rhs of the (reduced) exchange segment; local pids, local rows only
 void launch_landmarks(gingr_ctx *ctx, const gingr_model *m, const DevState *st, int32_t n_lm, const int32_t *lm_pid_local,
                       const double *lm_xyz, const double *lm_cov, double *G, double *rhs);
+// ---- the 3 x 3-weighted Gram pass (gp_gram_cov.hip; plan: gram_cov_plan.h): one observation with a full precision per local vertex --
+// obs_soa [3][M] the observed points, prec6 [6][M] the planes xx, xy, xz, yy, yz, zz of Lambda_i (all zero: no observation) --
+//   G += sum_i Q_i^T (R^T Lambda_i R) Q_i,   rhs += sum_i Q_i^T (R^T Lambda_i R) (R^T (obs_i - c - t) - m_i)
+// ADDED to what G and rhs hold (the reduced exchange segment, as launch_landmarks), fixed summation order, no atomics.
+// ws: gram_cov_ws_doubles(M, rp) doubles of the caller's
+int64_t gram_cov_ws_doubles(int64_t M, int32_t rp);
+void launch_gram_cov(gingr_ctx *ctx, const gingr_model *m, const DevState *st, const double *obs_soa, const double *prec6,
+                     const int32_t *lm_mask, double *ws, double *G, double *rhs);
 
 // ---- small dense kernels (gp.hip; the post-solve part: gp_post_solve.hip) ------------------------------------------------------------------------------------
 // a = (I + G)^-1 rhs  by Cholesky (work: posterior_work_doubles(rp)); sets st->err on failure

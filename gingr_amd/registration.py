@@ -662,6 +662,21 @@ class IcpRegistration(GingrAlgorithm):
         return idx
 
 
+def normalTangentCovariances(normals, varNormal, varTangent) -> np.ndarray:
+    """(K, 3, 3) covariances varTangent I + (varNormal - varTangent) n n^T for K directions: variance varNormal along n, varTangent in
+    the plane across it -- small along the surface normal and large in the tangent plane lets a vertex slide on the target surface
+    (point-to-plane ICP).  normals (K, 3) are normalised, a zero normal gives varTangent I; the variances are scalars or (K,) arrays."""
+    n = np.asarray(normals, dtype=np.float64)
+    if n.ndim != 2 or n.shape[1] != 3:
+        raise ValueError(f"normalTangentCovariances: normals of shape {n.shape}; need (K, 3)")
+    K = n.shape[0]
+    vn = np.broadcast_to(np.asarray(varNormal, dtype=np.float64), (K,))
+    vt = np.broadcast_to(np.asarray(varTangent, dtype=np.float64), (K,))
+    length = np.linalg.norm(n, axis=1)
+    unit = np.where(length[:, None] > 0.0, n / np.where(length > 0.0, length, 1.0)[:, None], 0.0)
+    return vt[:, None, None] * np.eye(3)[None] + (vn - vt)[:, None, None] * (unit[:, :, None] * unit[:, None, :])
+
+
 class TemplateRegistration(GingrAlgorithm):
     """A registration algorithm from its three inputs (Template.scala:46-60; the plugin surface of GingrAlgorithm.scala:65-74,256-258):
 
@@ -673,7 +688,9 @@ class TemplateRegistration(GingrAlgorithm):
                                                       update committed, fit already refreshed; not called after a failed update.
 
     Covariances that are exact multiples of the identity go to the fitter's isotropic list (one consolidated observation per
-    vertex, the weighted Gram pass), the others to its covariance list (the landmark pass: meant for few pairs).  Everything else
+    vertex, the weighted Gram pass), the others to its covariance list (the landmark pass: meant for few pairs) or, with
+    covariancePass="gram", to its dense covariance list (one consolidated precision per vertex, the 3 x 3-weighted Gram pass: meant
+    for a covariance per vertex, as point-to-plane ICP has -- normalTangentCovariances).  Everything else
     -- posterior, projections, step length, global transform, failure rules and retries, the sampled proposal, the transition
     density, posteriorCovariance / posteriorModel -- is the device's, as for CPD and ICP (flavour 3 of the fitter).
     The callbacks run once per `update`; a later query about the SAME state object (logTransitionProbability, posteriorCovariance
@@ -683,8 +700,11 @@ class TemplateRegistration(GingrAlgorithm):
     name = "Template"
 
     def __init__(self, ctx: Context, getCorrespondence: Optional[Callable] = None, getUncertainty: Optional[Callable] = None,
-                 updateSigma2: Optional[Callable] = None):
+                 updateSigma2: Optional[Callable] = None, covariancePass: str = "landmark"):
         super().__init__(ctx)
+        if covariancePass not in ("landmark", "gram"):
+            raise ValueError(f"covariancePass: {covariancePass!r}; need \"landmark\" or \"gram\"")
+        self.covariancePass = covariancePass
         self.getCorrespondence = getCorrespondence if getCorrespondence is not None else (lambda state: _empty_pairs())
         self.getUncertainty = getUncertainty if getUncertainty is not None else (lambda pids, state: 1.0)
         self._update_sigma2 = updateSigma2
@@ -741,9 +761,9 @@ class TemplateRegistration(GingrAlgorithm):
                                                                      dptr(iso[2]) if k else None), "gingr_fitter_set_pairs")
         if cov[0].shape[0] or n[1]:
             k = cov[0].shape[0]
-            _check(self.ctx.handle, self._lib.gingr_fitter_set_pairs_cov(self._fitter, k, iptr(cov[0]) if k else None,
-                                                                         dptr(cov[1]) if k else None, dptr(cov[2]) if k else None),
-                   "gingr_fitter_set_pairs_cov")
+            name = "gingr_fitter_set_pairs_cov_dense" if self.covariancePass == "gram" else "gingr_fitter_set_pairs_cov"
+            _check(self.ctx.handle, getattr(self._lib, name)(self._fitter, k, iptr(cov[0]) if k else None, dptr(cov[1]) if k else None,
+                                                             dptr(cov[2]) if k else None), name)
         self._held = (pairs.pids, pairs.points, unc, (iso[0].shape[0], cov[0].shape[0]))
 
     def _release(self):
@@ -801,3 +821,14 @@ class TemplateRegistration(GingrAlgorithm):
         obs, w = np.empty((M, 3)), np.empty(M)
         _check(self.ctx.handle, self._lib.gingr_fitter_get_pair_observations(self._fitter, dptr(obs), dptr(w)), "gingr_fitter_get_pair_observations")
         return obs, w
+
+    def pairPrecisions(self, state) -> Tuple[np.ndarray, np.ndarray]:
+        """The covariance pairs of `state` as the device consolidated them for covariancePass="gram": (observed point (M, 3),
+        precision (M, 6): xx, xy, xz, yy, yz, zz) per vertex -- the summed precision of a vertex's pairs and their precision-weighted
+        mean; all zero = no pair (and everywhere with covariancePass="landmark")."""
+        self._ensure_device_state(state)
+        self._push_pairs(state)
+        M = state.general.model.numberOfPoints
+        obs, prec = np.empty((M, 3)), np.empty((M, 6))
+        _check(self.ctx.handle, self._lib.gingr_fitter_get_pair_precisions(self._fitter, dptr(obs), dptr(prec)), "gingr_fitter_get_pair_precisions")
+        return obs, prec

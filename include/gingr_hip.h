@@ -490,10 +490,27 @@ int gingr_fitter_posterior_model_icp_surface(gingr_fitter *f, const gingr_icp_pa
  * working memory belongs to the fitter and is reused while K does not grow.  K = 0 clears the list.
  * gingr_fitter_set_pairs_cov: a second, independent list with a full 3 x 3 covariance per pair (row-major).  It is summed into G
  * and the right-hand side by the landmark pass, in ONE launch over "covariance pairs first, then the landmarks"; that pass costs
- * O(K r^2) -- it is meant for tens to hundreds of pairs, NOT for one pair per vertex (there is no 3 x 3-weighted Gram pass).
- * A vertex that a landmark overrides (gingr_fitter_set_landmarks) loses its isotropic and its covariance pairs
- * (GingrAlgorithm.scala:288-296); the two calls and gingr_fitter_set_landmarks may come in any order.
- * Both calls synchronise and forget the posterior memo (the same state with other pairs is another posterior).  A pid outside
+ * O(K r^2) -- it is meant for tens to hundreds of pairs, NOT for one pair per vertex: that is gingr_fitter_set_pairs_cov_dense.
+ * gingr_fitter_set_pairs_cov_dense: a third, independent list with a full 3 x 3 covariance per pair (row-major, world frame), for
+ * covariances at mesh scale -- one pair per vertex, point-to-plane ICP.  The contract of gingr_fitter_set_pairs (global pids in any
+ * order, repeated or not, any subset; host arrays; K <= 1 << 24; a row shard is given the WHOLE list; working memory of the fitter's,
+ * reused while K does not grow; K = 0 clears the list).  The pairs are consolidated ONCE, here, on the device -- the same stable
+ * radix sort, one gather thread per local vertex -- into one observation per vertex:
+ *     Lambda_i = sum_k Sigma_k^-1 (six doubles: xx, xy, xz, yy, yz, zz),   xbar_i = Lambda_i^-1 sum_k Sigma_k^-1 x_k
+ * (both sums in ascending pair position; a vertex with exactly one pair keeps that pair's point bit for bit; without pairs
+ * Lambda_i = 0 and xbar_i = 0).  Every update then adds, with the state's R, c, t and m_i = ref_i - c + mean_i,
+ *     G += sum_i Q_i^T W_i Q_i,   rhs += sum_i Q_i^T W_i v_i,     W_i = R^T Lambda_i R,   v_i = R^T (xbar_i - c - t) - m_i
+ * by a float64-MFMA pass over the basis (row slabs, partials combined in a fixed order, no atomics: two runs give the same bits),
+ * behind the isotropic pass and in front of the landmark pass, before the exchange segment is handed out.  The three lists are
+ * independent: a vertex may be in all of them and their contributions add.  With the dense list empty nothing of it is launched.
+ * Covered: gingr_fitter_update_pairs_async, _pairs_phase_async, _update_pairs_sample_async, _posterior_logpdf_pairs,
+ * _posterior_covariance_pairs, _posterior_model_pairs, and gingr_fitter_update_sharded_async / _posterior_logpdf_sharded with flavour 3.
+ * NOT covered, as the flavour itself: gingr_fitter_mh_step, the gingr_group_* and RCCL entry points.
+ * gingr_fitter_get_pair_precisions (synchronises): the consolidated planes of the dense list, obs_xyz[3 M_local] / prec6[6 M_local]
+ * (six doubles per vertex) in the caller's point order; either may be NULL.
+ * A vertex that a landmark overrides (gingr_fitter_set_landmarks) loses its isotropic, its covariance and its dense covariance pairs
+ * (GingrAlgorithm.scala:288-296); the three calls and gingr_fitter_set_landmarks may come in any order.
+ * All three calls synchronise and forget the posterior memo (the same state with other pairs is another posterior).  A pid outside
  * [0, M_total) is GINGR_ERR_BAD_ARGUMENT (nothing is changed).  VALUES are not validated; they follow the Try rules of `update`, as
  * the ICP flavours' do: a non-finite point, variance or covariance fails the posterior on the device (state unchanged at
  * iteration 0, ModelFlexibilityError later, a retry when sampled); var = +inf is weight 0, a dropped pair.
@@ -513,7 +530,9 @@ int gingr_fitter_posterior_model_icp_surface(gingr_fitter *f, const gingr_icp_pa
  * the gingr_group_* and RCCL entry points. */
 int gingr_fitter_set_pairs(gingr_fitter *f, int64_t K, const int32_t *pid, const double *xyz, const double *var);
 int gingr_fitter_set_pairs_cov(gingr_fitter *f, int64_t K, const int32_t *pid, const double *xyz, const double *cov);
+int gingr_fitter_set_pairs_cov_dense(gingr_fitter *f, int64_t K, const int32_t *pid, const double *xyz, const double *cov);
 int gingr_fitter_get_pair_observations(gingr_fitter *f, double *obs_xyz, double *weight);
+int gingr_fitter_get_pair_precisions(gingr_fitter *f, double *obs_xyz, double *prec6);
 int gingr_fitter_set_sigma2(gingr_fitter *f, double sigma2);
 int gingr_fitter_update_pairs_async(gingr_fitter *f, int32_t n_iterations);
 int gingr_fitter_pairs_phase_async(gingr_fitter *f, int32_t phase);

@@ -660,6 +660,15 @@ JFN(jint, fitterSetPairsCov)(JNIEnv *env, jclass, jlong f, jintArray pid, jdoubl
     Arr<int32_t> a(env, pid, true); Arr<double> b(env, xyz, true); Arr<double> c(env, cov, true);
     return gingr_fitter_set_pairs_cov(P<gingr_fitter>(f), n, a.ptr(), b.ptr(), c.ptr());
 }
+JFN(jint, fitterSetPairsCovDense)(JNIEnv *env, jclass, jlong f, jintArray pid, jdoubleArray xyz, jdoubleArray cov) {
+    const jsize n = pid ? env->GetArrayLength(pid) : 0;
+    Arr<int32_t> a(env, pid, true); Arr<double> b(env, xyz, true); Arr<double> c(env, cov, true);
+    return gingr_fitter_set_pairs_cov_dense(P<gingr_fitter>(f), n, a.ptr(), b.ptr(), c.ptr());
+}
+JFN(jint, fitterGetPairPrecisions)(JNIEnv *env, jclass, jlong f, jdoubleArray obs, jdoubleArray prec6) {
+    Arr<double> a(env, obs, false); Arr<double> b(env, prec6, false);
+    return gingr_fitter_get_pair_precisions(P<gingr_fitter>(f), a.ptr(), b.ptr());
+}
 JFN(jint, fitterGetPairObservations)(JNIEnv *env, jclass, jlong f, jdoubleArray obs, jdoubleArray w) {
     Arr<double> a(env, obs, false); Arr<double> b(env, w, false);
     return gingr_fitter_get_pair_observations(P<gingr_fitter>(f), a.ptr(), b.ptr());

@@ -222,6 +222,11 @@ public final class GingrHipNative {
     public static native int fitterSetPairs(long fitter, int[] pid, double[] xyz, double[] variance);
     /** pairs with a full covariance (cov9[9 K], row-major); summed by the landmark pass, O(K r^2): for few pairs */
     public static native int fitterSetPairsCov(long fitter, int[] pid, double[] xyz, double[] cov9);
+    /** pairs with a full covariance at mesh scale (one per vertex): consolidated once into one precision per vertex, summed by the
+     *  3 x 3-weighted Gram pass (float64 MFMA over the basis) */
+    public static native int fitterSetPairsCovDense(long fitter, int[] pid, double[] xyz, double[] cov9);
+    /** the consolidated dense covariance pairs: obs[3 M], precision[6 M] (xx, xy, xz, yy, yz, zz; all 0 = no pair) in the model's point order */
+    public static native int fitterGetPairPrecisions(long fitter, double[] obsXyz, double[] prec6);
     /** the consolidated isotropic pairs: obs[3 M], weight[M] (0 = no pair) in the model's point order */
     public static native int fitterGetPairObservations(long fitter, double[] obsXyz, double[] weight);
     /** sigma2 of the device state only (a host's own updateSigma2 between updates) */

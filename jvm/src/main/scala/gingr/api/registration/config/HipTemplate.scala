@@ -9,7 +9,9 @@
  * results of the two functions go to the fitter's pair lists (gingr_fitter_set_pairs / gingr_fitter_set_pairs_cov), ONE native
  * update follows, and updateSigma2(newState) is applied to the device state (gingr_fitter_set_sigma2) when the update committed.
  * Covariances that are exact multiples of the identity go to the isotropic list (one consolidated observation per vertex); the others to
- * the covariance list, which the device sums in its landmark pass -- meant for few pairs.  The landmark override of computePosterior
+ * the covariance list, which the device sums in its landmark pass -- meant for few pairs -- or, with covariancePass = "gram", to the
+ * dense covariance list (gingr_fitter_set_pairs_cov_dense): one consolidated precision per vertex and a 3 x 3-weighted Gram pass over
+ * the basis, meant for a covariance per vertex (point-to-plane ICP).  The landmark override of computePosterior
  * (:288-296) happens on the device.  `run`, the Metropolis-Hastings chain, loggers and evaluators are untouched; computePosterior-
  * based callers keep working because getCorrespondence / getUncertainty are the user's own functions.
  */
@@ -28,9 +30,11 @@ class HipTemplateRegistration(
   uncertainty: (PointId, TemplateRegistrationState) => MultivariateNormalDistribution = (_: PointId, _: TemplateRegistrationState) =>
     MultivariateNormalDistribution(DenseVector.zeros[Double](3), DenseMatrix.eye[Double](3)),
   sigma2Update: TemplateRegistrationState => Double = (s: TemplateRegistrationState) => s.general.sigma2,
-  device: Int = 0
+  device: Int = 0,
+  covariancePass: String = "landmark"
 ) extends GingrAlgorithm[TemplateRegistrationState, TemplateConfiguration]
     with AutoCloseable {
+  require(covariancePass == "landmark" || covariancePass == "gram", s"covariancePass: $covariancePass; need landmark or gram")
   private val session = new HipSession(device)
   def name = "Template-HIP"
 
@@ -59,9 +63,13 @@ class HipTemplateRegistration(
     if (iso.nonEmpty || heldCounts._1 > 0)
       rc = GingrHipNative.fitterSetPairs(f, iso.map(_._1.id).toArray, iso.flatMap(t => Seq(t._2.x, t._2.y, t._2.z)).toArray,
         iso.map(_._3(0, 0)).toArray)
-    if (rc == 0 && (full.nonEmpty || heldCounts._2 > 0))
-      rc = GingrHipNative.fitterSetPairsCov(f, full.map(_._1.id).toArray, full.flatMap(t => Seq(t._2.x, t._2.y, t._2.z)).toArray,
-        full.flatMap(t => for (i <- 0 until 3; j <- 0 until 3) yield t._3(i, j)).toArray)
+    if (rc == 0 && (full.nonEmpty || heldCounts._2 > 0)) {
+      val (ids, xyz) = (full.map(_._1.id).toArray, full.flatMap(t => Seq(t._2.x, t._2.y, t._2.z)).toArray)
+      val cov9 = full.flatMap(t => for (i <- 0 until 3; j <- 0 until 3) yield t._3(i, j)).toArray
+      rc =
+        if (covariancePass == "gram") GingrHipNative.fitterSetPairsCovDense(f, ids, xyz, cov9)
+        else GingrHipNative.fitterSetPairsCov(f, ids, xyz, cov9)
+    }
     if (rc == 0) {
       heldPairs = pairs
       heldState = current
