@@ -40,4 +40,4 @@ from .states import (  # noqa: F401
 from .registration import (  # noqa: F401
     CpdRegistration, GingrAlgorithm, IcpRegistration, TemplateRegistration, _initial_general, normalTangentCovariances,
 )
-from .metrics import GeneralizationResult, ModelMetrics, SpecificityResult  # noqa: F401
+from .metrics import GeneralizationResult, LeaveOneOutResult, ModelMetrics, SpecificityResult  # noqa: F401

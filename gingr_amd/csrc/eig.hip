@@ -20,7 +20,8 @@
 //     and three roots), which reaches the wave through scalar registers; then the round-robin tournament moves every column one
 //     place: inside a wave a register rename, between neighbouring waves one column each way through LDS -- one barrier per round,
 //     two LDS buffers;
-//   * 16 waves x 6 pairs x 2 columns = 192 columns of 192 rows at most; up to three problems per launch, one workgroup each.
+//   * 16 waves x 6 pairs x 2 columns = 192 columns of 192 rows at most; one workgroup per problem: up to three problems by pointer
+//     (sym_eig_cols_kernel) or any number of one size at fixed strides (sym_eig_cols_strided_kernel) per launch.
 // Rotation threshold |p.q| > sqrt(n) eps |p| |q| (LAPACK dgesvj's), at most 60 sweeps (8 at n = 171; the two-sided kernel needs 10).
 // n = 34 / 100 / 171: 0.26 / 1.3 / 3.2 ms (tools/ubench_sym_eig.hip, profiles/r06_ubench_sym_eig.txt).
 #include "gp.h"
@@ -113,12 +114,27 @@ struct EigBatch {
     EigProblem p[3];
 };
 
+// `count` problems of one size n at fixed strides (doubles; info: two words per problem), one workgroup each: the folds of
+// gingr_pca_leave_one_out (pca_leave_one_out.hip)
+struct EigStrided {
+    const double *G;
+    int64_t g_stride;
+    int32_t ldg, n;
+    double *work;  // per problem sym_eig_cols_work_doubles(n) doubles: H, then the norms
+    int64_t work_stride;
+    double *evals;
+    int64_t e_stride;
+    double *Vs;
+    int64_t v_stride;
+    int32_t *info;
+};
+
+// One decomposition by the workgroup: the body of both entries below
 template <int E, int P, int W>
-__global__ __launch_bounds__(W * 64) void sym_eig_cols_kernel(EigBatch batch) {
+__device__ __forceinline__ void sym_eig_cols_body(const EigProblem &pr) {
     __shared__ double xT[2][W][E * 64], xB[2][W][E * 64];
     __shared__ double nrm[2][2][W * P];  // squared column norms by slot: [.][0] top row, [.][1] bottom row
     __shared__ int32_t rank_of[2 * W * P];
-    const EigProblem pr = batch.p[blockIdx.x];
     const int n = pr.n;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // w: scalar
     const int positions = (n + 1) / 2;
@@ -390,6 +406,21 @@ __global__ __launch_bounds__(W * 64) void sym_eig_cols_kernel(EigBatch batch) {
         const double len = factored ? sqrt(pr.norms[i]) : pr.norms[i];
         pr.Vs[(int64_t)row * n + rank] = len > 0.0 ? pr.H[idx] / len : 0.0;
     }
+}
+
+template <int E, int P, int W>
+__global__ __launch_bounds__(W * 64) void sym_eig_cols_kernel(EigBatch batch) {
+    const EigProblem pr = batch.p[blockIdx.x];
+    sym_eig_cols_body<E, P, W>(pr);
+}
+
+template <int E, int P, int W>
+__global__ __launch_bounds__(W * 64) void sym_eig_cols_strided_kernel(EigStrided s) {
+    const int64_t q = blockIdx.x;
+    double *work = s.work + q * s.work_stride;
+    const EigProblem pr{s.G + q * s.g_stride, s.ldg, s.n, work, work + (int64_t)kEigSlots * s.n, s.evals + q * s.e_stride, s.Vs + q * s.v_stride,
+                        s.info + 2 * q};
+    sym_eig_cols_body<E, P, W>(pr);
 }
 
 // ---- 193 .. 512 columns: the same decomposition (Cholesky, then one-sided Jacobi on the factor's columns) on many workgroups ----
@@ -701,4 +732,18 @@ void launch_sym_eig_cols(gingr_ctx *ctx, int count, const double *const *G, cons
         hipLaunchKernelGGL((sym_eig_cols_kernel<2, 4, 16>), dim3(count), dim3(16 * 64), 0, ctx->stream, b);
     else
         hipLaunchKernelGGL((sym_eig_cols_kernel<3, 6, 16>), dim3(count), dim3(16 * 64), 0, ctx->stream, b);
+}
+
+// `count` decompositions of one size n <= kSymEigColsMaxN in one launch, one workgroup each: problem q reads G + q g_stride (row stride
+// ldg) and writes evals + q n, Vs + q n n, info + 2 q; work: count * sym_eig_cols_work_doubles(n) doubles.  The kernel of
+// launch_sym_eig_cols, the same arithmetic in the same order.
+void launch_sym_eig_cols_strided(gingr_ctx *ctx, int count, const double *G, int64_t g_stride, int32_t ldg, int32_t n, double *work, double *evals,
+                                 double *Vs, int32_t *info) {
+    const EigStrided s{G, g_stride, ldg, n, work, sym_eig_cols_work_doubles(n), evals, (int64_t)n, Vs, (int64_t)n * n, info};
+    if (n <= 64)
+        hipLaunchKernelGGL((sym_eig_cols_strided_kernel<1, 2, 16>), dim3(count), dim3(16 * 64), 0, ctx->stream, s);
+    else if (n <= 128)
+        hipLaunchKernelGGL((sym_eig_cols_strided_kernel<2, 4, 16>), dim3(count), dim3(16 * 64), 0, ctx->stream, s);
+    else
+        hipLaunchKernelGGL((sym_eig_cols_strided_kernel<3, 6, 16>), dim3(count), dim3(16 * 64), 0, ctx->stream, s);
 }

@@ -404,6 +404,14 @@ int sym_eig_blocks(gingr_ctx *ctx, int count, const double *const *G, const int3
                    double *const *evals, double *const *Vs, int32_t *const *info);
 void launch_sym_eig_cols(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ldg, const int32_t *n, double *const *work,
                          double *const *evals, double *const *Vs, int32_t *const *info);
+// eig.hip: `count` problems of one size n <= kSymEigColsMaxN at fixed strides in ONE launch of the register kernel, one workgroup each
+// (problem q: G + q g_stride, evals + q n, Vs + q n n, info + 2 q; work: count * sym_eig_cols_work_doubles(n) doubles)
+void launch_sym_eig_cols_strided(gingr_ctx *ctx, int count, const double *G, int64_t g_stride, int32_t ldg, int32_t n, double *work, double *evals,
+                                 double *Vs, int32_t *info);
+// sym_eig.hip: `count` decompositions of one size n <= kJacMaxN, problem q the n x n matrix at G + q n n with its results at evals + q n
+// and Vs + q n n: the launch above with the two-sided kernel behind it; above kSymEigColsMaxN sym_eig(..., blocks = true) three at a
+// time.  Synchronises the stream.
+int sym_eig_strided(gingr_ctx *ctx, int count, const double *G, int32_t n, double *evals, double *Vs);
 // doubles of the `work` buffer launch_posterior_solve / launch_posterior_logpdf need (used when r > 128)
 int64_t posterior_work_doubles(int32_t rp);
 // Binv = (S/eps + I)^-1  (work: [rp*rp]); *err_flag != 0 on failure

@@ -15,6 +15,7 @@
 // order; no float atomics): two calls with the same input give the same bits.
 #include "basis_rotate.h"
 #include "dense_spd.h"
+#include "model_metrics.h"
 #include "model_metrics_plan.h"
 
 #include <algorithm>
@@ -32,7 +33,7 @@ constexpr int kPackVerts = 64;  // vertices of a tile (device rows)
 constexpr int kPackCols = 64;   // shapes of a tile
 
 // D[3 s + d][col0 + j] = X_j[3 perm[s] + d] - ref[d][s] - mean[d][s] (center) or X_j[3 perm[s] + d] for the staged shapes j < cnt
-// (X: interleaved, caller's point order).  Block (b, d): the device rows [64 b, 64 b + 64), 64 shapes at a time through LDS
+// (X: interleaved, caller's point order; perm == nullptr: the rows keep that order).  Block (b, d): the device rows [64 b, 64 b + 64), 64 shapes at a time through LDS
 // (center_pack_kernel, pca_model.hip): the reads gather a shape's vertices in the model's order, the writes run along a row of D.
 __global__ __launch_bounds__(256) void shapes_pack_kernel(const double *__restrict__ X, int cnt, int col0, int np, int64_t M,
                                                           const int32_t *__restrict__ perm, const double *__restrict__ ref,
@@ -41,7 +42,7 @@ __global__ __launch_bounds__(256) void shapes_pack_kernel(const double *__restri
     const int d = blockIdx.y, tid = threadIdx.x, v = tid & 63;
     const int64_t s0 = (int64_t)blockIdx.x * kPackVerts, s = s0 + v;
     const bool live = s < M;
-    const int64_t src = live ? (int64_t)3 * perm[s] + d : 0;
+    const int64_t src = live ? (int64_t)3 * (perm ? perm[s] : s) + d : 0;
     const double rf = (live && center) ? ref[(int64_t)d * M + s] : 0.0, mn = (live && center) ? mean[(int64_t)d * M + s] : 0.0;
     for (int j0 = 0; j0 < cnt; j0 += kPackCols) {
         __syncthreads();
@@ -365,26 +366,6 @@ int check_finite(gingr_ctx *ctx, const double *x, int64_t per, int64_t n, const 
     return GINGR_OK;
 }
 
-// n shapes (host, interleaved, caller's point order) as the columns [0, n) of D [3 M + 48][np], centred or as points; the padding
-// columns and the slack rows are zero.  A few shapes per transfer through one staging buffer of at most 64 MB.
-int pack_shapes(gingr_ctx *ctx, const gingr_model *m, int n, const double *shapes, bool center, DevBuf &D, int np) {
-    const int64_t M = m->M;
-    DevBuf stage;
-    HIP_TRY(ctx, D.alloc((size_t)mp::block_rows(M) * np * sizeof(double)));
-    HIP_TRY(ctx, hipMemsetAsync(D.p, 0, (size_t)mp::block_rows(M) * np * sizeof(double), ctx->stream));
-    const int per_stage = (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)8 << 20) / (3 * M)));
-    HIP_TRY(ctx, stage.alloc((size_t)per_stage * 3 * M * sizeof(double)));
-    for (int i0 = 0; i0 < n; i0 += per_stage) {
-        const int cnt = std::min(per_stage, n - i0);
-        HIP_TRY(ctx, hipMemcpyAsync(stage.p, shapes + (size_t)i0 * 3 * M, (size_t)cnt * 3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(shapes_pack_kernel, dim3((unsigned)ceil_div(M, kPackVerts), 3), dim3(256), 0, ctx->stream, stage.as<double>(), cnt, i0, np, M,
-                           m->perm, m->ref, m->mean, center ? 1 : 0, D.as<double>());
-        GINGR_TRY(check_launch(ctx));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffer leaves scope
-    return GINGR_OK;
-}
-
 // P [3 M + 48][ldt] = ref + mean + Q0 T on ctx->stream (the slack rows are the caller's)
 void launch_instances(gingr_ctx *ctx, const gingr_model *m, const double *T, int ldt, double *P) {
     const int nchunks = (int)ceil_div(ldt / 16, kRotChunkTiles);
@@ -395,6 +376,42 @@ void launch_instances(gingr_ctx *ctx, const gingr_model *m, const double *T, int
 }
 
 }  // namespace
+
+// n shapes (host, interleaved, caller's point order) as the columns [0, n) of D [3 M + 48][np], centred or as points; the padding
+// columns and the slack rows are zero.  A few shapes per transfer through one staging buffer of at most 64 MB.
+int pack_shape_columns(gingr_ctx *ctx, int64_t M, const int32_t *perm, const double *ref, const double *mean, int n, const double *shapes, bool center,
+                       DevBuf &D, int np) {
+    DevBuf stage;
+    HIP_TRY(ctx, D.alloc((size_t)mp::block_rows(M) * np * sizeof(double)));
+    HIP_TRY(ctx, hipMemsetAsync(D.p, 0, (size_t)mp::block_rows(M) * np * sizeof(double), ctx->stream));
+    const int per_stage = (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)8 << 20) / (3 * M)));
+    HIP_TRY(ctx, stage.alloc((size_t)per_stage * 3 * M * sizeof(double)));
+    for (int i0 = 0; i0 < n; i0 += per_stage) {
+        const int cnt = std::min(per_stage, n - i0);
+        HIP_TRY(ctx, hipMemcpyAsync(stage.p, shapes + (size_t)i0 * 3 * M, (size_t)cnt * 3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(shapes_pack_kernel, dim3((unsigned)ceil_div(M, kPackVerts), 3), dim3(256), 0, ctx->stream, stage.as<double>(), cnt, i0, np, M,
+                           perm, ref, mean, center ? 1 : 0, D.as<double>());
+        GINGR_TRY(check_launch(ctx));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffer leaves scope
+    return GINGR_OK;
+}
+
+// kernel A and its finish on ctx->stream: avg [n_ranks][n] and max [n_ranks][n] into res (device, 2 n_ranks n doubles) of
+// |Q0 T - D| per vertex, column q np + i of T against column i of D.  Q0: [3 M + 48][rp], T: [rp][ldt], ldt = n_ranks np.
+int launch_project_measure(gingr_ctx *ctx, const double *Q0, int64_t M, int rp, const double *T, int ldt, const double *D, int np, int n, int n_ranks,
+                           DevBuf &partial, double *res) {
+    const mp::MeasurePlan plan = mp::make_measure_plan(M, ldt);
+    HIP_TRY(ctx, partial.alloc((size_t)plan.partial_doubles() * sizeof(double)));
+    {
+        TimerScope ts(ctx, 18);
+        hipLaunchKernelGGL(project_measure_kernel, dim3((unsigned)plan.workgroups()), dim3(64 * kRotWaves), 0, ctx->stream, Q0, M, rp, T, ldt, D, np,
+                           plan.verts_per_slab, (int)plan.chunks, partial.as<double>());
+    }
+    hipLaunchKernelGGL(measure_finish_kernel, dim3((unsigned)ceil_div((int64_t)n_ranks * n, 256)), dim3(256), 0, ctx->stream, partial.as<double>(),
+                       (int)plan.slabs, ldt, np, n, n_ranks, M, res, res + (size_t)n_ranks * n);
+    return check_launch(ctx);
+}
 
 extern "C" {
 
@@ -456,7 +473,7 @@ int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t
 
     // ---- D and b = Q0^T D
     DevBuf D, ws, C, work, T, coef, partial, res;
-    GINGR_TRY(pack_shapes(ctx, model, n, shapes_xyz, true, D, np));
+    GINGR_TRY(pack_shape_columns(ctx, M, model->perm, model->ref, model->mean, n, shapes_xyz, true, D, np));
     gingr_model dm;  // D as the second "basis" of the cross Gram pass, in this model's row order
     dm.M = M, dm.Q0 = D.as<double>(), dm.rp = np, dm.iperm = model->iperm;
     {
@@ -487,17 +504,8 @@ int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t
     GINGR_TRY(check_launch(ctx));
 
     // ---- kernel A and its finish
-    const mp::MeasurePlan plan = mp::make_measure_plan(M, ldt);
-    HIP_TRY(ctx, partial.alloc((size_t)plan.partial_doubles() * sizeof(double)));
     HIP_TRY(ctx, res.alloc((size_t)2 * n_ranks * n * sizeof(double)));
-    {
-        TimerScope ts(ctx, 18);
-        hipLaunchKernelGGL(project_measure_kernel, dim3((unsigned)plan.workgroups()), dim3(64 * kRotWaves), 0, ctx->stream, model->Q0, M, (int)rp,
-                           T.as<double>(), ldt, D.as<double>(), np, plan.verts_per_slab, (int)plan.chunks, partial.as<double>());
-    }
-    hipLaunchKernelGGL(measure_finish_kernel, dim3((unsigned)ceil_div((int64_t)n_ranks * n, 256)), dim3(256), 0, ctx->stream, partial.as<double>(),
-                       (int)plan.slabs, ldt, np, (int)n, (int)n_ranks, M, res.as<double>(), res.as<double>() + (size_t)n_ranks * n);
-    GINGR_TRY(check_launch(ctx));
+    GINGR_TRY(launch_project_measure(ctx, model->Q0, M, (int)rp, T.as<double>(), ldt, D.as<double>(), np, (int)n, (int)n_ranks, partial, res.as<double>()));
     int32_t bad = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(avg, res.p, (size_t)n_ranks * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -529,7 +537,7 @@ int gingr_model_specificity(gingr_ctx *ctx, const gingr_model *model, int32_t n_
     const int ldmax = (int)blocks.padded(0);
 
     DevBuf Tr, A, T, P, partial, best, besti;
-    GINGR_TRY(pack_shapes(ctx, model, n_train, train_xyz, false, Tr, tp));
+    GINGR_TRY(pack_shape_columns(ctx, M, model->perm, model->ref, model->mean, n_train, train_xyz, false, Tr, tp));
     HIP_TRY(ctx, A.alloc((size_t)ldmax * r * sizeof(double)));
     HIP_TRY(ctx, T.alloc((size_t)rp * ldmax * sizeof(double)));
     HIP_TRY(ctx, P.alloc((size_t)mp::block_rows(M) * ldmax * sizeof(double)));

@@ -392,3 +392,45 @@ int sym_eig(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ld
 int launch_jacobi_eig(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, double *evals, double *Vs, bool blocks) {
     return sym_eig(ctx, 1, &G, &ldg, &n, &evals, &Vs, blocks);
 }
+
+// `count` decompositions of one size n (1 .. kJacMaxN) side by side: problem q is the n x n matrix at G + q n n (row stride n), its
+// results go to evals + q n and Vs + q n n.  Up to kSymEigColsMaxN columns the register kernel of eig.hip, one workgroup per problem and
+// all of them in one launch (timing hook 22: that launch alone); a problem it reports as numerically singular or not converged takes
+// the two-sided kernel, as in sym_eig.  Larger problems go through sym_eig(..., blocks = true), three at a time.  Synchronises the
+// stream.
+int sym_eig_strided(gingr_ctx *ctx, int count, const double *G, int32_t n, double *evals, double *Vs) {
+    if (count < 1) return GINGR_OK;
+    if (n < 1 || n > kJacMaxN) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "sym_eig: n = %d outside 1..%d", (int)n, kJacMaxN);
+    const int64_t nn = (int64_t)n * n;
+    if (n > kSymEigColsMaxN) {
+        for (int q0 = 0; q0 < count; q0 += 3) {
+            const int c = std::min(3, count - q0);
+            const double *g[3];
+            double *e[3], *v[3];
+            int32_t ld[3], nq[3];
+            for (int q = 0; q < c; ++q) g[q] = G + (q0 + q) * nn, e[q] = evals + (int64_t)(q0 + q) * n, v[q] = Vs + (q0 + q) * nn, ld[q] = nq[q] = n;
+            GINGR_TRY(sym_eig(ctx, c, g, ld, nq, e, v, true));
+        }
+        return GINGR_OK;
+    }
+    DevBuf info, work;
+    HIP_TRY(ctx, info.alloc((size_t)count * 2 * sizeof(int32_t)));
+    HIP_TRY(ctx, work.alloc((size_t)count * sym_eig_cols_work_doubles(n) * sizeof(double)));
+    HIP_TRY(ctx, hipMemsetAsync(info.p, 0, (size_t)count * 2 * sizeof(int32_t), ctx->stream));
+    {
+        TimerScope ts(ctx, 22);
+        launch_sym_eig_cols_strided(ctx, count, G, nn, n, n, work.as<double>(), evals, Vs, info.as<int32_t>());
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<int32_t> h((size_t)count * 2);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), info.p, (size_t)count * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int q = 0; q < count; ++q) {
+        if (h[2 * (size_t)q] < 60 && h[2 * (size_t)q + 1] == 0) continue;
+        GINGR_TRY(jacobi_two_sided(ctx, G + q * nn, n, n, evals + (int64_t)q * n, Vs + q * nn, info.as<int32_t>() + 2 * q));
+        int32_t sw = 0;
+        HIP_TRY(ctx, hipMemcpy(&sw, info.as<int32_t>() + 2 * q, sizeof(sw), hipMemcpyDeviceToHost));
+        if (sw >= 60) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "sym_eig: Jacobi did not converge (n = %d)", (int)n);
+    }
+    return GINGR_OK;
+}

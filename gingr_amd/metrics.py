@@ -5,6 +5,9 @@ two expensive ones batched on the device:
   specificity      how far random samples of the model lie from the nearest real shape
   compactness      the share of the variance the k leading components keep (host only)
 
+and generalization the way the literature defines it when there are no shapes to spare, leave-one-out over the training shapes
+themselves (generalizationLeaveOneOut: every fold's model, projection and distance in one call).
+
 What is not scalismo's is this package's definition -- scalismo's own source is not in reach.  scalismo measures against the closest
 surface point; here every distance is vertex to corresponding vertex: the shapes must be in correspondence with the model's reference,
 as the shapes of PointDistributionModel.createUsingPCA are.  The projection of a shape onto k components is the existing rule,
@@ -46,8 +49,36 @@ class SpecificityResult:
         return self.min_avg.mean(axis=1)
 
 
+@dataclasses.dataclass
+class LeaveOneOutResult:
+    ranks: np.ndarray          # [n_ranks]
+    avg: np.ndarray            # [n_ranks, n] mean vertex distance between shape i and its projection onto the model of the others
+    max: np.ndarray            # [n_ranks, n] largest vertex distance
+    foldRanks: np.ndarray      # [n] rank of the model built without shape i (a rank k above it counts as that rank)
+
+    def curve(self) -> np.ndarray:
+        """the mean over the folds of the mean distance, per rank"""
+        return self.avg.mean(axis=1)
+
+
 class ModelMetrics:
     """model: a device-built model, a DeviceModel, or a host PointDistributionModel (uploaded for the call)."""
+
+    @staticmethod
+    def generalizationLeaveOneOut(ctx: Context, shapes, ranks=None, relativeTolerance: float = 1e-10) -> LeaveOneOutResult:
+        """Crossvalidation.leaveOneOutCrossvalidation with the generalization measure (gingr_pca_leave_one_out): for every one of the
+        3 <= n <= 512 shapes (n x M x 3, in correspondence, taken as aligned) the PCA model of the others -- createUsingPCA(alignment
+        "none", relativeTolerance) -- and that shape's distance to its projection onto the k leading components, for every k in ranks
+        (1 <= k <= n - 2, at most 16; None: n - 2 only).  One call: no model is built, nothing of mesh size is repeated per fold."""
+        X = f64(shapes)
+        if X.ndim != 3 or X.shape[2] != 3:
+            raise ValueError(f"shapes: expected (n, M, 3), got {X.shape}")
+        n, M = X.shape[0], X.shape[1]
+        k = np.ascontiguousarray([n - 2] if ranks is None else np.atleast_1d(ranks), dtype=np.int32)
+        avg, mx, fr = np.empty((k.size, n)), np.empty((k.size, n)), np.empty(n, dtype=np.int32)
+        _check(ctx.handle, ctx._lib.gingr_pca_leave_one_out(ctx.handle, M, n, dptr(X), float(relativeTolerance), k.size, iptr(k), dptr(avg), dptr(mx),
+                                                            iptr(fr)), "gingr_pca_leave_one_out")
+        return LeaveOneOutResult(k.astype(np.int64), avg, mx, fr.astype(np.int64))
 
     @staticmethod
     def generalization(ctx: Context, model, shapes, ranks=None) -> GeneralizationResult:

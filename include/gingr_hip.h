@@ -650,6 +650,31 @@ int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t
 int gingr_model_specificity(gingr_ctx *ctx, const gingr_model *model, int32_t n_train, const double *train_xyz, int64_t n_samples,
                             const double *alphas, int32_t n_ranks, const int32_t *ranks, double *min_avg, int32_t *argmin);
 
+/* ---- leave-one-out generalization of a PCA shape model --------------------------------------------------------------------------
+ * The measurement the literature defines generalization by (scalismo: Crossvalidation.leaveOneOutCrossvalidation with the
+ * generalization measure): for every shape i the model of the other n - 1 shapes, shape i projected onto it.  shapes_xyz: n_shapes
+ * host arrays of 3 M doubles, the layout of gingr_model_from_shapes, 3 <= n_shapes <= 512, taken as already aligned; ranks: n_ranks <= 16
+ * strictly increasing values 1 <= k <= n_shapes - 2.  No reference enters.
+ * Definition, for every i: the fold model is what gingr_model_from_shapes(alignment 0, relative_tolerance, max_rank 0) builds from the
+ * other shapes -- mean of the n - 1, covariance divisor n - 2, the components with lambda_j > relative_tolerance lambda_1 and > 0 kept,
+ * fold_rank [n_shapes] of them (<= n_shapes - 2); the projection of shape i onto k components is that of gingr_model_generalization (the
+ * regression with noise 1e-5) with k' = min(k, fold_rank[i]); avg [n_ranks][n_shapes] is the mean and max [n_ranks][n_shapes] the largest
+ * vertex-to-corresponding-vertex distance between shape i and that projection.  A fold whose other shapes are all identical -- its total
+ * variance lies within the rounding of the Gram entries it is formed from -- is no error: fold_rank[i] = 0, the projection is the
+ * fold's mean.
+ * Route: nothing of mesh size is repeated per fold.  The shapes centred on the mean of all n and their Gram matrix are formed once;
+ * every fold's Gram matrix is a rank-two correction of it, decomposed (with the mean-eigenvalue shift of gingr_model_from_shapes) side
+ * by side with the other folds, one workgroup each, up to n_shapes = 193; from 194 on the folds go through the block kernel three at a
+ * time (correct; no speed is promised there).  Every fold's error field is a combination of the centred shapes with weights worked
+ * out in n-space, formed on float64 MFMA and measured without being stored.  Float64 throughout, every sum in a fixed order, no float
+ * atomics: two calls with the same input give the same bits.  Synchronises.
+ * GINGR_ERR_BAD_ARGUMENT (the text contains "pca_leave_one_out" and names the cause): a null argument, n_shapes outside 3..512, M < 1,
+ * n_ranks outside 1..16, a rank outside 1..n_shapes - 2 or not above its predecessor, relative_tolerance outside [0, 1) or NaN, all
+ * shapes identical; GINGR_ERR_NONFINITE: a non-finite coordinate (the text names the shape) or eigenvalue.  Nothing is written then
+ * and the context stays usable. */
+int gingr_pca_leave_one_out(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const double *shapes_xyz, double relative_tolerance,
+                            int32_t n_ranks, const int32_t *ranks, double *avg, double *max, int32_t *fold_rank);
+
 /* ---- the inverse-Laplacian model from the sparse Laplacian's own eigenpairs -------------------------------------------------
  * The model of DiagonalKernel(LookupKernel(pinv(L)) * scaling) (GPMMHelper.scala:132-136, InvLapKernel) without the n x n
  * pseudo-inverse: a new, finalized, single-shard model on this context.  Everything is host memory: ref_xyz [3 M] the reference,
@@ -911,7 +936,8 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * the chosen size, sort, means, argmin), compaction of vertices and triangles, 17 = the Chebyshev step of gingr_model_from_laplacian
  * (lap_cheb_kernel) alone, 18 / 19 / 20 = the passes of the model metrics alone: reconstruct and measure (gingr_model_generalization), samples
  * against training shapes (gingr_model_specificity), the stored basis x factor product (gingr_model_instances, gingr_model_specificity),
- * 21 = the pivot step of gingr_model_localize alone.  Returns accumulated ms and launches since
+ * 21 = the pivot step of gingr_model_localize alone, 22 = the batched eigen-decomposition of the folds of gingr_pca_leave_one_out alone
+ * (one launch per batch of folds; up to n_shapes = 193).  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
