@@ -266,6 +266,9 @@ SIGNATURES = {
     "gingr_model_instances": (c_int, [c_void_p, c_void_p, c_int64, _dp, _dp]),
     "gingr_model_generalization": (c_int, [c_void_p, c_void_p, c_int32, _dp, c_int32, _ip, _dp, _dp, _dp]),
     "gingr_model_specificity": (c_int, [c_void_p, c_void_p, c_int32, _dp, c_int64, _dp, c_int32, _ip, _dp, _ip]),
+    "gingr_mesh_set_distances": (c_int, [c_void_p, c_int64, c_int64, _dp, c_int64, c_int64, _dp, c_int64, _ip, c_int32, c_int32, _dp, _dp]),
+    "gingr_model_generalization_surface": (c_int, [c_void_p, c_void_p, c_int32, _dp, c_int64, _ip, c_int32, _ip, _dp, _dp, _dp]),
+    "gingr_model_specificity_surface": (c_int, [c_void_p, c_void_p, c_int32, _dp, c_int64, _ip, c_int64, _dp, c_int32, _ip, _dp, _ip]),
     "gingr_pca_leave_one_out": (c_int, [c_void_p, c_int64, c_int32, _dp, c_double, c_int32, _ip, _dp, _dp, _ip]),
     "gingr_model_from_laplacian": (c_int, [c_void_p, c_int64, _dp, c_int64, _ip, c_double, c_int32, c_double, c_int32,
                                            POINTER(LaplacianInfo), POINTER(c_void_p)]),

@@ -163,6 +163,27 @@ class Context:
                "gingr_mesh_distance_stats")
         return float(out[0]), float(out[1]), int(out[2]), float(out[3])
 
+    def mesh_set_distances(self, sets, meshes, cells, pairing: str = "all", corresponding: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """(avg, max) of d = |p - closestPointOnSurface(p)| over the points of every query set (n_sets x n_points x 3) against the meshes
+        (n_meshes x n_vertices x 3) that share the triangles `cells` -- gingr_mesh_set_distances, one batched pass.  pairing "all":
+        every set against every mesh, (n_sets, n_meshes) each; "cyclic": set c against mesh c % n_meshes, (n_sets,) each.  The direction
+        is set -> mesh surface: per pair what mesh_distance_stats(set, mesh, cells) gives as sum / count and max (max bit for bit, avg to
+        the order of the sum).  corresponding=True (n_points == n_vertices) declares that point k of a set lies near vertex k of the
+        mesh: a hint that seeds the search and never changes a bit."""
+        S, V = f64(sets), f64(meshes)
+        S, V = (S[None] if S.ndim == 2 else S), (V[None] if V.ndim == 2 else V)
+        if S.ndim != 3 or S.shape[2] != 3 or V.ndim != 3 or V.shape[2] != 3:
+            raise ValueError(f"sets / meshes: expected (n, points, 3), got {S.shape} and {V.shape}")
+        if pairing not in ("all", "cyclic"):
+            raise ValueError(f"pairing: 'all' or 'cyclic', got {pairing!r}")
+        c = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        shape = (S.shape[0], V.shape[0]) if pairing == "all" else (S.shape[0],)
+        avg, mx = np.empty(shape), np.empty(shape)
+        _check(self.handle, self._lib.gingr_mesh_set_distances(self.handle, S.shape[1], S.shape[0], dptr(S), V.shape[1], V.shape[0], dptr(V),
+                                                               c.shape[0], iptr(c), 0 if pairing == "all" else 1, int(bool(corresponding)),
+                                                               dptr(avg), dptr(mx)), "gingr_mesh_set_distances")
+        return avg, mx
+
     def mesh_closest_points(self, points, vertices, cells) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """mesh.operations.closestPointOnSurface for every row of `points`: (closest points (n,3), squared distances (n,), triangle
         ids (n,), barycentric weights of that triangle's corners (n,3)) -- gingr_mesh_closest_points."""

@@ -366,8 +366,11 @@ int run_distance_stats(gingr_ctx *ctx, Cloud q, Cloud v, const int32_t *tri, con
     return GINGR_OK;
 }
 
+}  // namespace
+
 // spatial orders of a stateless mesh query: queries and vertices (device position -> original; vinv: original -> position) and
-// triangles by centroid (torder), with `tri` their vertex positions in that order
+// triangles by centroid (torder), with `tri` their vertex positions in that order (declared in surface.h: surface_metrics.hip plans
+// its shared topology with it)
 void mesh_orders(int64_t n_points, const double *points, int64_t n_vertices, const double *vertices, int64_t n_triangles,
                  const int32_t *triangles, std::vector<int32_t> &qorder, std::vector<int32_t> &vorder, std::vector<int32_t> &torder,
                  std::vector<int32_t> &vinv, std::vector<int32_t> &tri) {
@@ -387,6 +390,8 @@ void mesh_orders(int64_t n_points, const double *points, int64_t n_vertices, con
     for (int64_t s2 = 0; s2 < n_triangles; ++s2)
         for (int k = 0; k < 3; ++k) tri[(size_t)3 * s2 + k] = vinv[(size_t)triangles[(size_t)3 * torder[(size_t)s2] + k]];
 }
+
+namespace {
 
 // SoA planes of host points taken in the order `order` (device position -> input index)
 void gather_soa(const double *xyz, const std::vector<int32_t> &order, std::vector<double> &soa) {

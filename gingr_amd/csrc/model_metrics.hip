@@ -80,11 +80,6 @@ __global__ __launch_bounds__(256) void shapes_unpack_kernel(const double *__rest
     }
 }
 
-struct RankList {
-    int32_t n;
-    int32_t k[mp::kMaxRanks];
-};
-
 // Block i, shape i: u = b_i / eps, y = W^T u (y[j] needs the rows i' <= j alone: the same y for every rank), then row by row
 // alpha_k[row] = sum_{row <= j < k} W[row][j] y[j] as one running sum over j that is written out whenever j reaches the next rank.
 // T[row][q np + i] and coef[q][i][row] (nullable) get alpha_k(q)[row], zero from row k(q) on.  C: [rp][np] (b_i in column i).
@@ -334,8 +329,10 @@ struct MetricsElem {  // S_tot / eps + I: BinvElem of gp.hip
     __device__ double operator()(int64_t row, int64_t c) const { return S[row * rp + c] / GINGR_COEFF_NOISE + (row == c ? 1.0 : 0.0); }
 };
 
+}  // namespace
+
 // ---- host side
-int check_model(gingr_ctx *ctx, const gingr_model *m, const char *who) {
+int metrics_check_model(gingr_ctx *ctx, const gingr_model *m, const char *who) {
     if (m->ctx != ctx) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: the model belongs to another context", who);
     if (m->row_begin != 0 || m->row_end != m->M_total || m->M != m->M_total)
         return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: the model is a row shard; single-shard models only", who);
@@ -343,7 +340,7 @@ int check_model(gingr_ctx *ctx, const gingr_model *m, const char *who) {
     return GINGR_OK;
 }
 
-int check_ranks(gingr_ctx *ctx, const gingr_model *m, int32_t n_ranks, const int32_t *ranks, const char *who, RankList *out) {
+int metrics_check_ranks(gingr_ctx *ctx, const gingr_model *m, int32_t n_ranks, const int32_t *ranks, const char *who, RankList *out) {
     if (n_ranks < 1 || n_ranks > mp::kMaxRanks || !ranks)
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: %d ranks, need 1 <= n_ranks <= %d", who, (int)n_ranks, (int)mp::kMaxRanks);
     out->n = n_ranks;
@@ -360,7 +357,7 @@ int check_ranks(gingr_ctx *ctx, const gingr_model *m, int32_t n_ranks, const int
     return GINGR_OK;
 }
 
-int check_finite(gingr_ctx *ctx, const double *x, int64_t per, int64_t n, const char *who, const char *what) {
+int metrics_check_finite(gingr_ctx *ctx, const double *x, int64_t per, int64_t n, const char *who, const char *what) {
     for (int64_t e = 0; e < per * n; ++e)
         if (!std::isfinite(x[e])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite value in %s %lld", who, what, (long long)(e / per));
     return GINGR_OK;
@@ -375,7 +372,10 @@ void launch_instances(gingr_ctx *ctx, const gingr_model *m, const double *T, int
                        nchunks, P);
 }
 
-}  // namespace
+// T [rp][ldt] on the device: column c < cnt = the k leading entries of alphas[c] (device, [cnt][r]), zero elsewhere.  On ctx->stream.
+void launch_sample_factor(gingr_ctx *ctx, const double *alphas, int cnt, int r, int k, int rp, int ldt, double *T) {
+    hipLaunchKernelGGL(sample_factor_kernel, dim3((unsigned)ceil_div((int64_t)rp * ldt, 256)), dim3(256), 0, ctx->stream, alphas, cnt, r, k, rp, ldt, T);
+}
 
 // n shapes (host, interleaved, caller's point order) as the columns [0, n) of D [3 M + 48][np], centred or as points; the padding
 // columns and the slack rows are zero.  A few shapes per transfer through one staging buffer of at most 64 MB.
@@ -413,66 +413,16 @@ int launch_project_measure(gingr_ctx *ctx, const double *Q0, int64_t M, int rp, 
     return check_launch(ctx);
 }
 
-extern "C" {
-
-int gingr_model_instances(gingr_ctx *ctx, const gingr_model *model, int64_t n, const double *alphas, double *out_xyz) {
-    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
-    const char *who = "model_instances";
-    if (!model || !alphas || !out_xyz) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: null argument", who);
-    GINGR_TRY(check_model(ctx, model, who));
-    if (n < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: n = %lld < 1", who, (long long)n);
+// The front half of a generalization call, on ctx->stream: D [3 M + 48][np] the centred shapes, T [rp][n_ranks np] one column of
+// coefficients per (rank, shape) -- column q np + i = alpha_k(q) of shape i -- and coef [n_ranks][n][r] (when wanted).  f.flag (device,
+// inside f.work) is non-zero when S_tot / eps + I was not positive definite.  Nothing synchronises: f owns every buffer in flight.
+int project_rank_factors(gingr_ctx *ctx, const gingr_model *model, int32_t n, const double *shapes_xyz, const RankList &rl, bool want_coef,
+                         RankFactors &f) {
+    DevBuf &D = f.D, &ws = f.ws, &C = f.C, &work = f.work, &T = f.T, &coef = f.coef;
     const int64_t M = model->M;
-    const int32_t r = model->r, rp = model->rp;
-    GINGR_TRY(check_finite(ctx, alphas, r, n, who, "coefficient vector"));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const mp::ColumnBlocks blocks = mp::column_blocks(n);
-    const int ldmax = (int)blocks.padded(0);
-    // the instances leave through a staging buffer of at most 64 MB (at least one shape)
-    const int per_stage = (int)std::max<int64_t>(1, std::min<int64_t>(ldmax, ((int64_t)8 << 20) / (3 * M)));
-    DevBuf A, T, P, stage;
-    HIP_TRY(ctx, A.alloc((size_t)ldmax * r * sizeof(double)));
-    HIP_TRY(ctx, T.alloc((size_t)rp * ldmax * sizeof(double)));
-    HIP_TRY(ctx, P.alloc((size_t)mp::block_rows(M) * ldmax * sizeof(double)));
-    HIP_TRY(ctx, stage.alloc((size_t)per_stage * 3 * M * sizeof(double)));
-    for (int64_t b = 0; b < blocks.count; ++b) {
-        const int cnt = (int)blocks.length(b), ldt = (int)blocks.padded(b);
-        const int64_t c0 = blocks.begin(b);
-        HIP_TRY(ctx, hipMemcpyAsync(A.p, alphas + c0 * r, (size_t)cnt * r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(sample_factor_kernel, dim3((unsigned)ceil_div((int64_t)rp * ldt, 256)), dim3(256), 0, ctx->stream, A.as<double>(), cnt, (int)r,
-                           (int)r, (int)rp, ldt, T.as<double>());
-        launch_instances(ctx, model, T.as<double>(), ldt, P.as<double>());
-        GINGR_TRY(check_launch(ctx));
-        for (int i0 = 0; i0 < cnt; i0 += per_stage) {
-            const int part = std::min(per_stage, cnt - i0);
-            hipLaunchKernelGGL(shapes_unpack_kernel, dim3((unsigned)ceil_div(M, kPackVerts), 3), dim3(256), 0, ctx->stream, P.as<double>() + i0, part, ldt,
-                               M, model->perm, stage.as<double>());
-            GINGR_TRY(check_launch(ctx));
-            HIP_TRY(ctx, hipMemcpyAsync(out_xyz + (size_t)(c0 + i0) * 3 * M, stage.p, (size_t)part * 3 * M * sizeof(double), hipMemcpyDeviceToHost,
-                                        ctx->stream));
-        }
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return GINGR_OK;
-}
-
-int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t n, const double *shapes_xyz, int32_t n_ranks, const int32_t *ranks,
-                               double *coeffs, double *avg, double *max_out) {
-    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
-    const char *who = "model_generalization";
-    if (!model || !shapes_xyz || !avg || !max_out) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: null argument", who);
-    GINGR_TRY(check_model(ctx, model, who));
-    if (n < 1 || n > mp::kMaxShapes)
-        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: %d shapes, need 1 <= n <= %d per call", who, (int)n, (int)mp::kMaxShapes);
-    RankList rl;
-    GINGR_TRY(check_ranks(ctx, model, n_ranks, ranks, who, &rl));
-    const int64_t M = model->M;
-    const int32_t r = model->r, rp = model->rp;
-    GINGR_TRY(check_finite(ctx, shapes_xyz, 3 * M, n, who, "shape"));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int32_t r = model->r, rp = model->rp, n_ranks = rl.n;
     const int np = (int)mp::padded_cols(n), ldt = n_ranks * np;
-
     // ---- D and b = Q0^T D
-    DevBuf D, ws, C, work, T, coef, partial, res;
     GINGR_TRY(pack_shape_columns(ctx, M, model->perm, model->ref, model->mean, n, shapes_xyz, true, D, np));
     gingr_model dm;  // D as the second "basis" of the cross Gram pass, in this model's row order
     dm.M = M, dm.Q0 = D.as<double>(), dm.rp = np, dm.iperm = model->iperm;
@@ -498,10 +448,77 @@ int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t
     // ---- T: one column per (rank, shape)
     HIP_TRY(ctx, T.alloc((size_t)rp * ldt * sizeof(double)));
     HIP_TRY(ctx, hipMemsetAsync(T.p, 0, (size_t)rp * ldt * sizeof(double), ctx->stream));
-    if (coeffs) HIP_TRY(ctx, coef.alloc((size_t)n_ranks * n * r * sizeof(double)));
+    if (want_coef) HIP_TRY(ctx, coef.alloc((size_t)n_ranks * n * r * sizeof(double)));
     hipLaunchKernelGGL(rank_solve_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, (int)r, (int)rp, work.as<double>() + sw.lt(), sw.Mp, C.as<double>(),
-                       np, (int)n, rl, T.as<double>(), (int64_t)ldt, coeffs ? coef.as<double>() : nullptr);
+                       np, (int)n, rl, T.as<double>(), (int64_t)ldt, want_coef ? coef.as<double>() : nullptr);
     GINGR_TRY(check_launch(ctx));
+
+    f.flag = flag;
+    return GINGR_OK;
+}
+
+extern "C" {
+
+int gingr_model_instances(gingr_ctx *ctx, const gingr_model *model, int64_t n, const double *alphas, double *out_xyz) {
+    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
+    const char *who = "model_instances";
+    if (!model || !alphas || !out_xyz) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: null argument", who);
+    GINGR_TRY(metrics_check_model(ctx, model, who));
+    if (n < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: n = %lld < 1", who, (long long)n);
+    const int64_t M = model->M;
+    const int32_t r = model->r, rp = model->rp;
+    GINGR_TRY(metrics_check_finite(ctx, alphas, r, n, who, "coefficient vector"));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const mp::ColumnBlocks blocks = mp::column_blocks(n);
+    const int ldmax = (int)blocks.padded(0);
+    // the instances leave through a staging buffer of at most 64 MB (at least one shape)
+    const int per_stage = (int)std::max<int64_t>(1, std::min<int64_t>(ldmax, ((int64_t)8 << 20) / (3 * M)));
+    DevBuf A, T, P, stage;
+    HIP_TRY(ctx, A.alloc((size_t)ldmax * r * sizeof(double)));
+    HIP_TRY(ctx, T.alloc((size_t)rp * ldmax * sizeof(double)));
+    HIP_TRY(ctx, P.alloc((size_t)mp::block_rows(M) * ldmax * sizeof(double)));
+    HIP_TRY(ctx, stage.alloc((size_t)per_stage * 3 * M * sizeof(double)));
+    for (int64_t b = 0; b < blocks.count; ++b) {
+        const int cnt = (int)blocks.length(b), ldt = (int)blocks.padded(b);
+        const int64_t c0 = blocks.begin(b);
+        HIP_TRY(ctx, hipMemcpyAsync(A.p, alphas + c0 * r, (size_t)cnt * r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        launch_sample_factor(ctx, A.as<double>(), cnt, (int)r, (int)r, (int)rp, ldt, T.as<double>());
+        launch_instances(ctx, model, T.as<double>(), ldt, P.as<double>());
+        GINGR_TRY(check_launch(ctx));
+        for (int i0 = 0; i0 < cnt; i0 += per_stage) {
+            const int part = std::min(per_stage, cnt - i0);
+            hipLaunchKernelGGL(shapes_unpack_kernel, dim3((unsigned)ceil_div(M, kPackVerts), 3), dim3(256), 0, ctx->stream, P.as<double>() + i0, part, ldt,
+                               M, model->perm, stage.as<double>());
+            GINGR_TRY(check_launch(ctx));
+            HIP_TRY(ctx, hipMemcpyAsync(out_xyz + (size_t)(c0 + i0) * 3 * M, stage.p, (size_t)part * 3 * M * sizeof(double), hipMemcpyDeviceToHost,
+                                        ctx->stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return GINGR_OK;
+}
+
+int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t n, const double *shapes_xyz, int32_t n_ranks, const int32_t *ranks,
+                               double *coeffs, double *avg, double *max_out) {
+    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
+    const char *who = "model_generalization";
+    if (!model || !shapes_xyz || !avg || !max_out) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: null argument", who);
+    GINGR_TRY(metrics_check_model(ctx, model, who));
+    if (n < 1 || n > mp::kMaxShapes)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: %d shapes, need 1 <= n <= %d per call", who, (int)n, (int)mp::kMaxShapes);
+    RankList rl;
+    GINGR_TRY(metrics_check_ranks(ctx, model, n_ranks, ranks, who, &rl));
+    const int64_t M = model->M;
+    const int32_t r = model->r, rp = model->rp;
+    GINGR_TRY(metrics_check_finite(ctx, shapes_xyz, 3 * M, n, who, "shape"));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int np = (int)mp::padded_cols(n), ldt = n_ranks * np;
+
+    RankFactors f;
+    DevBuf partial, res;
+    GINGR_TRY(project_rank_factors(ctx, model, n, shapes_xyz, rl, coeffs != nullptr, f));
+    DevBuf &D = f.D, &T = f.T, &coef = f.coef;
+    const int32_t *flag = f.flag;
 
     // ---- kernel A and its finish
     HIP_TRY(ctx, res.alloc((size_t)2 * n_ranks * n * sizeof(double)));
@@ -521,16 +538,16 @@ int gingr_model_specificity(gingr_ctx *ctx, const gingr_model *model, int32_t n_
     if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
     const char *who = "model_specificity";
     if (!model || !train_xyz || !alphas || !min_avg || !argmin) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: null argument", who);
-    GINGR_TRY(check_model(ctx, model, who));
+    GINGR_TRY(metrics_check_model(ctx, model, who));
     if (n_train < 1 || n_train > mp::kMaxShapes)
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: %d training shapes, need 1 <= n_train <= %d", who, (int)n_train, (int)mp::kMaxShapes);
     if (n_samples < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: n_samples = %lld < 1", who, (long long)n_samples);
     RankList rl;
-    GINGR_TRY(check_ranks(ctx, model, n_ranks, ranks, who, &rl));
+    GINGR_TRY(metrics_check_ranks(ctx, model, n_ranks, ranks, who, &rl));
     const int64_t M = model->M;
     const int32_t r = model->r, rp = model->rp;
-    GINGR_TRY(check_finite(ctx, train_xyz, 3 * M, n_train, who, "training shape"));
-    GINGR_TRY(check_finite(ctx, alphas, r, n_samples, who, "coefficient vector"));
+    GINGR_TRY(metrics_check_finite(ctx, train_xyz, 3 * M, n_train, who, "training shape"));
+    GINGR_TRY(metrics_check_finite(ctx, alphas, r, n_samples, who, "coefficient vector"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int tp = (int)mp::padded_cols(n_train);
     const mp::ColumnBlocks blocks = mp::column_blocks(n_samples);
@@ -553,8 +570,7 @@ int gingr_model_specificity(gingr_ctx *ctx, const gingr_model *model, int32_t n_
         const mp::PairPlan plan = mp::make_pair_plan(M, cnt, n_train);
         HIP_TRY(ctx, hipMemcpyAsync(A.p, alphas + c0 * r, (size_t)cnt * r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         for (int32_t q = 0; q < n_ranks; ++q) {
-            hipLaunchKernelGGL(sample_factor_kernel, dim3((unsigned)ceil_div((int64_t)rp * ldt, 256)), dim3(256), 0, ctx->stream, A.as<double>(), cnt, (int)r,
-                               (int)rl.k[q], (int)rp, ldt, T.as<double>());
+            launch_sample_factor(ctx, A.as<double>(), cnt, (int)r, (int)rl.k[q], (int)rp, ldt, T.as<double>());
             launch_instances(ctx, model, T.as<double>(), ldt, P.as<double>());
             {
                 TimerScope ts(ctx, 19);

@@ -134,6 +134,12 @@ void launch_reversal_sums(gingr_ctx *ctx, int64_t M, Cloud tgt, const int32_t *n
                           int32_t *keys, int32_t *vals, int32_t *skeys, int32_t *svals, void *sort_temp, size_t sort_temp_bytes,
                           double *w01_targets, double *sums4);
 
+// spatial (k-d leaf) orders of a stateless mesh query on the host (fitter_surface.hip): queries and vertices (device position ->
+// original index; vinv: original -> position), triangles by centroid (torder), and `tri` [3 T]: their vertex POSITIONS in that order
+void mesh_orders(int64_t n_points, const double *points, int64_t n_vertices, const double *vertices, int64_t n_triangles,
+                 const int32_t *triangles, std::vector<int32_t> &qorder, std::vector<int32_t> &vorder, std::vector<int32_t> &torder,
+                 std::vector<int32_t> &vinv, std::vector<int32_t> &tri);
+
 // copies of every query held per workgroup of the tile scans (surface_cp_queue_kernel, self_intersect_queue_kernel), from the number of queries
 inline int surface_h(int64_t nq) {
     // measured (femur chain, 1 622 queries x 3 240 triangles: 1 007 / 1 151 / 1 237 / 1 257 steps per second at H = 2 / 4 / 8 / 16;

@@ -823,16 +823,35 @@ class DeviceModel:
                "gingr_model_instances")
         return out
 
-    def project(self, shapes, ranks=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def _surface_cells(self, distance: str, cells) -> Optional[np.ndarray]:
+        """None for distance="vertex"; for "surface" the triangles (t x 3 int32): `cells`, else the model's"""
+        if distance == "vertex":
+            return None
+        if distance != "surface":
+            raise ValueError(f"distance: 'vertex' or 'surface', got {distance!r}")
+        cells = _cells_of(self) if cells is None else cells
+        if cells is None:
+            raise ValueError("distance='surface' needs the triangles: pass cells=, or use a model that carries them")
+        return np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+
+    def project(self, shapes, ranks=None, distance: str = "vertex", cells=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """The shapes (n x M x 3, n <= 512) projected onto the k leading components for every k in ranks (gingr_model_generalization):
-        (coefficients [n_ranks, n, rank], zero from entry k on; mean vertex distance [n_ranks, n]; largest vertex distance
-        [n_ranks, n]) between each shape and its projection -- what truncate(k).coefficients(shape) and .instance give, shape by
-        shape.  Vertex to corresponding vertex."""
+        (coefficients [n_ranks, n, rank], zero from entry k on; mean distance [n_ranks, n]; largest distance [n_ranks, n]) between each
+        shape and its projection -- what truncate(k).coefficients(shape) and .instance give, shape by shape.  distance="vertex" (the
+        default): vertex to corresponding vertex.  distance="surface" (gingr_model_generalization_surface): every vertex of the
+        projection to the closest point on the surface of the shape, whose triangles are `cells`, else the model's; the same
+        coefficients bit for bit."""
         X, k = self._shapes(shapes), self._ranks(ranks)
+        c = self._surface_cells(distance, cells)
         n = X.shape[0]
         coef, avg, mx = np.empty((k.size, n, self.rank)), np.empty((k.size, n)), np.empty((k.size, n))
-        _check(self.ctx.handle, self._lib.gingr_model_generalization(self.ctx.handle, self.handle, n, dptr(X), k.size, iptr(k), dptr(coef),
-                                                                     dptr(avg), dptr(mx)), "gingr_model_generalization")
+        if c is None:
+            _check(self.ctx.handle, self._lib.gingr_model_generalization(self.ctx.handle, self.handle, n, dptr(X), k.size, iptr(k), dptr(coef),
+                                                                         dptr(avg), dptr(mx)), "gingr_model_generalization")
+        else:
+            _check(self.ctx.handle, self._lib.gingr_model_generalization_surface(self.ctx.handle, self.handle, n, dptr(X), c.shape[0], iptr(c), k.size,
+                                                                                 iptr(k), dptr(coef), dptr(avg), dptr(mx)),
+                   "gingr_model_generalization_surface")
         return coef, avg, mx
 
     def posterior_mean(self, obs_points, weights, euler=(0, 0, 0), center=(0, 0, 0), translation=(0, 0, 0),

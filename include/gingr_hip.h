@@ -624,7 +624,7 @@ int gingr_model_localize(gingr_ctx *ctx, const gingr_model *model, double sigma,
 /* ---- model metrics: many instances, many projections, many samples against many shapes ------------------------------------------
  * What the shape-model literature (and scalismo's ModelMetrics) measures a model by, batched on the device.  What is not scalismo's is
  * this library's definition: nothing in reach pins scalismo's own, and scalismo measures against the closest surface point, whereas
- * every distance here is vertex to corresponding vertex.  model: a complete (single-shard), finalized model of this context -- a row
+ * every distance of these three entries is vertex to corresponding vertex (the closest-surface-point measure: the next section).  model: a complete (single-shard), finalized model of this context -- a row
  * shard or a model that is not finalized is GINGR_ERR_STATE.  Shapes are host arrays of 3 M doubles each, one after the other,
  * interleaved xyz in the caller's point order (the layout of gingr_model_from_shapes).  ranks: n_ranks <= 16 strictly increasing values
  * 1 <= k <= rank.  Bad counts or ranks and null arguments are GINGR_ERR_BAD_ARGUMENT (the text names the cause); a non-finite
@@ -649,6 +649,44 @@ int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t
                                const int32_t *ranks, double *coeffs /* may be NULL */, double *avg, double *max);
 int gingr_model_specificity(gingr_ctx *ctx, const gingr_model *model, int32_t n_train, const double *train_xyz, int64_t n_samples,
                             const double *alphas, int32_t n_ranks, const int32_t *ranks, double *min_avg, int32_t *argmin);
+
+/* ---- surface-distance model metrics: many point sets against the surfaces of many meshes of one triangulation ---------------------
+ * The measure scalismo's ModelMetrics and the shape-model literature use (MeshMetrics.avgDistance) beside the vertex-to-vertex one above.
+ * Definition (this library's: scalismo's source is not in reach, so the DIRECTION is ours): the surface distance of a model-side mesh A
+ * -- a projection or a sample -- to a data shape B with the same triangles is, for every vertex p of A, d(p) = |p -
+ * closestPointOnSurface_B(p)|; avg is the mean over the M vertices, max the largest d(p).  Model side -> data surface: what
+ * gingr_mesh_distance_stats(A, B, triangles) gives as out[0] / out[2] and out[1].  No boundary-aware variant, no likelihood term.
+ * All three are float64, synchronise, sum in a fixed order without float atomics: two calls with the same input give the same bits.
+ *
+ * gingr_mesh_set_distances: n_sets query sets of n_points points each (sets_xyz [n_sets][3 n_points]) against n_meshes meshes of
+ *   n_vertices vertices each (meshes_xyz [n_meshes][3 n_vertices]) that share `triangles` [3 n_triangles]; host arrays, interleaved xyz.
+ *   pairing 0: every set against every mesh, avg and max are [n_sets][n_meshes]; pairing 1: set c against mesh c % n_meshes, avg and max
+ *   are [n_sets].  corresponding != 0 needs n_points == n_vertices and declares that point k of a set lies near vertex k of the mesh:
+ *   a HINT that seeds the search of point k with a triangle at vertex k and never changes a bit of a result; with 0 the search starts
+ *   cold.  Points need not be near anything.  A vertex of no triangle is legal (its point starts cold), and so are degenerate triangles,
+ *   as in gingr_mesh_closest_points.  The squared distance behind every d(p) has the bits gingr_mesh_closest_points returns, max the bits
+ *   of gingr_mesh_distance_stats' out[1]; avg differs from out[0] / out[2] by the order of the sum alone.
+ *   Route: the k-d order of the first mesh's vertices and triangle centroids serves every mesh (correct for any meshes: every mesh has
+ *   its own tile boxes, the pruning only gets looser when the meshes differ much); every mesh is resident at once, the sets pass in
+ *   blocks of 512.
+ * gingr_model_generalization_surface / gingr_model_specificity_surface: the arguments, limits (512 shapes, 16 ranks, samples in blocks
+ *   of 512), coefficient rule, tie rule (lowest index) and error codes of gingr_model_generalization / gingr_model_specificity, with the
+ *   shapes' shared `triangles` (vertex ids in the caller's point order); only the distance differs: projection (i, k) against the surface
+ *   of shape i, sample (s, k) against the surface of every training shape.  coeffs has the bits of gingr_model_generalization's.
+ * Errors: GINGR_ERR_BAD_ARGUMENT (the text names the cause) for a null argument, a count < 1, a vertex id of a triangle out of range,
+ *   corresponding with n_points != n_vertices, a pairing other than 0 or 1, more than 2^26 triangles, and a working set (every mesh, a
+ *   block of sets) that does not fit the device's free memory -- the text names the size; GINGR_ERR_NONFINITE (the text names the set,
+ *   mesh, shape or vector) for a non-finite coordinate, nothing is computed; GINGR_ERR_STATE for a row shard or a model that is not
+ *   finalized.  Nothing is written and the context stays usable after each of them. */
+int gingr_mesh_set_distances(gingr_ctx *ctx, int64_t n_points, int64_t n_sets, const double *sets_xyz, int64_t n_vertices, int64_t n_meshes,
+                             const double *meshes_xyz, int64_t n_triangles, const int32_t *triangles, int32_t pairing, int32_t corresponding,
+                             double *avg, double *max);
+int gingr_model_generalization_surface(gingr_ctx *ctx, const gingr_model *model, int32_t n, const double *shapes_xyz, int64_t n_triangles,
+                                       const int32_t *triangles, int32_t n_ranks, const int32_t *ranks, double *coeffs /* may be NULL */,
+                                       double *avg, double *max);
+int gingr_model_specificity_surface(gingr_ctx *ctx, const gingr_model *model, int32_t n_train, const double *train_xyz, int64_t n_triangles,
+                                    const int32_t *triangles, int64_t n_samples, const double *alphas, int32_t n_ranks, const int32_t *ranks,
+                                    double *min_avg, int32_t *argmin);
 
 /* ---- leave-one-out generalization of a PCA shape model --------------------------------------------------------------------------
  * The measurement the literature defines generalization by (scalismo: Crossvalidation.leaveOneOutCrossvalidation with the
@@ -937,7 +975,7 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * (lap_cheb_kernel) alone, 18 / 19 / 20 = the passes of the model metrics alone: reconstruct and measure (gingr_model_generalization), samples
  * against training shapes (gingr_model_specificity), the stored basis x factor product (gingr_model_instances, gingr_model_specificity),
  * 21 = the pivot step of gingr_model_localize alone, 22 = the batched eigen-decomposition of the folds of gingr_pca_leave_one_out alone
- * (one launch per batch of folds; up to n_shapes = 193).  Returns accumulated ms and launches since
+ * (one launch per batch of folds; up to n_shapes = 193), 23 = the batched closest-point scan of the surface-distance metrics alone.  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
