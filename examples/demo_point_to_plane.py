@@ -8,6 +8,7 @@ with a small variance along the target's normal there and a large one in the tan
 Printed next to plain IcpRegistration (closest target vertex, isotropic variance) from the same start."""
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -49,13 +50,34 @@ def report(name, state):
           f"after {state.general.iteration} iterations")
 
 
+def timed(name, run):
+    t0 = time.perf_counter()
+    out = run()
+    dt = time.perf_counter() - t0
+    report(name, out)
+    print(f"{'':24s}  wall time {dt * 1e3:.1f} ms")
+
+
 plane = ga.TemplateRegistration(ctx, correspondence, uncertainty, updateSigma2=lambda s: max(s.general.sigma2 * DECAY, FLOOR),
                                 covariancePass="gram")
 state = plane.createInitialState(model, tgt, ga.TemplateConfiguration(maxIterations=ITERATIONS), sigma2=100.0)
-report("point-to-plane", plane.run(state))
+timed("point-to-plane", lambda: plane.run(state))
+# The same algorithm resident on the device: PointToPlaneIcpRegistration makes correspondence and covariances there and enqueues the
+# whole run in one call.  It steps sigma2 by ICP's linear schedule, so the Template route is run once more with that schedule: those
+# two are the same algorithm by two routes.
+STEP = (100.0 - FLOOR) / ITERATIONS
+linear = ga.TemplateRegistration(ctx, correspondence, uncertainty, updateSigma2=lambda s: max(s.general.sigma2 - STEP, FLOOR),
+                                 covariancePass="gram")
+timed("Template, ICP schedule", lambda: linear.run(linear.createInitialState(model, tgt, ga.TemplateConfiguration(maxIterations=ITERATIONS),
+                                                                             sigma2=100.0)))
+native = ga.PointToPlaneIcpRegistration(ctx)
+pcfg = ga.PointToPlaneConfiguration(maxIterations=ITERATIONS, initialSigma=100.0, endSigma=FLOOR, tangentOverNormal=TANGENT_OVER_NORMAL)
+meshed = ga.PointDistributionModel(model.reference, model.mean, model.basis, model.variance, cells=cells)   # (it scans the surfaces)
+native.run(native.createInitialState(meshed, tgt, pcfg, targetCells=tgt_cells))         # (first run: uploads, code objects)
+timed("PointToPlaneIcp (native)", lambda: native.run(native.createInitialState(meshed, tgt, pcfg, targetCells=tgt_cells)))
 icp = ga.IcpRegistration(ctx)
 cfg = ga.IcpConfiguration(maxIterations=ITERATIONS, initialSigma=100.0, endSigma=1.0, correspondenceMethod="PointcloudClosestPoint")
-report("IcpRegistration", icp.run(icp.createInitialState(model, tgt, cfg)))
-plane.close()
-icp.close()
+timed("IcpRegistration", lambda: icp.run(icp.createInitialState(model, tgt, cfg)))
+for a in (plane, linear, native, icp):
+    a.close()
 ctx.close()

@@ -59,6 +59,11 @@ class IcpParams(ctypes.Structure):
     _fields_ = [("initial_sigma", c_double), ("end_sigma", c_double), ("max_iterations", c_int32)]
 
 
+class PlaneParams(ctypes.Structure):
+    """gingr_plane_params"""
+    _fields_ = [("tangent_over_normal", c_double), ("reject", c_int32)]
+
+
 class MhRequest(ctypes.Structure):
     """gingr_mh_request"""
     _fields_ = [
@@ -259,6 +264,9 @@ SIGNATURES = {
     "gingr_fitter_posterior_logpdf_pairs": (c_int, [c_void_p, _dp, _dp]),
     "gingr_fitter_posterior_covariance_pairs": (c_int, [c_void_p, _dp]),
     "gingr_fitter_posterior_model_pairs": (c_int, [c_void_p, POINTER(c_void_p)]),
+    # point-to-plane ICP: the dense list made on the device from the surface scan
+    "gingr_fitter_set_pairs_plane_async": (c_int, [c_void_p, POINTER(PlaneParams)]),
+    "gingr_fitter_update_plane_async": (c_int, [c_void_p, POINTER(PlaneParams), POINTER(IcpParams), c_int32]),
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),

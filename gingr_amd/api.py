@@ -7,7 +7,8 @@ error behaviour so that tests read like uses of the reference API:
   context        Context (gingr_ctx) and _check
   models         PointDistributionModel, the models built or adopted in HBM, DeviceModel, the GPMM helpers
   states         enums, fitting parameters, correspondence lists, the configuration / state records
-  registration   GingrAlgorithm, CpdRegistration, IcpRegistration, TemplateRegistration, normalTangentCovariances
+  registration   GingrAlgorithm, CpdRegistration, IcpRegistration, TemplateRegistration, PointToPlaneIcpRegistration,
+                 normalTangentCovariances
 
 Dependencies run one way, context <- models <- registration; states needs none of them.  In their comments G/ stands for
 src/main/scala/gingr/ of unibas-gravis/GiNGR.  All arithmetic runs in libgingr_hip.so on the GPU; nothing here computes on
@@ -35,9 +36,11 @@ from .models import (  # noqa: F401
 from .states import (  # noqa: F401
     CorrespondencePairs, CpdConfiguration, CpdRegistrationState, EulerAngles, FittingStatuses, GeneralRegistrationState,
     GlobalTranformationType, IcpConfiguration, IcpRegistrationState, LandmarkCorrespondences, ModelFittingParameters,
+    PointToPlaneConfiguration, PointToPlaneRegistrationState,
     TemplateConfiguration, TemplateRegistrationState, _cpd_converged, _empty_pairs, _never_converged, _with_fields,
 )
 from .registration import (  # noqa: F401
-    CpdRegistration, GingrAlgorithm, IcpRegistration, TemplateRegistration, _initial_general, normalTangentCovariances,
+    CpdRegistration, GingrAlgorithm, IcpRegistration, PointToPlaneIcpRegistration, TemplateRegistration, _initial_general,
+    normalTangentCovariances,
 )
 from .metrics import GeneralizationResult, LeaveOneOutResult, ModelMetrics, SpecificityResult  # noqa: F401

@@ -241,6 +241,10 @@ struct gingr_fitter {
     void *dsort = nullptr;
     size_t dsort_bytes = 0;
     DevBuf dense_ws;
+    // gingr_fitter_set_pairs_plane_async fills the same planes on the device (n_dense = M marks them as a list: nothing of the uploaded
+    // list is read per iteration).  plane_live: one device word, whether the state could take the update that follows
+    // (plane_pairs_kernel writes it, plane_schedule_kernel reads it); allocated on first use.
+    int32_t *plane_live = nullptr;
 };
 
 // GINGR_OPT_GRAM_DOWNDATE by default: from this many local rows on.  The downdate pays while fewer than ~20 % of the rows have weight 0
@@ -319,6 +323,8 @@ void launch_basis_rotate(gingr_ctx *ctx, const gingr_model *src, const double *T
 // ---- fitter_phases.hip
 int gather_fit(gingr_fitter *f, const Correspondence &c, gingr_allreduce_fn reduce, void *user, fitter_gather_fn gather, const char *who);
 int fitter_posterior_inputs(gingr_fitter *f, const Correspondence &c);  // phases 0 and 1 of the current state for a query (allow_alt)
+// the forward surface correspondence of the current fit on its own (phase0_surface; single shard, meshes set: the caller has checked)
+void fitter_surface_scan(gingr_fitter *f);
 // ---- fitter_surface.hip
 void free_meshes(gingr_fitter *f);
 // ---- fitter_pairs.hip

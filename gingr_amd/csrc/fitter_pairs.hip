@@ -7,6 +7,9 @@
 //   dense covariance pairs (pid, point, 3 x 3) x K ->  one precision and one precision-weighted point per vertex, once per
 //                     gingr_fitter_set_pairs_cov_dense: the same keys kernel and sort, a gather thread that adds the inverses;
 //                     summed every iteration by the 3 x 3-weighted Gram pass (gp_gram_cov.hip)
+//   point-to-plane pairs, made here           ->  the same planes written by one kernel from what the forward surface scan leaves
+//                     (gingr_fitter_set_pairs_plane_async), and the loop around them with ICP's sigma2 schedule on the device
+//                     (gingr_fitter_update_plane_async): no list, no transfer, no synchronisation
 // The phases themselves are in fitter_phases.hip (run_phase), the probabilistic queries next to their siblings.
 #include "fitter.h"
 #include "svd3.h"
@@ -108,6 +111,60 @@ __global__ __launch_bounds__(256) void pairs_gather_cov_kernel(int64_t M, int64_
     obs[2 * M + i] = x1[2];
 #pragma unroll
     for (int q = 0; q < 6; ++q) prec6[q * M + i] = L[q];
+}
+
+// Point-to-plane pairs made on the device, per local vertex i (device row), from what the forward surface scan left (phase0_surface):
+// the closest surface point cp [3][M], the winning triangle's position in the target's triangle array and the 0/1 rejection weight.
+// With n the stored unit normal of that triangle (tcn [3][Tt]), v_n = sigma2 along it and v_t = ratio sigma2 across it,
+//   prec6[.][i] = (1 / v_t) I + (1 / v_n - 1 / v_t) n n^T   (planes xx, xy, xz, yy, yz, zz),   obs[.][i] = cp[.][i] bit for bit
+// -- the closed-form inverse of v_t I + (v_n - v_t) n n^T, nothing is inverted numerically; ratio 1 gives (1 / sigma2) I exactly.  A
+// normal that is zero or non-finite (a degenerate target triangle) gives (1 / v_t) I.  reject != 0 and weight 0: no observation, all
+// zero; reject == 0: every vertex is observed and w01 is set to 1, so that the surface getter reports the weights that were used.
+// Thread 0 also notes in *live whether the state can still move (neither failed nor stopped): plane_schedule_kernel looks at it
+// behind the update.
+__global__ __launch_bounds__(256) void plane_pairs_kernel(int64_t M, int64_t Tt, const double *__restrict__ cp, const int32_t *__restrict__ tri_pos,
+                                                          double *__restrict__ w01, const double *__restrict__ tcn, const DevState *__restrict__ st,
+                                                          double ratio, int reject, double *__restrict__ obs, double *__restrict__ prec6,
+                                                          int32_t *__restrict__ live) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *live = !(st->status == GINGR_FIT_MODEL_FLEXIBILITY_ERROR || st->stopped);
+    if (i >= M) return;
+    double x = 0.0, y = 0.0, z = 0.0, L[6] = {0, 0, 0, 0, 0, 0};
+    const bool observed = !reject || w01[i] != 0.0;
+    if (!reject) w01[i] = 1.0;
+    if (observed) {
+        x = cp[i], y = cp[M + i], z = cp[2 * M + i];
+        const double vn = st->sigma2, vt = ratio * vn;
+        const double a = 1.0 / vt, b = 1.0 / vn - a;
+        const int64_t t = tri_pos[i];
+        double nx = 0.0, ny = 0.0, nz = 0.0;
+        if (t >= 0 && t < Tt) nx = tcn[t], ny = tcn[Tt + t], nz = tcn[2 * Tt + t];
+        const double nn = (nx * nx + ny * ny) + nz * nz;  // (NaN fails both comparisons)
+        if (!(nn > 0.0 && nn <= 1.79769313486231570815e308)) nx = ny = nz = 0.0;
+        const double bx = b * nx, by = b * ny, bz = b * nz;
+        L[0] = a + bx * nx, L[1] = bx * ny, L[2] = bx * nz;
+        L[3] = a + by * ny, L[4] = by * nz, L[5] = a + bz * nz;
+    }
+    obs[i] = x;
+    obs[M + i] = y;
+    obs[2 * M + i] = z;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) prec6[q * M + i] = L[q];
+}
+
+// ICP's sigma2 schedule behind a flavour-3 update (ICP.scala:65, :96-99; one thread), exactly where post_solve_kernel applies it for
+// the ICP flavours: only a state that took the update (*live) and only an update that committed (pad == 0) moves sigma2, and the run's
+// stopping rule compares sigma2 before and after -- the pairs update itself keeps sigma2, so its verdict is replaced here.
+__global__ void plane_schedule_kernel(DevState *st, const int32_t *live, double step, double end, double stop_threshold) {
+    if (!*live) return;
+    const double before = st->sigma2;
+    double after = before;
+    if (st->pad == 0) {
+        const double ns = before - step;
+        after = ns > end ? ns : end;
+        st->sigma2 = after;
+    }
+    st->stopped = (stop_threshold >= 0.0 && fabs(before - after) < stop_threshold) ? 1 : 0;
 }
 
 // sigma2 of the device state and of the scalars it was initialised from (one thread)
@@ -258,7 +315,44 @@ void free_pairs(gingr_fitter *f) {
     f->dobs = f->dprec = nullptr;
     f->dense_ws.release();
     f->n_dense = 0;
+    dev_free(f->plane_live);
+    f->plane_live = nullptr;
 }
+
+namespace {
+
+// what both point-to-plane entry points refuse, in the order of correspondence.h: ready, parameters, then what the flavour needs
+int plane_check(gingr_fitter *f, const gingr_plane_params *p, const char *who) {
+    GINGR_TRY(check_ready(f));
+    gingr_ctx *ctx = f->ctx;
+    if (!p) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: null parameters", who);
+    if (!(p->tangent_over_normal >= 1.0 && p->tangent_over_normal <= 1.79769313486231570815e308))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: tangent_over_normal must be finite and >= 1", who);
+    if (p->reject != 0 && p->reject != 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: reject must be 0 or 1", who);
+    if (!f->Tm || !f->Tt || !f->surf_cp) return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: no meshes set (gingr_fitter_set_meshes)", who);
+    if (f->sharded() || f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: single shard only", who);
+    if (f->surface_method != 0 || f->reversed)
+        return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: the TriangularClosestPoint method in the forward direction only", who);
+    return GINGR_OK;
+}
+
+// the forward surface scan of the current fit, then its planes; asynchronous.  The caller has run plane_check.
+int plane_refresh(gingr_fitter *f, const gingr_plane_params &p) {
+    gingr_ctx *ctx = f->ctx;
+    const int64_t M = f->m->M;
+    f->forget_posteriors();  // the same state with other pairs is another posterior
+    f->n_dense = 0;  // (until everything below is in place)
+    GINGR_TRY(dense_ensure_planes(f));
+    if (!f->plane_live) GINGR_TRY(dev_alloc(ctx, &f->plane_live, 1));
+    fitter_surface_scan(f);
+    hipLaunchKernelGGL(plane_pairs_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, f->Tt, f->surf_cp, f->surf_tri_pos,
+                       f->surf_w01, f->tcn, f->st, p.tangent_over_normal, (int)p.reject, f->dobs, f->dprec, f->plane_live);
+    GINGR_TRY(check_launch(ctx));
+    f->n_dense = M;  // one pair per vertex; the uploaded list's arrays are not read by an update
+    return GINGR_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -427,6 +521,31 @@ int gingr_fitter_set_sigma2(gingr_fitter *f, double sigma2) {
         f->state_key.v.back() = sigma2;
     else
         f->state_key_valid = false;
+    return check_launch(ctx);
+}
+
+int gingr_fitter_set_pairs_plane_async(gingr_fitter *f, const gingr_plane_params *p) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    GINGR_TRY(plane_check(f, p, "set_pairs_plane_async"));
+    return plane_refresh(f, *p);
+}
+
+int gingr_fitter_update_plane_async(gingr_fitter *f, const gingr_plane_params *p, const gingr_icp_params *schedule, int32_t n_iterations) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    GINGR_TRY(plane_check(f, p, "update_plane_async"));
+    gingr_ctx *ctx = f->ctx;
+    if (n_iterations < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "update_plane_async: n_iterations < 1");
+    if (!schedule || schedule->max_iterations < 1)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "update_plane_async: the schedule needs max_iterations >= 1");
+    const double step = (schedule->initial_sigma - schedule->end_sigma) / (double)schedule->max_iterations;  // ICP.scala:65
+    const Correspondence pairs = abi_correspondence(3, nullptr, nullptr);
+    for (int32_t it = 0; it < n_iterations; ++it) {
+        GINGR_TRY(plane_refresh(f, *p));
+        GINGR_TRY(fitter_update(f, pairs, 1));
+        hipLaunchKernelGGL(plane_schedule_kernel, dim3(1), dim3(1), 0, ctx->stream, f->st, f->plane_live, step, schedule->end_sigma,
+                           f->stop_threshold);
+        f->forget_posteriors();  // sigma2 is part of the state the memo is keyed by
+    }
     return check_launch(ctx);
 }
 

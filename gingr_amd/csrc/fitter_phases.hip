@@ -650,6 +650,14 @@ int run_phase(gingr_fitter *f, const Correspondence &c, int phase) {
 // One phase of one flavour (GINGR_PHASE_GATHER included); the caller has checked the descriptor (check_correspondence)
 int fitter_run_phase(gingr_fitter *f, const Correspondence &c, int phase) { return run_phase(f, c, phase); }
 
+// The launches of the forward surface correspondence alone, for a caller that turns their results into pairs of its own
+// (fitter_pairs.hip: gingr_fitter_set_pairs_plane_async).  The correspondence arrays belong to the current state afterwards.
+void fitter_surface_scan(gingr_fitter *f) {
+    const Cloud fit = cloud_of(f->fit, f->m->M);
+    phase0_surface(f, fit, cloud_of(f->target, f->N), fit);
+    f->corr_stale = false;
+}
+
 // The posterior inputs of the current state -- correspondences, Gram, right-hand side -- for a query that leaves the state as it is:
 // phases 0 and 1, which may bring a parked memo slot back (allow_alt)
 int fitter_posterior_inputs(gingr_fitter *f, const Correspondence &c) {

@@ -1,5 +1,5 @@
 """The algorithms: `GingrAlgorithm` (one native call sequence per iteration, the fused Metropolis-Hastings step, the queries about a
-state) and its three correspondence flavours `CpdRegistration`, `IcpRegistration` and `TemplateRegistration`.
+state) and its correspondence flavours `CpdRegistration`, `IcpRegistration`, `TemplateRegistration` and `PointToPlaneIcpRegistration`.
 
   GingrAlgorithm                                                G/api/GingrAlgorithm.scala:52-75,192-258
   CpdRegistration                                               G/api/registration/config/CPD.scala:52-155
@@ -21,7 +21,8 @@ from .context import Context, _check
 from .models import DeviceModel, PointDistributionModel, PosteriorDevicePointDistributionModel, _landmarks_native
 from .states import (CorrespondencePairs, CpdConfiguration, CpdRegistrationState, EulerAngles, FittingStatuses, GeneralRegistrationState,
                      GlobalTranformationType, IcpConfiguration, IcpRegistrationState, LandmarkCorrespondences, ModelFittingParameters,
-                     TemplateConfiguration, TemplateRegistrationState, _cpd_converged, _empty_pairs, _never_converged, _with_fields)
+                     PointToPlaneConfiguration, PointToPlaneRegistrationState, TemplateConfiguration, TemplateRegistrationState,
+                     _cpd_converged, _empty_pairs, _never_converged, _with_fields)
 
 
 # ----------------------------------------------------------------------------- the algorithm
@@ -832,3 +833,118 @@ class TemplateRegistration(GingrAlgorithm):
         obs, prec = np.empty((M, 3)), np.empty((M, 6))
         _check(self.ctx.handle, self._lib.gingr_fitter_get_pair_precisions(self._fitter, dptr(obs), dptr(prec)), "gingr_fitter_get_pair_precisions")
         return obs, prec
+
+
+class PointToPlaneIcpRegistration(GingrAlgorithm):
+    """Point-to-plane ICP on the surfaces as a resident algorithm: per model vertex the closest point of the target surface, observed
+    with the covariance v_t I + (v_n - v_t) n n^T -- v_n = sigma2 along the face normal n of the target triangle the point lies on,
+    v_t = tangentOverNormal * sigma2 across it -- and ICP's sigma2 schedule.  Correspondence, planes, update and schedule all run on the
+    device (gingr_fitter_update_plane_async): `update` is one such iteration, `run` without call-backs enqueues all of them in one call
+    and reads the state once.  What TemplateRegistration does with closest-point and normalTangentCovariances callbacks on the host,
+    without the host: no transfer and no synchronisation per iteration.
+
+    The update itself is the fitter's pairs flavour, so the sampled update, logTransitionProbability, posteriorCovariance and
+    posteriorModel are its queries; each refreshes the planes from the state it is asked about first.  Needs both triangulations
+    (model.cells and targetCells).  There is no fused Metropolis-Hastings step: enableFusedSteps keeps the call-by-call path."""
+    name = "PointToPlaneICP"
+
+    def __init__(self, ctx: Context):
+        super().__init__(ctx)
+        self._params_memo = None   # (config object, PlaneParams, IcpParams)
+        self._planes = None        # (state, closest points, weights, precisions): what the device used for `state`
+
+    def createInitialState(self, model: PointDistributionModel, target, config: PointToPlaneConfiguration,
+                           transform: int = GlobalTranformationType.RigidTransforms, stepLength: float = 1.0,
+                           landmarks: Optional[LandmarkCorrespondences] = None, initial_pose=None,
+                           targetCells: Optional[np.ndarray] = None) -> PointToPlaneRegistrationState:
+        if getattr(model, "cells", None) is None or targetCells is None:
+            raise ValueError("point-to-plane ICP needs the triangulations (model.cells and targetCells)")
+        g = _initial_general(self.ctx, model, target, 1.0, transform, stepLength, landmarks, initial_pose, targetCells)
+        return self.initializeState(g, config)
+
+    def initializeState(self, general: GeneralRegistrationState, config: PointToPlaneConfiguration) -> PointToPlaneRegistrationState:
+        if getattr(general.model, "cells", None) is None or general.targetCells is None:
+            raise ValueError("point-to-plane ICP needs the triangulations (model.cells and targetCells)")
+        if not (np.isfinite(config.tangentOverNormal) and config.tangentOverNormal >= 1.0):
+            raise ValueError(f"tangentOverNormal: {config.tangentOverNormal!r}; need a finite ratio >= 1")
+        return PointToPlaneRegistrationState(general.updateSigma2(float(config.initialSigma)), config)
+
+    def _params(self, config: PointToPlaneConfiguration):
+        memo = self._params_memo
+        if memo is None or memo[0] is not config:
+            memo = (config, nat.PlaneParams(float(config.tangentOverNormal), 1 if config.reject else 0),
+                    nat.IcpParams(float(config.initialSigma), float(config.endSigma), int(config.maxIterations)))
+            self._params_memo = memo
+        return memo[1], memo[2]
+
+    def _correspondence(self, state: PointToPlaneRegistrationState):
+        return nat.FLAVOUR_PAIRS, None
+
+    def _prepare_native(self, state: PointToPlaneRegistrationState):
+        # the queries of the pairs flavour read the planes as they stand: make them the ones of the state the device holds
+        pp, _ = self._params(state.config)
+        _check(self.ctx.handle, self._lib.gingr_fitter_set_pairs_plane_async(self._fitter, ctypes.byref(pp)),
+               "gingr_fitter_set_pairs_plane_async")
+
+    def _native_update(self, current: PointToPlaneRegistrationState, n: int):
+        pp, ip = self._params(current.config)
+        _check(self.ctx.handle, self._lib.gingr_fitter_update_plane_async(self._fitter, ctypes.byref(pp), ctypes.byref(ip), int(n)),
+               "gingr_fitter_update_plane_async")
+
+    def updateSigma2(self, state: PointToPlaneRegistrationState) -> float:
+        return max(state.general.sigma2 - state.config.sigmaStep, state.config.endSigma)   # ICP.scala:96-99
+
+    def update(self, current, probabilistic: bool = False, rnd: Optional[np.random.Generator] = None):
+        out = super().update(current, probabilistic, rnd)
+        if not probabilistic:
+            return out             # (the schedule ran on the device, behind the update)
+        err = ctypes.c_int32()
+        _check(self.ctx.handle, self._lib.gingr_fitter_last_update_error(self._fitter, ctypes.byref(err)), "gingr_fitter_last_update_error")
+        if err.value != 0 or out.general.status == FittingStatuses.ModelFlexibilityError:
+            return out             # the update did not commit: sigma2 stays
+        s2 = self.updateSigma2(out)
+        if s2 == out.general.sigma2:
+            return out
+        _check(self.ctx.handle, self._lib.gingr_fitter_set_sigma2(self._fitter, s2), "gingr_fitter_set_sigma2")
+        new = out.updateGeneral(out.general.updateSigma2(s2))
+        self._device_state = new
+        return new
+
+    def _observed(self, state):
+        """(closest points (M, 3), weights (M,), precisions (M, 6)) the device makes for `state`, asked once per state object"""
+        if self._planes is None or self._planes[0] is not state:
+            self._ensure_device_state(state)
+            self._prepare_native(state)
+            M = state.general.model.numberOfPoints
+            cp, w, obs, prec = np.empty((M, 3)), np.empty(M), np.empty((M, 3)), np.empty((M, 6))
+            _check(self.ctx.handle, self._lib.gingr_fitter_get_surface_correspondence(self._fitter, dptr(cp), dptr(w)),
+                   "gingr_fitter_get_surface_correspondence")
+            _check(self.ctx.handle, self._lib.gingr_fitter_get_pair_precisions(self._fitter, dptr(obs), dptr(prec)),
+                   "gingr_fitter_get_pair_precisions")
+            self._planes = (state, cp, w, prec)
+        return self._planes[1:]
+
+    def surfaceCorrespondence(self, state) -> Tuple[np.ndarray, np.ndarray]:
+        """(closest surface points (M, 3), weights in {0, 1}) as the device used them for the state's fit"""
+        cp, w, _ = self._observed(state)
+        return cp, w
+
+    def pairPrecisions(self, state) -> np.ndarray:
+        """(M, 6): the precision planes xx, xy, xz, yy, yz, zz the device used for `state`; all zero = no observation"""
+        return self._observed(state)[2]
+
+    def getCorrespondence(self, state) -> CorrespondencePairs:
+        cp, w, _ = self._observed(state)
+        keep = np.flatnonzero(w == 1.0)
+        return CorrespondencePairs(keep, cp[keep])
+
+    def getUncertainty(self, pid: int, state) -> np.ndarray:
+        """v_t I + (v_n - v_t) n n^T with the face normal the device used for vertex `pid` (read back from its precision)"""
+        _, _, prec = self._observed(state)
+        vn = float(state.general.sigma2)
+        vt = float(state.config.tangentOverNormal) * vn
+        a, b = 1.0 / vt, 1.0 / vn - 1.0 / vt
+        xx, xy, xz, yy, yz, zz = prec[int(pid)]
+        lam = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
+        nnt = (lam - a * np.eye(3)) / b if b > 0.0 else np.zeros((3, 3))
+        return vt * np.eye(3) + (vn - vt) * nnt

@@ -189,6 +189,34 @@ class TemplateRegistrationState:
         return dataclasses.replace(self, general=update)
 
 
+# ----------------------------------------------------------------------------- point-to-plane ICP, correspondence on the device
+@dataclasses.dataclass(frozen=True)
+class PointToPlaneConfiguration:
+    """Point-to-plane ICP on the surfaces: ICP's sigma2 schedule (ICP.scala:65, :96-99) with a covariance per vertex that is sigma2 along
+    the target's face normal and tangentOverNormal * sigma2 across it.  reject: the three rejection rules of the surface ICP."""
+    maxIterations: int = 100
+    initialSigma: float = 100.0
+    endSigma: float = 1.0
+    tangentOverNormal: float = 100.0
+    reject: bool = False
+    threshold: float = 1e-10
+    converged: Callable = _never_converged
+    useLandmarkCorrespondence: bool = True
+
+    @property
+    def sigmaStep(self) -> float:
+        return (self.initialSigma - self.endSigma) / float(self.maxIterations)
+
+
+@dataclasses.dataclass(frozen=True)
+class PointToPlaneRegistrationState:
+    general: GeneralRegistrationState
+    config: PointToPlaneConfiguration
+
+    def updateGeneral(self, update: GeneralRegistrationState) -> "PointToPlaneRegistrationState":
+        return dataclasses.replace(self, general=update)
+
+
 def _empty_pairs() -> CorrespondencePairs:
     return CorrespondencePairs(np.empty(0, dtype=np.int64), np.empty((0, 3)))
 

@@ -541,6 +541,45 @@ int gingr_fitter_posterior_logpdf_pairs(gingr_fitter *f, const double *mesh_xyz,
 int gingr_fitter_posterior_covariance_pairs(gingr_fitter *f, double *cov6_out);
 int gingr_fitter_posterior_model_pairs(gingr_fitter *f, gingr_model **out);
 
+/* ---- point-to-plane ICP on the surfaces, its correspondence made on the device ---------------------------------------------
+ * The pairs flavour with the dense list filled by the fitter itself: per model vertex the closest point of the target SURFACE and a
+ * covariance that is tight along the target's face normal and loose across it.  With r = tangent_over_normal, v_n = sigma2 of the
+ * device state, v_t = r sigma2 and n_i the unit normal of the target triangle the closest point of vertex i lies on (as
+ * gingr_fitter_set_meshes stored it: (b - a) x (c - a), normalised), every vertex gets
+ *     Lambda_i = (1 / v_t) I + (1 / v_n - 1 / v_t) n_i n_i^T   (six doubles: xx, xy, xz, yy, yz, zz),     xbar_i = closest point,
+ * the closed-form inverse of Sigma_i = v_t I + (v_n - v_t) n_i n_i^T -- nothing is inverted numerically, xbar_i is the scan's point bit
+ * for bit, and r = 1 gives (1 / sigma2) I exactly: point-to-point ICP against the surface.  A stored normal that is zero or non-finite
+ * (a degenerate target triangle) gives (1 / v_t) I.  reject = 1 applies the three rejection rules of the surface flavour (boundary
+ * vertex, opposing normals, self-intersection: gingr_fitter_update_icp_surface_async); a rejected vertex has Lambda_i = 0, xbar_i = 0,
+ * "no observation".  reject = 0 observes every vertex.  A vertex that a landmark overrides loses its plane, as every dense pair does.
+ *
+ * gingr_fitter_set_pairs_plane_async: the forward TriangularClosestPoint correspondence of the CURRENT device state's fit against the
+ * target -- the launches of the surface flavour, warm starts and triangle grid included -- then one kernel, one thread per local
+ * vertex, that writes the planes above.  Asynchronous on the context's stream: no transfer, no synchronisation.  The result BECOMES
+ * the dense list: it replaces what gingr_fitter_set_pairs_cov_dense put there, a later gingr_fitter_set_pairs_cov_dense replaces it in
+ * turn, K = 0 there clears it.  The isotropic list, the covariance list and the landmarks stay independent and keep adding, as
+ * documented for the dense list.  Forgets the posterior memo.  Afterwards gingr_fitter_get_surface_correspondence returns the closest
+ * points and the 0/1 weights that were used (all 1 with reject = 0), gingr_fitter_get_pair_precisions the planes; every entry point
+ * listed as covered under the dense list reads them -- the sampled update, the transition density, the covariance maps and the
+ * posterior model of a point-to-plane state are the _pairs queries behind this call.
+ * gingr_fitter_update_plane_async: n_iterations times { the call above; one update as gingr_fitter_update_pairs_async(f, 1) runs it;
+ * ICP's schedule  sigma2 <- max(sigma2 - (initial_sigma - end_sigma) / max_iterations, end_sigma)  on the device }.  The schedule
+ * is applied only to an update that committed, exactly where the ICP flavours apply it; a failed or stopped state is left as it is
+ * and the stop rule (gingr_fitter_set_stop_threshold) compares sigma2 before and after the schedule, as it does for ICP.
+ * Asynchronous, nothing is synchronised between iterations; two runs give the same bits, and n iterations in one call give the bits
+ * of n calls of one.
+ * Refused with nothing changed -- GINGR_ERR_STATE: no target or state set; no meshes set; a row shard (single shard only); surface
+ * method 1 or the reversed direction set.  GINGR_ERR_BAD_ARGUMENT: null params; tangent_over_normal < 1 or non-finite; reject not 0
+ * or 1; n_iterations < 1; schedule null or max_iterations < 1.
+ * NOT covered, as the pairs flavour itself: gingr_fitter_mh_step, the gingr_group_* and RCCL entry points. */
+typedef struct gingr_plane_params {
+    double tangent_over_normal;  /* >= 1, finite; 1 = isotropic: point-to-point against the surface */
+    int32_t reject;              /* 0: every vertex observed; 1: the three rejection rules of the surface flavour */
+} gingr_plane_params;
+int gingr_fitter_set_pairs_plane_async(gingr_fitter *f, const gingr_plane_params *p);
+int gingr_fitter_update_plane_async(gingr_fitter *f, const gingr_plane_params *p, const gingr_icp_params *schedule,
+                                    int32_t n_iterations);
+
 /* ---- a PCA model from shapes in correspondence ----------------------------------------------------------------------------
  * What DataCollection.gpa(...) followed by PointDistributionModel.createUsingPCA(...) gives a scalismo user, built on the device: a
  * new, finalized, single-shard model on this context.  ref_xyz [3 M]: the reference; shapes_xyz [n_shapes][3 M]: the shapes, point

@@ -696,6 +696,17 @@ JFN(jlong, fitterPosteriorModelPairs)(JNIEnv *, jclass, jlong f) {  // 0: failed
     gingr_model *m = nullptr;
     return gingr_fitter_posterior_model_pairs(P<gingr_fitter>(f), &m) == GINGR_OK ? H(m) : 0;
 }
+// ---- point-to-plane ICP: the dense list made on the device from the surface scan (gingr_fitter_set_pairs_plane_async ...)
+JFN(jint, fitterSetPairsPlane)(JNIEnv *, jclass, jlong f, jdouble tangentOverNormal, jint reject) {
+    gingr_plane_params p{tangentOverNormal, reject};
+    return gingr_fitter_set_pairs_plane_async(P<gingr_fitter>(f), &p);
+}
+JFN(jint, fitterUpdatePlane)(JNIEnv *, jclass, jlong f, jdouble tangentOverNormal, jint reject, jdouble initialSigma, jdouble endSigma,
+                             jint maxIterations, jint n) {
+    gingr_plane_params p{tangentOverNormal, reject};
+    gingr_icp_params s{initialSigma, endSigma, maxIterations};
+    return gingr_fitter_update_plane_async(P<gingr_fitter>(f), &p, &s, n);
+}
 #else
 // No JDK headers on this machine: the shim is not built (the C ABI it wraps is still covered by the Python tests).
 #endif

@@ -239,4 +239,12 @@ public final class GingrHipNative {
     public static native int fitterPosteriorCovariancePairs(long fitter, double[] cov6);
     /** the posterior of the current state as a new resident model (0: failed) */
     public static native long fitterPosteriorModelPairs(long fitter);
+
+    // ---- point-to-plane ICP: the dense covariance list made on the device (gingr_fitter_set_pairs_plane_async ...) ----------------
+    /** the surface correspondence of the current device state, then one precision per vertex -- sigma2 along the target's face normal,
+     *  tangentOverNormal * sigma2 across it; replaces the dense list; asynchronous.  reject: 0 every vertex, 1 the surface ICP's rules */
+    public static native int fitterSetPairsPlane(long fitter, double tangentOverNormal, int reject);
+    /** nIterations of { fitterSetPairsPlane; one pairs update; ICP's sigma2 schedule on the device }, enqueued in one call */
+    public static native int fitterUpdatePlane(long fitter, double tangentOverNormal, int reject, double initialSigma, double endSigma,
+                                               int maxIterations, int nIterations);
 }
