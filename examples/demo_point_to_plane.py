@@ -5,7 +5,9 @@ GiNGR's point is that an algorithm is a kernel, a correspondence function and an
 a full 3 x 3 covariance per vertex.  Here every template vertex is paired with its closest point on the target SURFACE and believed
 with a small variance along the target's normal there and a large one in the tangent plane, so a vertex may slide on the surface:
 `normalTangentCovariances` builds the covariances, `covariancePass="gram"` sends one per vertex through the 3 x 3-weighted Gram pass.
-Printed next to plain IcpRegistration (closest target vertex, isotropic variance) from the same start."""
+Printed next to plain IcpRegistration (closest target vertex, isotropic variance) from the same start.  It closes with the target as a
+scanner would deliver it -- its vertices only, no triangles: the normals are estimated from each point's 12 nearest neighbours on the
+device and the registration is point-to-plane against the cloud, judged against the true target mesh like the others."""
 import os
 import sys
 import time
@@ -78,6 +80,11 @@ timed("PointToPlaneIcp (native)", lambda: native.run(native.createInitialState(m
 icp = ga.IcpRegistration(ctx)
 cfg = ga.IcpConfiguration(maxIterations=ITERATIONS, initialSigma=100.0, endSigma=1.0, correspondenceMethod="PointcloudClosestPoint")
 timed("IcpRegistration", lambda: icp.run(icp.createInitialState(model, tgt, cfg)))
-for a in (plane, linear, native, icp):
+# The target's vertices only: no targetCells and no model.cells, a normal per target point estimated on the device (k = 12).  Beside
+# it above: the surface route (PointToPlaneIcp, native) and plain point-cloud ICP (IcpRegistration), from the same start.
+cloud = ga.PointToPlaneIcpRegistration(ctx)
+cloud.run(cloud.createInitialState(model, tgt, pcfg, targetNormals="estimate", targetNeighbours=12))   # (first run: uploads, code objects)
+timed("PointToPlaneIcp (cloud)", lambda: cloud.run(cloud.createInitialState(model, tgt, pcfg, targetNormals="estimate", targetNeighbours=12)))
+for a in (plane, linear, native, icp, cloud):
     a.close()
 ctx.close()

@@ -64,6 +64,16 @@ class PlaneParams(ctypes.Structure):
     _fields_ = [("tangent_over_normal", c_double), ("reject", c_int32)]
 
 
+class PlaneCloudParams(ctypes.Structure):
+    """gingr_plane_cloud_params"""
+    _fields_ = [("tangent_over_normal", c_double), ("max_distance", c_double)]
+
+
+class CloudKnnInfo(ctypes.Structure):
+    """gingr_cloud_knn_info"""
+    _fields_ = [("cell_size", c_double), ("grid", c_int32 * 3), ("flagged", c_int32)]
+
+
 class MhRequest(ctypes.Structure):
     """gingr_mh_request"""
     _fields_ = [
@@ -267,6 +277,14 @@ SIGNATURES = {
     # point-to-plane ICP: the dense list made on the device from the surface scan
     "gingr_fitter_set_pairs_plane_async": (c_int, [c_void_p, POINTER(PlaneParams)]),
     "gingr_fitter_update_plane_async": (c_int, [c_void_p, POINTER(PlaneParams), POINTER(IcpParams), c_int32]),
+    # k nearest neighbours of a cloud within itself, normals from them; point-to-plane ICP against a point cloud
+    "gingr_cloud_knn": (c_int, [c_void_p, c_int64, _dp, c_int32, _ip, _dp, POINTER(CloudKnnInfo)]),
+    "gingr_cloud_normals": (c_int, [c_void_p, c_int64, _dp, c_int32, _dp, _dp, _dp, POINTER(CloudKnnInfo)]),
+    "gingr_fitter_set_target_normals": (c_int, [c_void_p, _dp]),
+    "gingr_fitter_estimate_target_normals": (c_int, [c_void_p, c_int32, _dp, POINTER(CloudKnnInfo)]),
+    "gingr_fitter_get_target_normals": (c_int, [c_void_p, _dp]),
+    "gingr_fitter_set_pairs_plane_cloud_async": (c_int, [c_void_p, POINTER(PlaneCloudParams)]),
+    "gingr_fitter_update_plane_cloud_async": (c_int, [c_void_p, POINTER(PlaneCloudParams), POINTER(IcpParams), c_int32]),
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),

@@ -143,6 +143,36 @@ class Context:
                                                ctypes.byref(md)), "gingr_nn")
         return idx, d2, md.value
 
+    def cloud_knn(self, points, k: int, info: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The k nearest neighbours of every point of a cloud within the cloud itself -- gingr_cloud_knn: (idx (N, k) int32, d2 (N, k)),
+        each row sorted ascending by (d2, index), the point itself (or a lower-indexed duplicate) first; ties go to the lowest index and
+        d2 has the bits of dx*dx + dy*dy + dz*dz in float64.  3 <= k <= 64, k <= N.  info: a dict that receives the grid's cell_size,
+        its dimensions and the number of queries the grid could not certify (answered by a scan of the whole cloud)."""
+        x = f64(points).reshape(-1, 3)
+        n = x.shape[0]
+        idx, d2 = np.empty((n, max(int(k), 0)), dtype=np.int32), np.empty((n, max(int(k), 0)))
+        ki = nat.CloudKnnInfo()
+        _check(self.handle, self._lib.gingr_cloud_knn(self.handle, n, dptr(x), int(k), iptr(idx), dptr(d2), ctypes.byref(ki)), "gingr_cloud_knn")
+        if info is not None:
+            info.update(cell_size=float(ki.cell_size), grid=tuple(int(g) for g in ki.grid), flagged=int(ki.flagged))
+        return idx, d2
+
+    def cloud_normals(self, points, k: int = 16, viewpoint=None, info: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """A normal per point of an unorganised cloud from the PCA of its k nearest neighbours (Hoppe et al.) -- gingr_cloud_normals:
+        (normals (N, 3), variation (N,)).  The normal is the unit eigenvector of the smallest eigenvalue of the neighbourhood's
+        covariance, the zero vector where that direction is not defined (coincident points, a line, an isotropic blob); its largest
+        component is positive, or with a viewpoint (3,) it points towards the viewpoint.  variation = lam0 / trace, 0 on a plane."""
+        x = f64(points).reshape(-1, 3)
+        n = x.shape[0]
+        v = None if viewpoint is None else f64(viewpoint).reshape(3)
+        normals, var = np.empty((n, 3)), np.empty(n)
+        ki = nat.CloudKnnInfo()
+        _check(self.handle, self._lib.gingr_cloud_normals(self.handle, n, dptr(x), int(k), dptr(v), dptr(normals), dptr(var), ctypes.byref(ki)),
+               "gingr_cloud_normals")
+        if info is not None:
+            info.update(cell_size=float(ki.cell_size), grid=tuple(int(g) for g in ki.grid), flagged=int(ki.flagged))
+        return normals, var
+
     def gauss_block(self, A, B, sigma: float, scaling: float) -> np.ndarray:
         """scaling * exp(-|a-b|^2 / sigma^2)  (GPMMHelper.scala:99-102)."""
         A, B = f64(A), f64(B)

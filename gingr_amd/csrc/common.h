@@ -240,6 +240,12 @@ int nn_grid_build(gingr_ctx *ctx, const double *target_xyz, int64_t N, const int
 void nn_grid_free(NNGrid *g);
 bool launch_nn_grid(gingr_ctx *ctx, Cloud query, Cloud target, const int32_t *target_orig, NNGrid &g, const int32_t *warm,
                     int32_t *idx, double *d2);
+// ---------------------------------------------------------------------------- cloud_knn.hip (k nearest neighbours, normals)
+// gingr_cloud_normals on a cloud that lies on the device (SoA; orig: device position -> the caller's index, nullable = the same): the
+// normal of the point at position t goes to normals[t * point_stride + axis * axis_stride], its variation (nullable) to variation[t].
+// viewpoint: host, nullable.  Synchronises.
+int cloud_normals_device(gingr_ctx *ctx, Cloud c, const int32_t *orig, int32_t k, const double *viewpoint, double *normals, int64_t point_stride,
+                         int64_t axis_stride, double *variation, gingr_cloud_knn_info *info, const char *who);
 // ---------------------------------------------------------------------------- cloud_ops.hip (per-cloud kernels, layouts, k-d order)
 void launch_cloud_centroid(gingr_ctx *ctx, Cloud c, double *out3);
 void launch_cloud_absmax(gingr_ctx *ctx, Cloud c, const double *ctr, double *slot);

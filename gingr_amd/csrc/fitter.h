@@ -245,6 +245,9 @@ struct gingr_fitter {
     // list is read per iteration).  plane_live: one device word, whether the state could take the update that follows
     // (plane_pairs_kernel writes it, plane_schedule_kernel reads it); allocated on first use.
     int32_t *plane_live = nullptr;
+    // point-to-plane against a point cloud: a unit (or zero) normal per target point, planes [3][N] in the target's device order
+    // (gingr_fitter_set_target_normals / _estimate_target_normals); nullptr = none, and a new target drops them
+    double *tnormals = nullptr;
 };
 
 // GINGR_OPT_GRAM_DOWNDATE by default: from this many local rows on.  The downdate pays while fewer than ~20 % of the rows have weight 0
@@ -325,6 +328,8 @@ int gather_fit(gingr_fitter *f, const Correspondence &c, gingr_allreduce_fn redu
 int fitter_posterior_inputs(gingr_fitter *f, const Correspondence &c);  // phases 0 and 1 of the current state for a query (allow_alt)
 // the forward surface correspondence of the current fit on its own (phase0_surface; single shard, meshes set: the caller has checked)
 void fitter_surface_scan(gingr_fitter *f);
+// the forward point-cloud correspondence of the current fit on its own (phase0_nearest_vertex; single shard: the caller has checked)
+void fitter_cloud_scan(gingr_fitter *f);
 // ---- fitter_surface.hip
 void free_meshes(gingr_fitter *f);
 // ---- fitter_pairs.hip

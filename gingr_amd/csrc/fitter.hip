@@ -267,7 +267,7 @@ void gingr_fitter_destroy(gingr_fitter *f) {
                     f->zrand, f->pose, f->scalars, f->fxbuf[0], f->fxbuf[1], f->alt_seg, f->nfac[0], f->nfac[1],
                     f->lp_sync, f->lp_scratch, f->retry, f->part, f->absmax, f->tperm, f->tboxes, f->fboxes,
                     f->tile_bad, f->xch, f->fullfit, f->gstage, f->zero_counts, f->ws, f->work, f->aos, f->lm_pid,
-                    f->lm_xyz, f->lm_cov, f->lm_mask};
+                    f->lm_xyz, f->lm_cov, f->lm_mask, f->tnormals};
     for (void *q : ptrs) dev_free(q);
     if (f->pin) (void)hipHostFree(f->pin);
     if (f->zpin) (void)hipHostFree(f->zpin);
@@ -289,8 +289,9 @@ int gingr_fitter_set_target(gingr_fitter *f, int64_t N, const double *target_xyz
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const int64_t M = f->m->M;
     const int32_t rp = f->m->rp;
-    void *old[] = {f->target, f->inv_den, f->Pt1, f->xch, f->ws, f->aos, f->tperm, f->tboxes, f->fboxes, f->tile_bad};
+    void *old[] = {f->target, f->inv_den, f->Pt1, f->xch, f->ws, f->aos, f->tperm, f->tboxes, f->fboxes, f->tile_bad, f->tnormals};
     for (void *q : old) dev_free(q);
+    f->tnormals = nullptr;  // (normals of the previous target's points)
     free_meshes(f);  // the target triangles refer to the previous target
     f->target = f->inv_den = f->Pt1 = f->xch = f->ws = f->tboxes = f->fboxes = nullptr;
     f->aos = nullptr;

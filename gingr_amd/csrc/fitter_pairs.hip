@@ -10,6 +10,8 @@
 //   point-to-plane pairs, made here           ->  the same planes written by one kernel from what the forward surface scan leaves
 //                     (gingr_fitter_set_pairs_plane_async), and the loop around them with ICP's sigma2 schedule on the device
 //                     (gingr_fitter_update_plane_async): no list, no transfer, no synchronisation
+//   ... against a point cloud                 ->  the same again from what the forward point-cloud search leaves and a normal per target
+//                     point (gingr_fitter_set_pairs_plane_cloud_async, gingr_fitter_update_plane_cloud_async)
 // The phases themselves are in fitter_phases.hip (run_phase), the probabilistic queries next to their siblings.
 #include "fitter.h"
 #include "svd3.h"
@@ -113,6 +115,19 @@ __global__ __launch_bounds__(256) void pairs_gather_cov_kernel(int64_t M, int64_
     for (int q = 0; q < 6; ++q) prec6[q * M + i] = L[q];
 }
 
+// L = (1 / v_t) I + (1 / v_n - 1 / v_t) n n^T (planes xx, xy, xz, yy, yz, zz) with v_t = ratio v_n: the closed-form inverse of
+// v_t I + (v_n - v_t) n n^T for a unit n.  A normal that is zero or non-finite gives (1 / v_t) I; ratio 1 gives (1 / v_n) I exactly.
+// The ONE body both point-to-plane kernels below share.
+__device__ __forceinline__ void plane_precision(double nx, double ny, double nz, double vn, double ratio, double L[6]) {
+    const double vt = ratio * vn;
+    const double a = 1.0 / vt, b = 1.0 / vn - a;
+    const double nn = (nx * nx + ny * ny) + nz * nz;  // (NaN fails both comparisons)
+    if (!(nn > 0.0 && nn <= 1.79769313486231570815e308)) nx = ny = nz = 0.0;
+    const double bx = b * nx, by = b * ny, bz = b * nz;
+    L[0] = a + bx * nx, L[1] = bx * ny, L[2] = bx * nz;
+    L[3] = a + by * ny, L[4] = by * nz, L[5] = a + bz * nz;
+}
+
 // Point-to-plane pairs made on the device, per local vertex i (device row), from what the forward surface scan left (phase0_surface):
 // the closest surface point cp [3][M], the winning triangle's position in the target's triangle array and the 0/1 rejection weight.
 // With n the stored unit normal of that triangle (tcn [3][Tt]), v_n = sigma2 along it and v_t = ratio sigma2 across it,
@@ -134,16 +149,34 @@ __global__ __launch_bounds__(256) void plane_pairs_kernel(int64_t M, int64_t Tt,
     if (!reject) w01[i] = 1.0;
     if (observed) {
         x = cp[i], y = cp[M + i], z = cp[2 * M + i];
-        const double vn = st->sigma2, vt = ratio * vn;
-        const double a = 1.0 / vt, b = 1.0 / vn - a;
         const int64_t t = tri_pos[i];
         double nx = 0.0, ny = 0.0, nz = 0.0;
         if (t >= 0 && t < Tt) nx = tcn[t], ny = tcn[Tt + t], nz = tcn[2 * Tt + t];
-        const double nn = (nx * nx + ny * ny) + nz * nz;  // (NaN fails both comparisons)
-        if (!(nn > 0.0 && nn <= 1.79769313486231570815e308)) nx = ny = nz = 0.0;
-        const double bx = b * nx, by = b * ny, bz = b * nz;
-        L[0] = a + bx * nx, L[1] = bx * ny, L[2] = bx * nz;
-        L[3] = a + by * ny, L[4] = by * nz, L[5] = a + bz * nz;
+        plane_precision(nx, ny, nz, st->sigma2, ratio, L);
+    }
+    obs[i] = x;
+    obs[M + i] = y;
+    obs[2 * M + i] = z;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) prec6[q * M + i] = L[q];
+}
+
+// The same planes against a point cloud, per local vertex i (device row), from what the forward point-cloud search left
+// (phase0_nearest_vertex): nn [M] the nearest target point as a position in the target's device order, nnd2 [M] its squared distance.
+// obs[.][i] = that target point bit for bit, the normal is the one stored for it (tn [3][N]).  max2 > 0: a vertex with nnd2 > max2 is
+// not observed (all zero); a match outside the target (never, for a finite fit) is not observed either.  *live as above.
+__global__ __launch_bounds__(256) void plane_cloud_pairs_kernel(int64_t M, int64_t N, const double *__restrict__ tgt, const int32_t *__restrict__ nn,
+                                                                const double *__restrict__ nnd2, const double *__restrict__ tn,
+                                                                const DevState *__restrict__ st, double ratio, double max2,
+                                                                double *__restrict__ obs, double *__restrict__ prec6, int32_t *__restrict__ live) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *live = !(st->status == GINGR_FIT_MODEL_FLEXIBILITY_ERROR || st->stopped);
+    if (i >= M) return;
+    double x = 0.0, y = 0.0, z = 0.0, L[6] = {0, 0, 0, 0, 0, 0};
+    const int64_t t = nn[i];
+    if (t >= 0 && t < N && !(max2 > 0.0 && nnd2[i] > max2)) {
+        x = tgt[t], y = tgt[N + t], z = tgt[2 * N + t];
+        plane_precision(tn[t], tn[N + t], tn[2 * N + t], st->sigma2, ratio, L);
     }
     obs[i] = x;
     obs[M + i] = y;
@@ -352,6 +385,56 @@ int plane_refresh(gingr_fitter *f, const gingr_plane_params &p) {
     return GINGR_OK;
 }
 
+// what the point-cloud entry points refuse, in the order of plane_check: ready, parameters, then what the flavour needs
+int plane_cloud_check(gingr_fitter *f, const gingr_plane_cloud_params *p, const char *who) {
+    GINGR_TRY(check_ready(f));
+    gingr_ctx *ctx = f->ctx;
+    if (!p) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: null parameters", who);
+    if (!(p->tangent_over_normal >= 1.0 && p->tangent_over_normal <= 1.79769313486231570815e308))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: tangent_over_normal must be finite and >= 1", who);
+    if (p->max_distance != p->max_distance) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: max_distance is NaN", who);
+    if (!f->tnormals)
+        return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: no target normals (gingr_fitter_set_target_normals / _estimate_target_normals)", who);
+    if (f->sharded() || f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: single shard only", who);
+    return GINGR_OK;
+}
+
+// the forward point-cloud search of the current fit, then its planes; asynchronous.  The caller has run plane_cloud_check.
+int plane_cloud_refresh(gingr_fitter *f, const gingr_plane_cloud_params &p) {
+    gingr_ctx *ctx = f->ctx;
+    const int64_t M = f->m->M;
+    f->forget_posteriors();  // the same state with other pairs is another posterior
+    f->n_dense = 0;  // (until everything below is in place)
+    GINGR_TRY(dense_ensure_planes(f));
+    if (!f->plane_live) GINGR_TRY(dev_alloc(ctx, &f->plane_live, 1));
+    fitter_cloud_scan(f);
+    const double max2 = p.max_distance > 0.0 ? p.max_distance * p.max_distance : 0.0;
+    hipLaunchKernelGGL(plane_cloud_pairs_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, f->N, f->target, f->nn_idx, f->nn_d2,
+                       f->tnormals, f->st, p.tangent_over_normal, max2, f->dobs, f->dprec, f->plane_live);
+    GINGR_TRY(check_launch(ctx));
+    f->n_dense = M;  // one pair per vertex; the uploaded list's arrays are not read by an update
+    return GINGR_OK;
+}
+
+// the loop both point-to-plane updates run: n_iterations times { refresh the planes; one pairs update; ICP's schedule on the device }
+template <typename Refresh>
+int plane_loop(gingr_fitter *f, const gingr_icp_params *schedule, int32_t n_iterations, const char *who, Refresh refresh) {
+    gingr_ctx *ctx = f->ctx;
+    if (n_iterations < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: n_iterations < 1", who);
+    if (!schedule || schedule->max_iterations < 1)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: the schedule needs max_iterations >= 1", who);
+    const double step = (schedule->initial_sigma - schedule->end_sigma) / (double)schedule->max_iterations;  // ICP.scala:65
+    const Correspondence pairs = abi_correspondence(3, nullptr, nullptr);
+    for (int32_t it = 0; it < n_iterations; ++it) {
+        GINGR_TRY(refresh());
+        GINGR_TRY(fitter_update(f, pairs, 1));
+        hipLaunchKernelGGL(plane_schedule_kernel, dim3(1), dim3(1), 0, ctx->stream, f->st, f->plane_live, step, schedule->end_sigma,
+                           f->stop_threshold);
+        f->forget_posteriors();  // sigma2 is part of the state the memo is keyed by
+    }
+    return check_launch(ctx);
+}
+
 }  // namespace
 
 extern "C" {
@@ -533,20 +616,80 @@ int gingr_fitter_set_pairs_plane_async(gingr_fitter *f, const gingr_plane_params
 int gingr_fitter_update_plane_async(gingr_fitter *f, const gingr_plane_params *p, const gingr_icp_params *schedule, int32_t n_iterations) {
     if (!f) return GINGR_ERR_BAD_ARGUMENT;
     GINGR_TRY(plane_check(f, p, "update_plane_async"));
+    return plane_loop(f, schedule, n_iterations, "update_plane_async", [&] { return plane_refresh(f, *p); });
+}
+
+int gingr_fitter_set_target_normals(gingr_fitter *f, const double *normals) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
     gingr_ctx *ctx = f->ctx;
-    if (n_iterations < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "update_plane_async: n_iterations < 1");
-    if (!schedule || schedule->max_iterations < 1)
-        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "update_plane_async: the schedule needs max_iterations >= 1");
-    const double step = (schedule->initial_sigma - schedule->end_sigma) / (double)schedule->max_iterations;  // ICP.scala:65
-    const Correspondence pairs = abi_correspondence(3, nullptr, nullptr);
-    for (int32_t it = 0; it < n_iterations; ++it) {
-        GINGR_TRY(plane_refresh(f, *p));
-        GINGR_TRY(fitter_update(f, pairs, 1));
-        hipLaunchKernelGGL(plane_schedule_kernel, dim3(1), dim3(1), 0, ctx->stream, f->st, f->plane_live, step, schedule->end_sigma,
-                           f->stop_threshold);
-        f->forget_posteriors();  // sigma2 is part of the state the memo is keyed by
+    if (!normals) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_target_normals: null argument");
+    if (!f->target || !f->aos) return gingr_set_error(ctx, GINGR_ERR_STATE, "set_target_normals: no target set");
+    const int64_t N = f->N;
+    std::vector<double> unit((size_t)3 * N);
+    for (int64_t j = 0; j < N; ++j) {
+        const double x = normals[3 * j], y = normals[3 * j + 1], z = normals[3 * j + 2];
+        if (!(fabs(x) <= kDblMax && fabs(y) <= kDblMax && fabs(z) <= kDblMax))
+            return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "set_target_normals: normal %lld is not finite", (long long)j);
+        const double big = std::max(fabs(x), std::max(fabs(y), fabs(z)));  // (scaled: no overflow, no underflow of the squares)
+        double ux = 0.0, uy = 0.0, uz = 0.0;
+        if (big > 0.0) {
+            const double n2 = (x * x + y * y) + z * z;
+            if (fabs(n2 - 1.0) <= 0x1p-48) {  // already unit to rounding: taken as it is
+                ux = x, uy = y, uz = z;
+            } else {
+                const double sx = x / big, sy = y / big, sz = z / big, len = sqrt((sx * sx + sy * sy) + sz * sz);
+                ux = sx / len, uy = sy / len, uz = sz / len;
+            }
+        }
+        unit[(size_t)3 * j] = ux, unit[(size_t)3 * j + 1] = uy, unit[(size_t)3 * j + 2] = uz;
     }
-    return check_launch(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (an update in flight reads the normals and the staging buffer)
+    f->forget_posteriors();
+    if (!f->tnormals) GINGR_TRY(dev_alloc(ctx, &f->tnormals, (size_t)3 * N));
+    return upload_cloud(ctx, reinterpret_cast<double *>(f->aos), unit.data(), N, f->tnormals, f->tperm);
+}
+
+int gingr_fitter_estimate_target_normals(gingr_fitter *f, int32_t k, const double *viewpoint, gingr_cloud_knn_info *info) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    if (!f->target) return gingr_set_error(ctx, GINGR_ERR_STATE, "estimate_target_normals: no target set");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (an update in flight reads the normals)
+    f->forget_posteriors();
+    const int64_t N = f->N;
+    DevBuf fresh;  // (a refused call leaves the normals the fitter holds as they are)
+    HIP_TRY(ctx, fresh.alloc((size_t)3 * N * sizeof(double)));
+    GINGR_TRY(cloud_normals_device(ctx, cloud_of(f->target, N), f->tperm, k, viewpoint, fresh.as<double>(), 1, N, nullptr, info,
+                                   "estimate_target_normals"));
+    dev_free(f->tnormals);
+    f->tnormals = fresh.as<double>();
+    fresh.p = nullptr, fresh.bytes = 0;  // (the fitter owns it now)
+    return GINGR_OK;
+}
+
+int gingr_fitter_get_target_normals(gingr_fitter *f, double *normals) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    if (!normals) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "get_target_normals: null argument");
+    if (!f->tnormals) return gingr_set_error(ctx, GINGR_ERR_STATE, "get_target_normals: no target normals");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf stage;
+    HIP_TRY(ctx, stage.alloc((size_t)3 * f->N * sizeof(double)));
+    return download_cloud(ctx, stage.as<double>(), f->tnormals, f->N, normals, f->tperm);
+}
+
+int gingr_fitter_set_pairs_plane_cloud_async(gingr_fitter *f, const gingr_plane_cloud_params *p) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    GINGR_TRY(plane_cloud_check(f, p, "set_pairs_plane_cloud_async"));
+    return plane_cloud_refresh(f, *p);
+}
+
+int gingr_fitter_update_plane_cloud_async(gingr_fitter *f, const gingr_plane_cloud_params *p, const gingr_icp_params *schedule,
+                                          int32_t n_iterations) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    GINGR_TRY(plane_cloud_check(f, p, "update_plane_cloud_async"));
+    return plane_loop(f, schedule, n_iterations, "update_plane_cloud_async", [&] { return plane_cloud_refresh(f, *p); });
 }
 
 }  // extern "C"

@@ -658,6 +658,11 @@ void fitter_surface_scan(gingr_fitter *f) {
     f->corr_stale = false;
 }
 
+void fitter_cloud_scan(gingr_fitter *f) {
+    phase0_nearest_vertex(f, cloud_of(f->fit, f->m->M), cloud_of(f->target, f->N));
+    f->corr_stale = false;
+}
+
 // The posterior inputs of the current state -- correspondences, Gram, right-hand side -- for a query that leaves the state as it is:
 // phases 0 and 1, which may bring a parked memo slot back (allow_alt)
 int fitter_posterior_inputs(gingr_fitter *f, const Correspondence &c) {

@@ -845,49 +845,108 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
 
     The update itself is the fitter's pairs flavour, so the sampled update, logTransitionProbability, posteriorCovariance and
     posteriorModel are its queries; each refreshes the planes from the state it is asked about first.  Needs both triangulations
-    (model.cells and targetCells).  There is no fused Metropolis-Hastings step: enableFusedSteps keeps the call-by-call path."""
+    (model.cells and targetCells) -- or, against a target that is a point cloud (a depth or laser scan: no triangles), a normal per
+    target point: createInitialState(..., targetNormals=an (N, 3) array | "estimate").  There the observed point is the nearest target
+    point and n its normal (gingr_fitter_update_plane_cloud_async); "estimate" takes the normals from the PCA of each target point's
+    targetNeighbours nearest neighbours, on the device (Context.cloud_normals).  There is no fused Metropolis-Hastings step:
+    enableFusedSteps keeps the call-by-call path."""
     name = "PointToPlaneICP"
 
     def __init__(self, ctx: Context):
         super().__init__(ctx)
-        self._params_memo = None   # (config object, PlaneParams, IcpParams)
+        self._params_memo = None   # (config object, PlaneParams, PlaneCloudParams, IcpParams)
         self._planes = None        # (state, closest points, weights, precisions): what the device used for `state`
+        self._held_normals = None  # (model, target, normals, neighbours) behind the target normals the fitter holds
 
     def createInitialState(self, model: PointDistributionModel, target, config: PointToPlaneConfiguration,
                            transform: int = GlobalTranformationType.RigidTransforms, stepLength: float = 1.0,
                            landmarks: Optional[LandmarkCorrespondences] = None, initial_pose=None,
-                           targetCells: Optional[np.ndarray] = None) -> PointToPlaneRegistrationState:
-        if getattr(model, "cells", None) is None or targetCells is None:
-            raise ValueError("point-to-plane ICP needs the triangulations (model.cells and targetCells)")
+                           targetCells: Optional[np.ndarray] = None, targetNormals=None,
+                           targetNeighbours: int = 16) -> PointToPlaneRegistrationState:
+        """targetCells (with model.cells): the surface route.  targetCells None and targetNormals an (N, 3) array or "estimate": the
+        target is a point cloud with a normal per point; model.cells is not needed."""
+        if targetCells is not None or targetNormals is None:
+            if getattr(model, "cells", None) is None or targetCells is None:
+                raise ValueError("point-to-plane ICP needs the triangulations (model.cells and targetCells)")
+            targetNormals = None
         g = _initial_general(self.ctx, model, target, 1.0, transform, stepLength, landmarks, initial_pose, targetCells)
-        return self.initializeState(g, config)
+        return self.initializeState(g, config, targetNormals, targetNeighbours)
 
-    def initializeState(self, general: GeneralRegistrationState, config: PointToPlaneConfiguration) -> PointToPlaneRegistrationState:
-        if getattr(general.model, "cells", None) is None or general.targetCells is None:
-            raise ValueError("point-to-plane ICP needs the triangulations (model.cells and targetCells)")
+    def initializeState(self, general: GeneralRegistrationState, config: PointToPlaneConfiguration, targetNormals=None,
+                        targetNeighbours: int = 16) -> PointToPlaneRegistrationState:
+        if targetNormals is None:
+            if getattr(general.model, "cells", None) is None or general.targetCells is None:
+                raise ValueError("point-to-plane ICP needs the triangulations (model.cells and targetCells)")
+        else:
+            if config.reject:
+                raise ValueError("reject=True needs the triangulations: the three rejection rules of the surface ICP do not apply to a "
+                                 "point-cloud target (maxDistance does)")
+            if not isinstance(targetNormals, str):
+                targetNormals = f64(targetNormals)
+                if targetNormals.shape != np.shape(general.target):
+                    raise ValueError(f"targetNormals of shape {targetNormals.shape} for a target of shape {np.shape(general.target)}")
+            elif targetNormals != "estimate":
+                raise ValueError(f"targetNormals: {targetNormals!r}; need an (N, 3) array or \"estimate\"")
         if not (np.isfinite(config.tangentOverNormal) and config.tangentOverNormal >= 1.0):
             raise ValueError(f"tangentOverNormal: {config.tangentOverNormal!r}; need a finite ratio >= 1")
-        return PointToPlaneRegistrationState(general.updateSigma2(float(config.initialSigma)), config)
+        return PointToPlaneRegistrationState(general.updateSigma2(float(config.initialSigma)), config, targetNormals, int(targetNeighbours))
 
     def _params(self, config: PointToPlaneConfiguration):
         memo = self._params_memo
         if memo is None or memo[0] is not config:
             memo = (config, nat.PlaneParams(float(config.tangentOverNormal), 1 if config.reject else 0),
+                    nat.PlaneCloudParams(float(config.tangentOverNormal), float(config.maxDistance or 0.0)),
                     nat.IcpParams(float(config.initialSigma), float(config.endSigma), int(config.maxIterations)))
             self._params_memo = memo
-        return memo[1], memo[2]
+        return memo[1:]
 
     def _correspondence(self, state: PointToPlaneRegistrationState):
         return nat.FLAVOUR_PAIRS, None
 
+    def _release(self):
+        super()._release()
+        self._held_normals = None  # (the normals went with the fitter)
+
+    def _push_normals(self, state: PointToPlaneRegistrationState):
+        """the target normals of a point-cloud state onto the fitter, once per (model, target, normals)"""
+        want = (self._bound_model, self._bound_target, state.targetNormals, state.targetNeighbours)
+        held = self._held_normals
+        if held is not None and all(a is b for a, b in zip(held[:3], want[:3])) and held[3] == want[3]:
+            return
+        if isinstance(state.targetNormals, str):
+            _check(self.ctx.handle, self._lib.gingr_fitter_estimate_target_normals(self._fitter, int(state.targetNeighbours), None, None),
+                   "gingr_fitter_estimate_target_normals")
+        else:
+            _check(self.ctx.handle, self._lib.gingr_fitter_set_target_normals(self._fitter, dptr(state.targetNormals)),
+                   "gingr_fitter_set_target_normals")
+        self._held_normals = want
+
+    def targetNormals(self, state: PointToPlaneRegistrationState) -> np.ndarray:
+        """(N, 3): the unit (or zero) normals per target point the device uses for a point-cloud state"""
+        self._ensure_device_state(state)
+        self._push_normals(state)
+        out = np.empty((np.shape(state.general.target)[0], 3))
+        _check(self.ctx.handle, self._lib.gingr_fitter_get_target_normals(self._fitter, dptr(out)), "gingr_fitter_get_target_normals")
+        return out
+
     def _prepare_native(self, state: PointToPlaneRegistrationState):
         # the queries of the pairs flavour read the planes as they stand: make them the ones of the state the device holds
-        pp, _ = self._params(state.config)
+        pp, pc, _ = self._params(state.config)
+        if state.targetNormals is not None:
+            self._push_normals(state)
+            _check(self.ctx.handle, self._lib.gingr_fitter_set_pairs_plane_cloud_async(self._fitter, ctypes.byref(pc)),
+                   "gingr_fitter_set_pairs_plane_cloud_async")
+            return
         _check(self.ctx.handle, self._lib.gingr_fitter_set_pairs_plane_async(self._fitter, ctypes.byref(pp)),
                "gingr_fitter_set_pairs_plane_async")
 
     def _native_update(self, current: PointToPlaneRegistrationState, n: int):
-        pp, ip = self._params(current.config)
+        pp, pc, ip = self._params(current.config)
+        if current.targetNormals is not None:
+            self._push_normals(current)
+            _check(self.ctx.handle, self._lib.gingr_fitter_update_plane_cloud_async(self._fitter, ctypes.byref(pc), ctypes.byref(ip), int(n)),
+                   "gingr_fitter_update_plane_cloud_async")
+            return
         _check(self.ctx.handle, self._lib.gingr_fitter_update_plane_async(self._fitter, ctypes.byref(pp), ctypes.byref(ip), int(n)),
                "gingr_fitter_update_plane_async")
 
@@ -917,15 +976,23 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
             self._prepare_native(state)
             M = state.general.model.numberOfPoints
             cp, w, obs, prec = np.empty((M, 3)), np.empty(M), np.empty((M, 3)), np.empty((M, 6))
-            _check(self.ctx.handle, self._lib.gingr_fitter_get_surface_correspondence(self._fitter, dptr(cp), dptr(w)),
-                   "gingr_fitter_get_surface_correspondence")
+            if state.targetNormals is not None:    # the nearest target points, and who lies within maxDistance
+                idx, d2 = np.empty(M, dtype=np.int32), np.empty(M)
+                _check(self.ctx.handle, self._lib.gingr_fitter_get_icp_idx(self._fitter, iptr(idx), dptr(d2)), "gingr_fitter_get_icp_idx")
+                cp = f64(state.general.target)[idx]
+                far = float(state.config.maxDistance or 0.0)
+                w = np.where(d2 > far * far, 0.0, 1.0) if far > 0.0 else np.ones(M)
+            else:
+                _check(self.ctx.handle, self._lib.gingr_fitter_get_surface_correspondence(self._fitter, dptr(cp), dptr(w)),
+                       "gingr_fitter_get_surface_correspondence")
             _check(self.ctx.handle, self._lib.gingr_fitter_get_pair_precisions(self._fitter, dptr(obs), dptr(prec)),
                    "gingr_fitter_get_pair_precisions")
             self._planes = (state, cp, w, prec)
         return self._planes[1:]
 
     def surfaceCorrespondence(self, state) -> Tuple[np.ndarray, np.ndarray]:
-        """(closest surface points (M, 3), weights in {0, 1}) as the device used them for the state's fit"""
+        """(closest surface points (M, 3), weights in {0, 1}) as the device used them for the state's fit; against a point-cloud
+        target the nearest target points"""
         cp, w, _ = self._observed(state)
         return cp, w
 

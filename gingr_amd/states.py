@@ -193,7 +193,8 @@ class TemplateRegistrationState:
 @dataclasses.dataclass(frozen=True)
 class PointToPlaneConfiguration:
     """Point-to-plane ICP on the surfaces: ICP's sigma2 schedule (ICP.scala:65, :96-99) with a covariance per vertex that is sigma2 along
-    the target's face normal and tangentOverNormal * sigma2 across it.  reject: the three rejection rules of the surface ICP."""
+    the target's face normal and tangentOverNormal * sigma2 across it.  reject: the three rejection rules of the surface ICP.
+    maxDistance (against a point-cloud target only): a vertex farther than this from its nearest target point is not observed."""
     maxIterations: int = 100
     initialSigma: float = 100.0
     endSigma: float = 1.0
@@ -202,6 +203,7 @@ class PointToPlaneConfiguration:
     threshold: float = 1e-10
     converged: Callable = _never_converged
     useLandmarkCorrespondence: bool = True
+    maxDistance: Optional[float] = None
 
     @property
     def sigmaStep(self) -> float:
@@ -212,6 +214,10 @@ class PointToPlaneConfiguration:
 class PointToPlaneRegistrationState:
     general: GeneralRegistrationState
     config: PointToPlaneConfiguration
+    # against a point-cloud target: an (N, 3) array of normals, one per target point, or "estimate" (from targetNeighbours nearest
+    # neighbours on the device); None: the surface route, normals of the target's triangles
+    targetNormals: object = None
+    targetNeighbours: int = 16
 
     def updateGeneral(self, update: GeneralRegistrationState) -> "PointToPlaneRegistrationState":
         return dataclasses.replace(self, general=update)

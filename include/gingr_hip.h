@@ -580,6 +580,63 @@ int gingr_fitter_set_pairs_plane_async(gingr_fitter *f, const gingr_plane_params
 int gingr_fitter_update_plane_async(gingr_fitter *f, const gingr_plane_params *p, const gingr_icp_params *schedule,
                                     int32_t n_iterations);
 
+/* ---- k nearest neighbours of a cloud within itself, and the normals of those neighbourhoods (cloud_knn.hip) -----------------
+ * gingr_cloud_knn: for every point j of xyz [N][3] the k points of the cloud with the smallest (d2, index), d2 = dx*dx + dy*dy + dz*dz
+ * of x_i - x_j with separately rounded products and sums (the bits of that expression in float64 on a CPU), ties to the lowest index.
+ * idx [N][k] / d2 [N][k] (nullable): row j sorted ascending by (d2, index).  The point itself is a candidate: the first entry is j, or
+ * a lower-indexed duplicate of it.  3 <= k <= 64 and k <= N (N <= 2^27), else GINGR_ERR_BAD_ARGUMENT; a non-finite coordinate is
+ * GINGR_ERR_NONFINITE and nothing is computed.  A uniform grid over the cloud is built on the device per call; a query the grid cannot
+ * certify (a far outlier, a crowded row of cells) is answered by a scan of the whole cloud -- the same lists either way.  info
+ * (nullable): the grid's cell size and dimensions and the number of queries that took the scan.  Two calls give the same bits.
+ * Synchronises.
+ * gingr_cloud_normals: a normal per point from its k-neighbourhood -- THIS PACKAGE'S DEFINITION, not a toolkit's.  With the list of
+ * gingr_cloud_knn in its order: q_i = x_i - x_j (taken first: the result does not depend on where the cloud lies, up to rounding),
+ * m = sum q_i / k, C = sum (q_i - m)(q_i - m)^T / k in float64 in list order, lam0 <= lam1 <= lam2 its eigenvalues.  normals [N][3]:
+ * the unit eigenvector of lam0; the ZERO vector when lam1 - lam0 <= 2^-26 lam2 (coincident points, a line, an isotropic blob: the
+ * direction has no correct digit).  Sign: the component of largest magnitude is positive, the lowest axis on ties; with a viewpoint v
+ * [3] (nullable) the normal is turned so that n . (v - x_j) >= 0.  variation [N] (nullable): lam0 / (lam0 + lam1 + lam2), Pauly's surface
+ * variation, 0 on a plane and 0 when the trace is 0.  Arguments, errors and info as gingr_cloud_knn; a non-finite viewpoint is
+ * GINGR_ERR_NONFINITE.  Synchronises. */
+typedef struct gingr_cloud_knn_info {
+    double cell_size;  /* edge of a grid cell */
+    int32_t grid[3];   /* cells per axis */
+    int32_t flagged;   /* queries the grid did not certify: answered by the scan of the whole cloud */
+} gingr_cloud_knn_info;
+int gingr_cloud_knn(gingr_ctx *ctx, int64_t N, const double *xyz, int32_t k, int32_t *idx, double *d2, gingr_cloud_knn_info *info);
+int gingr_cloud_normals(gingr_ctx *ctx, int64_t N, const double *xyz, int32_t k, const double *viewpoint, double *normals, double *variation,
+                        gingr_cloud_knn_info *info);
+
+/* ---- point-to-plane ICP against a point cloud: a normal per target point instead of target triangles ------------------------
+ * The planes of gingr_fitter_set_pairs_plane_async with the nearest target POINT in place of the closest surface point and that
+ * point's stored normal in place of the face normal: xbar_i = the nearest target point of vertex i bit for bit (the forward search of
+ * gingr_fitter_update_icp_async, grid and warm start as they stand), Lambda_i = (1 / v_t) I + (1 / v_n - 1 / v_t) n n^T by the same
+ * arithmetic, a zero normal gives (1 / v_t) I, tangent_over_normal = 1 gives (1 / sigma2) I exactly: point-to-point ICP against the
+ * cloud.  max_distance > 0: a vertex whose squared distance to its nearest target point exceeds max_distance * max_distance is not
+ * observed (Lambda_i = 0, xbar_i = 0).  No meshes are needed.
+ * Target normals, [N][3] in the order of the target set last; a new gingr_fitter_set_target drops them.
+ *   gingr_fitter_set_target_normals       the caller's (a scanner's own): each is normalised on upload -- one whose squared length is
+ *                                         within 2^-48 of 1 is taken as it is, zero stays zero; non-finite: GINGR_ERR_NONFINITE
+ *   gingr_fitter_estimate_target_normals  gingr_cloud_normals (k, viewpoint, info) on the target as it lies on the device: no download,
+ *                                         no upload, the same bits
+ *   gingr_fitter_get_target_normals       what the fitter holds (GINGR_ERR_STATE without normals)
+ * gingr_fitter_set_pairs_plane_cloud_async / gingr_fitter_update_plane_cloud_async: as the two surface entry points above -- the result
+ * becomes the dense list, the loop applies ICP's schedule on the device, n iterations in one call give the bits of n calls of one, a
+ * landmark overrides a vertex.  gingr_fitter_get_icp_idx reports the matches that were used, gingr_fitter_get_pair_precisions the planes;
+ * the sampled update, transition density, posterior covariance and posterior model are the _pairs queries.
+ * Refused with nothing changed -- GINGR_ERR_STATE: no target or state set; no target normals; a row shard (single shard, forward
+ * direction only).  GINGR_ERR_BAD_ARGUMENT: null params; tangent_over_normal < 1 or non-finite; max_distance NaN; n_iterations < 1;
+ * schedule null or max_iterations < 1. */
+typedef struct gingr_plane_cloud_params {
+    double tangent_over_normal;  /* >= 1, finite; 1 = point-to-point against the cloud */
+    double max_distance;         /* <= 0: no rejection; else a vertex farther than this from its nearest target point is not observed */
+} gingr_plane_cloud_params;
+int gingr_fitter_set_target_normals(gingr_fitter *f, const double *normals);
+int gingr_fitter_estimate_target_normals(gingr_fitter *f, int32_t k, const double *viewpoint, gingr_cloud_knn_info *info);
+int gingr_fitter_get_target_normals(gingr_fitter *f, double *normals);
+int gingr_fitter_set_pairs_plane_cloud_async(gingr_fitter *f, const gingr_plane_cloud_params *p);
+int gingr_fitter_update_plane_cloud_async(gingr_fitter *f, const gingr_plane_cloud_params *p, const gingr_icp_params *schedule,
+                                          int32_t n_iterations);
+
 /* ---- a PCA model from shapes in correspondence ----------------------------------------------------------------------------
  * What DataCollection.gpa(...) followed by PointDistributionModel.createUsingPCA(...) gives a scalismo user, built on the device: a
  * new, finalized, single-shard model on this context.  ref_xyz [3 M]: the reference; shapes_xyz [n_shapes][3 M]: the shapes, point
