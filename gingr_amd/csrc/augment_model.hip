@@ -8,7 +8,10 @@
 // The two models order their rows by the Morton code of their own ref + mean: a vertex sits at different rows of the two bases, and
 // at a third one of the result.  Every sum is taken in a fixed order (slab partials combined by one thread each, no float atomics):
 // two builds of the same input give the same bits.
+// The shifted eigen step, the factor rows and the moment trace are the shared tail of posterior_model.hip (gp.h), the choice of k is
+// spectrum_plan.h, the complete-model check is model.hip's (gp.h).
 #include "basis_rotate.h"
+#include "spectrum_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -163,7 +166,7 @@ __global__ __launch_bounds__(64 * kRotWaves) void basis_rotate2_kernel(const dou
     }
 }
 
-// ---- the r x r glue
+// ---- the r x r step
 // Gs [n][n], n = ra + rb: [[S_a, C], [C^T, S_b]] + shift on the diagonal (S_a: row stride rpa; C [rpa][rpb]; S_b: row stride rpb).  Both
 // off-diagonal blocks read the same entry of C: Gs is symmetric to the bit.  *bad is set when an entry is not finite.
 __global__ __launch_bounds__(256) void augment_gram_kernel(const double *__restrict__ Sa, int ra, int rpa, const double *__restrict__ C,
@@ -180,15 +183,6 @@ __global__ __launch_bounds__(256) void augment_gram_kernel(const double *__restr
         v = j < ra ? C[(int64_t)j * rpb + (i - ra)] : Sb[(int64_t)(i - ra) * rpb + (j - ra)];
     if (!isfinite(v)) atomicOr(bad, 1);
     Gs[e] = v + (i == j ? shift : 0.0);
-}
-
-// T [rsp][kp]: T[i][j] = V[(row0 + i) n + j] (component row0 + i of eigenvector j) for i < rs, j < k, zero elsewhere: one row block of V[:, :k]
-__global__ __launch_bounds__(256) void augment_factor_kernel(const double *__restrict__ V, int n, int row0, int rs, int rsp, int k, int kp,
-                                                             double *__restrict__ T) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)rsp * kp) return;
-    const int i = (int)(e / kp), j = (int)(e - (int64_t)i * kp);
-    T[e] = (i < rs && j < k) ? V[(int64_t)(row0 + i) * n + j] : 0.0;
 }
 
 }  // namespace
@@ -226,23 +220,6 @@ void launch_basis_rotate2(gingr_ctx *ctx, const gingr_model *a, const double *Ta
     TimerScope ts(ctx, 12);
     hipLaunchKernelGGL(basis_rotate2_kernel, dim3((unsigned)blocks), dim3(64 * kRotWaves), 0, ctx->stream, a->Q0, (int)a->rp, a->iperm, Ta, b->Q0,
                        (int)b->rp, b->iperm, Tb, dst->M, (int)dst->rp, dst->perm, nchunks, dst->Q0);
-}
-
-// the trace of the leading r x r block of a moment (row stride rp), summed on the host in ascending order
-int moment_trace(gingr_ctx *ctx, const double *S, int32_t r, int32_t rp, double *trace) {
-    std::vector<double> diag((size_t)r);
-    HIP_TRY(ctx, hipMemcpy2D(diag.data(), sizeof(double), S, (size_t)(rp + 1) * sizeof(double), sizeof(double), (size_t)r, hipMemcpyDeviceToHost));
-    double t = 0.0;
-    for (int32_t j = 0; j < r; ++j) t += diag[(size_t)j];
-    *trace = t;
-    return GINGR_OK;
-}
-
-const char *complete_model_fault(const gingr_ctx *ctx, const gingr_model *m) {
-    if (m->ctx != ctx) return "belongs to another context";
-    if (m->row_begin != 0 || m->row_end != m->M_total || m->M != m->M_total) return "is a row shard";
-    if (!m->finalized) return "is not finalized";
-    return nullptr;
 }
 
 }  // namespace
@@ -323,29 +300,19 @@ int gingr_model_augment(gingr_ctx *ctx, const gingr_model *a, const gingr_model 
     if (bad) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite Gram matrix of the two bases", who);
 
     // ---- 3. G = V diag(lambda) V^T, lambda descending
-    GINGR_TRY(launch_jacobi_eig(ctx, Gs.as<double>(), n, n, evals.as<double>(), V.as<double>(), true));
-    std::vector<double> lam((size_t)n);
-    HIP_TRY(ctx, hipMemcpyAsync(lam.data(), evals.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int j = 0; j < n; ++j) {
-        if (!std::isfinite(lam[(size_t)j])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite eigenvalue", who);
-        lam[(size_t)j] = std::max(lam[(size_t)j] - shift, 0.0);  // (a null direction: rounding around zero)
-    }
-    const int kmax = std::min(n, max_rank > 0 ? std::min<int>(max_rank, 512) : 512);
-    int k = 0;
-    while (k < kmax && lam[(size_t)k] > relative_tolerance * lam[0] && lam[(size_t)k] > 0.0) ++k;
+    std::vector<double> lam;
+    GINGR_TRY(eig_descending_to_host(ctx, Gs.as<double>(), n, n, shift, who, "eigenvalue", evals.as<double>(), V.as<double>(), lam));
+    // (lam is un-shifted already: the cut subtracts nothing more)
+    const spectrum_plan::Cut cut = spectrum_plan::cut(lam.data(), n, 0.0, n, max_rank, relative_tolerance);
+    const int k = cut.k;
     if (k < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: no eigenvalue of the summed covariance passes the cutoff (rank 0)", who);
-    double kept = 0.0;
-    for (int j = 0; j < k; ++j) kept += lam[(size_t)j];
 
     // ---- 4. Q0 = Q_a V[:ra, :k] + Q_b V[ra:, :k] into the model proper
     const int kp = (int)round_up(k, 16);
     HIP_TRY(ctx, Ta.alloc((size_t)rpa * kp * sizeof(double)));
     HIP_TRY(ctx, Tb.alloc((size_t)rpb * kp * sizeof(double)));
-    hipLaunchKernelGGL(augment_factor_kernel, dim3((unsigned)ceil_div((int64_t)rpa * kp, 256)), dim3(256), 0, ctx->stream, V.as<double>(), n, 0, (int)ra,
-                       (int)rpa, k, kp, Ta.as<double>());
-    hipLaunchKernelGGL(augment_factor_kernel, dim3((unsigned)ceil_div((int64_t)rpb * kp, 256)), dim3(256), 0, ctx->stream, V.as<double>(), n, (int)ra,
-                       (int)rb, (int)rpb, k, kp, Tb.as<double>());
+    launch_factor_rows(ctx, V.as<double>(), n, 0, (int)ra, (int)rpa, k, kp, Ta.as<double>());
+    launch_factor_rows(ctx, V.as<double>(), n, (int)ra, (int)rb, (int)rpb, k, kp, Tb.as<double>());
     GINGR_TRY(check_launch(ctx));
     auto fill = [&](gingr_model *nm) -> int {
         launch_basis_rotate2(ctx, a, Ta.as<double>(), b, Tb.as<double>(), nm);
@@ -356,7 +323,7 @@ int gingr_model_augment(gingr_ctx *ctx, const gingr_model *a, const gingr_model 
         info->columns = n;
         info->rank = k;
         info->total_variance = trace;
-        info->kept_variance = kept;
+        info->kept_variance = cut.kept;
     }
     return GINGR_OK;
 }

@@ -161,6 +161,17 @@ void launch_interp_pack(gingr_ctx *ctx, const double *Qs, int32_t rp, const int3
 int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const double *ref, const double *mean,
                       const double *variance, int64_t row_begin, int64_t row_end,
                       const std::function<int(gingr_model *)> &fill_basis, gingr_model **out, bool finalize = true);
+// model.hip: what the builders of a model from models or shapes share in front of model_create_impl.
+// Why m is no complete, finalized model of ctx ("belongs to another context", "is a row shard", "is not finalized"), or nullptr: it is
+const char *complete_model_fault(const gingr_ctx *ctx, const gingr_model *m);
+// GINGR_ERR_NONFINITE naming the first of the n items of `per` doubles that holds a value that is not finite (`what`: the item's noun)
+int check_finite(gingr_ctx *ctx, const double *x, int64_t per, int64_t n, const char *who, const char *what);
+// n shapes of M points (host, interleaved) through the staging buffer `stage`, allocated here with at most 64 MB, a few shapes per
+// transfer: fn(cnt, i0) launches on ctx->stream what takes the shapes [i0, i0 + cnt) out of it.  The caller synchronises before it
+// frees the buffer.
+int for_each_shape_stage(gingr_ctx *ctx, int64_t M, int n, const double *shapes, DevBuf &stage, const std::function<int(int, int)> &fn);
+// reference and mean displacement of a model on the host, interleaved in the caller's point order (model_create_impl takes them there)
+int download_ref_mean(gingr_ctx *ctx, const gingr_model *m, std::vector<double> &href, std::vector<double> &hmean);
 
 // fitter.hip hooks for the device group (group.hip): where phases 0 / 1 write this shard's partial exchange segments, and where
 // the gather step of a sharded surface update writes the shard's contribution to the full fit (nullptr: in place)
@@ -394,6 +405,16 @@ int sym_eig(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ld
             double *const *Vs, bool blocks = false);
 // the same for one matrix
 int launch_jacobi_eig(gingr_ctx *ctx, const double *G, int32_t ldg, int32_t n, double *evals, double *Vs, bool blocks = false);
+// posterior_model.hip: the r x r tail of a derived model.  launch_jacobi_eig(..., true) on Gs = G + shift I, the eigenvalues on the host
+// (one synchronisation), GINGR_ERR_NONFINITE "<who>: non-finite <what>" when one is not finite, lam = max(evals - shift, 0)
+// (spectrum_plan.h) descending; evals [n] and V [n * n] stay on the device
+int eig_descending_to_host(gingr_ctx *ctx, const double *Gs, int32_t ld, int32_t n, double shift, const char *who, const char *what, double *evals,
+                           double *V, std::vector<double> &lam);
+// T [rsp][kp] on ctx->stream: T[i][j] = V[(row0 + i) n + j] (component row0 + i of eigenvector j) for i < rs, j < k, zero elsewhere -- a row
+// block of V[:, :k] as the factor of launch_basis_rotate
+void launch_factor_rows(gingr_ctx *ctx, const double *V, int n, int row0, int rs, int rsp, int k, int kp, double *T);
+// the trace of the leading r x r block of a moment (row stride rp), summed on the host in ascending order
+int moment_trace(gingr_ctx *ctx, const double *S, int32_t r, int32_t rp, double *trace);
 // eig.hip: one-sided register Jacobi on the Cholesky factor, n <= kSymEigColsMaxN, up to three problems per launch (see sym_eig)
 constexpr int kSymEigColsMaxN = 192;
 int64_t sym_eig_cols_work_doubles(int32_t n);

@@ -6,11 +6,13 @@
 // coordinate) entries (gpmm.hip: pc_step_kernel<Tapered> under gpmm_factor::Factor's driver -- the GPMM builder's pivot, tie and stop
 // rules) and re-diagonalised by the tail of the generic GPMM build (gpmm_factor::generic_tail).  The factor works in the caller's entry
 // order with lanes along the entries, so the basis is gathered and transposed once per call: Qt[q][3i+d] = Q0[3 iperm[i] + d][q].
-// Only reference and mean pass through the host.  Every sum has a fixed order: two calls give the same bits.
+// Only reference and mean pass through the host (download_ref_mean, model.hip).  The kept components are the cut of spectrum_plan.h, the
+// complete-model check is model.hip's (gp.h).  Every sum has a fixed order: two calls give the same bits.
 #include "gp.h"
 
 #include "gpmm_factor.h"
 #include "gpmm_plan.h"
+#include "spectrum_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -53,10 +55,8 @@ int gingr_model_localize(gingr_ctx *ctx, const gingr_model *model, double sigma,
     if (!ctx || !out) return GINGR_ERR_BAD_ARGUMENT;
     const char *who = "model_localize";
     if (!model) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: null argument", who);
-    if (model->ctx != ctx) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: the model belongs to another context", who);
-    if (model->row_begin != 0 || model->row_end != model->M_total || model->M != model->M_total)
-        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: the model is a row shard (need a complete model)", who);
-    if (!model->finalized) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: the model is not finalized", who);
+    if (const char *fault = complete_model_fault(ctx, model))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: the model %s (need a complete, finalized model of this context)", who, fault);
     if (!(sigma > 0.0) || !std::isfinite(sigma)) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: sigma must be positive and finite", who);
     if (!(relative_tolerance >= 0.0) || !(relative_tolerance < 1.0))
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: relative_tolerance must be in [0, 1)", who);
@@ -67,8 +67,8 @@ int gingr_model_localize(gingr_ctx *ctx, const gingr_model *model, double sigma,
 
     // ---- 1. reference and mean pass through the host once (model_create_impl takes them there); the reference goes back as the planes
     // of the caller's order that the factor's taper reads
-    std::vector<double> href((size_t)n), hmean((size_t)n);
-    GINGR_TRY(gingr_model_download(ctx, model, href.data(), hmean.data(), nullptr, nullptr));
+    std::vector<double> href, hmean;
+    GINGR_TRY(download_ref_mean(ctx, model, href, hmean));
     DevBuf aos, soa, qt;
     HIP_TRY(ctx, aos.alloc((size_t)n * sizeof(double)));
     HIP_TRY(ctx, soa.alloc((size_t)n * sizeof(double)));
@@ -98,18 +98,15 @@ int gingr_model_localize(gingr_ctx *ctx, const gingr_model *model, double sigma,
     const bool reached = gpmm_plan::below_tolerance(residual, trace, relative_tolerance) || cols < cap || (int64_t)cols == n;
 
     // ---- 4. L^T L = V diag(lambda') V^T, Q' = L V; the leading components above the noise floor of the Gram route
-    const int32_t kmax = std::min<int32_t>(cols, max_rank > 0 ? std::min<int32_t>(max_rank, 512) : 512);
+    // (spectrum_plan.h: no shift, the noise floor of the Gram route as the tolerance)
     double kept = 0.0;
     std::vector<double> lam;
     auto choose = [&](std::vector<double> &ev, int32_t *keep) -> int {
-        for (double v : ev)
-            if (!std::isfinite(v)) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite eigenvalue", who);
-        for (double &v : ev) v = v > 0.0 ? v : 0.0;
-        int32_t k = 0;
-        while (k < kmax && ev[(size_t)k] > 1e-12 * ev[0] && ev[(size_t)k] > 0.0) ++k;
-        if (k < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: no eigenvalue of the tapered covariance passes the cutoff (rank 0)", who);
-        for (int32_t j = 0; j < k; ++j) kept += ev[(size_t)j];
-        *keep = k;
+        const spectrum_plan::Cut cut = spectrum_plan::cut(ev.data(), (int)ev.size(), 0.0, cols, max_rank, 1e-12);
+        if (cut.first_nonfinite >= 0) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite eigenvalue", who);
+        if (cut.k < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: no eigenvalue of the tapered covariance passes the cutoff (rank 0)", who);
+        kept = cut.kept;
+        *keep = cut.k;
         return GINGR_OK;
     };
     GINGR_TRY(gpmm_factor::generic_tail(ctx, fg, M, href.data(), hmean.data(), 0, M, lam, choose, out));

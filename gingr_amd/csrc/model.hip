@@ -1,5 +1,6 @@
 // Model upload, finalize, download, truncation and re-sampling on a new reference, and the stateless model operators (instance,
-// coefficients, posterior mean), which borrow a short-lived fitter (C ABI in include/gingr_hip.h).
+// coefficients, posterior mean), which borrow a short-lived fitter (C ABI in include/gingr_hip.h).  Behind model_create_impl: the checks
+// and transfers the derived-model builders share (complete_model_fault, check_finite, for_each_shape_stage, download_ref_mean; gp.h).
 #include "fitter.h"
 
 #include <algorithm>
@@ -311,6 +312,38 @@ int model_create_impl(gingr_ctx *ctx, int64_t M_total, int32_t rank, const doubl
     return GINGR_OK;
 }
 
+// ---- what the builders of a model from models or shapes share in front of model_create_impl (declared in gp.h)
+const char *complete_model_fault(const gingr_ctx *ctx, const gingr_model *m) {
+    if (m->ctx != ctx) return "belongs to another context";
+    if (m->row_begin != 0 || m->row_end != m->M_total || m->M != m->M_total) return "is a row shard";
+    if (!m->finalized) return "is not finalized";
+    return nullptr;
+}
+
+int check_finite(gingr_ctx *ctx, const double *x, int64_t per, int64_t n, const char *who, const char *what) {
+    for (int64_t e = 0; e < per * n; ++e)
+        if (!std::isfinite(x[e])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite value in %s %lld", who, what, (long long)(e / per));
+    return GINGR_OK;
+}
+
+int for_each_shape_stage(gingr_ctx *ctx, int64_t M, int n, const double *shapes, DevBuf &stage, const std::function<int(int, int)> &fn) {
+    const int per_stage = (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)8 << 20) / (3 * M)));  // <= 64 MB of staging
+    HIP_TRY(ctx, stage.alloc((size_t)per_stage * 3 * M * sizeof(double)));
+    for (int i0 = 0; i0 < n; i0 += per_stage) {
+        const int cnt = std::min(per_stage, n - i0);
+        HIP_TRY(ctx, hipMemcpyAsync(stage.p, shapes + (size_t)i0 * 3 * M, (size_t)cnt * 3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        GINGR_TRY(fn(cnt, i0));
+        GINGR_TRY(check_launch(ctx));
+    }
+    return GINGR_OK;
+}
+
+int download_ref_mean(gingr_ctx *ctx, const gingr_model *m, std::vector<double> &href, std::vector<double> &hmean) {
+    href.resize((size_t)3 * m->M);
+    hmean.resize((size_t)3 * m->M);
+    return gingr_model_download(ctx, m, href.data(), hmean.data(), nullptr, nullptr);
+}
+
 extern "C" {
 
 int gingr_model_upload(gingr_ctx *ctx, int64_t M_total, int32_t rank, const double *ref, const double *mean,
@@ -615,16 +648,15 @@ int gingr_model_truncate(gingr_ctx *ctx, const gingr_model *src, int32_t k, ging
     if (!ctx || !out) return GINGR_ERR_BAD_ARGUMENT;
     *out = nullptr;
     if (!src) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: no model");
-    if (src->ctx != ctx || !src->finalized)
-        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: the source must be a finalized model of this context");
-    if (src->row_begin != 0 || src->row_end != src->M_total)
-        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: the source is a row shard; truncate the complete model (or build the shard with keep_rank)");
+    if (const char *fault = complete_model_fault(ctx, src))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT,
+                               "model_truncate: the source %s; truncate a complete, finalized model of this context (or build the shard with keep_rank)", fault);
     if (k < 1 || k > src->r)
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "model_truncate: k = %d outside 1..%d (the model's rank)", (int)k, (int)src->r);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t M = src->M;
-    std::vector<double> href((size_t)3 * M), hmean((size_t)3 * M);
-    GINGR_TRY(gingr_model_download(ctx, src, href.data(), hmean.data(), nullptr, nullptr));
+    std::vector<double> href, hmean;
+    GINGR_TRY(download_ref_mean(ctx, src, href, hmean));
     auto fill = [&](gingr_model *m) -> int {
         // the same points and mean give the same row order (Morton order of ref + mean): rows are copied in place
         if (m->M != M || m->hperm != src->hperm) return gingr_set_error(ctx, GINGR_ERR_STATE, "model_truncate: row order differs from the source's");

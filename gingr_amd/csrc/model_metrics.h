@@ -11,11 +11,11 @@ struct RankList {
     int32_t k[model_metrics_plan::kMaxRanks];
 };
 
-// the argument checks of gingr_model_generalization / _specificity: a complete, finalized model of this context (GINGR_ERR_STATE
-// otherwise); 1 <= n_ranks <= 16 strictly increasing ranks within the model's; finite values (`what` names the item of `per` doubles)
+// the argument checks of gingr_model_generalization / _specificity: a complete, finalized model of this context (complete_model_fault,
+// gp.h, as GINGR_ERR_STATE for a shard or a model that is not finalized); 1 <= n_ranks <= 16 strictly increasing ranks within the
+// model's.  Finite values: check_finite (gp.h).
 int metrics_check_model(gingr_ctx *ctx, const gingr_model *m, const char *who);
 int metrics_check_ranks(gingr_ctx *ctx, const gingr_model *m, int32_t n_ranks, const int32_t *ranks, const char *who, RankList *out);
-int metrics_check_finite(gingr_ctx *ctx, const double *x, int64_t per, int64_t n, const char *who, const char *what);
 
 // P [3 M + 48][ldt] = ref + mean + Q0 T on ctx->stream, rows in the model's order (the slack rows are the caller's).  T: [rp][ldt],
 // ldt a multiple of 16.  Timing hook 20.

@@ -333,11 +333,8 @@ struct MetricsElem {  // S_tot / eps + I: BinvElem of gp.hip
 
 // ---- host side
 int metrics_check_model(gingr_ctx *ctx, const gingr_model *m, const char *who) {
-    if (m->ctx != ctx) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: the model belongs to another context", who);
-    if (m->row_begin != 0 || m->row_end != m->M_total || m->M != m->M_total)
-        return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: the model is a row shard; single-shard models only", who);
-    if (!m->finalized) return gingr_set_error(ctx, GINGR_ERR_STATE, "%s: the model is not finalized", who);
-    return GINGR_OK;
+    const char *fault = complete_model_fault(ctx, m);  // (a model of another context is a bad argument, the other two a state)
+    return !fault ? GINGR_OK : gingr_set_error(ctx, m->ctx != ctx ? GINGR_ERR_BAD_ARGUMENT : GINGR_ERR_STATE, "%s: the model %s", who, fault);
 }
 
 int metrics_check_ranks(gingr_ctx *ctx, const gingr_model *m, int32_t n_ranks, const int32_t *ranks, const char *who, RankList *out) {
@@ -357,12 +354,6 @@ int metrics_check_ranks(gingr_ctx *ctx, const gingr_model *m, int32_t n_ranks, c
     return GINGR_OK;
 }
 
-int metrics_check_finite(gingr_ctx *ctx, const double *x, int64_t per, int64_t n, const char *who, const char *what) {
-    for (int64_t e = 0; e < per * n; ++e)
-        if (!std::isfinite(x[e])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite value in %s %lld", who, what, (long long)(e / per));
-    return GINGR_OK;
-}
-
 // P [3 M + 48][ldt] = ref + mean + Q0 T on ctx->stream (the slack rows are the caller's)
 void launch_instances(gingr_ctx *ctx, const gingr_model *m, const double *T, int ldt, double *P) {
     const int nchunks = (int)ceil_div(ldt / 16, kRotChunkTiles);
@@ -378,21 +369,17 @@ void launch_sample_factor(gingr_ctx *ctx, const double *alphas, int cnt, int r, 
 }
 
 // n shapes (host, interleaved, caller's point order) as the columns [0, n) of D [3 M + 48][np], centred or as points; the padding
-// columns and the slack rows are zero.  A few shapes per transfer through one staging buffer of at most 64 MB.
+// columns and the slack rows are zero.  The shapes pass through the staging buffer of for_each_shape_stage (model.hip).
 int pack_shape_columns(gingr_ctx *ctx, int64_t M, const int32_t *perm, const double *ref, const double *mean, int n, const double *shapes, bool center,
                        DevBuf &D, int np) {
     DevBuf stage;
     HIP_TRY(ctx, D.alloc((size_t)mp::block_rows(M) * np * sizeof(double)));
     HIP_TRY(ctx, hipMemsetAsync(D.p, 0, (size_t)mp::block_rows(M) * np * sizeof(double), ctx->stream));
-    const int per_stage = (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)8 << 20) / (3 * M)));
-    HIP_TRY(ctx, stage.alloc((size_t)per_stage * 3 * M * sizeof(double)));
-    for (int i0 = 0; i0 < n; i0 += per_stage) {
-        const int cnt = std::min(per_stage, n - i0);
-        HIP_TRY(ctx, hipMemcpyAsync(stage.p, shapes + (size_t)i0 * 3 * M, (size_t)cnt * 3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    GINGR_TRY(for_each_shape_stage(ctx, M, n, shapes, stage, [&](int cnt, int i0) -> int {
         hipLaunchKernelGGL(shapes_pack_kernel, dim3((unsigned)ceil_div(M, kPackVerts), 3), dim3(256), 0, ctx->stream, stage.as<double>(), cnt, i0, np, M,
                            perm, ref, mean, center ? 1 : 0, D.as<double>());
-        GINGR_TRY(check_launch(ctx));
-    }
+        return GINGR_OK;
+    }));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffer leaves scope
     return GINGR_OK;
 }
@@ -467,7 +454,7 @@ int gingr_model_instances(gingr_ctx *ctx, const gingr_model *model, int64_t n, c
     if (n < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: n = %lld < 1", who, (long long)n);
     const int64_t M = model->M;
     const int32_t r = model->r, rp = model->rp;
-    GINGR_TRY(metrics_check_finite(ctx, alphas, r, n, who, "coefficient vector"));
+    GINGR_TRY(check_finite(ctx, alphas, r, n, who, "coefficient vector"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const mp::ColumnBlocks blocks = mp::column_blocks(n);
     const int ldmax = (int)blocks.padded(0);
@@ -510,7 +497,7 @@ int gingr_model_generalization(gingr_ctx *ctx, const gingr_model *model, int32_t
     GINGR_TRY(metrics_check_ranks(ctx, model, n_ranks, ranks, who, &rl));
     const int64_t M = model->M;
     const int32_t r = model->r, rp = model->rp;
-    GINGR_TRY(metrics_check_finite(ctx, shapes_xyz, 3 * M, n, who, "shape"));
+    GINGR_TRY(check_finite(ctx, shapes_xyz, 3 * M, n, who, "shape"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int np = (int)mp::padded_cols(n), ldt = n_ranks * np;
 
@@ -546,8 +533,8 @@ int gingr_model_specificity(gingr_ctx *ctx, const gingr_model *model, int32_t n_
     GINGR_TRY(metrics_check_ranks(ctx, model, n_ranks, ranks, who, &rl));
     const int64_t M = model->M;
     const int32_t r = model->r, rp = model->rp;
-    GINGR_TRY(metrics_check_finite(ctx, train_xyz, 3 * M, n_train, who, "training shape"));
-    GINGR_TRY(metrics_check_finite(ctx, alphas, r, n_samples, who, "coefficient vector"));
+    GINGR_TRY(check_finite(ctx, train_xyz, 3 * M, n_train, who, "training shape"));
+    GINGR_TRY(check_finite(ctx, alphas, r, n_samples, who, "coefficient vector"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int tp = (int)mp::padded_cols(n_train);
     const mp::ColumnBlocks blocks = mp::column_blocks(n_samples);

@@ -17,6 +17,7 @@
 #include "gp.h"
 #include "model_metrics.h"
 #include "pca_loo_plan.h"
+#include "spectrum_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(kFoldThreads) void fold_gram_kernel(const double *_
 }
 
 // Workgroup f, fold i = fold0 + f, thread = local row / component.  lambda_j = max(evals_j - shift, 0); fold rank = the leading
-// components with lambda_j > relative_tolerance lambda_0 and > 0, at most n - 2; b, alpha and, per rank q with k' = min(k(q), fold rank),
+// components with lambda_j > relative_tolerance lambda_0 and > 0, at most n - 2 (both: spectrum_plan.h); b, alpha and, per rank q with k' = min(k(q), fold rank),
 // c as one running sum over the components that is written out whenever it reaches the next k'.  W[shape][q np + i] = w + e_i (the
 // measure pass subtracts column i of D): c_r at the shapes that stay, a sum c - a at shape i.  flag: set on a non-finite eigenvalue.
 __global__ __launch_bounds__(kFoldThreads) void fold_factor_kernel(const double *__restrict__ evals, const double *__restrict__ V, const double *__restrict__ g,
@@ -127,13 +128,12 @@ __global__ __launch_bounds__(kFoldThreads) void fold_factor_kernel(const double 
     if (t < nf) {
         const double ev = evals[(int64_t)f * nf + t];
         if (!(fabs(ev) <= kDblMax)) atomicOr(flag, 1);
-        lam[t] = none ? 0.0 : fmax(ev - shift[f], 0.0);
+        lam[t] = none ? 0.0 : spectrum_plan::unshift(ev, shift[f]);
         gs[t] = g[(int64_t)f * nf + t];
     }
     __syncthreads();
     if (t == 0) {
-        int k = 0;
-        while (k < n - 2 && lam[k] > relative_tolerance * lam[0] && lam[k] > 0.0) ++k;
+        const int k = spectrum_plan::leading_rank(lam, n - 2, relative_tolerance);
         rank_s = k;
         fold_rank[i] = k;
     }
@@ -157,12 +157,6 @@ __global__ __launch_bounds__(kFoldThreads) void fold_factor_kernel(const double 
         if (t < nf) col[lp::fold_shape(i, t) * ldw] = c;
         if (t == 0) col[i * ldw] = a * sum - a;
     }
-}
-
-int check_finite(gingr_ctx *ctx, const double *x, int64_t per, int64_t n, const char *who) {
-    for (int64_t e = 0; e < per * n; ++e)
-        if (!std::isfinite(x[e])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite coordinate in shape %lld", who, (long long)(e / per));
-    return GINGR_OK;
 }
 
 }  // namespace
@@ -198,7 +192,7 @@ int gingr_pca_leave_one_out(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const d
         rl.n = n_ranks;
         for (int q = 0; q < n_ranks; ++q) rl.k[q] = ranks[q];
     }
-    GINGR_TRY(check_finite(ctx, shapes_xyz, 3 * M, n, who));
+    GINGR_TRY(check_finite(ctx, shapes_xyz, 3 * M, n, who, "shape"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int np = (int)lp::padded_shapes(n), ldt = (int)lp::weight_columns(n, n_ranks);
     const int64_t rows = 3 * M;

@@ -7,9 +7,12 @@
 //   Xc^T Xc       = V diag(lambda) V^T: the raw model's moment S_tot (launch_gram) and the solvers of eig.hip.  A centred Gram matrix is
 //                 singular (its columns sum to zero, often with a larger null space), so they decompose Xc^T Xc + (trace / n) I
 //   Q0            = Xc V[:, :k] = U sqrt(lambda) (launch_basis_rotate, identity rotation), variance lambda[:k]
+// The shifted eigen step, the factor rows and the moment trace are the shared tail of posterior_model.hip (gp.h), the choice of k is
+// spectrum_plan.h, the finite checks and the staged upload are model.hip's (gp.h).
 // Every sum is taken in a fixed order (block partials combined by one thread or one workgroup, no float atomics): two builds of the
 // same input give the same bits.
 #include "fitter.h"
+#include "spectrum_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -197,14 +200,6 @@ __global__ __launch_bounds__(256) void center_pack_kernel(const double *__restri
     }
 }
 
-// T [np][kp]: T[i][j] = V[i n + j] (component i of eigenvector j) for i < n, j < k, zero elsewhere
-__global__ __launch_bounds__(256) void pca_factor_kernel(const double *__restrict__ V, int n, int np, int k, int kp, double *__restrict__ T) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (int64_t)np * kp) return;
-    const int i = (int)(e / kp), j = (int)(e - (int64_t)i * kp);
-    T[e] = (i < n && j < k) ? V[(int64_t)i * n + j] : 0.0;
-}
-
 // Gs [n][n] = the leading n x n block of G (row stride ldg) + shift on the diagonal
 __global__ __launch_bounds__(256) void gram_shift_kernel(const double *__restrict__ G, int ldg, int n, double shift, double *__restrict__ Gs) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -267,31 +262,23 @@ int gingr_model_from_shapes(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const d
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: max_rank, relative_tolerance and gpa_tolerance must not be negative", who);
     if (M > (int64_t)0x7fffffff / 3) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: M = %lld too large", who, (long long)M);
     const int n = n_shapes;
-    for (int64_t e = 0; e < 3 * M; ++e)
-        if (!std::isfinite(ref_xyz[e])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite reference coordinate", who);
-    for (int64_t e = 0; e < (int64_t)n * 3 * M; ++e)
-        if (!std::isfinite(shapes_xyz[e]))
-            return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite coordinate in shape %lld", who, (long long)(e / (3 * M)));
+    GINGR_TRY(check_finite(ctx, ref_xyz, 3 * M, 1, who, "reference"));
+    GINGR_TRY(check_finite(ctx, shapes_xyz, 3 * M, n, who, "shape"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int np = (int)round_up(n, 16);
     const int sweeps_max = gpa_max_iterations > 0 ? gpa_max_iterations : 3;
 
-    // ---- 1. the shapes as planes on the device (a few shapes per transfer through one staging buffer)
+    // ---- 1. the shapes as planes on the device (for_each_shape_stage, model.hip; the staging buffer serves step 3 once more)
     DevBuf X, stage, tgt, mu, aos;
     HIP_TRY(ctx, X.alloc((size_t)n * 3 * M * sizeof(double)));
-    const int per_stage = (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)8 << 20) / (3 * M)));  // <= 64 MB of staging
-    HIP_TRY(ctx, stage.alloc((size_t)per_stage * 3 * M * sizeof(double)));
     HIP_TRY(ctx, tgt.alloc((size_t)3 * M * sizeof(double)));
     HIP_TRY(ctx, mu.alloc((size_t)3 * M * sizeof(double)));
     HIP_TRY(ctx, aos.alloc((size_t)3 * M * sizeof(double)));
-    for (int i0 = 0; i0 < n; i0 += per_stage) {
-        const int cnt = std::min(per_stage, n - i0);
-        HIP_TRY(ctx, hipMemcpyAsync(stage.p, shapes_xyz + (size_t)i0 * 3 * M, (size_t)cnt * 3 * M * sizeof(double), hipMemcpyHostToDevice,
-                                    ctx->stream));
+    GINGR_TRY(for_each_shape_stage(ctx, M, n, shapes_xyz, stage, [&](int cnt, int i0) -> int {
         for (int q = 0; q < cnt; ++q)
             launch_aos_to_soa(ctx, stage.as<double>() + (size_t)q * 3 * M, M, X.as<double>() + (size_t)(i0 + q) * 3 * M);
-        GINGR_TRY(check_launch(ctx));
-    }
+        return GINGR_OK;
+    }));
     HIP_TRY(ctx, hipMemcpyAsync(aos.p, ref_xyz, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     launch_aos_to_soa(ctx, aos.as<double>(), M, tgt.as<double>());
     GINGR_TRY(check_launch(ctx));
@@ -373,10 +360,8 @@ int gingr_model_from_shapes(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const d
     X.release();
     stage.release();
     const double *G = raw->mom + MomentLayout{raw->rp}.stot();
-    std::vector<double> diag((size_t)n);
-    HIP_TRY(ctx, hipMemcpy2D(diag.data(), sizeof(double), G, (size_t)(np + 1) * sizeof(double), sizeof(double), (size_t)n, hipMemcpyDeviceToHost));
     double trace = 0.0;
-    for (int j = 0; j < n; ++j) trace += diag[(size_t)j];
+    GINGR_TRY(moment_trace(ctx, G, n, np, &trace));
     if (!std::isfinite(trace)) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite Gram matrix of the centred shapes", who);
     // identical shapes leave the rounding of the mean behind: the n - 1 additions of shape_mean_kernel and its division move an entry
     // by at most n (eps / 2) |mu_e|, so the trace, n / (n - 1) sum_e (x_e - mu_e)^2, stays below n^2 eps^2 |mu|^2 / 2.  A total
@@ -401,27 +386,17 @@ int gingr_model_from_shapes(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const d
     HIP_TRY(ctx, Gs.alloc((size_t)n * n * sizeof(double)));
     hipLaunchKernelGGL(gram_shift_kernel, dim3((unsigned)ceil_div((int64_t)n * n, 256)), dim3(256), 0, ctx->stream, G, np, n, shift, Gs.as<double>());
     GINGR_TRY(check_launch(ctx));
-    GINGR_TRY(launch_jacobi_eig(ctx, Gs.as<double>(), n, n, evals.as<double>(), V.as<double>(), true));
-    std::vector<double> lam((size_t)n);
-    HIP_TRY(ctx, hipMemcpy(lam.data(), evals.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    double total = 0.0;
-    for (int j = 0; j < n; ++j) {
-        if (!std::isfinite(lam[(size_t)j])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite eigenvalue", who);
-        lam[(size_t)j] = std::max(lam[(size_t)j] - shift, 0.0);  // (a null direction: rounding around zero)
-        total += lam[(size_t)j];
-    }
-    const int kmax = std::min(n - 1, max_rank > 0 ? std::min<int>(max_rank, 512) : 512);
-    int k = 0;
-    while (k < kmax && lam[(size_t)k] > relative_tolerance * lam[0] && lam[(size_t)k] > 0.0) ++k;
+    std::vector<double> lam;
+    GINGR_TRY(eig_descending_to_host(ctx, Gs.as<double>(), n, n, shift, who, "eigenvalue", evals.as<double>(), V.as<double>(), lam));
+    // centred shapes span at most n - 1 directions (lam is un-shifted already: the cut subtracts nothing more)
+    const spectrum_plan::Cut cut = spectrum_plan::cut(lam.data(), n, 0.0, n - 1, max_rank, relative_tolerance);
+    const int k = cut.k;
     if (k < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: all shapes are identical (rank 0)", who);
-    double kept = 0.0;
-    for (int j = 0; j < k; ++j) kept += lam[(size_t)j];
 
     // ---- 6. Q0 = Xc V[:, :k] into the model proper
     const int kp = (int)round_up(k, 16);
     HIP_TRY(ctx, T.alloc((size_t)np * kp * sizeof(double)));
-    hipLaunchKernelGGL(pca_factor_kernel, dim3((unsigned)ceil_div((int64_t)np * kp, 256)), dim3(256), 0, ctx->stream, V.as<double>(), n, np, k, kp,
-                       T.as<double>());
+    launch_factor_rows(ctx, V.as<double>(), n, 0, n, np, k, kp, T.as<double>());
     GINGR_TRY(check_launch(ctx));
     const Rot3 identity{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
     auto fill = [&](gingr_model *nm) -> int {
@@ -433,8 +408,8 @@ int gingr_model_from_shapes(gingr_ctx *ctx, int64_t M, int32_t n_shapes, const d
         info->rank = k;
         info->gpa_sweeps = sweeps;
         info->gpa_last_change = last_change;
-        info->total_variance = total;
-        info->kept_variance = kept;
+        info->total_variance = cut.total;
+        info->kept_variance = cut.kept;
     }
     return GINGR_OK;
 }

@@ -5,7 +5,10 @@
 //   T = W V,   Q0_new = R (Q0 T) = U_p sqrt(lambda_p)    (one pass over the basis: basis_rotate_kernel)
 //   a = W W^T rhs,   mean_new = R (mean + Q0 a),   ref_new = R (ref - c) + c + t
 // No division by a prior variance anywhere: a model with lambda_k = 0 gives lambda_p = 0 for that direction.
+// Also the home of the r x r tail every derived-model builder ends in (gp.h): eig_descending_to_host, launch_factor_rows, moment_trace
+// and launch_basis_rotate; the cut of the spectrum is spectrum_plan.h.
 #include "basis_rotate.h"
+#include "spectrum_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -74,6 +77,15 @@ __global__ __launch_bounds__(256) void factor_vectors_kernel(int r, int rp, cons
     T[(int64_t)i * rp + j] = acc;
 }
 
+// T [rsp][kp]: rows row0 .. row0 + rs of V[:, :k] (V [n][n]), zero padded (launch_factor_rows, gp.h)
+__global__ __launch_bounds__(256) void factor_rows_kernel(const double *__restrict__ V, int n, int row0, int rs, int rsp, int k, int kp,
+                                                          double *__restrict__ T) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)rsp * kp) return;
+    const int i = (int)(e / kp), j = (int)(e - (int64_t)i * kp);
+    T[e] = (i < rs && j < k) ? V[(int64_t)(row0 + i) * n + j] : 0.0;
+}
+
 // a [rp] = W (W^T rhs) = (I + G)^-1 rhs, zero beyond the rank; one workgroup
 __global__ __launch_bounds__(512) void posterior_coeff_kernel(int r, int rp, const double *__restrict__ W, int64_t ldw, const double *__restrict__ rhs,
                                                               double *__restrict__ a) {
@@ -105,6 +117,33 @@ void launch_basis_rotate(gingr_ctx *ctx, const gingr_model *src, const double *T
                        rot, dst->perm, src->iperm, nchunks, dst->Q0);
 }
 
+// ---- the r x r tail the derived-model builders share (declared in gp.h)
+int eig_descending_to_host(gingr_ctx *ctx, const double *Gs, int32_t ld, int32_t n, double shift, const char *who, const char *what, double *evals,
+                           double *V, std::vector<double> &lam) {
+    GINGR_TRY(launch_jacobi_eig(ctx, Gs, ld, n, evals, V, true));
+    lam.resize((size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(lam.data(), evals, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (double &v : lam) {
+        if (!std::isfinite(v)) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite %s", who, what);
+        v = spectrum_plan::unshift(v, shift);
+    }
+    return GINGR_OK;
+}
+
+void launch_factor_rows(gingr_ctx *ctx, const double *V, int n, int row0, int rs, int rsp, int k, int kp, double *T) {
+    hipLaunchKernelGGL(factor_rows_kernel, dim3((unsigned)ceil_div((int64_t)rsp * kp, 256)), dim3(256), 0, ctx->stream, V, n, row0, rs, rsp, k, kp, T);
+}
+
+int moment_trace(gingr_ctx *ctx, const double *S, int32_t r, int32_t rp, double *trace) {
+    std::vector<double> diag((size_t)r);
+    HIP_TRY(ctx, hipMemcpy2D(diag.data(), sizeof(double), S, (size_t)(rp + 1) * sizeof(double), sizeof(double), (size_t)r, hipMemcpyDeviceToHost));
+    double t = 0.0;
+    for (int32_t j = 0; j < r; ++j) t += diag[(size_t)j];
+    *trace = t;
+    return GINGR_OK;
+}
+
 // the new model from G and rhs of the observations; f: a fitter on the source model whose state holds the rigid transform
 static int posterior_model_build(gingr_fitter *f, const double *G, const double *rhs, const char *who, gingr_model **out) {
     gingr_ctx *ctx = f->ctx;
@@ -132,7 +171,7 @@ static int posterior_model_build(gingr_fitter *f, const double *G, const double 
     launch_sweep(ctx, SWEEP_POSED, sa);
     launch_soa_to_aos(ctx, shape.as<double>(), M, aos.as<double>(), m->perm);
     GINGR_TRY(check_launch(ctx));
-    std::vector<double> mesh((size_t)3 * M), href((size_t)3 * M), hmean((size_t)3 * M), lam_h((size_t)r);
+    std::vector<double> mesh((size_t)3 * M), href((size_t)3 * M), hmean((size_t)3 * M), lam_h;
     DevState hst;
     int32_t bad = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
@@ -146,15 +185,10 @@ static int posterior_model_build(gingr_fitter *f, const double *G, const double 
     HIP_TRY(ctx, hipMemcpyAsync(lam, m->variance.data(), (size_t)r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(factor_gram_kernel, tiles, dim3(256), 0, ctx->stream, (int)r, W, ldw, lam, H.as<double>(), (int)rp);
     GINGR_TRY(check_launch(ctx));
-    GINGR_TRY(launch_jacobi_eig(ctx, H.as<double>(), rp, r, lam_p, V.as<double>(), true));
+    // (no shift: H is as definite as the prior; a direction the prior does not have is rounding around zero and clamps to 0)
+    GINGR_TRY(eig_descending_to_host(ctx, H.as<double>(), rp, r, 0.0, who, "posterior variance", lam_p, V.as<double>(), lam_h));
     hipLaunchKernelGGL(factor_vectors_kernel, tiles, dim3(256), 0, ctx->stream, (int)r, (int)rp, W, ldw, V.as<double>(), T.as<double>());
     GINGR_TRY(check_launch(ctx));
-    HIP_TRY(ctx, hipMemcpyAsync(lam_h.data(), lam_p, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int32_t k = 0; k < r; ++k) {
-        if (!std::isfinite(lam_h[(size_t)k])) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite posterior variance", who);
-        lam_h[(size_t)k] = std::max(lam_h[(size_t)k], 0.0);  // (a direction the prior does not have: rounding around zero)
-    }
     // reference and mean displacement of the new model (host: they fix its row order)
     GINGR_TRY(gingr_model_download(ctx, m, href.data(), nullptr, nullptr, nullptr));
     for (int64_t i = 0; i < M; ++i) {

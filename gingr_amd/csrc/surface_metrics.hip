@@ -433,8 +433,8 @@ int gingr_mesh_set_distances(gingr_ctx *ctx, int64_t n_points, int64_t n_sets, c
     const mp::ColumnBlocks blocks = mp::column_blocks(n_sets);
     const int64_t block_sets = blocks.length(0), out_cols = pairing == 0 ? n_meshes : 1;
     GINGR_TRY(check_working_set(ctx, who, n_points, block_sets, n_vertices, n_meshes, n_triangles, 0));  // (before the arrays are read)
-    GINGR_TRY(metrics_check_finite(ctx, sets_xyz, 3 * n_points, n_sets, who, "set"));
-    GINGR_TRY(metrics_check_finite(ctx, meshes_xyz, 3 * n_vertices, n_meshes, who, "mesh"));
+    GINGR_TRY(check_finite(ctx, sets_xyz, 3 * n_points, n_sets, who, "set"));
+    GINGR_TRY(check_finite(ctx, meshes_xyz, 3 * n_vertices, n_meshes, who, "mesh"));
 
     std::vector<int32_t> qorder, vorder, torder, vinv, tri;
     mesh_orders(n_points, sets_xyz, n_vertices, meshes_xyz, n_triangles, triangles, qorder, vorder, torder, vinv, tri);
@@ -472,7 +472,7 @@ int gingr_model_generalization_surface(gingr_ctx *ctx, const gingr_model *model,
     const int64_t M = model->M;
     const int32_t r = model->r, rp = model->rp;
     GINGR_TRY(check_triangles(ctx, who, M, n_triangles, triangles));
-    GINGR_TRY(metrics_check_finite(ctx, shapes_xyz, 3 * M, n, who, "shape"));
+    GINGR_TRY(check_finite(ctx, shapes_xyz, 3 * M, n, who, "shape"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int np = (int)mp::padded_cols(n), ldt = n_ranks * np;
     GINGR_TRY(check_working_set(ctx, who, M, n, M, n, n_triangles, mp::block_rows(M)));
@@ -524,8 +524,8 @@ int gingr_model_specificity_surface(gingr_ctx *ctx, const gingr_model *model, in
     const int64_t M = model->M;
     const int32_t r = model->r, rp = model->rp;
     GINGR_TRY(check_triangles(ctx, who, M, n_triangles, triangles));
-    GINGR_TRY(metrics_check_finite(ctx, train_xyz, 3 * M, n_train, who, "training shape"));
-    GINGR_TRY(metrics_check_finite(ctx, alphas, r, n_samples, who, "coefficient vector"));
+    GINGR_TRY(check_finite(ctx, train_xyz, 3 * M, n_train, who, "training shape"));
+    GINGR_TRY(check_finite(ctx, alphas, r, n_samples, who, "coefficient vector"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const mp::ColumnBlocks blocks = mp::column_blocks(n_samples);
     const int ldmax = (int)blocks.padded(0);

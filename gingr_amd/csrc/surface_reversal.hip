@@ -1,5 +1,5 @@
 // The reversed correspondence direction of the surface ICP: one sort of the target vertices by the template vertex they map to,
-// then one observation (or one row of sums) per template vertex.  The only user of hipcub.
+// then one observation (or one row of sums) per template vertex.  One of the four users of hipcub (with fitter_pairs.hip, mesh_decimate.hip and cloud_knn.hip).
 #include "surface.h"
 
 #include <hipcub/hipcub.hpp>
