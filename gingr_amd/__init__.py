@@ -15,7 +15,7 @@ from .api import (  # noqa: F401
     AugmentedDevicePointDistributionModel, AugmentInfo, LaplacianDevicePointDistributionModel, LaplacianInfo,
     LocalizedDevicePointDistributionModel, LocalizeInfo,
     TemplateConfiguration, TemplateRegistration, TemplateRegistrationState, ModelMetrics, normalTangentCovariances,
-    PointToPlaneConfiguration, PointToPlaneIcpRegistration, PointToPlaneRegistrationState,
+    PointToPlaneConfiguration, PointToPlaneIcpRegistration, PointToPlaneRegistrationState, RobustLoss,
 )
 from . import metrics  # noqa: F401  (generalization, specificity, compactness of a shape model)
 from ._native import GingrNativeError  # noqa: F401

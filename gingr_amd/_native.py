@@ -69,6 +69,11 @@ class PlaneCloudParams(ctypes.Structure):
     _fields_ = [("tangent_over_normal", c_double), ("max_distance", c_double)]
 
 
+class RobustParams(ctypes.Structure):
+    """gingr_robust_params"""
+    _fields_ = [("loss", c_int32), ("scale_mode", c_int32), ("scale", c_double), ("min_scale", c_double)]
+
+
 class CloudKnnInfo(ctypes.Structure):
     """gingr_cloud_knn_info"""
     _fields_ = [("cell_size", c_double), ("grid", c_int32 * 3), ("flagged", c_int32)]
@@ -285,6 +290,10 @@ SIGNATURES = {
     "gingr_fitter_get_target_normals": (c_int, [c_void_p, _dp]),
     "gingr_fitter_set_pairs_plane_cloud_async": (c_int, [c_void_p, POINTER(PlaneCloudParams)]),
     "gingr_fitter_update_plane_cloud_async": (c_int, [c_void_p, POINTER(PlaneCloudParams), POINTER(IcpParams), c_int32]),
+    # robust point-to-plane ICP: M-estimator weights with the median scale on the device; the selection as an operator
+    "gingr_fitter_set_plane_robust": (c_int, [c_void_p, POINTER(RobustParams)]),
+    "gingr_fitter_get_plane_robust": (c_int, [c_void_p, _dp, _dp, _dp, _dp, POINTER(c_int64)]),
+    "gingr_order_statistic": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp]),
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),

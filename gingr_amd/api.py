@@ -36,7 +36,7 @@ from .models import (  # noqa: F401
 from .states import (  # noqa: F401
     CorrespondencePairs, CpdConfiguration, CpdRegistrationState, EulerAngles, FittingStatuses, GeneralRegistrationState,
     GlobalTranformationType, IcpConfiguration, IcpRegistrationState, LandmarkCorrespondences, ModelFittingParameters,
-    PointToPlaneConfiguration, PointToPlaneRegistrationState,
+    PointToPlaneConfiguration, PointToPlaneRegistrationState, RobustLoss,
     TemplateConfiguration, TemplateRegistrationState, _cpd_converged, _empty_pairs, _never_converged, _with_fields,
 )
 from .registration import (  # noqa: F401

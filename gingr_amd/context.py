@@ -173,6 +173,14 @@ class Context:
             info.update(cell_size=float(ki.cell_size), grid=tuple(int(g) for g in ki.grid), flagged=int(ki.flagged))
         return normals, var
 
+    def order_statistic(self, values, k: int) -> float:
+        """The k-th smallest (0-based) of non-negative values, the element itself bit for bit -- gingr_order_statistic: the exact radix
+        selection behind the robust scale of point-to-plane ICP, as an operator.  +inf is a value; a negative or NaN value raises."""
+        v = f64(values).reshape(-1)
+        out = ctypes.c_double()
+        _check(self.handle, self._lib.gingr_order_statistic(self.handle, v.shape[0], dptr(v), int(k), ctypes.byref(out)), "gingr_order_statistic")
+        return float(out.value)
+
     def gauss_block(self, A, B, sigma: float, scaling: float) -> np.ndarray:
         """scaling * exp(-|a-b|^2 / sigma^2)  (GPMMHelper.scala:99-102)."""
         A, B = f64(A), f64(B)

@@ -248,6 +248,16 @@ struct gingr_fitter {
     // point-to-plane against a point cloud: a unit (or zero) normal per target point, planes [3][N] in the target's device order
     // (gingr_fitter_set_target_normals / _estimate_target_normals); nullptr = none, and a new target drops them
     double *tnormals = nullptr;
+    // robust (M-estimator) weighting of the point-to-plane pairs (gingr_fitter_set_plane_robust; loss 0 = off: nothing below is
+    // allocated, launched or read).  Per device row: the residual rs_s, its selection key rs_key and the variance inflation rs_u
+    // (0 = not observed); rs_parts: observed rows per workgroup of the residual kernel; rs_counts / rs_sel: the selection's partial
+    // counts and words (robust_select.hip).  rs_fresh: a robust refresh has filled them for the current setting.
+    gingr_robust_params robust = {0, 0, 0.0, 0.0};
+    double *rs_s = nullptr, *rs_u = nullptr;
+    uint64_t *rs_key = nullptr, *rs_sel = nullptr;
+    int32_t *rs_parts = nullptr;
+    uint32_t *rs_counts = nullptr;
+    bool rs_fresh = false;
 };
 
 // GINGR_OPT_GRAM_DOWNDATE by default: from this many local rows on.  The downdate pays while fewer than ~20 % of the rows have weight 0
@@ -336,3 +346,9 @@ void free_meshes(gingr_fitter *f);
 int pairs_ensure_planes(gingr_fitter *f);  // pobs / pwin exist (all zero before the first gingr_fitter_set_pairs)
 int pairs_rebuild_cov_list(gingr_fitter *f);  // cat_* from the host copies of the covariance pairs and the landmarks
 void free_pairs(gingr_fitter *f);
+// ---- robust_select.hip: the key of rank k among keys [n_keys] into sel[2], everything enqueued on the context's stream.  parts != nullptr:
+// the keys that take part are counted by parts [nparts] and k is their lower median's rank; else n_fixed / k_fixed.  counts:
+// robust_select_plan::count_words(n_keys) words; sel: kRobustSelWords words ([0] n, [1] k, [2] key, [3] the scale c when `robust` is given)
+constexpr int kRobustSelWords = 24;
+void robust_select_enqueue(gingr_ctx *ctx, int64_t n_keys, const uint64_t *keys, int64_t nparts, const int32_t *parts, int64_t n_fixed,
+                           int64_t k_fixed, uint32_t *counts, uint64_t *sel, const gingr_robust_params *robust);

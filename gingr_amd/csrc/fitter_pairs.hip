@@ -12,8 +12,12 @@
 //                     (gingr_fitter_update_plane_async): no list, no transfer, no synchronisation
 //   ... against a point cloud                 ->  the same again from what the forward point-cloud search leaves and a normal per target
 //                     point (gingr_fitter_set_pairs_plane_cloud_async, gingr_fitter_update_plane_cloud_async)
+//   ... robustly weighted                     ->  with gingr_fitter_set_plane_robust on, both routes put a residual kernel, the exact median
+//                     (robust_select.hip) and the robust variant of their plane kernel behind the correspondence: a variance
+//                     inflation u_i per vertex, still nothing but launches
 // The phases themselves are in fitter_phases.hip (run_phase), the probabilistic queries next to their siblings.
 #include "fitter.h"
+#include "robust_select_plan.h"
 #include "svd3.h"
 
 #include <hipcub/hipcub.hpp>
@@ -178,6 +182,137 @@ __global__ __launch_bounds__(256) void plane_cloud_pairs_kernel(int64_t M, int64
         x = tgt[t], y = tgt[N + t], z = tgt[2 * N + t];
         plane_precision(tn[t], tn[N + t], tn[2 * N + t], st->sigma2, ratio, L);
     }
+    obs[i] = x;
+    obs[M + i] = y;
+    obs[2 * M + i] = z;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) prec6[q * M + i] = L[q];
+}
+
+// ---- robust weighting (C ABI: gingr_fitter_set_plane_robust).  The residual of an observed vertex in the metric of its observation,
+//   s = e_n^2 + max(|d|^2 - e_n^2, 0) / ratio,   d = fit vertex - observed point,   e_n = n . d
+// = sigma2 d^T Lambda d of the plane plane_precision writes: ratio 1 gives |d|^2 exactly, a normal that is zero or non-finite |d|^2 / ratio.
+__device__ __forceinline__ double plane_residual(double dx, double dy, double dz, double nx, double ny, double nz, double ratio) {
+    const double d2 = (dx * dx + dy * dy) + dz * dz;
+    if (ratio == 1.0) return d2;
+    const double nn = (nx * nx + ny * ny) + nz * nz;  // (NaN fails both comparisons)
+    if (!(nn > 0.0 && nn <= 1.79769313486231570815e308)) nx = ny = nz = 0.0;
+    const double en = (nx * dx + ny * dy) + nz * dz, en2 = en * en;
+    double tang = d2 - en2;  // (a normal is unit to rounding only: a few ulp below zero for d along it)
+    if (tang < 0.0) tang = 0.0;
+    return en2 + tang / ratio;
+}
+
+// The variance inflation u >= 1 of a residual s at scale c; 0: Tukey removes the vertex.  c == 0 (no observed vertex, or a perfect fit
+// under the median scale): 1.  loss: 1 Cauchy, 2 Huber, 3 Tukey.
+__device__ __forceinline__ double robust_inflation(int loss, double s, double c) {
+    if (!(c > 0.0)) return 1.0;
+    if (loss == 2) {
+        const double q = sqrt(s) / c;
+        return q > 1.0 ? q : 1.0;
+    }
+    const double r = (s / c) / c;  // (c * c may overflow or underflow where this does not)
+    if (loss == 1) return 1.0 + r;
+    if (s >= c * c || r >= 1.0) return 0.0;
+    const double w = 1.0 - r;
+    return 1.0 / (w * w);
+}
+
+// s, its selection key (the sentinel for a row that is not observed) and this workgroup's number of observed rows, one store each
+__device__ __forceinline__ void residual_store(int64_t i, int64_t M, bool observed, double r, double *__restrict__ s, uint64_t *__restrict__ key,
+                                               int32_t *__restrict__ parts) {
+    __shared__ int count;
+    if (threadIdx.x == 0) count = 0;
+    __syncthreads();
+    if (i < M) {
+        s[i] = r;
+        key[i] = observed ? robust_select_plan::key_of(r) : robust_select_plan::kSentinel;
+    }
+    if (observed) atomicAdd(&count, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) parts[blockIdx.x] = count;
+}
+
+// Residuals of the surface route, per device row, from what plane_pairs_kernel reads (w01 is only read here) and the fit [3][M]
+__global__ __launch_bounds__(256) void plane_residual_kernel(int64_t M, int64_t Tt, const double *__restrict__ fit, const double *__restrict__ cp,
+                                                             const int32_t *__restrict__ tri_pos, const double *__restrict__ w01,
+                                                             const double *__restrict__ tcn, double ratio, int reject, double *__restrict__ s,
+                                                             uint64_t *__restrict__ key, int32_t *__restrict__ parts) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool observed = i < M && (!reject || w01[i] != 0.0);
+    double r = 0.0;
+    if (observed) {
+        const int64_t t = tri_pos[i];
+        double nx = 0.0, ny = 0.0, nz = 0.0;
+        if (t >= 0 && t < Tt) nx = tcn[t], ny = tcn[Tt + t], nz = tcn[2 * Tt + t];
+        r = plane_residual(fit[i] - cp[i], fit[M + i] - cp[M + i], fit[2 * M + i] - cp[2 * M + i], nx, ny, nz, ratio);
+    }
+    residual_store(i, M, observed, r, s, key, parts);
+}
+
+// ... and of the cloud route, from what plane_cloud_pairs_kernel reads
+__global__ __launch_bounds__(256) void plane_cloud_residual_kernel(int64_t M, int64_t N, const double *__restrict__ fit, const double *__restrict__ tgt,
+                                                                   const int32_t *__restrict__ nn, const double *__restrict__ nnd2,
+                                                                   const double *__restrict__ tn, double ratio, double max2,
+                                                                   double *__restrict__ s, uint64_t *__restrict__ key, int32_t *__restrict__ parts) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t t = i < M ? (int64_t)nn[i] : -1;
+    const bool observed = i < M && t >= 0 && t < N && !(max2 > 0.0 && nnd2[i] > max2);
+    double r = 0.0;
+    if (observed)
+        r = plane_residual(fit[i] - tgt[t], fit[M + i] - tgt[N + t], fit[2 * M + i] - tgt[2 * N + t], tn[t], tn[N + t], tn[2 * N + t], ratio);
+    residual_store(i, M, observed, r, s, key, parts);
+}
+
+// plane_pairs_kernel with the variance of every observed vertex inflated: v_n = sigma2 u_i, u_i = robust_inflation(s[i], c), c the scale
+// the selection left in sel[3].  u [M]: what was used, 0 for a vertex that is not observed or that Tukey removes (all-zero planes).
+__global__ __launch_bounds__(256) void plane_pairs_robust_kernel(int64_t M, int64_t Tt, const double *__restrict__ cp, const int32_t *__restrict__ tri_pos,
+                                                                 double *__restrict__ w01, const double *__restrict__ tcn,
+                                                                 const DevState *__restrict__ st, double ratio, int reject, int loss,
+                                                                 const double *__restrict__ s, const uint64_t *__restrict__ sel,
+                                                                 double *__restrict__ u, double *__restrict__ obs, double *__restrict__ prec6,
+                                                                 int32_t *__restrict__ live) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *live = !(st->status == GINGR_FIT_MODEL_FLEXIBILITY_ERROR || st->stopped);
+    if (i >= M) return;
+    double x = 0.0, y = 0.0, z = 0.0, L[6] = {0, 0, 0, 0, 0, 0}, ui = 0.0;
+    const bool observed = !reject || w01[i] != 0.0;
+    if (!reject) w01[i] = 1.0;
+    if (observed) ui = robust_inflation(loss, s[i], robust_select_plan::value_of(sel[3]));
+    if (ui != 0.0) {
+        x = cp[i], y = cp[M + i], z = cp[2 * M + i];
+        const int64_t t = tri_pos[i];
+        double nx = 0.0, ny = 0.0, nz = 0.0;
+        if (t >= 0 && t < Tt) nx = tcn[t], ny = tcn[Tt + t], nz = tcn[2 * Tt + t];
+        plane_precision(nx, ny, nz, st->sigma2 * ui, ratio, L);
+    }
+    u[i] = ui;
+    obs[i] = x;
+    obs[M + i] = y;
+    obs[2 * M + i] = z;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) prec6[q * M + i] = L[q];
+}
+
+// ... and plane_cloud_pairs_kernel likewise
+__global__ __launch_bounds__(256) void plane_cloud_pairs_robust_kernel(int64_t M, int64_t N, const double *__restrict__ tgt, const int32_t *__restrict__ nn,
+                                                                       const double *__restrict__ nnd2, const double *__restrict__ tn,
+                                                                       const DevState *__restrict__ st, double ratio, double max2, int loss,
+                                                                       const double *__restrict__ s, const uint64_t *__restrict__ sel,
+                                                                       double *__restrict__ u, double *__restrict__ obs, double *__restrict__ prec6,
+                                                                       int32_t *__restrict__ live) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *live = !(st->status == GINGR_FIT_MODEL_FLEXIBILITY_ERROR || st->stopped);
+    if (i >= M) return;
+    double x = 0.0, y = 0.0, z = 0.0, L[6] = {0, 0, 0, 0, 0, 0}, ui = 0.0;
+    const int64_t t = nn[i];
+    const bool observed = t >= 0 && t < N && !(max2 > 0.0 && nnd2[i] > max2);
+    if (observed) ui = robust_inflation(loss, s[i], robust_select_plan::value_of(sel[3]));
+    if (ui != 0.0) {
+        x = tgt[t], y = tgt[N + t], z = tgt[2 * N + t];
+        plane_precision(tn[t], tn[N + t], tn[2 * N + t], st->sigma2 * ui, ratio, L);
+    }
+    u[i] = ui;
     obs[i] = x;
     obs[M + i] = y;
     obs[2 * M + i] = z;
@@ -350,9 +485,35 @@ void free_pairs(gingr_fitter *f) {
     f->n_dense = 0;
     dev_free(f->plane_live);
     f->plane_live = nullptr;
+    void *robust[] = {f->rs_s, f->rs_u, f->rs_key, f->rs_sel, f->rs_parts, f->rs_counts};
+    for (void *q : robust) dev_free(q);
+    f->rs_s = f->rs_u = nullptr;
+    f->rs_key = f->rs_sel = nullptr;
+    f->rs_parts = nullptr;
+    f->rs_counts = nullptr;
+    f->rs_fresh = false;
 }
 
 namespace {
+
+// the buffers of the robust weighting exist (allocated on the first robust refresh, kept)
+int robust_ensure(gingr_fitter *f) {
+    gingr_ctx *ctx = f->ctx;
+    const int64_t M = f->m->M;
+    if (!f->rs_s) GINGR_TRY(dev_alloc(ctx, &f->rs_s, (size_t)M));
+    if (!f->rs_u) GINGR_TRY(dev_alloc(ctx, &f->rs_u, (size_t)M));
+    if (!f->rs_key) GINGR_TRY(dev_alloc(ctx, &f->rs_key, (size_t)M));
+    if (!f->rs_parts) GINGR_TRY(dev_alloc(ctx, &f->rs_parts, (size_t)ceil_div(M, 256)));
+    if (!f->rs_counts) GINGR_TRY(dev_alloc(ctx, &f->rs_counts, (size_t)robust_select_plan::count_words(M)));
+    if (!f->rs_sel) GINGR_TRY(dev_alloc(ctx, &f->rs_sel, (size_t)kRobustSelWords));
+    return GINGR_OK;
+}
+
+// the observed rows' lower median of rs_s and the scale c into rs_sel, behind a residual kernel
+void robust_scale(gingr_fitter *f) {
+    const int64_t M = f->m->M;
+    robust_select_enqueue(f->ctx, M, f->rs_key, ceil_div(M, 256), f->rs_parts, 0, 0, f->rs_counts, f->rs_sel, &f->robust);
+}
 
 // what both point-to-plane entry points refuse, in the order of correspondence.h: ready, parameters, then what the flavour needs
 int plane_check(gingr_fitter *f, const gingr_plane_params *p, const char *who) {
@@ -378,6 +539,19 @@ int plane_refresh(gingr_fitter *f, const gingr_plane_params &p) {
     GINGR_TRY(dense_ensure_planes(f));
     if (!f->plane_live) GINGR_TRY(dev_alloc(ctx, &f->plane_live, 1));
     fitter_surface_scan(f);
+    if (f->robust.loss != 0) {
+        GINGR_TRY(robust_ensure(f));
+        hipLaunchKernelGGL(plane_residual_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, f->Tt, f->fit, f->surf_cp,
+                           f->surf_tri_pos, f->surf_w01, f->tcn, p.tangent_over_normal, (int)p.reject, f->rs_s, f->rs_key, f->rs_parts);
+        robust_scale(f);
+        hipLaunchKernelGGL(plane_pairs_robust_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, f->Tt, f->surf_cp,
+                           f->surf_tri_pos, f->surf_w01, f->tcn, f->st, p.tangent_over_normal, (int)p.reject, (int)f->robust.loss, f->rs_s,
+                           f->rs_sel, f->rs_u, f->dobs, f->dprec, f->plane_live);
+        GINGR_TRY(check_launch(ctx));
+        f->rs_fresh = true;
+        f->n_dense = M;
+        return GINGR_OK;
+    }
     hipLaunchKernelGGL(plane_pairs_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, f->Tt, f->surf_cp, f->surf_tri_pos,
                        f->surf_w01, f->tcn, f->st, p.tangent_over_normal, (int)p.reject, f->dobs, f->dprec, f->plane_live);
     GINGR_TRY(check_launch(ctx));
@@ -409,6 +583,19 @@ int plane_cloud_refresh(gingr_fitter *f, const gingr_plane_cloud_params &p) {
     if (!f->plane_live) GINGR_TRY(dev_alloc(ctx, &f->plane_live, 1));
     fitter_cloud_scan(f);
     const double max2 = p.max_distance > 0.0 ? p.max_distance * p.max_distance : 0.0;
+    if (f->robust.loss != 0) {
+        GINGR_TRY(robust_ensure(f));
+        hipLaunchKernelGGL(plane_cloud_residual_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, f->N, f->fit, f->target,
+                           f->nn_idx, f->nn_d2, f->tnormals, p.tangent_over_normal, max2, f->rs_s, f->rs_key, f->rs_parts);
+        robust_scale(f);
+        hipLaunchKernelGGL(plane_cloud_pairs_robust_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, f->N, f->target,
+                           f->nn_idx, f->nn_d2, f->tnormals, f->st, p.tangent_over_normal, max2, (int)f->robust.loss, f->rs_s, f->rs_sel,
+                           f->rs_u, f->dobs, f->dprec, f->plane_live);
+        GINGR_TRY(check_launch(ctx));
+        f->rs_fresh = true;
+        f->n_dense = M;
+        return GINGR_OK;
+    }
     hipLaunchKernelGGL(plane_cloud_pairs_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, M, f->N, f->target, f->nn_idx, f->nn_d2,
                        f->tnormals, f->st, p.tangent_over_normal, max2, f->dobs, f->dprec, f->plane_live);
     GINGR_TRY(check_launch(ctx));
@@ -617,6 +804,52 @@ int gingr_fitter_update_plane_async(gingr_fitter *f, const gingr_plane_params *p
     if (!f) return GINGR_ERR_BAD_ARGUMENT;
     GINGR_TRY(plane_check(f, p, "update_plane_async"));
     return plane_loop(f, schedule, n_iterations, "update_plane_async", [&] { return plane_refresh(f, *p); });
+}
+
+int gingr_fitter_set_plane_robust(gingr_fitter *f, const gingr_robust_params *p) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    gingr_robust_params next = {0, 0, 0.0, 0.0};
+    if (p && p->loss != 0) {
+        if (p->loss < 0 || p->loss > 3) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_plane_robust: loss %d outside 0..3", (int)p->loss);
+        if (p->scale_mode != 0 && p->scale_mode != 1)
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_plane_robust: scale_mode %d outside 0..1", (int)p->scale_mode);
+        if (!(p->scale > 0.0 && p->scale <= kDblMax)) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_plane_robust: scale must be finite and > 0");
+        if (!(p->min_scale >= 0.0 && p->min_scale <= kDblMax))
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "set_plane_robust: min_scale must be finite and >= 0");
+        if (f->sharded() || f->partial_out) return gingr_set_error(ctx, GINGR_ERR_STATE, "set_plane_robust: single shard only");
+        next = *p;
+    }
+    f->robust = next;
+    f->rs_fresh = false;  // what the buffers hold belongs to the setting before
+    f->forget_posteriors();
+    return GINGR_OK;
+}
+
+int gingr_fitter_get_plane_robust(gingr_fitter *f, double *s, double *u, double *selected, double *c, int64_t *n_observed) {
+    if (!f) return GINGR_ERR_BAD_ARGUMENT;
+    gingr_ctx *ctx = f->ctx;
+    if (f->robust.loss == 0 || !f->rs_fresh) return gingr_set_error(ctx, GINGR_ERR_STATE, "get_plane_robust: no robust refresh yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int64_t M = f->m->M;
+    DevBuf tmp;
+    HIP_TRY(ctx, tmp.alloc((size_t)2 * M * sizeof(double)));
+    if (s) {  // back to the caller's point order
+        launch_scatter(ctx, f->rs_s, M, f->m->perm, tmp.as<double>());
+        HIP_TRY(ctx, hipMemcpyAsync(s, tmp.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (u) {
+        launch_scatter(ctx, f->rs_u, M, f->m->perm, tmp.as<double>() + M);
+        HIP_TRY(ctx, hipMemcpyAsync(u, tmp.as<double>() + M, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    uint64_t words[4] = {0, 0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(words, f->rs_sel, sizeof words, hipMemcpyDeviceToHost, ctx->stream));
+    GINGR_TRY(check_launch(ctx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_observed) *n_observed = (int64_t)words[0];
+    if (selected) *selected = robust_select_plan::value_of(words[2]);
+    if (c) *c = robust_select_plan::value_of(words[3]);
+    return GINGR_OK;
 }
 
 int gingr_fitter_set_target_normals(gingr_fitter *f, const double *normals) {

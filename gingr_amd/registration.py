@@ -21,7 +21,7 @@ from .context import Context, _check
 from .models import DeviceModel, PointDistributionModel, PosteriorDevicePointDistributionModel, _landmarks_native
 from .states import (CorrespondencePairs, CpdConfiguration, CpdRegistrationState, EulerAngles, FittingStatuses, GeneralRegistrationState,
                      GlobalTranformationType, IcpConfiguration, IcpRegistrationState, LandmarkCorrespondences, ModelFittingParameters,
-                     PointToPlaneConfiguration, PointToPlaneRegistrationState, TemplateConfiguration, TemplateRegistrationState,
+                     PointToPlaneConfiguration, PointToPlaneRegistrationState, RobustLoss, TemplateConfiguration, TemplateRegistrationState,
                      _cpd_converged, _empty_pairs, _never_converged, _with_fields)
 
 
@@ -857,6 +857,7 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
         self._params_memo = None   # (config object, PlaneParams, PlaneCloudParams, IcpParams)
         self._planes = None        # (state, closest points, weights, precisions): what the device used for `state`
         self._held_normals = None  # (model, target, normals, neighbours) behind the target normals the fitter holds
+        self._held_robust = None   # native parameters of the robust setting the fitter holds; None: off
 
     def createInitialState(self, model: PointDistributionModel, target, config: PointToPlaneConfiguration,
                            transform: int = GlobalTranformationType.RigidTransforms, stepLength: float = 1.0,
@@ -889,6 +890,8 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
                 raise ValueError(f"targetNormals: {targetNormals!r}; need an (N, 3) array or \"estimate\"")
         if not (np.isfinite(config.tangentOverNormal) and config.tangentOverNormal >= 1.0):
             raise ValueError(f"tangentOverNormal: {config.tangentOverNormal!r}; need a finite ratio >= 1")
+        if config.robust is not None and not isinstance(config.robust, RobustLoss):
+            raise ValueError(f"robust: {config.robust!r}; need a RobustLoss or None")
         return PointToPlaneRegistrationState(general.updateSigma2(float(config.initialSigma)), config, targetNormals, int(targetNeighbours))
 
     def _params(self, config: PointToPlaneConfiguration):
@@ -906,6 +909,17 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
     def _release(self):
         super()._release()
         self._held_normals = None  # (the normals went with the fitter)
+        self._held_robust = None
+
+    def _push_robust(self, config: PointToPlaneConfiguration):
+        """the robust setting of `config` onto the fitter, once per (fitter, setting)"""
+        want = None if config.robust is None else config.robust.native
+        if self._held_robust == want:       # (a new fitter holds none: _release)
+            return
+        rp = None if want is None else nat.RobustParams(*want)
+        _check(self.ctx.handle, self._lib.gingr_fitter_set_plane_robust(self._fitter, None if rp is None else ctypes.byref(rp)),
+               "gingr_fitter_set_plane_robust")
+        self._held_robust = want
 
     def _push_normals(self, state: PointToPlaneRegistrationState):
         """the target normals of a point-cloud state onto the fitter, once per (model, target, normals)"""
@@ -932,6 +946,7 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
     def _prepare_native(self, state: PointToPlaneRegistrationState):
         # the queries of the pairs flavour read the planes as they stand: make them the ones of the state the device holds
         pp, pc, _ = self._params(state.config)
+        self._push_robust(state.config)
         if state.targetNormals is not None:
             self._push_normals(state)
             _check(self.ctx.handle, self._lib.gingr_fitter_set_pairs_plane_cloud_async(self._fitter, ctypes.byref(pc)),
@@ -942,6 +957,7 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
 
     def _native_update(self, current: PointToPlaneRegistrationState, n: int):
         pp, pc, ip = self._params(current.config)
+        self._push_robust(current.config)
         if current.targetNormals is not None:
             self._push_normals(current)
             _check(self.ctx.handle, self._lib.gingr_fitter_update_plane_cloud_async(self._fitter, ctypes.byref(pc), ctypes.byref(ip), int(n)),
@@ -987,8 +1003,25 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
                        "gingr_fitter_get_surface_correspondence")
             _check(self.ctx.handle, self._lib.gingr_fitter_get_pair_precisions(self._fitter, dptr(obs), dptr(prec)),
                    "gingr_fitter_get_pair_precisions")
-            self._planes = (state, cp, w, prec)
-        return self._planes[1:]
+            robust = None
+            if state.config.robust is not None:    # the inflation per vertex; a vertex Tukey removed is not observed
+                u, c, n = np.empty(M), ctypes.c_double(), ctypes.c_int64()
+                _check(self.ctx.handle, self._lib.gingr_fitter_get_plane_robust(self._fitter, None, dptr(u), None, ctypes.byref(c), ctypes.byref(n)),
+                       "gingr_fitter_get_plane_robust")
+                w = np.where(u > 0.0, w, 0.0)
+                robust = (u, float(c.value), int(n.value))
+            self._planes = (state, cp, w, prec, robust)
+        return self._planes[1:4]
+
+    def robustWeights(self, state) -> Tuple[np.ndarray, float, int]:
+        """(weights (M,), c, nObserved) the device used for `state` under config.robust: the weight 1 / u of every vertex -- 1 = taken at
+        sigma2, towards 0 = discounted, 0 = not observed (rejected, beyond maxDistance, or removed by Tukey's loss) -- the scale c and
+        the number of vertices the correspondence observed (the ones the median is taken over)."""
+        if state.config.robust is None:
+            raise ValueError("robustWeights: the state's configuration has no robust loss")
+        self._observed(state)
+        u, c, n = self._planes[4]
+        return np.where(u > 0.0, 1.0 / np.where(u > 0.0, u, 1.0), 0.0), c, n
 
     def surfaceCorrespondence(self, state) -> Tuple[np.ndarray, np.ndarray]:
         """(closest surface points (M, 3), weights in {0, 1}) as the device used them for the state's fit; against a point-cloud
@@ -1009,6 +1042,9 @@ class PointToPlaneIcpRegistration(GingrAlgorithm):
         """v_t I + (v_n - v_t) n n^T with the face normal the device used for vertex `pid` (read back from its precision)"""
         _, _, prec = self._observed(state)
         vn = float(state.general.sigma2)
+        if state.config.robust is not None:        # the inflated variance sigma2 * u the device used
+            u = self._planes[4][0][int(pid)]
+            vn *= float(u) if u > 0.0 else np.inf
         vt = float(state.config.tangentOverNormal) * vn
         a, b = 1.0 / vt, 1.0 / vn - 1.0 / vt
         xx, xy, xz, yy, yz, zz = prec[int(pid)]

@@ -190,11 +190,52 @@ class TemplateRegistrationState:
 
 
 # ----------------------------------------------------------------------------- point-to-plane ICP, correspondence on the device
+ROBUST_LOSSES = {"cauchy": 1, "huber": 2, "tukey": 3}
+ROBUST_TUNINGS = {"cauchy": 2.385, "huber": 1.345, "tukey": 4.685}     # 95 % efficiency at the normal distribution
+
+
+@dataclasses.dataclass(frozen=True)
+class RobustLoss:
+    """M-estimator weighting of point-to-plane ICP (gingr_robust_params): every observed vertex's variance is sigma2 * u, u >= 1 from
+    its residual s (the squared distance in the metric of its observation) and a scale c --
+    cauchy u = 1 + s / c^2, huber u = max(1, sqrt(s) / c), tukey u = 1 / (1 - s / c^2)^2 and no observation from s >= c^2 on.
+    scale="median": c = tuning * 1.4826 * sqrt(lower median of s over the observed vertices), found on the device every iteration
+    (tuning None: the loss's 95 % constant -- 2.385, 1.345, 4.685); scale=a float: c itself, fixed.  minScale: a floor under c."""
+    kind: str
+    scale: object = "median"
+    tuning: Optional[float] = None
+    minScale: float = 0.0
+
+    def __post_init__(self):
+        if self.kind not in ROBUST_LOSSES:
+            raise ValueError(f"RobustLoss: kind {self.kind!r}; need one of {sorted(ROBUST_LOSSES)}")
+        if isinstance(self.scale, str):
+            if self.scale != "median":
+                raise ValueError(f"RobustLoss: scale {self.scale!r}; need \"median\" or a positive number")
+            value = ROBUST_TUNINGS[self.kind] if self.tuning is None else float(self.tuning)
+        else:
+            if self.tuning is not None:
+                raise ValueError("RobustLoss: a tuning constant goes with scale=\"median\"")
+            value = float(self.scale)
+        if not (np.isfinite(value) and value > 0.0):
+            raise ValueError(f"RobustLoss: scale / tuning {value!r}; need a finite number > 0")
+        if not (np.isfinite(self.minScale) and self.minScale >= 0.0):
+            raise ValueError(f"RobustLoss: minScale {self.minScale!r}; need a finite number >= 0")
+
+    @property
+    def native(self) -> Tuple[int, int, float, float]:
+        """(loss, scale_mode, scale, min_scale) of gingr_robust_params"""
+        if isinstance(self.scale, str):
+            return ROBUST_LOSSES[self.kind], 1, ROBUST_TUNINGS[self.kind] if self.tuning is None else float(self.tuning), float(self.minScale)
+        return ROBUST_LOSSES[self.kind], 0, float(self.scale), float(self.minScale)
+
+
 @dataclasses.dataclass(frozen=True)
 class PointToPlaneConfiguration:
     """Point-to-plane ICP on the surfaces: ICP's sigma2 schedule (ICP.scala:65, :96-99) with a covariance per vertex that is sigma2 along
     the target's face normal and tangentOverNormal * sigma2 across it.  reject: the three rejection rules of the surface ICP.
-    maxDistance (against a point-cloud target only): a vertex farther than this from its nearest target point is not observed."""
+    maxDistance (against a point-cloud target only): a vertex farther than this from its nearest target point is not observed.
+    robust: M-estimator weights on top (RobustLoss); None: plain."""
     maxIterations: int = 100
     initialSigma: float = 100.0
     endSigma: float = 1.0
@@ -204,6 +245,7 @@ class PointToPlaneConfiguration:
     converged: Callable = _never_converged
     useLandmarkCorrespondence: bool = True
     maxDistance: Optional[float] = None
+    robust: Optional[RobustLoss] = None
 
     @property
     def sigmaStep(self) -> float:

@@ -637,6 +637,44 @@ int gingr_fitter_set_pairs_plane_cloud_async(gingr_fitter *f, const gingr_plane_
 int gingr_fitter_update_plane_cloud_async(gingr_fitter *f, const gingr_plane_cloud_params *p, const gingr_icp_params *schedule,
                                           int32_t n_iterations);
 
+/* ---- robust point-to-plane ICP: M-estimator weights as a variance per vertex, the scale from a median on the device ----------
+ * THIS PACKAGE'S DEFINITION.  For every vertex i the correspondence observed (after `reject` on the surface route, after max_distance on
+ * the cloud route), with d_i = fit vertex - observed point, n_i the unit normal of its plane and r = tangent_over_normal:
+ *   residual   s_i = e_n^2 + max(|d_i|^2 - e_n^2, 0) / r,  e_n = n_i . d_i   -- sigma2 d_i^T Lambda_i d_i, the squared distance in the
+ *              metric of the observation; r = 1: |d_i|^2 exactly; a zero or non-finite normal: |d_i|^2 / r, as the planes treat it
+ *   scale      c = scale (scale_mode 0), or c = scale * 1.4826 * sqrt(s_(k)) (scale_mode 1; scale is the tuning constant): s_(k) the k-th
+ *              smallest s_i of the n observed vertices, k = (n - 1) / 2 -- the lower median, an element of the data, found exactly by a
+ *              radix selection over the bit patterns (robust_select.hip).  Then c = max(c, min_scale).  n = 0 or c = 0: u_i = 1
+ *   inflation  Cauchy u = 1 + s / c^2;  Huber u = max(1, sqrt(s) / c);  Tukey: s >= c^2 removes the vertex (Lambda_i = 0, xbar_i = 0),
+ *              else u = 1 / (1 - s / c^2)^2.  The vertex's plane is the one above at v_n = sigma2 u_i.
+ * A vertex Tukey removes still counts in the median: the scale never depends on the weights.  The usual 95 % tunings with the median
+ * scale: Cauchy 2.385, Huber 1.345, Tukey 4.685.
+ * gingr_fitter_set_plane_robust: a persistent setting of the fitter; NULL or loss 0 turns it off (the default).  While it is on, the
+ * four plane entry points -- gingr_fitter_set_pairs_plane_async, gingr_fitter_update_plane_async, gingr_fitter_set_pairs_plane_cloud_async,
+ * gingr_fitter_update_plane_cloud_async -- run, behind the correspondence, a residual kernel, the selection (a handful of short
+ * launches, kernel boundaries the only synchronisation) and the robust variant of their plane kernel; still no transfer and no
+ * synchronisation, two runs give the same bits and n iterations in one call give the bits of n calls of one.  While it is off nothing
+ * of this is launched and every result keeps its bits.  Forgets the posterior memo.  Refused with nothing changed --
+ * GINGR_ERR_BAD_ARGUMENT: loss outside 0..3, scale_mode outside 0..1, scale or min_scale non-finite, scale <= 0, min_scale < 0;
+ * GINGR_ERR_STATE: a row shard.
+ * gingr_fitter_get_plane_robust (every pointer nullable): s [M] and u [M] in the caller's point order (u = 0: not observed, s = 0
+ * there), *selected = s_(k) (0 for n = 0), *c, *n_observed, of the last robust refresh.  Synchronises.  GINGR_ERR_STATE before the
+ * first robust refresh under the current setting.
+ * The sampled update, the transition density, the posterior covariance and the posterior model stay the pairs flavour's and take the
+ * robust planes as they are.  NOT covered: gingr_fitter_mh_step, the gingr_group_* and RCCL entry points, the JVM binding.
+ * gingr_order_statistic: the selection as a stateless operator -- *out = the k-th smallest (0-based) of values [n], host arrays, the
+ * element itself bit for bit (-0 counts as +0).  +inf is a value like any other.  A negative or NaN value: GINGR_ERR_NONFINITE;
+ * n < 1, n >= 2^31 or k outside [0, n): GINGR_ERR_BAD_ARGUMENT.  Two calls give the same bits.  Synchronises. */
+typedef struct gingr_robust_params {
+    int32_t loss;        /* 0 none, 1 Cauchy, 2 Huber, 3 Tukey */
+    int32_t scale_mode;  /* 0: fixed, scale = c > 0;  1: median, scale = the tuning constant > 0 */
+    double scale;
+    double min_scale;    /* >= 0: a floor under c */
+} gingr_robust_params;
+int gingr_fitter_set_plane_robust(gingr_fitter *f, const gingr_robust_params *p);
+int gingr_fitter_get_plane_robust(gingr_fitter *f, double *s, double *u, double *selected, double *c, int64_t *n_observed);
+int gingr_order_statistic(gingr_ctx *ctx, int64_t n, const double *values, int64_t k, double *out);
+
 /* ---- a PCA model from shapes in correspondence ----------------------------------------------------------------------------
  * What DataCollection.gpa(...) followed by PointDistributionModel.createUsingPCA(...) gives a scalismo user, built on the device: a
  * new, finalized, single-shard model on this context.  ref_xyz [3 M]: the reference; shapes_xyz [n_shapes][3 M]: the shapes, point
