@@ -113,6 +113,17 @@ class ScalarKernel(ctypes.Structure):
 
 
 GPMM_MAX_COLUMNS = 1536
+RADIAL_GAUSSIAN, RADIAL_RATIONAL_QUADRATIC, RADIAL_INVERSE_MULTIQUADRIC = 0, 1, 2
+
+
+class RadialTerm(ctypes.Structure):
+    """gingr_radial_term"""
+    _fields_ = [("family", c_int32), ("parameter", c_double), ("scaling", c_double), ("weight", _dp)]
+
+
+class RadialKernel(ctypes.Structure):
+    """gingr_radial_kernel"""
+    _fields_ = [("n_terms", c_int32), ("terms", POINTER(RadialTerm))]
 
 
 class GpmmInfo(ctypes.Structure):
@@ -231,6 +242,8 @@ SIGNATURES = {
     "gingr_gpmm_build_diagonal_ex": (c_int, [c_void_p, c_int64, _dp, POINTER(ScalarKernel), POINTER(ScalarKernel), POINTER(ScalarKernel),
                                              c_double, c_int32, c_int32, c_int64, c_int64, POINTER(GpmmInfo), POINTER(c_void_p)]),
     "gingr_model_truncate": (c_int, [c_void_p, c_void_p, c_int32, POINTER(c_void_p)]),
+    "gingr_gpmm_build_radial": (c_int, [c_void_p, c_int64, _dp, POINTER(RadialKernel), POINTER(RadialKernel), POINTER(RadialKernel),
+                                        c_double, c_int32, c_int32, c_int64, c_int64, POINTER(GpmmInfo), POINTER(c_void_p)]),
     "gingr_gpmm_build_gaussian": (c_int, [c_void_p, c_int64, _dp, c_int32, _dp, _dp, c_double, c_int32, c_int64, c_int64,
                                           POINTER(c_void_p)]),
     "gingr_pointset_distance_extrema": (c_int, [c_void_p, _dp, c_int64, _dp, _dp]),

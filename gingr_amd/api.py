@@ -30,8 +30,8 @@ from .models import (  # noqa: F401
     AugmentInfo, AugmentedDevicePointDistributionModel, DeviceModel, DevicePointDistributionModel, GPMMTriangleMesh3D,
     GaussianKernelParameters, GpmmBuildInfo, InterpolatedDevicePointDistributionModel, LaplacianDevicePointDistributionModel,
     LaplacianHelper, LaplacianInfo, LocalizeInfo, LocalizedDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo, PointDistributionModel, PointSetHelper,
-    PosteriorDevicePointDistributionModel, ScalarKernelSpec, TruncatedDevicePointDistributionModel, _cells_of, _resident,
-    automaticGPMMfromTemplate,
+    PosteriorDevicePointDistributionModel, RadialKernelTerm, ScalarKernelSpec, TruncatedDevicePointDistributionModel, _cells_of, _resident,
+    automaticGPMMfromTemplate, sigmoidField,
 )
 from .states import (  # noqa: F401
     CorrespondencePairs, CpdConfiguration, CpdRegistrationState, EulerAngles, FittingStatuses, GeneralRegistrationState,

@@ -20,6 +20,11 @@
 // Exact ties between residuals follow scalismo's rule -- the first maximum in the permuted index order -- through a log of the
 // swaps that is replayed for tied candidates (PosLog).
 //
+// gingr_gpmm_build_radial builds the same way from kernels the reference can only reach through a dense table: per coordinate a sum of
+// radial terms (Gaussian, RationalQuadratic, InverseMultiquadric: KernelHelper.scala:53-73), each with an optional weight field over the
+// points, sum_t w_t[i] w_t[j] scaling_t f_t(|x_i - x_j|^2) -- a kernel scaled by a function of position, scalismo's ChangePointKernel.
+// Only the kernel value differs (radial_value, in pc_*_kernel<RadialScalar / RadialDiagonal>).
+//
 // Kernels here are one-off (model construction), not the per-iteration path; they are written for exactness of the pivot
 // rule (unfused |x-y|^2, multiply-then-add dot products in ascending column order like the JVM) rather than for speed.
 #include "gp.h"
@@ -66,6 +71,36 @@ __device__ __forceinline__ double kspec_value(const KSpec &k, const Cloud &pts, 
         const double mx = __dmul_rn(pts.x[c], -1.0) - px;
         const double m2 = __dadd_rn(__dadd_rn(__dmul_rn(mx, mx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
         v = __dadd_rn(v, __dmul_rn(mixture_value(k.mix, m2, T), k.mirror));
+    }
+    return v;
+}
+
+// f_t(nn) of one radial term (gingr_gpmm_build_radial): the Gaussian through the table exponential exactly as mixture_value has it; the
+// other two as the reference writes them (KernelHelper.scala:53-73), IEEE division and square root, par = beta * beta
+__device__ __forceinline__ double radial_family_value(int32_t family, double par, double nn, const double *T) {
+    if (family == GINGR_RADIAL_RATIONAL_QUADRATIC) return __dsub_rn(1.0, __ddiv_rn(nn, __dadd_rn(nn, par)));
+    if (family == GINGR_RADIAL_INVERSE_MULTIQUADRIC) return __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(nn, par)));
+    return fastexp2_scaled<3>(fastexp_clamp_d2(nn, fastexp_d2_limit(par)), par, T);
+}
+
+// k(x_c, x_p) = sum_t ((scaling_t f_t(nn)) w_t[c]) w_t[p], terms added left to right, the first assigned; a term without a field has no
+// weight factors (a field of ones gives the same bits: x * 1.0 == x).  c == p is the diagonal: nn = 0, the Gaussian's f is exactly 1.
+__device__ __forceinline__ double radial_value(const KSpec &k, const Cloud &pts, int64_t c, int64_t p, double px, double py, double pz,
+                                               const double *T) {
+    double nn = 0.0;
+    if (c != p) {
+        const double dx = pts.x[c] - px, dy = pts.y[c] - py, dz = pts.z[c] - pz;
+        nn = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+    }
+    const gpmm_factor::RadialFields &rf = *k.radial;
+    double v = 0.0;
+    for (int i = 0; i < k.mix.n; ++i) {
+        const int32_t family = rf.family[i];
+        const double f = c == p && family == GINGR_RADIAL_GAUSSIAN ? 1.0 : radial_family_value(family, k.mix.c[i], nn, T);
+        double e = __dmul_rn(k.mix.s[i], f);
+        const double *w = rf.weight[i];
+        if (w) e = __dmul_rn(__dmul_rn(e, w[c]), w[p]);
+        v = i == 0 ? e : __dadd_rn(v, e);
     }
     return v;
 }
@@ -145,7 +180,8 @@ __device__ __forceinline__ void block_best_sum(Best &b, double &sum, Best *shb, 
 // different coordinates never interact: their column values are exact zeros).  KIND = Tapered: the same 3M entries under the full
 // block kernel g(x_i, x_j) <Q[3i+a,:], Q[3j+b,:]> of gingr_model_localize (g = specs.k[0], one Gaussian of scaling 1; Q^T = basis.qt):
 // every entry interacts with every other.  g(x, x) = 1, so an entry's own value is its row's dot product with itself, summed as the
-// step kernel sums it (multiply, then add, ascending columns).
+// step kernel sums it (multiply, then add, ascending columns).  KIND = RadialScalar / RadialDiagonal: Scalar / Diagonal over radial terms
+// with weight fields (radial_value); an entry whose weights are all zero has a zero diagonal, never wins a pivot and gets zeros.
 template <FactorKind KIND>
 __global__ __launch_bounds__(kPcBlock) void pc_init_kernel(Cloud pts, KSpec3 specs, TaperBasis basis, double *__restrict__ diag,
                                                            int32_t *__restrict__ pivoted, double *__restrict__ pmax,
@@ -154,7 +190,8 @@ __global__ __launch_bounds__(kPcBlock) void pc_init_kernel(Cloud pts, KSpec3 spe
     __shared__ double T[GINGR_EXP_TABLE];
     __shared__ Best shb[kPcBlock];
     __shared__ double shs[kPcBlock];
-    constexpr bool GEN = KIND != FactorKind::Scalar, TAP = KIND == FactorKind::Tapered;
+    constexpr bool RAD = KIND == FactorKind::RadialScalar || KIND == FactorKind::RadialDiagonal;
+    constexpr bool GEN = KIND != FactorKind::Scalar && KIND != FactorKind::RadialScalar, TAP = KIND == FactorKind::Tapered;
     fastexp_table_init(T);
     __syncthreads();
     const int64_t n = GEN ? 3 * pts.n : pts.n;
@@ -165,7 +202,9 @@ __global__ __launch_bounds__(kPcBlock) void pc_init_kernel(Cloud pts, KSpec3 spe
         const int64_t pc = GEN ? c / 3 : c;
         const KSpec &spec = specs.k[GEN ? (int)(c - 3 * pc) : 0];
         double d0;
-        if (TAP) {
+        if (RAD) {
+            d0 = radial_value(spec, pts, pc, pc, 0.0, 0.0, 0.0, T);  // sum_t scaling_t f_t(0) w_t[c]^2
+        } else if (TAP) {
             d0 = 0.0;
             for (int q = 0; q < basis.r; ++q) {
                 const double v = basis.qt[(int64_t)q * n + c];
@@ -215,7 +254,8 @@ __global__ __launch_bounds__(kPcBlock) void pc_step_kernel(Cloud pts, KSpec3 spe
     __shared__ double Lp[512];
     __shared__ int32_t s_piv[512], s_dis[512], s_old[512];
     __shared__ int32_t finished, sh_dis, sh_old;
-    constexpr bool GEN = KIND != FactorKind::Scalar, TAP = KIND == FactorKind::Tapered;
+    constexpr bool RAD = KIND == FactorKind::RadialScalar || KIND == FactorKind::RadialDiagonal;
+    constexpr bool GEN = KIND != FactorKind::Scalar && KIND != FactorKind::RadialScalar, TAP = KIND == FactorKind::Tapered;
     __shared__ double Qp[TAP ? 512 : 1];  // the pivot's row of the basis (a model holds at most 512 columns)
     const int t = threadIdx.x;
     if (t == 0) finished = ctl[1];  // set by an earlier launch (or, harmlessly, by workgroup 0 of this one)
@@ -282,14 +322,14 @@ __global__ __launch_bounds__(kPcBlock) void pc_step_kernel(Cloud pts, KSpec3 spe
             pivoted[c] = 1;
         } else if (pivoted[c]) {
             l = 0.0;
-        } else if (KIND == FactorKind::Diagonal && (int)(c - 3 * pc) != pd) {
+        } else if ((KIND == FactorKind::Diagonal || KIND == FactorKind::RadialDiagonal) && (int)(c - 3 * pc) != pd) {
             l = 0.0;  // another coordinate: exact zero, the residual is untouched
             b = Best{diag[c], (int32_t)c};
             tr = b.v;
         } else {
             double S = 0.0;
             for (int r = 0; r < k; ++r) S = __dadd_rn(S, __dmul_rn(L[(int64_t)r * n + c], Lp[r]));
-            double kv = kspec_value(spec, pts, pc, pp, px, py, pz, T);
+            double kv = RAD ? radial_value(spec, pts, pc, pp, px, py, pz, T) : kspec_value(spec, pts, pc, pp, px, py, pz, T);
             if (TAP) {  // the taper times <Q[c,:], Q[p,:]>
                 double A = 0.0;
                 for (int q = 0; q < basis.r; ++q) A = __dadd_rn(A, __dmul_rn(basis.qt[(int64_t)q * n + c], Qp[q]));
@@ -425,7 +465,8 @@ __global__ __launch_bounds__(256) void gpmm_pack_generic_kernel(const double *__
 // The pivoted Cholesky factorisation (gpmm_factor.h) over the kernels above
 namespace gpmm_factor {
 
-int Factor::init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap) {
+int Factor::init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap, bool radial) {
+    if (radial) return init_kind(c, k, p, gen ? FactorKind::RadialDiagonal : FactorKind::RadialScalar, cap);
     return init_kind(c, k, p, gen ? FactorKind::Diagonal : FactorKind::Scalar, cap);
 }
 
@@ -435,11 +476,13 @@ int Factor::init_tapered(gingr_ctx *c, const KSpec3 &taper, const Cloud &p, cons
 }
 
 int Factor::init_kind(gingr_ctx *c, const KSpec3 &k, const Cloud &p, FactorKind kind, int32_t cap) {
-    const bool gen = kind != FactorKind::Scalar;
+    const bool gen = kind != FactorKind::Scalar && kind != FactorKind::RadialScalar;
     ctx = c, specs = k, pts = p, n = gen ? 3 * p.n : p.n, kcap = cap;
-    step_kernel = kind == FactorKind::Tapered    ? pc_step_kernel<FactorKind::Tapered>
-                  : kind == FactorKind::Diagonal ? pc_step_kernel<FactorKind::Diagonal>
-                                                 : pc_step_kernel<FactorKind::Scalar>;
+    step_kernel = kind == FactorKind::Tapered          ? pc_step_kernel<FactorKind::Tapered>
+                  : kind == FactorKind::Diagonal       ? pc_step_kernel<FactorKind::Diagonal>
+                  : kind == FactorKind::RadialScalar   ? pc_step_kernel<FactorKind::RadialScalar>
+                  : kind == FactorKind::RadialDiagonal ? pc_step_kernel<FactorKind::RadialDiagonal>
+                                                       : pc_step_kernel<FactorKind::Scalar>;
     nb = (int)ceil_div(n, kPcBlock);
     HIP_TRY(ctx, Lb.alloc((size_t)kcap * n * sizeof(double)));
     HIP_TRY(ctx, diag.alloc((size_t)n * sizeof(double)));
@@ -453,9 +496,11 @@ int Factor::init_kind(gingr_ctx *c, const KSpec3 &k, const Cloud &p, FactorKind 
     pmaxv[0] = part.as<double>(), pmaxv[1] = part.as<double>() + nb;
     ptrv[0] = part.as<double>() + 2 * nb, ptrv[1] = part.as<double>() + 3 * nb;
     pidxv[0] = reinterpret_cast<int32_t *>(part.as<double>() + 4 * nb), pidxv[1] = pidxv[0] + nb;
-    hipLaunchKernelGGL(kind == FactorKind::Tapered    ? pc_init_kernel<FactorKind::Tapered>
-                       : kind == FactorKind::Diagonal ? pc_init_kernel<FactorKind::Diagonal>
-                                                      : pc_init_kernel<FactorKind::Scalar>,
+    hipLaunchKernelGGL(kind == FactorKind::Tapered          ? pc_init_kernel<FactorKind::Tapered>
+                       : kind == FactorKind::Diagonal       ? pc_init_kernel<FactorKind::Diagonal>
+                       : kind == FactorKind::RadialScalar   ? pc_init_kernel<FactorKind::RadialScalar>
+                       : kind == FactorKind::RadialDiagonal ? pc_init_kernel<FactorKind::RadialDiagonal>
+                                                            : pc_init_kernel<FactorKind::Scalar>,
                        dim3(nb), dim3(kPcBlock), 0, ctx->stream, pts, specs, basis, diag.as<double>(), piv.as<int32_t>(), pmaxv[0], pidxv[0],
                        ptrv[0], ctl.as<int32_t>());
     return check_launch(ctx);
@@ -582,6 +627,7 @@ struct Build {
     gingr_model **out;
     Cloud pts;
     KSpec3 specs;
+    bool radial;  // the kernels are radial terms with weight fields (gingr_gpmm_build_radial)
 };
 
 // the caller's gingr_gpmm_info from the plan's values, and the entry's answer to a refusal
@@ -613,7 +659,7 @@ int build_generic(const Build &b) {
     const int64_t M = b.M;
     Factor fg;
     const int32_t gcap = (int32_t)std::min<int64_t>(std::min<int64_t>(3 * M, b.max_rank), 512);  // (the pivot step's swap log: 512 entries)
-    GINGR_TRY(fg.init(ctx, b.specs, b.pts, true, gcap));
+    GINGR_TRY(fg.init(ctx, b.specs, b.pts, true, gcap, b.radial));
     GINGR_TRY(fg.run_to_tolerance(b.rel_tol));
     const int32_t n = fg.ks;
     if (n < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: empty model (tolerance too large)");
@@ -644,7 +690,7 @@ int build_scalar(const Build &b) {
     const int64_t M = b.M;
     Factor fac;
     const int32_t kmax = (int32_t)std::min<int64_t>(M, (b.max_rank + 2) / 3);  // scalar columns that can ever be needed
-    GINGR_TRY(fac.init(ctx, b.specs, b.pts, false, kmax));
+    GINGR_TRY(fac.init(ctx, b.specs, b.pts, false, kmax, b.radial));
     GINGR_TRY(fac.run_to_tolerance(b.rel_tol));
     if (fac.ks < 1) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: empty model (tolerance too large)");
     const gpmm_plan::Columns c = gpmm_plan::count_columns(fac.htrace.data(), fac.ks, b.max_rank, b.rel_tol, M);
@@ -711,12 +757,12 @@ int build_scalar(const Build &b) {
 
 }  // namespace
 
-// The construction behind gingr_gpmm_build_diagonal (`ex` false: max_columns is its max_rank, silently clamped to the model's rank
-// limit, no truncation) and gingr_gpmm_build_diagonal_ex (`ex` true: max_columns <= 0 runs to the tolerance under the library's
-// ceiling, nothing is ever shortened silently, keep_rank leading eigenpairs of the merged spectrum are kept).
-static int gpmm_build_impl(gingr_ctx *ctx, int64_t M, const double *ref, const gingr_scalar_kernel *kx, const gingr_scalar_kernel *ky,
-                           const gingr_scalar_kernel *kz, double relative_tolerance, bool ex, int32_t max_columns, int32_t keep_rank,
-                           int64_t row_begin, int64_t row_end, gingr_gpmm_info *info, gingr_model **out) {
+// What every entry checks before it looks at its kernels, and the Build that follows from it.
+// `ex` false (gingr_gpmm_build_diagonal): max_columns is its max_rank, silently clamped to the model's rank limit, no truncation.
+// `ex` true (gingr_gpmm_build_diagonal_ex, gingr_gpmm_build_radial): max_columns <= 0 runs to the tolerance under the library's
+// ceiling, nothing is ever shortened silently, keep_rank leading eigenpairs of the merged spectrum are kept.
+static int start_build(gingr_ctx *ctx, int64_t M, const double *ref, bool kernels, double relative_tolerance, bool ex, int32_t max_columns,
+                       int32_t keep_rank, int64_t row_begin, int64_t row_end, gingr_gpmm_info *info, gingr_model **out, Build &b) {
     if (!ctx || !out) return GINGR_ERR_BAD_ARGUMENT;
     *out = nullptr;
     if (info) memset(info, 0, sizeof(*info));
@@ -724,7 +770,7 @@ static int gpmm_build_impl(gingr_ctx *ctx, int64_t M, const double *ref, const g
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: max_columns = %d is above the ceiling of %d factor columns",
                                (int)max_columns, GINGR_GPMM_MAX_COLUMNS);
     const bool to_tolerance = ex && max_columns <= 0;
-    if (M < 1 || !ref || !kx || !ky || !kz) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: need M >= 1, a reference and three kernels");
+    if (M < 1 || !ref || !kernels) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: need M >= 1, a reference and three kernels");
     if (!(relative_tolerance >= 0.0) || !(relative_tolerance < 1.0))
         return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build: relative tolerance must be in [0, 1)");
     int32_t max_rank = max_columns;  // factor columns at most
@@ -734,7 +780,29 @@ static int gpmm_build_impl(gingr_ctx *ctx, int64_t M, const double *ref, const g
         max_rank = 512;  // the model's rank limit (gingr_model_upload)
     }
     if ((int64_t)max_rank > 3 * M) max_rank = (int32_t)(3 * M);
-    Build b{ctx, M, ref, relative_tolerance, ex, to_tolerance, max_rank, keep_rank, row_begin, row_end <= 0 ? M : row_end, info, out, Cloud{}, KSpec3{}};
+    b = Build{ctx, M, ref, relative_tolerance, ex, to_tolerance, max_rank, keep_rank, row_begin, row_end <= 0 ? M : row_end, info, out, Cloud{}, KSpec3{}, false};
+    return GINGR_OK;
+}
+
+// the reference to the device, then the route: one scalar factorisation, or the generic one when the coordinates' kernels differ
+static int run_build(Build &b, bool generic) {
+    gingr_ctx *ctx = b.ctx;
+    const int64_t M = b.M;
+    DevBuf aos, soa;
+    HIP_TRY(ctx, aos.alloc((size_t)3 * M * sizeof(double)));
+    HIP_TRY(ctx, soa.alloc((size_t)3 * M * sizeof(double)));
+    HIP_TRY(ctx, hipMemcpyAsync(aos.p, b.ref, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_aos_to_soa(ctx, aos.as<double>(), M, soa.as<double>());
+    const double *s = soa.as<double>();
+    b.pts = Cloud{s, s + M, s + 2 * M, M};
+    return generic ? build_generic(b) : build_scalar(b);
+}
+
+static int gpmm_build_impl(gingr_ctx *ctx, int64_t M, const double *ref, const gingr_scalar_kernel *kx, const gingr_scalar_kernel *ky,
+                           const gingr_scalar_kernel *kz, double relative_tolerance, bool ex, int32_t max_columns, int32_t keep_rank,
+                           int64_t row_begin, int64_t row_end, gingr_gpmm_info *info, gingr_model **out) {
+    Build b;
+    GINGR_TRY(start_build(ctx, M, ref, kx && ky && kz, relative_tolerance, ex, max_columns, keep_rank, row_begin, row_end, info, out, b));
 
     // the kernels, one device form per distinct one
     const gingr_scalar_kernel *kd[3] = {kx, ky, kz};
@@ -745,18 +813,64 @@ static int gpmm_build_impl(gingr_ctx *ctx, int64_t M, const double *ref, const g
     KSpec specs[3];
     for (int q = 0; q < nsets; ++q) GINGR_TRY(make_kspec(ctx, kd[first[q]], M, lookups[q], specs[q]));
     for (int d = 0; d < 3; ++d) b.specs.k[d] = specs[set_of[d]];
-
-    // the reference
-    DevBuf aos, soa;
-    HIP_TRY(ctx, aos.alloc((size_t)3 * M * sizeof(double)));
-    HIP_TRY(ctx, soa.alloc((size_t)3 * M * sizeof(double)));
-    HIP_TRY(ctx, hipMemcpyAsync(aos.p, ref, (size_t)3 * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_aos_to_soa(ctx, aos.as<double>(), M, soa.as<double>());
-    const double *s = soa.as<double>();
-    b.pts = Cloud{s, s + M, s + 2 * M, M};
-
-    return nsets > 1 ? build_generic(b) : build_scalar(b);
+    return run_build(b, nsets > 1);
 }
+
+// ---- gingr_gpmm_build_radial: radial terms with weight fields
+namespace {
+
+bool same_field(const double *a, const double *b, int64_t M) {
+    return a == b || (a && b && memcmp(a, b, (size_t)M * sizeof(double)) == 0);  // by pointer, then by content
+}
+
+bool same_radial(const gingr_radial_kernel *a, const gingr_radial_kernel *b, int64_t M) {
+    if (a == b) return true;
+    if (a->n_terms != b->n_terms) return false;
+    for (int t = 0; t < a->n_terms; ++t) {
+        const gingr_radial_term &x = a->terms[t], &y = b->terms[t];
+        if (x.family != y.family || x.parameter != y.parameter || x.scaling != y.scaling || !same_field(x.weight, y.weight, M)) return false;
+    }
+    return true;
+}
+
+// one kernel of the caller's, checked: every refusal names the coordinate's kernel and the term
+int check_radial(gingr_ctx *ctx, const gingr_radial_kernel *k, char coord, int64_t M) {
+    if (k->n_terms < 1 || k->n_terms > kMaxMix || !k->terms)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build_radial: kernel %c: n_terms = %d, need 1..%d terms", coord, (int)k->n_terms,
+                               kMaxMix);
+    for (int t = 0; t < k->n_terms; ++t) {
+        const gingr_radial_term &term = k->terms[t];
+        if (term.family != GINGR_RADIAL_GAUSSIAN && term.family != GINGR_RADIAL_RATIONAL_QUADRATIC &&
+            term.family != GINGR_RADIAL_INVERSE_MULTIQUADRIC)
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build_radial: kernel %c term %d: unknown family %d", coord, t, (int)term.family);
+        if (!(term.parameter > 0.0) || !std::isfinite(term.parameter))
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build_radial: kernel %c term %d: the parameter must be finite and positive", coord, t);
+        if (!(term.scaling > 0.0) || !std::isfinite(term.scaling))
+            return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build_radial: kernel %c term %d: the scaling must be finite and positive", coord, t);
+        if (term.weight)
+            for (int64_t i = 0; i < M; ++i)
+                if (!std::isfinite(term.weight[i]))
+                    return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "gpmm_build_radial: kernel %c term %d: weight %lld is not finite", coord, t,
+                                           (long long)i);
+    }
+    // k(x_i, x_i) = sum_t scaling_t f_t(0) w_t[i]^2 as the device sums it: positive somewhere, or there is nothing to factor
+    for (int64_t i = 0; i < M; ++i) {
+        double d = 0.0;
+        for (int t = 0; t < k->n_terms; ++t) {
+            const gingr_radial_term &term = k->terms[t];
+            const double f0 = term.family == GINGR_RADIAL_INVERSE_MULTIQUADRIC ? 1.0 / std::sqrt(term.parameter * term.parameter) : 1.0;
+            double e = term.scaling * f0;
+            if (term.weight) e = e * term.weight[i] * term.weight[i];
+            d = t == 0 ? e : d + e;
+        }
+        if (d > 0.0) return GINGR_OK;
+    }
+    return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT,
+                           "gpmm_build_radial: kernel %c: the diagonal is zero at every point (the weights of terms 0..%d vanish everywhere)", coord,
+                           (int)k->n_terms - 1);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -771,6 +885,57 @@ int gingr_gpmm_build_diagonal_ex(gingr_ctx *ctx, int64_t M_total, const double *
                                  int32_t max_columns, int32_t keep_rank, int64_t row_begin, int64_t row_end, gingr_gpmm_info *info,
                                  gingr_model **out) {
     return gpmm_build_impl(ctx, M_total, ref, kx, ky, kz, relative_tolerance, true, max_columns, keep_rank, row_begin, row_end, info, out);
+}
+
+int gingr_gpmm_build_radial(gingr_ctx *ctx, int64_t M_total, const double *ref, const gingr_radial_kernel *kx,
+                            const gingr_radial_kernel *ky, const gingr_radial_kernel *kz, double relative_tolerance, int32_t max_columns,
+                            int32_t keep_rank, int64_t row_begin, int64_t row_end, gingr_gpmm_info *info, gingr_model **out) {
+    Build b;
+    GINGR_TRY(start_build(ctx, M_total, ref, kx && ky && kz, relative_tolerance, true, max_columns, keep_rank, row_begin, row_end, info, out, b));
+    b.radial = true;
+    const int64_t M = M_total;
+    const gingr_radial_kernel *kd[3] = {kx, ky, kz};
+    int set_of[3], first[3];
+    for (int d = 0; d < 3; ++d)  // (checked before they are compared: the comparison reads the terms)
+        if (d == 0 || (kd[d] != kd[0] && kd[d] != kd[d - 1])) GINGR_TRY(check_radial(ctx, kd[d], "xyz"[d], M));
+    const int nsets = gpmm_plan::group3([&](int e, int d) { return same_radial(kd[e], kd[d], M); }, gpmm_plan::none, set_of, first);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    // the device form of every distinct kernel; every distinct field (by pointer) is uploaded once
+    const double *host_field[3 * kMaxMix];
+    DevBuf dev_field[3 * kMaxMix], dev_terms;
+    int nfields = 0;
+    gpmm_factor::RadialFields hterms[3];
+    memset(hterms, 0, sizeof(hterms));
+    HIP_TRY(ctx, dev_terms.alloc(sizeof(hterms)));
+    KSpec specs[3];
+    for (int q = 0; q < nsets; ++q) {
+        const gingr_radial_kernel *k = kd[first[q]];
+        KSpec &sp = specs[q];
+        memset(&sp, 0, sizeof(sp));
+        sp.kind = gpmm_factor::kKernelRadial;
+        sp.mix.n = k->n_terms;
+        sp.radial = dev_terms.as<gpmm_factor::RadialFields>() + q;
+        for (int t = 0; t < k->n_terms; ++t) {
+            const gingr_radial_term &term = k->terms[t];
+            const double p2 = term.parameter * term.parameter;
+            sp.mix.c[t] = term.family == GINGR_RADIAL_GAUSSIAN ? -(double)GINGR_EXP_TABLE * 1.4426950408889634074 / p2 : p2;
+            sp.mix.s[t] = term.scaling;
+            hterms[q].family[t] = term.family;
+            if (!term.weight) continue;
+            int f = 0;
+            while (f < nfields && host_field[f] != term.weight) ++f;
+            if (f == nfields) {
+                host_field[nfields++] = term.weight;
+                HIP_TRY(ctx, dev_field[f].alloc((size_t)M * sizeof(double)));
+                HIP_TRY(ctx, hipMemcpyAsync(dev_field[f].p, term.weight, (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            }
+            hterms[q].weight[t] = dev_field[f].as<double>();
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(dev_terms.p, hterms, sizeof(hterms), hipMemcpyHostToDevice, ctx->stream));
+    for (int d = 0; d < 3; ++d) b.specs.k[d] = specs[set_of[d]];
+    return run_build(b, nsets > 1);
 }
 
 int gingr_gpmm_build_gaussian(gingr_ctx *ctx, int64_t M_total, const double *ref, int32_t n_kernels, const double *sigmas,

@@ -24,13 +24,26 @@ struct Mixture {
 //   kind 1  scale * (x . y)          DotProductKernel.k returns x.dot(y) whatever kernel / gamma it wraps (KernelHelper.scala:43-51)
 //   kind 2  scale * m[i][j]          LookupKernel on the reference points themselves (closest reference point of a reference
 //                                     point = the point), m = pinv(graph Laplacian) (LaplacianHelper.scala:27-41)
+//   kind 3  sum_t w_t[i] w_t[j] scaling_t f_t(|x-y|^2)   (gingr_gpmm_build_radial; only the Radial* factor kinds evaluate it): radial
+//           terms with an optional weight field each over the points of the full reference.  mix.n terms, mix.s[t] = scaling_t,
+//           mix.c[t] = the Gaussian's exponent factor as for kind 0, or beta^2 (KernelHelper.scala:53-73: val beta2 = beta * beta)
+struct RadialFields {
+    int32_t family[kMaxMix];        // GINGR_RADIAL_*
+    const double *weight[kMaxMix];  // device, [M_total], or null: no field
+};
+
 struct KSpec {
     int32_t kind;
     Mixture mix;
     double mirror;
     double scale;
-    const double *lookup;  // device, M x M row-major
+    union {
+        const double *lookup;        // kind 2: device, M x M row-major
+        const RadialFields *radial;  // kind 3: device
+    };
 };
+
+constexpr int32_t kKernelRadial = 3;
 
 struct KSpec3 {
     KSpec k[3];
@@ -57,8 +70,10 @@ struct TaperBasis {
 };
 
 // What the pivoted Cholesky factors: one scalar kernel over the points; a DiagonalKernel with different kernels per coordinate over the
-// 3M (point, coordinate) entries; or the full 3 x 3 block kernel g(x_i, x_j) (Q Q^T)[(i,a),(j,b)] over the same entries, g = specs.k[0]
-enum class FactorKind { Scalar = 0, Diagonal = 1, Tapered = 2 };
+// 3M (point, coordinate) entries; or the full 3 x 3 block kernel g(x_i, x_j) (Q Q^T)[(i,a),(j,b)] over the same entries, g = specs.k[0].
+// RadialScalar / RadialDiagonal: the first two over kernels of kind 3 -- instantiations of their own, so that the three above neither load
+// a field nor branch on a family.
+enum class FactorKind { Scalar = 0, Diagonal = 1, Tapered = 2, RadialScalar = 3, RadialDiagonal = 4 };
 
 // pc_step_kernel<kind> of gpmm.hip
 using StepKernel = void (*)(Cloud, KSpec3, TaperBasis, int32_t, int32_t, double, int32_t, double *, double *, int32_t *, const double *,
@@ -83,7 +98,7 @@ struct Factor {
     double *pmaxv[2]{}, *ptrv[2]{};
     int32_t *pidxv[2]{};
 
-    int init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap);
+    int init(gingr_ctx *c, const KSpec3 &k, const Cloud &p, bool gen, int32_t cap, bool radial = false);
     // the tapered kernel of `taper` (one Gaussian, all three coordinates) and the basis qb over the 3 p.n entries
     int init_tapered(gingr_ctx *c, const KSpec3 &taper, const Cloud &p, const TaperBasis &qb, int32_t cap, int timer_hook);
     int init_kind(gingr_ctx *c, const KSpec3 &k, const Cloud &p, FactorKind kind, int32_t cap);  // what the two above share

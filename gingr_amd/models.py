@@ -172,6 +172,71 @@ def _native_kernels(kernels: Sequence[ScalarKernelSpec]) -> Tuple[list, list]:
     return [uniq[id(spec)] for spec in kernels], keep
 
 
+RADIAL_FAMILIES = {"gaussian": nat.RADIAL_GAUSSIAN, "rationalQuadratic": nat.RADIAL_RATIONAL_QUADRATIC,
+                   "inverseMultiquadric": nat.RADIAL_INVERSE_MULTIQUADRIC}
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class RadialKernelTerm:
+    """One term w[i] w[j] scaling f(|x_i - x_j|^2) of a scalar kernel (gingr_radial_term).  `family`: "gaussian" (parameter = sigma:
+    exp(-nn / sigma^2)), "rationalQuadratic" (parameter = beta: 1 - nn / (nn + beta^2), KernelHelper.scala:64-73) or
+    "inverseMultiquadric" (1 / sqrt(nn + beta^2), :53-61).  `weight`: a field over the reference's vertices (any real values), or
+    None.  Terms that are given the same array share one upload."""
+    family: str
+    parameter: float
+    scaling: float
+    weight: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        if not isinstance(self.family, int) and self.family not in RADIAL_FAMILIES:
+            raise ValueError(f"unknown radial family {self.family!r}: one of {sorted(RADIAL_FAMILIES)}")
+        if self.weight is not None:
+            w = f64(self.weight)
+            if w.ndim != 1:
+                raise ValueError(f"a weight field is one value per vertex, got an array of shape {w.shape}")
+            object.__setattr__(self, "weight", w)
+
+    @property
+    def family_code(self) -> int:
+        return int(self.family) if isinstance(self.family, int) else RADIAL_FAMILIES[self.family]
+
+
+def _native_radial(kernels: Sequence[Sequence[RadialKernelTerm]]) -> Tuple[list, list]:
+    """(the gingr_radial_kernel structs of (k_x, k_y, k_z), what they point into -- hold on to it over the call).  The same list of
+    terms -> the SAME native struct; the same weight array -> the same pointer."""
+    keep: list = []
+    uniq = {}
+    for terms in kernels:
+        if id(terms) in uniq:
+            continue
+        arr = (nat.RadialTerm * max(len(terms), 1))()
+        for i, t in enumerate(terms):
+            arr[i].family, arr[i].parameter, arr[i].scaling = t.family_code, float(t.parameter), float(t.scaling)
+            if t.weight is not None:
+                keep.append(t.weight)
+                arr[i].weight = dptr(t.weight)
+        k = nat.RadialKernel()
+        k.n_terms, k.terms = len(terms), arr
+        keep.append(arr)
+        uniq[id(terms)] = k
+    return [uniq[id(terms)] for terms in kernels], keep
+
+
+def sigmoidField(reference, point, normal, width: float) -> np.ndarray:
+    """1 / (1 + exp(-((x - point) . n) / width)) over the vertices x of `reference`, n = normal / |normal|: 0 far behind the plane
+    through `point`, 1 far in front of it, `width` the length over which it changes -- the indicator of a ChangePoint kernel or
+    (scaled and shifted) the amplitude of a ScaledGaussian."""
+    n = f64(normal).reshape(3)
+    length = float(np.sqrt((n * n).sum()))
+    if not length > 0.0 or not np.isfinite(length):
+        raise ValueError("sigmoidField: the normal must be a finite, non-zero vector")
+    if not float(width) > 0.0:
+        raise ValueError(f"sigmoidField: width = {width} must be positive")
+    s = ((f64(reference).reshape(-1, 3) - f64(point).reshape(1, 3)) @ (n / length)) / float(width)
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-s))
+
+
 def _landmarks_native(landmarks) -> tuple:
     """(n, pids int32, points, covs) of a LandmarkCorrespondences as the landmark arguments of the library take them; none or
     empty -> (0, None, None, None)"""
@@ -188,15 +253,19 @@ class DevicePointDistributionModel:
 
     _kernel_built = True                    # built from kernels by _build; False for the kinds made from other models or from data
     _kernels, _to_tolerance, _keep, _info = None, False, 0, None   # the kernel build's own; the other kinds leave them alone
+    _radial = None                                   # (terms_x, terms_y, terms_z) of a model of radial terms (gingr_gpmm_build_radial)
     _full: Optional["DeviceModel"] = None            # the complete model on self.ctx, once built or adopted
     _host: Optional[PointDistributionModel] = None   # what has been downloaded of it
 
     def __init__(self, ctx: Context, reference, sigmas: Sequence[float], scalings: Sequence[float],
                  relativeTolerance: float, maxRank: int = 0, kernels: Optional[Sequence[ScalarKernelSpec]] = None,
-                 cells: Optional[np.ndarray] = None, toTolerance: bool = False, keepRank: int = 0):
+                 cells: Optional[np.ndarray] = None, toTolerance: bool = False, keepRank: int = 0,
+                 radial: Optional[Sequence[Sequence["RadialKernelTerm"]]] = None):
         """toTolerance / keepRank: the build goes through gingr_gpmm_build_diagonal_ex -- maxRank is then the largest number of FACTOR
         columns (0: run to relativeTolerance, an error if the library's ceiling comes first; nothing is shortened silently) and the
-        model keeps the keepRank leading eigenpairs (0: all).  Without them: today's call, maxRank silently clamped to 512."""
+        model keeps the keepRank leading eigenpairs (0: all).  Without them: today's call, maxRank silently clamped to 512.
+        radial: three lists of RadialKernelTerm instead of sigmas / scalings / kernels (gingr_gpmm_build_radial: the stops of
+        gingr_gpmm_build_diagonal_ex, so buildInfo is always there)."""
         self.ctx = ctx
         self.reference = f64(reference)
         self._sig, self._sc = f64(sigmas), f64(scalings)
@@ -204,31 +273,36 @@ class DevicePointDistributionModel:
         self._kernels = None if kernels is None else tuple(kernels)          # (k_x, k_y, k_z) of a DiagonalKernel
         self.cells = cells
         self._to_tolerance, self._keep = bool(toTolerance), int(keepRank)
+        self._radial = None if radial is None else tuple(radial)
 
     def _build_ex(self, ctx: Context, row_begin: int, row_end: int):
         kernels = self._kernels
-        if kernels is None:
-            k = ScalarKernelSpec("gauss", tuple(float(v) for v in self._sig), tuple(float(v) for v in self._sc))
-            kernels = (k, k, k)
-        nk, keep = _native_kernels(kernels)
+        if self._radial is not None:
+            entry, (nk, keep) = "gingr_gpmm_build_radial", _native_radial(self._radial)
+        else:
+            if kernels is None:
+                k = ScalarKernelSpec("gauss", tuple(float(v) for v in self._sig), tuple(float(v) for v in self._sc))
+                kernels = (k, k, k)
+            entry, (nk, keep) = "gingr_gpmm_build_diagonal_ex", _native_kernels(kernels)
         if self._to_tolerance:
             max_columns = self._maxrank
         else:            # today's stop (maxRank clamped to the rank limit), with a truncation folded in
             max_columns = self._maxrank if 0 < self._maxrank <= 512 else 512
         h, info = c_void_p(), nat.GpmmInfo()
-        rc = ctx._lib.gingr_gpmm_build_diagonal_ex(ctx.handle, self.numberOfPoints, dptr(self.reference), ctypes.byref(nk[0]),
-                                                   ctypes.byref(nk[1]), ctypes.byref(nk[2]), self._tol, int(max_columns), self._keep,
-                                                   row_begin, row_end, ctypes.byref(info), ctypes.byref(h))
+        rc = getattr(ctx._lib, entry)(ctx.handle, self.numberOfPoints, dptr(self.reference), ctypes.byref(nk[0]), ctypes.byref(nk[1]),
+                                      ctypes.byref(nk[2]), self._tol, int(max_columns), self._keep, row_begin, row_end,
+                                      ctypes.byref(info), ctypes.byref(h))
+        del keep
         self._info = GpmmBuildInfo(int(info.columns), int(info.rank), bool(info.tolerance_reached), float(info.residual_fraction),
                                    float(info.kept_variance_fraction))
-        _check(ctx.handle, rc, "gingr_gpmm_build_diagonal_ex")
+        _check(ctx.handle, rc, entry)
         return h
 
     @property
     def buildInfo(self) -> Optional[GpmmBuildInfo]:
         """gingr_gpmm_info of the build (builds the model if that has not happened); None for a model that was not built through
-        gingr_gpmm_build_diagonal_ex (toTolerance / truncate)."""
-        if self._to_tolerance or self._keep > 0:
+        gingr_gpmm_build_diagonal_ex or gingr_gpmm_build_radial (toTolerance / truncate / radial terms)."""
+        if self._to_tolerance or self._keep > 0 or self._radial is not None:
             self.device()
         return self._info
 
@@ -242,11 +316,11 @@ class DevicePointDistributionModel:
         if self._full is None and self._kernel_built:
             keep = k if self._keep <= 0 else min(k, self._keep)
             return DevicePointDistributionModel(self.ctx, self.reference, self._sig, self._sc, self._tol, self._maxrank, self._kernels,
-                                                self.cells, toTolerance=self._to_tolerance, keepRank=keep)
+                                                self.cells, toTolerance=self._to_tolerance, keepRank=keep, radial=self._radial)
         return TruncatedDevicePointDistributionModel(self.device(), k, cells=self.cells)
 
     def _build(self, ctx: Context, row_begin: int, row_end: int):
-        if self._to_tolerance or self._keep > 0:
+        if self._to_tolerance or self._keep > 0 or self._radial is not None:
             return self._build_ex(ctx, row_begin, row_end)
         h = c_void_p()
         if self._kernels is not None:
@@ -573,6 +647,61 @@ class GPMMTriangleMesh3D:
         kx = ScalarKernelSpec("gauss", (float(sigma),), (float(scaling),), mirror=-1.0)
         kyz = ScalarKernelSpec("gauss", (float(sigma),), (float(scaling),), mirror=1.0)
         return self._diagonal(kx, kyz, kyz)
+
+    # -- radial terms with weight fields (gingr_gpmm_build_radial)
+    def RadialMixture(self, terms) -> DevicePointDistributionModel:
+        """k(x_i, x_j) = sum_t w_t[i] w_t[j] scaling_t f_t(|x_i - x_j|^2) on every coordinate: `terms` a list of at most eight
+        RadialKernelTerm, or (termsX, termsY, termsZ) for coordinates that differ (the generic factorisation over the 3M entries)."""
+        terms = list(terms)
+        if len(terms) == 3 and not isinstance(terms[0], RadialKernelTerm):
+            lists: dict = {}
+            kernels = [lists.setdefault(id(t), list(t)) for t in terms]     # the same list twice stays one kernel
+        else:
+            kernels = [terms] * 3
+        M = self.reference.shape[0]
+        for k in kernels:
+            for i, t in enumerate(k):
+                if not isinstance(t, RadialKernelTerm):
+                    raise TypeError(f"term {i} is {type(t).__name__}, not a RadialKernelTerm")
+                if t.weight is not None and t.weight.shape[0] != M:
+                    raise ValueError(f"term {i}: a weight field of {t.weight.shape[0]} values on a reference of {M} vertices")
+        return DevicePointDistributionModel(self.ctx, self.reference, [], [], self.relativeTolerance, self.maxRank, cells=self.cells,
+                                            toTolerance=self.toTolerance, radial=kernels)
+
+    def RationalQuadratic(self, beta: float, scaling: float) -> DevicePointDistributionModel:
+        """DiagonalKernel(RationalQuadratic(beta) * scaling, 3) (KernelHelper.scala:64-73)"""
+        return self.RadialMixture([RadialKernelTerm("rationalQuadratic", beta, scaling)])
+
+    def InverseMultiquadric(self, beta: float, scaling: float) -> DevicePointDistributionModel:
+        """DiagonalKernel(InverseMultiquadric(beta) * scaling, 3) (KernelHelper.scala:53-61)"""
+        return self.RadialMixture([RadialKernelTerm("inverseMultiquadric", beta, scaling)])
+
+    @staticmethod
+    def _terms(pars, weight) -> list:
+        """`pars` (GaussianKernelParameters, or RadialKernelTerm without a field of their own) as terms weighted by `weight`"""
+        out = []
+        for p in pars:
+            if isinstance(p, RadialKernelTerm):
+                if p.weight is not None:
+                    raise ValueError("a term that is given a field here must not bring one of its own")
+                out.append(RadialKernelTerm(p.family, p.parameter, p.scaling, weight))
+            else:
+                out.append(RadialKernelTerm("gaussian", p.sigma, p.scaling, weight))
+        return out
+
+    def ScaledGaussian(self, pars: Sequence[GaussianKernelParameters], amplitude) -> DevicePointDistributionModel:
+        """a(x) a(y) sum_i scaling_i exp(-|x-y|^2 / sigma_i^2): the Gaussian mixture with its amplitude a function of position --
+        every term weighted by the one field `amplitude` (one value per vertex)."""
+        a = f64(amplitude).reshape(-1)
+        return self.RadialMixture(self._terms(pars, a))
+
+    def ChangePoint(self, parsA, parsB, indicator) -> DevicePointDistributionModel:
+        """scalismo's ChangePointKernel(kA, kB, s): s(x) s(y) kA(x, y) + (1 - s(x)) (1 - s(y)) kB(x, y) -- the terms of A weighted by
+        `indicator`, then those of B by 1 - indicator.  The indicator (one value per vertex, e.g. sigmoidField) lies in [0, 1]."""
+        s = f64(indicator).reshape(-1)
+        if not np.all(np.isfinite(s)) or s.min(initial=0.0) < 0.0 or s.max(initial=0.0) > 1.0:
+            raise ValueError("ChangePoint: the indicator must lie in [0, 1]")
+        return self.RadialMixture(self._terms(parsA, s) + self._terms(parsB, 1.0 - s))
 
     def InverseLaplacian(self, scaling: float) -> DevicePointDistributionModel:
         """GPMMHelper.scala:132-136: LookupKernel(reference, pinv(graph Laplacian)) * scaling.  The dense pseudo-inverse is one-off

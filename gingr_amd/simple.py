@@ -19,7 +19,8 @@ from typing import Callable, Optional, Sequence, Tuple
 import numpy as np
 
 from .api import (GPMMTriangleMesh3D, InterpolatedDevicePointDistributionModel, Context, CpdConfiguration, CpdRegistration, DeviceModel, EulerAngles, FittingStatuses, GeneralRegistrationState,
-                  GlobalTranformationType, IcpConfiguration, IcpRegistration, ModelFittingParameters, PointDistributionModel, f64)
+                  GlobalTranformationType, IcpConfiguration, IcpRegistration, ModelFittingParameters, PointDistributionModel, f64,
+                  GaussianKernelParameters, sigmoidField)
 from . import io as gio
 from .sampling import (IndependentPoints, JSONStateLogger, ModelToTargetEvaluation, ProbabilisticSettings, Random,
                        RegistrationComparison, TriangleMesh3D)
@@ -363,6 +364,48 @@ class GaussMirrorKernel:
         return f"{self.scaling}_{self.sigma}"
 
 
+@dataclasses.dataclass(frozen=True)
+class RationalQuadraticKernel:
+    """RationalQuadratic(beta) * scaling (KernelHelper.scala:64-73)"""
+    scaling: float
+    beta: float
+    name = "RationalQuadratic"
+
+    @property
+    def printpars(self) -> str:
+        return f"{self.scaling}_{self.beta}"
+
+
+@dataclasses.dataclass(frozen=True)
+class InverseMultiquadricKernel:
+    """InverseMultiquadric(beta) * scaling (KernelHelper.scala:53-61)"""
+    scaling: float
+    beta: float
+    name = "InverseMultiquadric"
+
+    @property
+    def printpars(self) -> str:
+        return f"{self.scaling}_{self.beta}"
+
+
+@dataclasses.dataclass(frozen=True)
+class ChangePointKernel:
+    """Two Gaussians either side of the plane through `point` with normal `normal`: (scalingA, sigmaA) in front of it, (scalingB,
+    sigmaB) behind it, blended by a sigmoid of width `width` (GPMMTriangleMesh3D.ChangePoint with sigmoidField)."""
+    scalingA: float
+    sigmaA: float
+    scalingB: float
+    sigmaB: float
+    point: Tuple[float, float, float]
+    normal: Tuple[float, float, float]
+    width: float
+    name = "ChangePoint"
+
+    @property
+    def printpars(self) -> str:
+        return f"{self.scalingA}_{self.sigmaA}_{self.scalingB}_{self.sigmaB}_{self.width}"
+
+
 class SimpleTriangleModels3D:
     """G/simple/SimpleModels.scala:52-75: one call from a kernel choice to a model, built in HBM."""
 
@@ -385,4 +428,12 @@ class SimpleTriangleModels3D:
             return g.GaussianDot(sigma=kernelSelect.sigma, scaling=kernelSelect.scaling)
         if isinstance(kernelSelect, GaussMirrorKernel):
             return g.GaussianSymmetry(sigma=kernelSelect.sigma, scaling=kernelSelect.scaling)
+        if isinstance(kernelSelect, RationalQuadraticKernel):
+            return g.RationalQuadratic(beta=kernelSelect.beta, scaling=kernelSelect.scaling)
+        if isinstance(kernelSelect, InverseMultiquadricKernel):
+            return g.InverseMultiquadric(beta=kernelSelect.beta, scaling=kernelSelect.scaling)
+        if isinstance(kernelSelect, ChangePointKernel):
+            s = sigmoidField(reference.points, kernelSelect.point, kernelSelect.normal, kernelSelect.width)
+            return g.ChangePoint([GaussianKernelParameters(kernelSelect.sigmaA, kernelSelect.scalingA)],
+                                 [GaussianKernelParameters(kernelSelect.sigmaB, kernelSelect.scalingB)], s)
         raise TypeError(f"unknown kernel choice {kernelSelect!r}")

@@ -237,6 +237,40 @@ int gingr_gpmm_build_diagonal_ex(gingr_ctx *ctx, int64_t M_total, const double *
                                  const gingr_scalar_kernel *ky, const gingr_scalar_kernel *kz, double relative_tolerance,
                                  int32_t max_columns, int32_t keep_rank, int64_t row_begin, int64_t row_end, gingr_gpmm_info *info,
                                  gingr_model **out);
+/* Spatially varying and non-Gaussian kernels: one scalar kernel per coordinate of the form
+ *     k(x_i, x_j) = sum_t  w_t[i] w_t[j] scaling_t f_t(|x_i - x_j|^2)          1 <= n_terms <= 8
+ * with a radial family per term,
+ *   GINGR_RADIAL_GAUSSIAN              exp(-nn / parameter^2)          (parameter = sigma; the arithmetic of the mixture above)
+ *   GINGR_RADIAL_RATIONAL_QUADRATIC    1 - nn / (nn + parameter^2)     (RationalQuadratic(beta), KernelHelper.scala:64-73)
+ *   GINGR_RADIAL_INVERSE_MULTIQUADRIC  1 / sqrt(nn + parameter^2)      (InverseMultiquadric(beta), KernelHelper.scala:53-61)
+ * and an optional weight field per term over the M_total points of the full reference (host, any real values; NULL: none).  The sum
+ * is D_t K_t D_t over the terms, positive semi-definite for any weights: a kernel scaled by a function of position, and with two
+ * terms weighted by s and 1 - s scalismo's ChangePointKernel.  One term's value is ((scaling * f) * w[i]) * w[j], terms are added
+ * left to right; a field of ones gives the bits of no field, and Gaussian terms without fields give the bits of
+ * gingr_gpmm_build_diagonal_ex with the same mixture.  A point whose weights are all zero never becomes a pivot and its basis rows
+ * are exact zeros: it stays on the reference.
+ * max_columns, keep_rank, info, the row shard and every stop and error are those of gingr_gpmm_build_diagonal_ex.  kx / ky / kz may
+ * be the same pointer; kernels that are equal term by term (fields by pointer, then by content) run one scalar factorisation,
+ * different ones the generic factorisation over the 3 M_total entries (at most 512 factor columns).  Every distinct field goes to the
+ * device once.  GINGR_ERR_BAD_ARGUMENT with a message that names the term, *out == NULL: n_terms outside 1..8, an unknown family, a
+ * parameter or scaling that is not finite and positive, a weight that is not finite, a kernel whose diagonal is zero at every point. */
+#define GINGR_RADIAL_GAUSSIAN 0
+#define GINGR_RADIAL_RATIONAL_QUADRATIC 1
+#define GINGR_RADIAL_INVERSE_MULTIQUADRIC 2
+typedef struct gingr_radial_term {
+    int32_t family;
+    double parameter;     /* sigma or beta */
+    double scaling;
+    const double *weight; /* host, M_total, or NULL */
+} gingr_radial_term;
+typedef struct gingr_radial_kernel {
+    int32_t n_terms;
+    const gingr_radial_term *terms;
+} gingr_radial_kernel;
+int gingr_gpmm_build_radial(gingr_ctx *ctx, int64_t M_total, const double *ref, const gingr_radial_kernel *kx,
+                            const gingr_radial_kernel *ky, const gingr_radial_kernel *kz, double relative_tolerance,
+                            int32_t max_columns, int32_t keep_rank, int64_t row_begin, int64_t row_end, gingr_gpmm_info *info,
+                            gingr_model **out);
 /* PointDistributionModel.truncate(k): a new, finalized, independent model of the k leading basis functions of a complete
  * (single-shard, finalized) model of this context, built or uploaded; 1 <= k <= rank, else GINGR_ERR_BAD_ARGUMENT.  A row
  * shard is refused: build the shards with keep_rank, or truncate the complete model. */
