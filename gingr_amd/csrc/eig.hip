@@ -503,13 +503,15 @@ __global__ __launch_bounds__(256) void eigb_chol_update_kernel(EigbBatch b, int3
 }
 
 // One launch of the tournament of column blocks: workgroup (m, q) rotates the columns of its pair of blocks of problem q against
-// each other.  E = ldx / 64 values of a column per lane.  `full`: all pairs of the 32 columns, not only the cross pairs.
+// each other.  E = ldx / 64 values of a column per lane.  `full`: all pairs of the 32 columns, not only the cross pairs.  A problem
+// whose Cholesky pivot failed (`failed[q]`) holds no factor to rotate: its workgroups return at once.
 template <int E>
 __global__ __launch_bounds__(kEbThreads) void eigb_round_kernel(EigbBatch b, int32_t nblk, int32_t rd, int32_t full,
-                                                                int32_t *__restrict__ rotations) {
+                                                                int32_t *__restrict__ rotations, const int32_t *__restrict__ failed) {
     extern __shared__ double eb_cols[];  // [32][E * 64]
     constexpr int ldx = E * 64;
     const int q = blockIdx.y;
+    if (failed[q]) return;  // (uniform over the workgroup, before its first barrier)
     const int n = b.n[q];
     double *X = b.X[q];
     const int m = blockIdx.x;
@@ -632,11 +634,11 @@ __global__ __launch_bounds__(256) void eigb_vectors_kernel(EigbBatch b, int32_t 
 }
 
 template <int E>
-void launch_eigb_round(gingr_ctx *ctx, const EigbBatch &b, int count, int nblk, int rd, int32_t *rotations) {
+void launch_eigb_round(gingr_ctx *ctx, const EigbBatch &b, int count, int nblk, int rd, int32_t *rotations, const int32_t *failed) {
     const size_t lds = (size_t)2 * kEbCols * E * 64 * sizeof(double);
     set_dynamic_lds(eigb_round_kernel<E>, lds);
     hipLaunchKernelGGL((eigb_round_kernel<E>), dim3(nblk / 2, count), dim3(kEbThreads), lds, ctx->stream, b, nblk, rd, rd == 0 ? 1 : 0,
-                       rotations);
+                       rotations, failed);
 }
 
 }  // namespace
@@ -647,7 +649,9 @@ int64_t sym_eig_blocks_work_doubles(int32_t n) {
 }
 
 // Up to three decompositions side by side, every n in kSymEigColsMaxN + 1 .. 512.  work[q]: sym_eig_blocks_work_doubles(largest n)
-// doubles; info[q]: two int32 on the device (sweeps, singular flag), valid when the call returns.  Synchronises the stream.
+// doubles; info[q]: two int32 on the device (sweeps of the call, singular flag of the problem), valid when the call returns.  A
+// problem with a failed pivot is reported singular (its evals / Vs are not a decomposition) and is no concern of the other problems
+// of the call, which are rotated and reported as they are in a call where nothing fails.  Synchronises the stream.
 int sym_eig_blocks(gingr_ctx *ctx, int count, const double *const *G, const int32_t *ldg, const int32_t *n, double *const *work,
                    double *const *evals, double *const *Vs, int32_t *const *info) {
     int32_t nmax = 0;
@@ -680,16 +684,23 @@ int sym_eig_blocks(gingr_ctx *ctx, int count, const double *const *G, const int3
     int32_t hfail[3] = {0, 0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(hfail, failed, sizeof(hfail), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // A failed pivot concerns its own problem only: the workgroups of that problem leave eigb_round_kernel at once (`failed`), the
+    // sweeps run as long as one problem of the call factored, and the problems that factored keep their arithmetic -- and their
+    // bits -- whatever their neighbours did.  (Of the two remedies for the sweeps once skipped for the whole call, this is the first:
+    // the failed words go to the round kernel; info[1] is not raised for the problems that factored.)  The failed problem comes
+    // back with info[1] = 1 and the caller's other kernel decomposes its G itself.
+    bool any_factored = false;
+    for (int q = 0; q < count; ++q) any_factored = any_factored || !hfail[q];
     int sweep = 0;
-    if (!(hfail[0] | hfail[1] | hfail[2])) {  // (a failed pivot: the caller's other kernel decomposes G itself)
+    if (any_factored) {
         for (; sweep < kMaxSweeps; ++sweep) {
             int32_t *rot = words.as<int32_t>() + 3 + 3 * sweep;
             for (int rd = 0; rd < nblk - 1; ++rd) switch (ldx / 64) {
-                    case 4: launch_eigb_round<4>(ctx, b, count, nblk, rd, rot); break;
-                    case 5: launch_eigb_round<5>(ctx, b, count, nblk, rd, rot); break;
-                    case 6: launch_eigb_round<6>(ctx, b, count, nblk, rd, rot); break;
-                    case 7: launch_eigb_round<7>(ctx, b, count, nblk, rd, rot); break;
-                    default: launch_eigb_round<8>(ctx, b, count, nblk, rd, rot); break;
+                    case 4: launch_eigb_round<4>(ctx, b, count, nblk, rd, rot, failed); break;
+                    case 5: launch_eigb_round<5>(ctx, b, count, nblk, rd, rot, failed); break;
+                    case 6: launch_eigb_round<6>(ctx, b, count, nblk, rd, rot, failed); break;
+                    case 7: launch_eigb_round<7>(ctx, b, count, nblk, rd, rot, failed); break;
+                    default: launch_eigb_round<8>(ctx, b, count, nblk, rd, rot, failed); break;
                 }
             HIP_TRY(ctx, hipGetLastError());
             int32_t h[3] = {0, 0, 0};
