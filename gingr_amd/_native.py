@@ -307,6 +307,9 @@ SIGNATURES = {
     "gingr_fitter_set_plane_robust": (c_int, [c_void_p, POINTER(RobustParams)]),
     "gingr_fitter_get_plane_robust": (c_int, [c_void_p, _dp, _dp, _dp, _dp, POINTER(c_int64)]),
     "gingr_order_statistic": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp]),
+    "gingr_rotation_samples": (c_int, [c_int64, _dp]),
+    "gingr_rigid_search": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_int64, _dp, c_int32, c_double, POINTER(c_int64), _dp, _dp,
+                                   POINTER(c_int64), _ip]),
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),

@@ -470,6 +470,74 @@ class RigidICPRegistration:
         return tgt[:n] + (reg[:n] - tgt[:n])
 
 
+# ------------------------------------------------------------------------------------------------ global rigid pre-alignment
+class GlobalRigidAlignment:
+    """From an arbitrary pose to the start the local methods need (no reference counterpart: its demos ship pre-aligned data).
+    register(target): Context.rigid_search over `starts` spiral rotations (or an (S, 3, 3) array), `iterations` iterations, the `overlap`
+    fraction of closest pairs kept -- on every stride-th template point when the template has more than maxPoints points, stride =
+    ceil(M / maxPoints) -- then the best pose refined on ALL points by the RigidICP task (its convergence test, at most
+    refineIterations iterations), started from the transformed template; the two transforms are composed.  With overlap < 1 the
+    task, which does not trim, gets the ceil(overlap M) template points closest to the target at the search's pose (ties included;
+    .refineInliers, else None) and the composed transform is applied to all points.  Returns the aligned
+    template points; .transform = (R, t) with aligned = template R^T + t, .searchResult = the search's record.
+    Trimming from a centroid start does not recover PARTIAL targets reliably (README): pass the known part of the pose as `starts`."""
+
+    def __init__(self, ctx: Context, template, starts=64, iterations: int = 10, overlap: float = 1.0, maxPoints: int = 2000,
+                 refineIterations: int = 50, tolerance: float = 0.001):
+        if int(maxPoints) < 1:
+            raise ValueError("maxPoints >= 1 required")
+        if int(refineIterations) < 0:
+            raise ValueError("refineIterations >= 0 required")
+        self.ctx, self.template = ctx, f64(template).reshape(-1, 3)
+        self.starts, self.iterations, self.overlap = starts, int(iterations), float(overlap)
+        self.maxPoints, self.refineIterations, self.tolerance = int(maxPoints), int(refineIterations), float(tolerance)
+        self.transform: Optional[Tuple[np.ndarray, np.ndarray]] = None
+        self.searchResult = None
+        self.refineIterationsDone = 0
+        self.refineInliers = None
+
+    def searchPoints(self) -> np.ndarray:
+        """the template points the search runs on: every stride-th one, stride = ceil(M / maxPoints)"""
+        M = self.template.shape[0]
+        stride = -(-M // self.maxPoints) if M > self.maxPoints else 1
+        return np.ascontiguousarray(self.template[::stride])
+
+    def register(self, target) -> np.ndarray:
+        tgt = f64(target).reshape(-1, 3)
+        res = self.ctx.rigid_search(self.searchPoints(), tgt, self.starts, self.iterations, self.overlap)
+        self.searchResult = res
+        R, t = res.R.copy(), res.t.copy()
+        points = self.template @ R.T + t
+        self.refineIterationsDone = 0
+        M = points.shape[0]
+        keep = min(M, max(1, int(np.ceil(self.overlap * M))))
+        inliers = None
+        if keep < M:
+            # RigidICP does not trim, and the points the search trimmed away (clutter) would pull it off again (8 degrees with 15 %
+            # clutter on the femur): it runs on the template points the trimming keeps at the search's pose, ties included
+            d2 = self.ctx.nn(points, tgt)[1]
+            inliers = d2 <= np.partition(d2, keep - 1)[keep - 1]
+        self.refineInliers = inliers
+        if self.refineIterations > 0:
+            task = ICPFactory(self.ctx, points if inliers is None else points[inliers]).registerRigidly(tgt)
+            lib, h = self.ctx._lib, self.ctx.handle
+            try:
+                last, d = 0.0, np.empty(1)
+                for _ in range(self.refineIterations):              # RigidICP.Registration's loop, with the steps composed
+                    _check(h, lib.gingr_rigid_icp_iterate(task._h, 1, dptr(d)), "gingr_rigid_icp_iterate")
+                    _, Rk, tk = task.transform()
+                    R, t = Rk @ R, Rk @ t + tk
+                    self.refineIterationsDone += 1
+                    if abs(d[0] - last) < self.tolerance:
+                        break
+                    last = float(d[0])
+                points = task.points() if inliers is None else self.template @ R.T + t
+            finally:
+                task.close()
+        self.transform = (R, t)
+        return points
+
+
 # ------------------------------------------------------------------------------------------------ optimal-step non-rigid ICP
 NICP_DEFAULT_ALPHA = [1e1] * 11   # NonRigidOptimalStepICP.scala:63-65: the scanLeft / reverse chain ends in `.map(_ => 1e1)`
 

@@ -3,6 +3,7 @@ turns a native error code into a GingrNativeError.  Everything else in the packa
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from ctypes import c_int64, c_void_p
 from typing import Optional, Tuple
 
@@ -18,6 +19,22 @@ def _check(ctx_handle, code: int, where: str):
         if ctx_handle:
             text = (nat.load().gingr_last_error(ctx_handle) or b"").decode("utf-8", "replace")
         raise GingrNativeError(code, where, text)
+
+
+@dataclasses.dataclass
+class RigidSearchResult:
+    """What Context.rigid_search returns: the winner (best, R, t, score) and every pose's end state -- rotations (S, 3, 3), translations
+    (S, 3), scores (S,), kept (S,) pairs of the scoring pass, failed (S,) -- so that the runner-up basins of a near-symmetric shape can
+    be inspected."""
+    best: int
+    R: np.ndarray
+    t: np.ndarray
+    score: float
+    rotations: np.ndarray
+    translations: np.ndarray
+    scores: np.ndarray
+    kept: np.ndarray
+    failed: np.ndarray
 
 
 # ----------------------------------------------------------------------------- context + operators
@@ -180,6 +197,34 @@ class Context:
         out = ctypes.c_double()
         _check(self.handle, self._lib.gingr_order_statistic(self.handle, v.shape[0], dptr(v), int(k), ctypes.byref(out)), "gingr_order_statistic")
         return float(out.value)
+
+    def rotation_samples(self, n: int) -> np.ndarray:
+        """The n rotations (n, 3, 3) of the super-Fibonacci spiral over SO(3) (Alexa 2022) -- gingr_rotation_samples: the default start
+        rotations of rigid_search.  Computed on the host."""
+        if int(n) < 1:
+            raise ValueError("n >= 1 required")
+        out = np.empty((int(n), 3, 3))
+        _check(self.handle, self._lib.gingr_rotation_samples(int(n), dptr(out)), "gingr_rotation_samples")
+        return out
+
+    def rigid_search(self, moving, target, rotations=64, iterations: int = 10, overlap: float = 1.0) -> "RigidSearchResult":
+        """Global rigid pre-alignment -- gingr_rigid_search: every start rotation (a count of spiral samples, or an (S, 3, 3) array) gives
+        the start pose R0 (x - mean moving) + mean target; all poses run `iterations` iterations of trimmed ICP (the `overlap` fraction
+        of closest pairs is kept, ties included) together on the device, and the pose of the smallest score sqrt(mean kept d2) wins,
+        the lowest index on ties.  p -> R p + t maps `moving` onto `target`."""
+        x, y = f64(moving).reshape(-1, 3), f64(target).reshape(-1, 3)
+        r0 = self.rotation_samples(rotations) if np.ndim(rotations) == 0 else f64(rotations).reshape(-1, 3, 3)
+        S = r0.shape[0]
+        best = c_int64(-1)
+        poses, scores = np.empty((S, 12)), np.empty(S)
+        kept, failed = np.empty(S, dtype=np.int64), np.empty(S, dtype=np.int32)
+        _check(self.handle, self._lib.gingr_rigid_search(self.handle, x.shape[0], dptr(x), y.shape[0], dptr(y), S, dptr(r0), int(iterations),
+                                                         float(overlap), ctypes.byref(best), dptr(poses), dptr(scores),
+                                                         kept.ctypes.data_as(ctypes.POINTER(c_int64)), iptr(failed)), "gingr_rigid_search")
+        b = int(best.value)
+        rot, tr = poses[:, :9].reshape(S, 3, 3).copy(), poses[:, 9:].copy()
+        return RigidSearchResult(best=b, R=rot[b].copy(), t=tr[b].copy(), score=float(scores[b]), rotations=rot, translations=tr,
+                                 scores=scores, kept=kept, failed=failed.astype(bool))
 
     def gauss_block(self, A, B, sigma: float, scaling: float) -> np.ndarray:
         """scaling * exp(-|a-b|^2 / sigma^2)  (GPMMHelper.scala:99-102)."""

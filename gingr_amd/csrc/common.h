@@ -14,7 +14,7 @@
 #include "../../include/gingr_hip.h"
 #include "host_device.h"
 
-#define GINGR_TIMERS 24
+#define GINGR_TIMERS 27
 
 struct gingr_ctx {
     int device = 0;

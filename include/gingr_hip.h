@@ -1143,7 +1143,8 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * (lap_cheb_kernel) alone, 18 / 19 / 20 = the passes of the model metrics alone: reconstruct and measure (gingr_model_generalization), samples
  * against training shapes (gingr_model_specificity), the stored basis x factor product (gingr_model_instances, gingr_model_specificity),
  * 21 = the pivot step of gingr_model_localize alone, 22 = the batched eigen-decomposition of the folds of gingr_pca_leave_one_out alone
- * (one launch per batch of folds; up to n_shapes = 193), 23 = the batched closest-point scan of the surface-distance metrics alone.  Returns accumulated ms and launches since
+ * (one launch per batch of folds; up to n_shapes = 193), 23 = the batched closest-point scan of the surface-distance metrics alone, 24 / 25 / 26 = the stages of gingr_rigid_search beside
+ * its search (which is 8): the segmented selection, the segmented sums, the rest (pose, step and argmin kernels).  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
@@ -1283,6 +1284,33 @@ void gingr_rigid_icp_destroy(gingr_rigid_icp *h);
 int gingr_rigid_icp_iterate(gingr_rigid_icp *h, int32_t n_iterations, double *distances);
 int gingr_rigid_icp_get(gingr_rigid_icp *h, double *points_xyz, double *transform13);
 int gingr_rigid_icp_set(gingr_rigid_icp *h, const double *points_xyz);
+
+/* ---- global rigid pre-alignment: batched multi-start trimmed ICP ---------------------------------------------------------
+ * No reference counterpart (its demos ship pre-aligned data): what brings a scan from an arbitrary pose to the start every local
+ * method above needs.  S poses advance together on the device (csrc/rigid_search.hip, planning in csrc/rigid_search_plan.h); the
+ * definition is restated in numpy in tests/rigid_search_restatement.py.
+ * Start pose of s: T_s(x) = R0_s (x - mean X) + mean Y, held as (R_s, t_s) with p = R_s x + t_s.  One iteration, per pose: p_i =
+ * R_s x_i + t_s from the ORIGINAL points (the returned pose reproduces the points exactly); j_i = the exact nearest target (lowest
+ * index on ties, d2 = dx*dx + dy*dy + dz*dz separately rounded); keep = ceil(overlap * M) of the float64 product, tau = the order
+ * statistic of rank keep - 1 of d2 and the kept set {i: d2_i <= tau}, ties included (overlap = 1: everything, no selection is
+ * launched); from the kept pairs, with sums centred on mean Y, H = sum (y - mu_y)(p - mu_p)^T / n, dR = the proper rotation closest
+ * to H (polar factor, else SVD with the determinant fix; no Euler round trip), dt = mu_y - dR mu_p; R_s <- dR R_s, t_s <- dR t_s + dt.
+ * After K iterations one more search and selection: score_s = sqrt(mean of the kept d2).  A pose whose transform is not finite gets
+ * score +inf and failed = 1 and takes no further part.  *best_out = the pose of the smallest score, the lowest s on ties.
+ * rotations9 [S][9] row-major: the start rotations (gingr_rotation_samples gives the default ones).  Outputs, each nullable:
+ * poses12_out [S][12] (R row-major, then t), scores_out [S], kept_out [S] (size of the kept set of the scoring pass), failed_out [S].
+ * Poses run in slabs whose size depends on M and N alone; no sum reaches across poses, every sum has a fixed order and there is no
+ * float atomic: two calls give the same bits, and a pose's outputs do not depend on which other poses are in the call.  Nothing is
+ * read back before the end: the call synchronises once.
+ * GINGR_ERR_NONFINITE (before anything is launched): a non-finite coordinate or rotation entry; (after the run) every pose failed.
+ * GINGR_ERR_BAD_ARGUMENT: M < 1, N < 1 or N >= 2^31, S < 1, K < 0, overlap outside (0, 1], a null input or best_out.
+ * gingr_rotation_samples: host only -- the n >= 1 rotations of the super-Fibonacci spiral (Alexa 2022), row-major [n][9]: with
+ * phi = sqrt 2, psi = 1.533751168755204288118041 and s = i + 1/2 the quaternion (x, y, z, w) = (sqrt(s/n) sin(2 pi s / phi),
+ * sqrt(s/n) cos(2 pi s / phi), sqrt(1 - s/n) sin(2 pi s / psi), sqrt(1 - s/n) cos(2 pi s / psi)). */
+int gingr_rotation_samples(int64_t n, double *rotations9_out);
+int gingr_rigid_search(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t S,
+                       const double *rotations9, int32_t K, double overlap, int64_t *best_out, double *poses12_out, double *scores_out,
+                       int64_t *kept_out, int32_t *failed_out);
 
 
 /* ---- optimal-step non-rigid ICP baselines (G/other/algorithms/icp/NonRigidOptimalStepICP.scala:31-284) ------------------------
