@@ -16,7 +16,7 @@ from .api import (  # noqa: F401
     LocalizedDevicePointDistributionModel, LocalizeInfo,
     TemplateConfiguration, TemplateRegistration, TemplateRegistrationState, ModelMetrics, normalTangentCovariances,
     PointToPlaneConfiguration, PointToPlaneIcpRegistration, PointToPlaneRegistrationState, RobustLoss,
-    RadialKernelTerm, sigmoidField, RigidSearchResult,
+    RadialKernelTerm, sigmoidField, RigidSearchResult, RigidSearchPosesResult,
 )
 from . import metrics  # noqa: F401  (generalization, specificity, compactness of a shape model)
 from ._native import GingrNativeError  # noqa: F401

@@ -310,6 +310,12 @@ SIGNATURES = {
     "gingr_rotation_samples": (c_int, [c_int64, _dp]),
     "gingr_rigid_search": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_int64, _dp, c_int32, c_double, POINTER(c_int64), _dp, _dp,
                                    POINTER(c_int64), _ip]),
+    "gingr_rigid_search_poses": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_int64, _dp, c_int32, c_double, c_double, c_int32,
+                                         POINTER(c_int64), _dp, _dp, POINTER(c_int64), _ip, POINTER(c_int64)]),
+    # feature-based global alignment: descriptors, their match, poses from triples of matches
+    "gingr_cloud_fpfh": (c_int, [c_void_p, c_int64, _dp, _dp, c_int32, c_double, _ip, _ip, _dp, POINTER(CloudKnnInfo)]),
+    "gingr_feature_match": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_int32, _ip, _dp]),
+    "gingr_rigid_poses_from_triples": (c_int, [c_void_p, c_int64, _dp, c_int64, _dp, c_int64, _ip, _ip, _dp, _ip]),
     "gingr_model_from_shapes": (c_int, [c_void_p, c_int64, c_int32, _dp, _dp, c_int32, c_int32, c_double, c_double, c_int32,
                                         POINTER(c_void_p), POINTER(PcaInfo)]),
     "gingr_model_augment": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int32, POINTER(c_void_p), POINTER(AugmentInfo)]),

@@ -25,7 +25,7 @@ import numpy as np  # noqa: F401
 
 from . import _native as nat  # noqa: F401
 from ._native import GingrNativeError, f64, dptr, iptr  # noqa: F401
-from .context import Context, RigidSearchResult, _check  # noqa: F401
+from .context import Context, RigidSearchResult, RigidSearchPosesResult, _check  # noqa: F401
 from .models import (  # noqa: F401
     AugmentInfo, AugmentedDevicePointDistributionModel, DeviceModel, DevicePointDistributionModel, GPMMTriangleMesh3D,
     GaussianKernelParameters, GpmmBuildInfo, InterpolatedDevicePointDistributionModel, LaplacianDevicePointDistributionModel,

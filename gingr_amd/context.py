@@ -37,6 +37,13 @@ class RigidSearchResult:
     failed: np.ndarray
 
 
+@dataclasses.dataclass
+class RigidSearchPosesResult(RigidSearchResult):
+    """What Context.rigid_search_poses returns: a RigidSearchResult with inliers (S,), the moving points of every pose within the
+    inlier distance of the target in the scoring pass.  The field is defaulted, so a record built without it is the plain one."""
+    inliers: Optional[np.ndarray] = None
+
+
 # ----------------------------------------------------------------------------- context + operators
 class Context:
     """One device + one stream (gingr_ctx).  Not thread-safe; one per chain / per GPU."""
@@ -225,6 +232,73 @@ class Context:
         rot, tr = poses[:, :9].reshape(S, 3, 3).copy(), poses[:, 9:].copy()
         return RigidSearchResult(best=b, R=rot[b].copy(), t=tr[b].copy(), score=float(scores[b]), rotations=rot, translations=tr,
                                  scores=scores, kept=kept, failed=failed.astype(bool))
+
+    def rigid_search_poses(self, moving, target, poses, iterations: int = 10, overlap: float = 1.0, inlierDistance: float = 0.0,
+                           select: int = 0) -> "RigidSearchPosesResult":
+        """rigid_search from given start poses -- gingr_rigid_search_poses: poses (S, 12), R row-major then t (or a pair (R (S, 3, 3),
+        t (S, 3))).  A pose with a non-finite word is failed from the start and takes no part.  inliers = the moving points with
+        d2 <= inlierDistance^2 in the scoring pass; select 0 picks the smallest score, 1 the most inliers, then the smaller score, then
+        the lowest index.  Given (R0, mean target - R0 mean moving) the outputs are rigid_search's, bit for bit."""
+        x, y = f64(moving).reshape(-1, 3), f64(target).reshape(-1, 3)
+        if isinstance(poses, tuple):
+            poses = np.concatenate([f64(poses[0]).reshape(-1, 9), f64(poses[1]).reshape(-1, 3)], axis=1)
+        p = f64(poses).reshape(-1, 12)
+        S = p.shape[0]
+        best = c_int64(-1)
+        out, scores = np.empty((S, 12)), np.empty(S)
+        kept, failed, inliers = np.empty(S, dtype=np.int64), np.empty(S, dtype=np.int32), np.empty(S, dtype=np.int64)
+        i64 = ctypes.POINTER(c_int64)
+        _check(self.handle, self._lib.gingr_rigid_search_poses(self.handle, x.shape[0], dptr(x), y.shape[0], dptr(y), S, dptr(p), int(iterations),
+                                                               float(overlap), float(inlierDistance), int(select), ctypes.byref(best),
+                                                               dptr(out), dptr(scores), kept.ctypes.data_as(i64), iptr(failed),
+                                                               inliers.ctypes.data_as(i64)), "gingr_rigid_search_poses")
+        b = int(best.value)
+        rot, tr = out[:, :9].reshape(S, 3, 3).copy(), out[:, 9:].copy()
+        return RigidSearchPosesResult(best=b, R=rot[b].copy(), t=tr[b].copy(), score=float(scores[b]), rotations=rot, translations=tr,
+                                      scores=scores, kept=kept, failed=failed.astype(bool), inliers=inliers)
+
+    def cloud_fpfh(self, points, normals, k: int = 64, radius: float = 0.0, info: Optional[dict] = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Fast Point Feature Histograms of a cloud with normals -- gingr_cloud_fpfh, this package's definition (include/gingr_hip.h):
+        (fpfh (N, 33), counts (N, 33) int32, valid (N,) int32).  The neighbours of a point are the entries of its k-nearest list within
+        `radius` (required, > 0); a zero normal means "none" and its pairs are skipped.  3 <= k <= 64, k <= N."""
+        x, n = f64(points).reshape(-1, 3), f64(normals).reshape(-1, 3)
+        if n.shape[0] != x.shape[0]:
+            raise ValueError("one normal per point required")
+        N = x.shape[0]
+        fpfh, counts, valid = np.empty((N, 33)), np.empty((N, 33), dtype=np.int32), np.empty(N, dtype=np.int32)
+        ki = nat.CloudKnnInfo()
+        _check(self.handle, self._lib.gingr_cloud_fpfh(self.handle, N, dptr(x), dptr(n), int(k), float(radius), iptr(counts), iptr(valid),
+                                                       dptr(fpfh), ctypes.byref(ki)), "gingr_cloud_fpfh")
+        if info is not None:
+            info.update(cell_size=float(ki.cell_size), grid=tuple(int(g) for g in ki.grid), flagged=int(ki.flagged))
+        return fpfh, counts, valid
+
+    def feature_match(self, a, b) -> Tuple[np.ndarray, np.ndarray]:
+        """For every row of a (M, D) the closest row of b (N, D) in feature space -- gingr_feature_match: (idx (M,) int32, d2 (M,)),
+        d2 = sum_c (a_c - b_c)^2 added in ascending c with the bits of that expression in float64, the lowest index on ties.  D <= 64."""
+        a, b = f64(a), f64(b)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError("two matrices with the same number of columns required")
+        idx, d2 = np.empty(a.shape[0], dtype=np.int32), np.empty(a.shape[0])
+        _check(self.handle, self._lib.gingr_feature_match(self.handle, a.shape[0], dptr(a), b.shape[0], dptr(b), a.shape[1], iptr(idx), dptr(d2)),
+               "gingr_feature_match")
+        return idx, d2
+
+    def rigid_poses_from_triples(self, moving, target, triMoving, triTarget) -> Tuple[np.ndarray, np.ndarray]:
+        """The rigid pose of every triple of pairs (moving[triMoving[h]], target[triTarget[h]]) -- gingr_rigid_poses_from_triples:
+        (poses (H, 12): R row-major then t, degenerate (H,) bool).  A degenerate triple (a repeated index, a triangle without area in
+        either cloud) gives a NaN pose, which rigid_search_poses passes over."""
+        x, y = f64(moving).reshape(-1, 3), f64(target).reshape(-1, 3)
+        tm = np.ascontiguousarray(triMoving, dtype=np.int32).reshape(-1, 3)
+        tt = np.ascontiguousarray(triTarget, dtype=np.int32).reshape(-1, 3)
+        if tm.shape != tt.shape:
+            raise ValueError("as many target triples as moving triples required")
+        H = tm.shape[0]
+        poses, deg = np.empty((H, 12)), np.empty(H, dtype=np.int32)
+        _check(self.handle, self._lib.gingr_rigid_poses_from_triples(self.handle, x.shape[0], dptr(x), y.shape[0], dptr(y), H, iptr(tm), iptr(tt),
+                                                                     dptr(poses), iptr(deg)), "gingr_rigid_poses_from_triples")
+        return poses, deg.astype(bool)
 
     def gauss_block(self, A, B, sigma: float, scaling: float) -> np.ndarray:
         """scaling * exp(-|a-b|^2 / sigma^2)  (GPMMHelper.scala:99-102)."""

@@ -353,6 +353,12 @@ int cloud_normals_device(gingr_ctx *ctx, Cloud c, const int32_t *orig, int32_t k
     return GINGR_OK;
 }
 
+int cloud_knn_device(gingr_ctx *ctx, Cloud c, int32_t k, int32_t *idx, double *d2, gingr_cloud_knn_info *info, const char *who) {
+    GINGR_TRY(check_k(ctx, c.n, k, who));
+    KnnWork w;
+    return knn_search(ctx, c, nullptr, k, idx, d2, nullptr, w, info, who);  // (synchronises: the work buffers go out of scope)
+}
+
 extern "C" {
 
 int gingr_cloud_knn(gingr_ctx *ctx, int64_t N, const double *xyz, int32_t k, int32_t *idx, double *d2, gingr_cloud_knn_info *info) {

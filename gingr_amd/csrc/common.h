@@ -14,7 +14,7 @@
 #include "../../include/gingr_hip.h"
 #include "host_device.h"
 
-#define GINGR_TIMERS 27
+#define GINGR_TIMERS 30
 
 struct gingr_ctx {
     int device = 0;
@@ -246,6 +246,9 @@ bool launch_nn_grid(gingr_ctx *ctx, Cloud query, Cloud target, const int32_t *ta
 // viewpoint: host, nullable.  Synchronises.
 int cloud_normals_device(gingr_ctx *ctx, Cloud c, const int32_t *orig, int32_t k, const double *viewpoint, double *normals, int64_t point_stride,
                          int64_t axis_stride, double *variation, gingr_cloud_knn_info *info, const char *who);
+// gingr_cloud_knn on a cloud that lies on the device in the caller's order (SoA): idx / d2 [N][k] on the device, d2 nullable, row t the
+// list of the point at position t.  Checks k.  Synchronises; the lists stay on the device (feature_align.hip reads them there).
+int cloud_knn_device(gingr_ctx *ctx, Cloud c, int32_t k, int32_t *idx, double *d2, gingr_cloud_knn_info *info, const char *who);
 // ---------------------------------------------------------------------------- cloud_ops.hip (per-cloud kernels, layouts, k-d order)
 void launch_cloud_centroid(gingr_ctx *ctx, Cloud c, double *out3);
 void launch_cloud_absmax(gingr_ctx *ctx, Cloud c, const double *ctr, double *slot);

@@ -15,11 +15,16 @@
 //   step kernel     one pose per lane: the partials summed in workgroup order, dR = the Kabsch rotation (polar factor, else svd3 with
 //                   the determinant fix: kabsch3_rotation of svd3.h), dt, the composed pose; on the scoring pass score and kept count
 //   argmin kernel   one workgroup: the smallest score, the lowest pose on ties
+// gingr_rigid_search_poses is the same run from start poses the caller gives (a non-finite one is failed from the beginning), with two
+// additions behind the scoring pass: an inlier kernel (a workgroup per pose: the integer count of d2 <= distance^2 over ALL moving
+// points, LDS integers) and, for select = 1, a selection kernel (most inliers, then the smaller score, then the lowest pose).  Both
+// entries run run_search below; gingr_rigid_search only builds its start poses first.
 // A kernel boundary is the only synchronisation; no float atomic, integer counts in LDS only; nothing is read back before the end.
 // No sum reaches across poses and the grids of the segmented kernels depend on M alone, so a pose's bits do not depend on its slab.
 #include "common.h"
 #include "cloud_sums.h"
 #include "rigid_search_plan.h"
+#include "rigid_step.h"
 #include "robust_select_plan.h"
 #include "svd3.h"
 
@@ -166,18 +171,12 @@ __global__ __launch_bounds__(rs::kStepThreads) void search_step_kernel(int64_t P
         return;
     }
     const double c[3] = {cx, cy, cz};
-    double mup[3], muy[3], H[9];
-    for (int a = 0; a < 3; ++a) mup[a] = S[1 + a] / n, muy[a] = S[4 + a] / n;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) H[a * 3 + b] = S[7 + a * 3 + b] / n - muy[a] * mup[b];
-    double dR[9], trace = 0.0;
-    kabsch3_rotation(H, dR, &trace);
+    double dR[9], dt[3];
+    kabsch_step_from_sums(S, c, dR, dt);
     double *T = poses + rs::kPoseWords * s, Tn[rs::kPoseWords];
     for (int a = 0; a < 3; ++a) {
         for (int b = 0; b < 3; ++b) Tn[a * 3 + b] = (dR[a * 3] * T[b] + dR[a * 3 + 1] * T[3 + b]) + dR[a * 3 + 2] * T[6 + b];
-        const double mpa[3] = {mup[0] + c[0], mup[1] + c[1], mup[2] + c[2]};
-        const double dt = (muy[a] + c[a]) - ((dR[a * 3] * mpa[0] + dR[a * 3 + 1] * mpa[1]) + dR[a * 3 + 2] * mpa[2]);
-        Tn[9 + a] = ((dR[a * 3] * T[9] + dR[a * 3 + 1] * T[10]) + dR[a * 3 + 2] * T[11]) + dt;
+        Tn[9 + a] = ((dR[a * 3] * T[9] + dR[a * 3 + 1] * T[10]) + dR[a * 3 + 2] * T[11]) + dt[a];
     }
     bool fin = true;
     for (int k = 0; k < rs::kPoseWords; ++k) fin = fin && finite_d(Tn[k]);
@@ -211,6 +210,46 @@ __global__ __launch_bounds__(256) void search_argmin_kernel(int64_t S, const dou
     if (t == 0) *best = shi[0];
 }
 
+// inliers[s] = the moving points of pose s with d2 <= lim in the scoring pass (0 for a failed pose); a workgroup per pose
+__global__ __launch_bounds__(256) void search_inliers_kernel(int64_t M, const double *__restrict__ d2, const int32_t *__restrict__ failed, double lim,
+                                                             int64_t *__restrict__ inliers) {
+    __shared__ uint32_t total;
+    const int64_t s = blockIdx.x;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    uint32_t n = 0;
+    if (!failed[s])
+        for (int64_t i = threadIdx.x; i < M; i += 256) n += d2[s * M + i] <= lim ? 1u : 0u;  // (a NaN is no inlier)
+    if (n) atomicAdd(&total, n);  // (LDS, integers)
+    __syncthreads();
+    if (threadIdx.x == 0) inliers[s] = (int64_t)total;
+}
+
+// pose a before pose b: more inliers, then the smaller score, then the lower index
+__device__ __forceinline__ bool better_pose(int64_t ia, double sa, int64_t a, int64_t ib, double sb, int64_t b) {
+    return ia > ib || (ia == ib && (sa < sb || (sa == sb && a < b)));
+}
+
+// *best = the first pose by better_pose among those that did not fail; -1: every pose failed.  One workgroup.
+__global__ __launch_bounds__(256) void search_select_inliers_kernel(int64_t S, const double *__restrict__ scores, const int64_t *__restrict__ inliers,
+                                                                    const int32_t *__restrict__ failed, int64_t *__restrict__ best) {
+    __shared__ int64_t shi[256];
+    const int t = threadIdx.x;
+    int64_t bi = -1;
+    for (int64_t s = t; s < S; s += 256)
+        if (!failed[s] && (bi < 0 || better_pose(inliers[s], scores[s], s, inliers[bi], scores[bi], bi))) bi = s;
+    shi[t] = bi;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) {
+            const int64_t a = shi[t], o = shi[t + off];
+            if (o >= 0 && (a < 0 || better_pose(inliers[o], scores[o], o, inliers[a], scores[a], a))) shi[t] = o;
+        }
+        __syncthreads();
+    }
+    if (t == 0) *best = shi[0];
+}
+
 bool all_finite(const double *v, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
         if (!std::isfinite(v[i])) return false;
@@ -224,44 +263,30 @@ void mean3(const double *xyz, int64_t n, double out[3]) {
     for (int d = 0; d < 3; ++d) out[d] /= (double)n;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gingr_rotation_samples(int64_t n, double *rotations9_out) {
-    if (n < 1 || !rotations9_out) return GINGR_ERR_BAD_ARGUMENT;
-    rs::rotation_samples(n, rotations9_out);
+// the checks the two entries share; `who` names the entry in the message
+int check_search(gingr_ctx *ctx, const char *who, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t S, int32_t K,
+                 double overlap) {
+    if (M < 1 || M > INT32_MAX || N < 1 || N > INT32_MAX || S < 1 || S > INT32_MAX || K < 0)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: M = %lld, N = %lld, S = %lld, K = %d: sizes >= 1 (below 2^31), K >= 0", who,
+                               (long long)M, (long long)N, (long long)S, (int)K);
+    if (!(overlap > 0.0 && overlap <= 1.0)) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "%s: overlap = %g outside (0, 1]", who, overlap);
+    if (!all_finite(moving_xyz, 3 * M) || !all_finite(target_xyz, 3 * N))
+        return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: non-finite coordinate", who);
     return GINGR_OK;
 }
 
-int gingr_rigid_search(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t S,
-                       const double *rotations9, int32_t K, double overlap, int64_t *best_out, double *poses12_out, double *scores_out,
-                       int64_t *kept_out, int32_t *failed_out) {
-    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
-    if (!moving_xyz || !target_xyz || !rotations9 || !best_out) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "rigid_search: null argument");
-    if (M < 1 || M > INT32_MAX || N < 1 || N > INT32_MAX || S < 1 || S > INT32_MAX || K < 0)
-        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "rigid_search: M = %lld, N = %lld, S = %lld, K = %d: sizes >= 1 (below 2^31), K >= 0",
-                               (long long)M, (long long)N, (long long)S, (int)K);
-    if (!(overlap > 0.0 && overlap <= 1.0)) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "rigid_search: overlap = %g outside (0, 1]", overlap);
-    if (!all_finite(moving_xyz, 3 * M) || !all_finite(target_xyz, 3 * N))
-        return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "rigid_search: non-finite coordinate");
-    if (!all_finite(rotations9, 9 * S)) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "rigid_search: non-finite rotation");
-    *best_out = -1;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+// what gingr_rigid_search_poses adds behind the scoring pass
+struct SearchExtras {
+    double inlier_lim;     // inlier_distance^2
+    int select;            // 0: the smallest score; 1: the most inliers, then the smaller score, then the lowest pose
+    int64_t *inliers_out;  // [S], nullable
+};
 
-    // start poses: T_s(x) = R0_s (x - mean X) + mean Y
-    double mx[3], c[3];
-    mean3(moving_xyz, M, mx);
-    mean3(target_xyz, N, c);
-    std::vector<double> start((size_t)S * rs::kPoseWords);
-    for (int64_t s = 0; s < S; ++s) {
-        const double *R = rotations9 + 9 * s;
-        double *T = start.data() + rs::kPoseWords * s;
-        for (int k = 0; k < 9; ++k) T[k] = R[k];
-        for (int a = 0; a < 3; ++a) T[9 + a] = c[a] - ((R[a * 3] * mx[0] + R[a * 3 + 1] * mx[1]) + R[a * 3 + 2] * mx[2]);
-    }
-    if (!all_finite(start.data(), (int64_t)start.size())) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "rigid_search: non-finite start pose");
-
+// The run of both entries from the start poses `start` [S][12] (host; start_failed [S]: 1 = takes no part), sums centred on c = mean Y.
+// extras == nullptr: gingr_rigid_search.
+int run_search(gingr_ctx *ctx, const char *who, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t S,
+               const std::vector<double> &start, const std::vector<int32_t> &start_failed, const double c[3], int32_t K, double overlap,
+               const SearchExtras *extras, int64_t *best_out, double *poses12_out, double *scores_out, int64_t *kept_out, int32_t *failed_out) {
     const int64_t slab = rs::slab_poses(M, N), Pmax = S < slab ? S : slab, Qmax = Pmax * M;
     const int64_t keep = rs::keep_count(M, overlap);
     const bool trimmed = keep < M;
@@ -271,7 +296,8 @@ int gingr_rigid_search(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int6
         const int64_t w = nn_ws_bytes((S % slab) * M, N);
         if (w > ws_bytes) ws_bytes = w;
     }
-    DevBuf stage, tpl, tgt, torig, tboxes, ws, q, idx, d2, counts, sel, part, poses, failed, scores, kept, best;
+    DevBuf stage, tpl, tgt, torig, tboxes, ws, q, idx, d2, counts, sel, part, poses, failed, scores, kept, best, inliers;
+    if (extras) HIP_TRY(ctx, inliers.alloc((size_t)S * sizeof(int64_t)));
     HIP_TRY(ctx, stage.alloc((size_t)3 * (M > N ? M : N) * sizeof(double)));
     HIP_TRY(ctx, tpl.alloc((size_t)3 * M * sizeof(double)));
     HIP_TRY(ctx, tgt.alloc((size_t)3 * N * sizeof(double)));
@@ -302,7 +328,7 @@ int gingr_rigid_search(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int6
     const Cloud cx{x, x + M, x + 2 * M, M}, ct{t, t + N, t + 2 * N, N};
     launch_tile_bbox(ctx, ct, tboxes.as<double>());
     HIP_TRY(ctx, hipMemcpyAsync(poses.p, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(failed.p, 0, (size_t)S * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(failed.p, start_failed.data(), (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     GINGR_TRY(check_launch(ctx));
     struct GridOwner {
         NNGrid g;
@@ -348,13 +374,20 @@ int gingr_rigid_search(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int6
                 hipLaunchKernelGGL(search_step_kernel, dim3((unsigned)ceil_div(P, rs::kStepThreads)), dim3(rs::kStepThreads), 0, ctx->stream, P, B,
                                    part.as<double>(), c[0], c[1], c[2], last, pose_s, failed_s, scores.as<double>() + first,
                                    kept.as<int64_t>() + first);
+                if (last && extras)  // (behind the step kernel: a pose it just failed counts nothing)
+                    hipLaunchKernelGGL(search_inliers_kernel, dim3((unsigned)P), dim3(256), 0, ctx->stream, M, d2.as<double>(), failed_s,
+                                       extras->inlier_lim, inliers.as<int64_t>() + first);
             }
         }
     }
     {
         TimerScope ts(ctx, 26);
-        hipLaunchKernelGGL(search_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, S, scores.as<double>(), failed.as<int32_t>(),
-                           best.as<int64_t>());
+        if (extras && extras->select == 1)
+            hipLaunchKernelGGL(search_select_inliers_kernel, dim3(1), dim3(256), 0, ctx->stream, S, scores.as<double>(), inliers.as<int64_t>(),
+                               failed.as<int32_t>(), best.as<int64_t>());
+        else
+            hipLaunchKernelGGL(search_argmin_kernel, dim3(1), dim3(256), 0, ctx->stream, S, scores.as<double>(), failed.as<int32_t>(),
+                               best.as<int64_t>());
     }
     GINGR_TRY(check_launch(ctx));
     int64_t b = -1;
@@ -363,10 +396,71 @@ int gingr_rigid_search(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int6
     if (scores_out) HIP_TRY(ctx, hipMemcpyAsync(scores_out, scores.p, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (kept_out) HIP_TRY(ctx, hipMemcpyAsync(kept_out, kept.p, (size_t)S * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (failed_out) HIP_TRY(ctx, hipMemcpyAsync(failed_out, failed.p, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (extras && extras->inliers_out)
+        HIP_TRY(ctx, hipMemcpyAsync(extras->inliers_out, inliers.p, (size_t)S * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (b < 0) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "rigid_search: every pose failed (non-finite transform)");
+    if (b < 0) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "%s: every pose failed (non-finite transform)", who);
     *best_out = b;
     return GINGR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gingr_rotation_samples(int64_t n, double *rotations9_out) {
+    if (n < 1 || !rotations9_out) return GINGR_ERR_BAD_ARGUMENT;
+    rs::rotation_samples(n, rotations9_out);
+    return GINGR_OK;
+}
+
+int gingr_rigid_search(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t S,
+                       const double *rotations9, int32_t K, double overlap, int64_t *best_out, double *poses12_out, double *scores_out,
+                       int64_t *kept_out, int32_t *failed_out) {
+    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
+    if (!moving_xyz || !target_xyz || !rotations9 || !best_out) return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "rigid_search: null argument");
+    GINGR_TRY(check_search(ctx, "rigid_search", M, moving_xyz, N, target_xyz, S, K, overlap));
+    if (!all_finite(rotations9, 9 * S)) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "rigid_search: non-finite rotation");
+    *best_out = -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    // start poses: T_s(x) = R0_s (x - mean X) + mean Y
+    double mx[3], c[3];
+    mean3(moving_xyz, M, mx);
+    mean3(target_xyz, N, c);
+    std::vector<double> start((size_t)S * rs::kPoseWords);
+    for (int64_t s = 0; s < S; ++s) {
+        const double *R = rotations9 + 9 * s;
+        double *T = start.data() + rs::kPoseWords * s;
+        for (int k = 0; k < 9; ++k) T[k] = R[k];
+        for (int a = 0; a < 3; ++a) T[9 + a] = c[a] - ((R[a * 3] * mx[0] + R[a * 3 + 1] * mx[1]) + R[a * 3 + 2] * mx[2]);
+    }
+    if (!all_finite(start.data(), (int64_t)start.size())) return gingr_set_error(ctx, GINGR_ERR_NONFINITE, "rigid_search: non-finite start pose");
+    return run_search(ctx, "rigid_search", M, moving_xyz, N, target_xyz, S, start, std::vector<int32_t>((size_t)S, 0), c, K, overlap, nullptr,
+                      best_out, poses12_out, scores_out, kept_out, failed_out);
+}
+
+int gingr_rigid_search_poses(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t S,
+                             const double *poses12_in, int32_t K, double overlap, double inlier_distance, int32_t select, int64_t *best_out,
+                             double *poses12_out, double *scores_out, int64_t *kept_out, int32_t *failed_out, int64_t *inliers_out) {
+    if (!ctx) return GINGR_ERR_BAD_ARGUMENT;
+    if (!moving_xyz || !target_xyz || !poses12_in || !best_out)
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "rigid_search_poses: null argument");
+    GINGR_TRY(check_search(ctx, "rigid_search_poses", M, moving_xyz, N, target_xyz, S, K, overlap));
+    if (!(inlier_distance >= 0.0) || (select != 0 && select != 1))
+        return gingr_set_error(ctx, GINGR_ERR_BAD_ARGUMENT, "rigid_search_poses: inlier_distance = %g, select = %d: need a distance >= 0, select 0 or 1",
+                               inlier_distance, (int)select);
+    *best_out = -1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double c[3];
+    mean3(target_xyz, N, c);
+    std::vector<double> start(poses12_in, poses12_in + (size_t)S * rs::kPoseWords);
+    std::vector<int32_t> start_failed((size_t)S, 0);
+    for (int64_t s = 0; s < S; ++s)  // a non-finite start pose (a degenerate triple's) takes no part
+        start_failed[(size_t)s] = all_finite(poses12_in + rs::kPoseWords * s, rs::kPoseWords) ? 0 : 1;
+    const SearchExtras extras{inlier_distance * inlier_distance, (int)select, inliers_out};
+    return run_search(ctx, "rigid_search_poses", M, moving_xyz, N, target_xyz, S, start, start_failed, c, K, overlap, &extras, best_out,
+                      poses12_out, scores_out, kept_out, failed_out);
 }
 
 }  // extern "C"

@@ -1144,7 +1144,9 @@ int gingr_group_exchange_info(const gingr_group *g, int32_t *distinct_devices, i
  * against training shapes (gingr_model_specificity), the stored basis x factor product (gingr_model_instances, gingr_model_specificity),
  * 21 = the pivot step of gingr_model_localize alone, 22 = the batched eigen-decomposition of the folds of gingr_pca_leave_one_out alone
  * (one launch per batch of folds; up to n_shapes = 193), 23 = the batched closest-point scan of the surface-distance metrics alone, 24 / 25 / 26 = the stages of gingr_rigid_search beside
- * its search (which is 8): the segmented selection, the segmented sums, the rest (pose, step and argmin kernels).  Returns accumulated ms and launches since
+ * its search (which is 8): the segmented selection, the segmented sums, the rest (pose, step and argmin kernels; the inlier and selection kernels of
+ * gingr_rigid_search_poses), 27 / 28 / 29 = the kernels of gingr_cloud_fpfh behind its neighbour search (SPFH and FPFH), of
+ * gingr_feature_match (chunks and their combination) and of gingr_rigid_poses_from_triples alone.  Returns accumulated ms and launches since
  * the last reset.  Enabling adds two event records per launch. */
 int gingr_ctx_timing_enable(gingr_ctx *ctx, int32_t enable);
 int gingr_ctx_timing_read(gingr_ctx *ctx, int32_t which, double *total_ms, int64_t *launches);
@@ -1311,6 +1313,51 @@ int gingr_rotation_samples(int64_t n, double *rotations9_out);
 int gingr_rigid_search(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t S,
                        const double *rotations9, int32_t K, double overlap, int64_t *best_out, double *poses12_out, double *scores_out,
                        int64_t *kept_out, int32_t *failed_out);
+/* gingr_rigid_search_poses: the same run from start poses the caller gives -- poses12_in [S][12], R row-major then t -- instead of
+ * rotations about the centroids: given (R0, mean Y - R0 mean X) it runs the very code gingr_rigid_search runs from there and returns
+ * its bits.  A start pose with a non-finite word is failed from the beginning and takes no part (score +inf, kept 0, inliers 0, the
+ * pose returned as given): the way the degenerate triples of gingr_rigid_poses_from_triples pass through.  inliers_out [S]
+ * (nullable): the number of moving points -- all of them, trimmed or not -- with d2 <= inlier_distance^2 in the scoring pass, an
+ * integer sum per pose.  select = 0: *best_out as above; select = 1: the pose with the most inliers, then the smaller score, then the
+ * lowest s.  Errors as above; also GINGR_ERR_BAD_ARGUMENT for inlier_distance < 0 or NaN and select outside {0, 1}. */
+int gingr_rigid_search_poses(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t S,
+                             const double *poses12_in, int32_t K, double overlap, double inlier_distance, int32_t select, int64_t *best_out,
+                             double *poses12_out, double *scores_out, int64_t *kept_out, int32_t *failed_out, int64_t *inliers_out);
+
+/* ---- feature-based global alignment for partial targets: descriptors, their match, poses from triples of matches -------------
+ * No reference counterpart.  Trimmed ICP from a centroid start slides along the shaft when the target is only a part of the
+ * template; correspondences from local shape descriptors do not need the centroids.  csrc/feature_align.hip, planning in
+ * csrc/feature_align_plan.h; the definitions restated in numpy in tests/feature_alignment_restatement.py.
+ *
+ * gingr_cloud_fpfh: Fast Point Feature Histograms (Rusu, Blodow, Beetz 2009) -- THIS PACKAGE'S DEFINITION, not a toolkit's.
+ * Neighbours of i: the entries of i's gingr_cloud_knn list (k nearest by (d2, index)), in list order, with 0 < d2 <= radius^2 -- the
+ * point itself and its duplicates drop out; the list never leaves the device.  Pair (i, j), u = n_i, d = x_j - x_i, dn = d / |d|:
+ * phi = u . dn; v = dn x u, the pair is SKIPPED when |v|^2 <= 2^-40 or either normal is zero, else v is normalised; w = u x v;
+ * alpha = v . n_j; theta = atan2(w . n_j, u . n_j).  Eleven bins per feature: min(10, max(0, floor((f + 1) / 2 * 11))) for alpha and
+ * phi, the same of (theta + pi) / (2 pi).  counts_out [N][33] (nullable): the integer tallies, alpha bins, then phi, then theta;
+ * valid_out [N] (nullable): the counted pairs.  SPFH_i = 100 counts_i / valid_i (0 when valid_i = 0);
+ * FPFH_i = SPFH_i + (sum_j SPFH_j / d_j) / (sum_j 1 / d_j) over ALL neighbours in list order, d_j = sqrt(d2_j) (0 without
+ * neighbours); then each third is rescaled to sum 100 (a third that sums to 0 is left alone): fpfh_out [N][33].
+ * normals [N][3] are normalised on upload by the rule of gingr_fitter_set_target_normals; a zero normal means "none".  The tallies
+ * are integers and every float sum has a fixed order: two calls give the same bits.  info as gingr_cloud_knn (nullable).
+ * GINGR_ERR_BAD_ARGUMENT: k outside [3, 64] or above N, radius not a finite number > 0, a null input or fpfh_out;
+ * GINGR_ERR_NONFINITE (before any launch): a non-finite coordinate or normal.
+ *
+ * gingr_feature_match: for every row of a [M][D] the row of b [N][D] with the smallest sum_c (a_c - b_c)^2, 1 <= D <= 64: products
+ * and sums separately rounded, added in ascending c from 0 -- the bits of that expression on a CPU -- and the lowest index on ties.
+ * idx_out [M], d2_out [M] (nullable).  No matrix instruction: the norm-expansion form would change the bits and the tie rule.
+ * GINGR_ERR_NONFINITE: a non-finite entry.
+ *
+ * gingr_rigid_poses_from_triples: H triples of pairs (moving[tri_moving[h][q]], target[tri_target[h][q]]), q = 0, 1, 2 -> the rigid
+ * pose of each, poses12_out [H][12] (R row-major, then t): the Kabsch step of the three pairs with the reflection fix -- the
+ * routine the pose step of gingr_rigid_search uses -- with sums centred on the triple's own target mean.  degenerate_out [H]
+ * (nullable) = 1 and the pose NaN when an index repeats within a triple or the squared area of either triangle is
+ * <= 2^-40 (longest edge)^4.  GINGR_ERR_BAD_ARGUMENT: an index out of range; GINGR_ERR_NONFINITE: a non-finite coordinate. */
+int gingr_cloud_fpfh(gingr_ctx *ctx, int64_t N, const double *xyz, const double *normals, int32_t k, double radius, int32_t *counts_out,
+                     int32_t *valid_out, double *fpfh_out, gingr_cloud_knn_info *info);
+int gingr_feature_match(gingr_ctx *ctx, int64_t M, const double *a, int64_t N, const double *b, int32_t D, int32_t *idx_out, double *d2_out);
+int gingr_rigid_poses_from_triples(gingr_ctx *ctx, int64_t M, const double *moving_xyz, int64_t N, const double *target_xyz, int64_t H,
+                                   const int32_t *tri_moving, const int32_t *tri_target, double *poses12_out, int32_t *degenerate_out);
 
 
 /* ---- optimal-step non-rigid ICP baselines (G/other/algorithms/icp/NonRigidOptimalStepICP.scala:31-284) ------------------------
