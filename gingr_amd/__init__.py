@@ -13,7 +13,7 @@ from .api import (  # noqa: F401
     DevicePointDistributionModel, GaussianKernelParameters, GPMMTriangleMesh3D, PointSetHelper, automaticGPMMfromTemplate,
     GpmmBuildInfo, TruncatedDevicePointDistributionModel, PosteriorDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo,
     AugmentedDevicePointDistributionModel, AugmentInfo, LaplacianDevicePointDistributionModel, LaplacianInfo,
-    LocalizedDevicePointDistributionModel, LocalizeInfo,
+    LocalizedDevicePointDistributionModel, LocalizeInfo, ExtendedDevicePointDistributionModel, KernelExtensionInfo,
     TemplateConfiguration, TemplateRegistration, TemplateRegistrationState, ModelMetrics, normalTangentCovariances,
     PointToPlaneConfiguration, PointToPlaneIcpRegistration, PointToPlaneRegistrationState, RobustLoss,
     RadialKernelTerm, sigmoidField, RigidSearchResult, RigidSearchPosesResult,

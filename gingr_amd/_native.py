@@ -242,6 +242,10 @@ SIGNATURES = {
     "gingr_gpmm_build_diagonal_ex": (c_int, [c_void_p, c_int64, _dp, POINTER(ScalarKernel), POINTER(ScalarKernel), POINTER(ScalarKernel),
                                              c_double, c_int32, c_int32, c_int64, c_int64, POINTER(GpmmInfo), POINTER(c_void_p)]),
     "gingr_model_truncate": (c_int, [c_void_p, c_void_p, c_int32, POINTER(c_void_p)]),
+    "gingr_model_kernel_extension": (c_int, [c_void_p, _ip, _ip, _ip]),
+    "gingr_model_get_kernel_extension": (c_int, [c_void_p, c_void_p, c_int32, _ip, _dp]),
+    "gingr_model_extend": (c_int, [c_void_p, c_void_p, c_int64, _dp, POINTER(c_void_p)]),
+    "gingr_model_warp_points": (c_int, [c_void_p, c_void_p, _dp, _dp, _dp, _dp, c_double, c_int64, _dp, _dp]),
     "gingr_gpmm_build_radial": (c_int, [c_void_p, c_int64, _dp, POINTER(RadialKernel), POINTER(RadialKernel), POINTER(RadialKernel),
                                         c_double, c_int32, c_int32, c_int64, c_int64, POINTER(GpmmInfo), POINTER(c_void_p)]),
     "gingr_gpmm_build_gaussian": (c_int, [c_void_p, c_int64, _dp, c_int32, _dp, _dp, c_double, c_int32, c_int64, c_int64,

@@ -27,7 +27,8 @@ from . import _native as nat  # noqa: F401
 from ._native import GingrNativeError, f64, dptr, iptr  # noqa: F401
 from .context import Context, RigidSearchResult, RigidSearchPosesResult, _check  # noqa: F401
 from .models import (  # noqa: F401
-    AugmentInfo, AugmentedDevicePointDistributionModel, DeviceModel, DevicePointDistributionModel, GPMMTriangleMesh3D,
+    AugmentInfo, AugmentedDevicePointDistributionModel, DeviceModel, DevicePointDistributionModel, ExtendedDevicePointDistributionModel,
+    GPMMTriangleMesh3D, KernelExtensionInfo,
     GaussianKernelParameters, GpmmBuildInfo, InterpolatedDevicePointDistributionModel, LaplacianDevicePointDistributionModel,
     LaplacianHelper, LaplacianInfo, LocalizeInfo, LocalizedDevicePointDistributionModel, PcaDevicePointDistributionModel, PcaInfo, PointDistributionModel, PointSetHelper,
     PosteriorDevicePointDistributionModel, RadialKernelTerm, ScalarKernelSpec, TruncatedDevicePointDistributionModel, _cells_of, _resident,

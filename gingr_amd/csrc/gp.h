@@ -6,6 +6,7 @@
 #include "svd3.h"
 
 #include <functional>
+#include <memory>
 
 // Regularisation of PointDistributionModel.coefficients (scalismo DiscreteLowRankGaussianProcess.coefficients:
 // "val sigma2 = 1e-5"); reached from G/api/GingrAlgorithm.scala:215,236.
@@ -100,6 +101,8 @@ struct PostVec {
 // moment blocks, which take the basis as M rows of width 3 rp (launch_moment_grams).
 constexpr int kBasisRowSlack = 144;
 
+struct KernelExtension;  // model_extend.h
+
 struct gingr_model {
     gingr_ctx *ctx = nullptr;
     int64_t M_total = 0, row_begin = 0, row_end = 0, M = 0;  // M = local points
@@ -136,6 +139,12 @@ struct gingr_model {
     // (non-null) only for a separable single-shard model with rp <= 112 and every rc[d] <= kCompactCols; Q0 stays what everything else reads.
     double *Qc = nullptr;
     int32_t *sep_map = nullptr;  // SepMap, on the device; non-null exactly when Qc is
+    // ---- kernel extension (model_extend.h): what evaluates the basis functions of a kernel-built model at points off its reference.
+    // Set by the GPMM builders (gpmm.hip), cut by gingr_model_truncate, shared by gingr_model_extend; null for every other model, and
+    // ext_missing then says why (the text of the GINGR_ERR_STATE the extension entries answer with).
+    std::shared_ptr<KernelExtension> ext;
+    const char *ext_missing = "it was not built from a kernel on the device (uploaded, interpolated, posterior, PCA, augmented, localized and "
+                              "spectral-Laplacian models carry no kernel extension)";
 };
 
 constexpr int kCompactCols = 48;      // width of a plane of Qc: three 16-column tiles

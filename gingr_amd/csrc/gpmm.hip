@@ -31,7 +31,9 @@
 
 #include "fastexp.h"
 #include "gpmm_factor.h"
+#include "gpmm_kernel_value.h"
 #include "gpmm_plan.h"
+#include "model_extend.h"
 
 #include <algorithm>
 #include <cmath>
@@ -48,39 +50,14 @@ using gpmm_factor::Mixture;
 
 constexpr int kPcBlock = 256;
 
-__device__ __forceinline__ double mixture_value(const Mixture &mix, double d2, const double *T) {
-    double v = 0.0;
-    for (int i = 0; i < mix.n; ++i) {
-        const double e = mix.s[i] * fastexp2_scaled<3>(fastexp_clamp_d2(d2, fastexp_d2_limit(mix.c[i])), mix.c[i], T);
-        v = i == 0 ? e : v + e;
-    }
-    return v;
-}
+using gpmm_factor::mixture_value;
+using gpmm_factor::radial_family_value;
 
+// the kernel value between reference point c and pivot p (coordinates px, py, pz): gpmm_kernel_value.h, or the lookup table's entry
 __device__ __forceinline__ double kspec_value(const KSpec &k, const Cloud &pts, int64_t c, int64_t p, double px, double py,
                                               double pz, const double *T) {
-    if (k.kind == 1) {
-        const double dot = __dadd_rn(__dadd_rn(__dmul_rn(pts.x[c], px), __dmul_rn(pts.y[c], py)), __dmul_rn(pts.z[c], pz));
-        return __dmul_rn(dot, k.scale);
-    }
     if (k.kind == 2) return __dmul_rn(k.lookup[c * pts.n + p], k.scale);
-    const double dx = pts.x[c] - px, dy = pts.y[c] - py, dz = pts.z[c] - pz;
-    const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-    double v = mixture_value(k.mix, d2, T);
-    if (k.mirror != 0.0) {
-        const double mx = __dmul_rn(pts.x[c], -1.0) - px;
-        const double m2 = __dadd_rn(__dadd_rn(__dmul_rn(mx, mx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-        v = __dadd_rn(v, __dmul_rn(mixture_value(k.mix, m2, T), k.mirror));
-    }
-    return v;
-}
-
-// f_t(nn) of one radial term (gingr_gpmm_build_radial): the Gaussian through the table exponential exactly as mixture_value has it; the
-// other two as the reference writes them (KernelHelper.scala:53-73), IEEE division and square root, par = beta * beta
-__device__ __forceinline__ double radial_family_value(int32_t family, double par, double nn, const double *T) {
-    if (family == GINGR_RADIAL_RATIONAL_QUADRATIC) return __dsub_rn(1.0, __ddiv_rn(nn, __dadd_rn(nn, par)));
-    if (family == GINGR_RADIAL_INVERSE_MULTIQUADRIC) return __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(nn, par)));
-    return fastexp2_scaled<3>(fastexp_clamp_d2(nn, fastexp_d2_limit(par)), par, T);
+    return gpmm_factor::kspec_value_xyz(k, pts.x[c], pts.y[c], pts.z[c], px, py, pz, T);
 }
 
 // k(x_c, x_p) = sum_t ((scaling_t f_t(nn)) w_t[c]) w_t[p], terms added left to right, the first assigned; a term without a field has no
@@ -539,7 +516,8 @@ int Factor::run_to_tolerance(double rel_tol) {
 
 // G = L^T L of the n columns, its eigenpairs, the caller's choice of the leading `keep`, U sqrt(lambda) = L V for those, the model
 int generic_tail(gingr_ctx *ctx, Factor &fg, int64_t M, const double *ref, const double *mean, int64_t row_begin, int64_t row_end,
-                 std::vector<double> &hev, const std::function<int(std::vector<double> &, int32_t *)> &choose, gingr_model **out) {
+                 std::vector<double> &hev, const std::function<int(std::vector<double> &, int32_t *)> &choose, gingr_model **out,
+                 const std::function<int(const double *, int32_t)> &keep_extension) {
     const int32_t n = fg.ks;
     DevBuf G, ev, V, B;
     HIP_TRY(ctx, G.alloc((size_t)n * n * sizeof(double)));
@@ -562,6 +540,7 @@ int generic_tail(gingr_ctx *ctx, Factor &fg, int64_t M, const double *ref, const
                            M, m->row_begin, m->M, m->r, m->rp, m->perm, m->Q0);
         return check_launch(ctx);
     };
+    if (keep_extension) GINGR_TRY(keep_extension(V.as<double>(), keep));
     return model_create_impl(ctx, M, keep, ref, mean, hev.data(), row_begin, row_end, fill, out);
 }
 
@@ -627,7 +606,9 @@ struct Build {
     gingr_model **out;
     Cloud pts;
     KSpec3 specs;
-    bool radial;  // the kernels are radial terms with weight fields (gingr_gpmm_build_radial)
+    bool radial;  // the kernels are sums of radial terms, with or without weight fields (gingr_gpmm_build_radial)
+    int32_t family[3][kMaxMix];  // radial: the families of every coordinate's terms (host copy of RadialFields::family)
+    bool weighted;               // radial: some term carries a weight field
 };
 
 // the caller's gingr_gpmm_info from the plan's values, and the entry's answer to a refusal
@@ -649,6 +630,29 @@ int report(const Build &b, gpmm_plan::Refusal refusal, const gpmm_plan::Info &pi
 int create_model(const Build &b, int32_t rank, const double *variance, const std::function<int(gingr_model *)> &fill) {
     const std::vector<double> zero_mean((size_t)3 * b.M, 0.0);
     return model_create_impl(b.ctx, b.M, rank, b.ref, zero_mean.data(), variance, b.row_begin, b.row_end, fill, b.out);
+}
+
+// Why a model of this build carries no kernel extension (model_extend.h); null: it carries one
+const char *extension_fault(const Build &b) {
+    if (b.row_begin != 0 || b.row_end != b.M) return "it is a row shard";
+    for (const KSpec &k : b.specs.k)
+        if (k.kind == GINGR_KERNEL_LOOKUP)
+            return "its kernel is a lookup table over the reference points (InverseLaplacian), which has no value off the reference";
+    if (b.radial && b.weighted)
+        return "its radial terms carry weight fields (ScaledGaussian, ChangePoint), and a field is not defined off the reference";
+    return nullptr;
+}
+
+// the extension of a model of `rank` columns with the build's kernels by value; the caller adds the pivots and what forms C
+std::shared_ptr<KernelExtension> new_extension(const Build &b, bool shared, int32_t rank) {
+    auto x = std::make_shared<KernelExtension>();
+    x->shared = shared, x->r = rank, x->rp = (int32_t)round_up(rank, 16);
+    for (int d = 0; d < 3; ++d) {
+        x->kernel[d].spec = b.specs.k[d];
+        x->kernel[d].spec.lookup = nullptr;  // (the build's device table of families dies with the build: family[] replaces it)
+        memcpy(x->kernel[d].family, b.family[d], sizeof(b.family[d]));
+    }
+    return x;
 }
 
 // Coordinates with different kernels: scalismo's generic factorisation itself, over the 3M (point, coordinate) entries -- argmax of the
@@ -679,7 +683,20 @@ int build_generic(const Build &b) {
         for (auto &v : lam) v = v > 0.0 ? v : 0.0;
         return report(b, gpmm_plan::conclude(b.ex, b.keep_rank, n, reached, fraction, lam, *keep, pi), pi);
     };
-    return gpmm_factor::generic_tail(ctx, fg, M, b.ref, zero_mean.data(), b.row_begin, b.row_end, hev, choose, b.out);
+    // what the kernel extension needs, while the factor is alive: a pivot is a (point, coordinate) entry of its own coordinate's list
+    const char *fault = extension_fault(b);
+    std::shared_ptr<KernelExtension> x;
+    auto keep_extension = [&](const double *V, int32_t keep) -> int {
+        if (fault) return GINGR_OK;
+        x = new_extension(b, false, keep);
+        const double *const Vs[3] = {V, nullptr, nullptr};
+        const int32_t vn[3] = {n, 0, 0};
+        return kernel_extension_keep(ctx, fg, n, true, Vs, vn, *x);
+    };
+    GINGR_TRY(gpmm_factor::generic_tail(ctx, fg, M, b.ref, zero_mean.data(), b.row_begin, b.row_end, hev, choose, b.out, keep_extension));
+    (*b.out)->ext = x;
+    if (fault) (*b.out)->ext_missing = fault;
+    return GINGR_OK;
 }
 
 // One kernel for all coordinates: the scalar factorisation (M x k_s), the generic column count from its traces (gpmm_plan.h:
@@ -752,7 +769,22 @@ int build_scalar(const Build &b) {
                            dq.as<int32_t>() + rank, dq.as<int32_t>() + 2 * rank, mdl->Q0);
         return check_launch(ctx);
     };
-    return create_model(b, rank, m.variance.data(), fill);
+    // what the kernel extension needs, while the factor is alive and ahead of the synchronisations of the model's construction: the
+    // three pivot lists are prefixes of the scalar pivot sequence
+    const char *fault = extension_fault(b);
+    std::shared_ptr<KernelExtension> x;
+    if (!fault) {
+        x = new_extension(b, true, rank);
+        for (int d = 0; d < 3; ++d) x->cnt[d] = c.cnt[d], x->block_of[d] = block_of[d];
+        x->qdim.assign(m.qdim.begin(), m.qdim.begin() + rank);
+        x->qidx.assign(m.qidx.begin(), m.qidx.begin() + rank);
+        const double *const Vs[3] = {V[0].as<double>(), V[1].as<double>(), V[2].as<double>()};
+        GINGR_TRY(kernel_extension_keep(ctx, fac, kkmax, false, Vs, block_n, *x));
+    }
+    GINGR_TRY(create_model(b, rank, m.variance.data(), fill));
+    (*b.out)->ext = x;
+    if (fault) (*b.out)->ext_missing = fault;
+    return GINGR_OK;
 }
 
 }  // namespace
@@ -923,6 +955,7 @@ int gingr_gpmm_build_radial(gingr_ctx *ctx, int64_t M_total, const double *ref, 
             sp.mix.s[t] = term.scaling;
             hterms[q].family[t] = term.family;
             if (!term.weight) continue;
+            b.weighted = true;
             int f = 0;
             while (f < nfields && host_field[f] != term.weight) ++f;
             if (f == nfields) {
@@ -934,7 +967,10 @@ int gingr_gpmm_build_radial(gingr_ctx *ctx, int64_t M_total, const double *ref, 
         }
     }
     HIP_TRY(ctx, hipMemcpyAsync(dev_terms.p, hterms, sizeof(hterms), hipMemcpyHostToDevice, ctx->stream));
-    for (int d = 0; d < 3; ++d) b.specs.k[d] = specs[set_of[d]];
+    for (int d = 0; d < 3; ++d) {
+        b.specs.k[d] = specs[set_of[d]];
+        memcpy(b.family[d], hterms[set_of[d]].family, sizeof(b.family[d]));
+    }
     return run_build(b, nsets > 1);
 }
 

@@ -110,8 +110,11 @@ struct Factor {
 // The tail of a generic build (gpmm.hip), shared by the GPMM of coordinate-wise different kernels and gingr_model_localize: from the
 // fg.ks columns of a factor over the 3M entries, G = L^T L and its eigenpairs (descending, as the solver leaves them, in lam); `choose`
 // clamps or refuses them and names the leading columns to keep (or returns an error code, which ends the build); then the model of
-// U sqrt(lambda) = L V for those columns on ref with `mean` ([3M] interleaved).
+// U sqrt(lambda) = L V for those columns on ref with `mean` ([3M] interleaved).  `keep` (optional) sees the eigenvectors
+// V (device, fg.ks x fg.ks, V[row fg.ks + column]) and the number of kept columns right before the model is made, while the factor is
+// alive and ahead of the synchronisations of the model's construction; its failure ends the build.
 int generic_tail(gingr_ctx *ctx, Factor &fg, int64_t M, const double *ref, const double *mean, int64_t row_begin, int64_t row_end,
-                 std::vector<double> &lam, const std::function<int(std::vector<double> &, int32_t *)> &choose, gingr_model **out);
+                 std::vector<double> &lam, const std::function<int(std::vector<double> &, int32_t *)> &choose, gingr_model **out,
+                 const std::function<int(const double *, int32_t)> &keep_extension = nullptr);
 
 }  // namespace gpmm_factor

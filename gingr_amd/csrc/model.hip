@@ -2,6 +2,7 @@
 // coefficients, posterior mean), which borrow a short-lived fitter (C ABI in include/gingr_hip.h).  Behind model_create_impl: the checks
 // and transfers the derived-model builders share (complete_model_fault, check_finite, for_each_shape_stage, download_ref_mean; gp.h).
 #include "fitter.h"
+#include "model_extend.h"
 
 #include <algorithm>
 #include <cmath>
@@ -665,7 +666,13 @@ int gingr_model_truncate(gingr_ctx *ctx, const gingr_model *src, int32_t k, ging
                            m->Q0);
         return check_launch(ctx);
     };
-    return model_create_impl(ctx, src->M_total, k, href.data(), hmean.data(), src->variance.data(), 0, src->M_total, fill, out);
+    // a kernel-built model stays one: the columns of its extension's coefficients are cut with the basis
+    std::shared_ptr<KernelExtension> ext;
+    GINGR_TRY(kernel_extension_truncate(ctx, src, k, &ext));
+    GINGR_TRY(model_create_impl(ctx, src->M_total, k, href.data(), hmean.data(), src->variance.data(), 0, src->M_total, fill, out));
+    (*out)->ext = ext;
+    (*out)->ext_missing = src->ext_missing;
+    return GINGR_OK;
 }
 
 }  // extern "C"

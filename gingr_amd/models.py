@@ -125,6 +125,14 @@ class LaplacianInfo:
 
 
 @dataclasses.dataclass(frozen=True)
+class KernelExtensionInfo:
+    """gingr_model_kernel_extension: `counts` pivots per coordinate; `shared`: the coordinates share one kernel, and their pivot
+    lists are prefixes of one sequence."""
+    counts: Tuple[int, int, int]
+    shared: bool
+
+
+@dataclasses.dataclass(frozen=True)
 class GpmmBuildInfo:
     """gingr_gpmm_info: what the factorisation behind a device-built model did."""
     columns: int                   # factor columns of the pivoted Cholesky (= the model's rank before truncation)
@@ -319,6 +327,12 @@ class DevicePointDistributionModel:
                                                 self.cells, toTolerance=self._to_tolerance, keepRank=keep, radial=self._radial)
         return TruncatedDevicePointDistributionModel(self.device(), k, cells=self.cells)
 
+    def extend(self, newReference, cells=None) -> "ExtendedDevicePointDistributionModel":
+        """This model on the points newReference (anywhere in space) by the kernel extension: see ExtendedDevicePointDistributionModel.
+        Kernel models without lookup kernels or weight fields, and what truncate / extend make of them; others raise
+        GingrNativeError (GINGR_ERR_STATE) when the extended model is first used."""
+        return ExtendedDevicePointDistributionModel(self.device(), newReference, cells=cells)
+
     def _build(self, ctx: Context, row_begin: int, row_end: int):
         if self._to_tolerance or self._keep > 0 or self._radial is not None:
             return self._build_ex(ctx, row_begin, row_end)
@@ -441,6 +455,28 @@ class TruncatedDevicePointDistributionModel(_DerivedDevicePointDistributionModel
             raise ValueError("a truncated resident model lives whole on the context of its source; download it (to_host) for anything else")
         h = c_void_p()
         _check(ctx.handle, ctx._lib.gingr_model_truncate(ctx.handle, self._src_dev.handle, self._k, ctypes.byref(h)), "gingr_model_truncate")
+        return h
+
+
+class ExtendedDevicePointDistributionModel(_DerivedDevicePointDistributionModel):
+    """A kernel-built model on other points (gingr_model_extend): every basis function evaluated at the new points from the kernel
+    and the build's pivots (the Nystroem extension) -- exact on the source's own vertices, defined anywhere in space; zero mean, the
+    source's variances.  Far from every pivot the extended model has no variance.  Carries `cells` of the new points."""
+
+    def __init__(self, source: "DeviceModel", new_reference, cells=None):
+        if not isinstance(source, DeviceModel):
+            source = source.device()
+        self.ctx = source.ctx
+        self.reference = f64(new_reference).reshape(-1, 3)
+        self._src_dev = source
+        self.cells = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32)
+
+    def _build(self, ctx: Context, row_begin: int, row_end: int):
+        if ctx is not self.ctx or int(row_begin) != 0 or int(row_end) != self.numberOfPoints:
+            raise ValueError("an extended model lives whole on the context of its source; download it (to_host) for anything else")
+        h = c_void_p()
+        _check(ctx.handle, ctx._lib.gingr_model_extend(ctx.handle, self._src_dev.handle, self.numberOfPoints, dptr(self.reference),
+                                                       ctypes.byref(h)), "gingr_model_extend")
         return h
 
 
@@ -897,6 +933,52 @@ class DeviceModel:
         _check(self.ctx.handle, self._lib.gingr_model_separable(self.handle, ctypes.byref(sep), counts, ctypes.byref(compact)),
                "gingr_model_separable")
         return bool(sep.value), tuple(counts), bool(compact.value)
+
+    # ---- kernel extension: the model at points off its reference -------------------------------
+    @property
+    def kernelExtension(self) -> Optional["KernelExtensionInfo"]:
+        """gingr_model_kernel_extension: the pivots per coordinate and whether the coordinates share one kernel, for a model that
+        carries the extension (built from a kernel without lookup tables or weight fields; truncated or extended from one); else None.
+        A query, except for a model of coordinate-wise different kernels before its first use: its pivots are counted by forming C."""
+        avail, shared, counts = ctypes.c_int32(), ctypes.c_int32(), (ctypes.c_int32 * 3)()
+        _check(self.ctx.handle, self._lib.gingr_model_kernel_extension(self.handle, ctypes.byref(avail), counts, ctypes.byref(shared)),
+               "gingr_model_kernel_extension")
+        return KernelExtensionInfo(tuple(int(c) for c in counts), bool(shared.value)) if avail.value else None
+
+    def kernelExtensionCoefficients(self, d: int) -> Tuple[np.ndarray, np.ndarray]:
+        """gingr_model_get_kernel_extension: (ids of coordinate d's pivots, C_d [pivots, rank]) -- basis row 3 x + d of a point x is
+        sum_j k_d(x, p_j) C_d[j].  The ids index the reference of the model the extension was BUILT on: this model's own reference,
+        unless it was made by extend(), which shares its source's extension and has other points -- read the ids of such a model
+        against its source's reference."""
+        info = self.kernelExtension
+        n = info.counts[int(d)] if info is not None else 0          # (no extension: the native call names the reason)
+        ids, C = np.empty(n, dtype=np.int32), np.empty((n, self.rank))
+        _check(self.ctx.handle, self._lib.gingr_model_get_kernel_extension(self.ctx.handle, self.handle, int(d), iptr(ids), dptr(C)),
+               "gingr_model_get_kernel_extension")
+        return ids, C
+
+    def _points(self, points) -> np.ndarray:
+        P = f64(points)
+        if P.ndim != 2 or P.shape[1] != 3:
+            raise ValueError(f"points: expected (n, 3), got {P.shape}")
+        return P
+
+    def extend(self, points, cells=None) -> "DeviceModel":
+        """This model on other points as a new resident model (gingr_model_extend): zero mean, the same variances, basis rows
+        evaluated from the kernel at the points (the Nystroem extension) -- anywhere in space, not only on the surface.  The result
+        is an ordinary DeviceModel, independent of this one; its host is an ExtendedDevicePointDistributionModel carrying `cells`."""
+        return ExtendedDevicePointDistributionModel(self, points, cells=cells).device()
+
+    def warpPoints(self, points, alpha, euler=(0, 0, 0), center=(0, 0, 0), translation=(0, 0, 0), scale: float = 1.0) -> np.ndarray:
+        """s (R (x + u(x) - c) + c + t) for every point x (n x 3), u the model's deformation field for the coefficients alpha
+        (gingr_model_warp_points): what extend(points).instance(alpha, ...) returns, without forming a basis of the points."""
+        P, a, e, c, t = self._points(points), f64(alpha), f64(euler), f64(center), f64(translation)
+        if a.shape != (self.rank,):
+            raise ValueError(f"alpha: expected ({self.rank},), got {a.shape}")
+        out = np.empty_like(P)
+        _check(self.ctx.handle, self._lib.gingr_model_warp_points(self.ctx.handle, self.handle, dptr(a), dptr(e), dptr(c), dptr(t), float(scale),
+                                                                  P.shape[0], dptr(P), dptr(out)), "gingr_model_warp_points")
+        return out
 
     def close(self):
         if getattr(self, "handle", None):

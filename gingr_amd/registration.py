@@ -49,6 +49,7 @@ class GingrAlgorithm:
         self._plan_memo = None            # (config object, what _correspondence said about it + the argument its entry points take)
         self._mh_plan_memo = None         # (config object, what _mh_flavour said about it + ctypes pointers)
         self._mh_req = None               # the request / result structs of the fused step, reused (the call is synchronous)
+        self._warp_model = None           # (model, its DeviceModel) of transformPoints for a model that is not the bound one
         self._sel = {}                    # selections already made on the current fitter (options, direction, surface method): set again only when they change
 
     # -- native plumbing ------------------------------------------------------------------
@@ -92,7 +93,13 @@ class GingrAlgorithm:
             _check(self.ctx.handle, self._lib.gingr_fitter_set_options(self._fitter, opts[0], opts[1]), "gingr_fitter_set_options")
             self._sel["options"] = opts
 
+    def _drop_warp_model(self):
+        if self._warp_model is not None:
+            self._warp_model[1].close()
+            self._warp_model = None
+
     def _release(self):
+        self._drop_warp_model()
         if self._fitter:
             if getattr(self.ctx, "handle", None):   # (never into a context that has been closed)
                 self._lib.gingr_fitter_destroy(self._fitter)
@@ -106,6 +113,22 @@ class GingrAlgorithm:
 
     def close(self):
         self._release()
+
+    def transformPoints(self, state, points) -> np.ndarray:
+        """The state's fit carried to arbitrary points (n x 3): s (R (x + u(x) - c) + c + t) with u the deformation field of the
+        state's shape coefficients, evaluated by the model's kernel extension (DeviceModel.warpPoints) -- landmarks that are no
+        vertices, an inner structure, a finer mesh.  At the model's own points this is the state's fit.  The model must carry the
+        extension (a device-built kernel model, truncated or extended); others raise GingrNativeError (GINGR_ERR_STATE)."""
+        general = getattr(state, "general", state)
+        mp = general.modelParameters
+        if self._bound_model is general.model and self._dev_model is not None:
+            dm = self._dev_model
+        else:                                       # not the bound model: made resident once and kept until another one is asked for
+            if self._warp_model is None or self._warp_model[0] is not general.model:
+                self._drop_warp_model()
+                self._warp_model = (general.model, DeviceModel(self.ctx, general.model))
+            dm = self._warp_model[1]
+        return dm.warpPoints(points, mp.shape, (mp.rotation.phi, mp.rotation.theta, mp.rotation.psi), mp.center, mp.translation, mp.scale)
 
     @property
     def retryCounter(self) -> int:

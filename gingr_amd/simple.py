@@ -89,6 +89,16 @@ def new_reference_triangle_mesh(ctx: Context, model, new_reference, new_cells=No
     return InterpolatedDevicePointDistributionModel(ctx, model, new_reference, ids, bary, new_cells)
 
 
+def kernel_new_reference(ctx: Context, model, new_reference, new_cells=None):
+    """A kernel-built model on a new reference by its kernel extension (gingr_model_extend): every basis function is evaluated at the
+    new points themselves -- smooth, exact on the old vertices, defined off the surface too -- instead of being copied from the
+    closest old point or blended over a triangle.  Only for models built on the device from a kernel (no lookup kernels, no weight
+    fields); the mean of such a model is zero."""
+    if model.ctx is not ctx:
+        raise ValueError("the model lives on another context")
+    return model.extend(f64(new_reference).reshape(-1, 3), new_cells)
+
+
 def cluster_decimate(vertices, cells, n_target: int) -> Tuple[np.ndarray, np.ndarray]:
     """Deterministic vertex clustering to about `n_target` vertices (NOT scalismo's decimation, see the module docstring): the
     bounding box is cut into cubes, every occupied cube keeps its vertex closest to the cube's mean (lowest index on ties), the

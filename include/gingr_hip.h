@@ -275,6 +275,39 @@ int gingr_gpmm_build_radial(gingr_ctx *ctx, int64_t M_total, const double *ref, 
  * (single-shard, finalized) model of this context, built or uploaded; 1 <= k <= rank, else GINGR_ERR_BAD_ARGUMENT.  A row
  * shard is refused: build the shards with keep_rank, or truncate the complete model. */
 int gingr_model_truncate(gingr_ctx *ctx, const gingr_model *src, int32_t k, gingr_model **out);
+/* ---- Kernel extension: a model built from a kernel, at points off its reference.
+ * The pivoted Cholesky of a GPMM build reproduces the kernel exactly on its pivot rows, so every basis function of the model is a fixed
+ * combination of kernel functions centred at the pivots:  Q(x)[d, :] = sum_j k_d(x, p_dj) C_d[j, :],  L_P^T C_d = V_d  (L_P: the factor's
+ * rows at coordinate d's pivots, V_d: the kept eigenvectors).  At the model's own vertices this gives back the model's rows, elsewhere
+ * the Nystroem extension of scalismo's continuous LowRankGaussianProcess.  Far from every pivot the extended model has no variance (the
+ * deformation goes to zero): that is the extension's nature.
+ * A complete model carries the extension when it was built by gingr_gpmm_build_gaussian / _diagonal / _diagonal_ex / _radial from
+ * Gaussian mixtures (with or without mirror), the dot-product kernel or radial terms WITHOUT weight fields; so does what
+ * gingr_model_truncate and gingr_model_extend make of such a model.  Lookup kernels, radial terms with weight fields, row shards and
+ * every other model (uploaded, interpolated, posterior, PCA, augmented, localized, spectral) carry none: the entries below that need
+ * one answer GINGR_ERR_STATE, and the message names the reason.  C is formed at the first use (one back substitution on the device).
+ *
+ * gingr_model_kernel_extension: available = 0 / 1 (no error for a model without one); counts (nullable): pivots per coordinate;
+ * shared_kernel (nullable): 1 when the three coordinates share one kernel and their pivot lists are prefixes of one sequence.  A query:
+ * nothing is computed, except for a model whose coordinates have different kernels and whose extension has not been used yet -- its
+ * pivots are counted per coordinate by forming the extension, which can fail with GINGR_ERR_HIP. */
+int gingr_model_kernel_extension(const gingr_model *model, int32_t *available, int32_t counts[3], int32_t *shared_kernel);
+/* The pivots of coordinate d (0..2) in pivot order: their ids (pivot_ids [counts[d]], nullable) into the reference of the model the
+ * extension was BUILT on -- this model's own reference, unless it was made by gingr_model_extend, which shares its source's extension
+ * and has other points: read the ids of such a model against its source's reference --, and C_d row-major [counts[d]][rank] (coeff,
+ * nullable). */
+int gingr_model_get_kernel_extension(gingr_ctx *ctx, const gingr_model *model, int32_t d, int32_t *pivot_ids, double *coeff);
+/* A new, finalized, independent single-shard model on the M_new >= 1 points new_ref_xyz [3 M_new]: zero mean, the source's variances
+ * bit for bit, basis rows Q(x) evaluated on the device (float64 MFMA) straight into the new model; it carries the source's extension
+ * (the same pivots and C), so it extends again to the same rows.  A point's row depends on the point alone, not on the other points
+ * of the call.  Non-finite points: GINGR_ERR_NONFINITE. */
+int gingr_model_extend(gingr_ctx *ctx, const gingr_model *src, int64_t M_new, const double *new_ref_xyz, gingr_model **out);
+/* out_p = s (R (x_p + u(x_p) - c) + c + t),  u(x)[d] = sum_j k_d(x, p_dj) (C_d alpha)[j]: the model's deformation field for the
+ * coefficients alpha [rank] at the P >= 1 host points points_xyz [3 P] under the pose convention of gingr_model_instance; out_xyz [3 P]
+ * (may be points_xyz).  No basis of the P points is formed; the points stream through the device in slabs, P is limited by host memory
+ * alone.  Non-finite points or coefficients: GINGR_ERR_NONFINITE, and out_xyz is left untouched. */
+int gingr_model_warp_points(gingr_ctx *ctx, const gingr_model *model, const double *alpha, const double euler[3], const double center[3],
+                            const double translation[3], double scale, int64_t P, const double *points_xyz, double *out_xyz);
 /* PointSetHelper.maximumPointDistance / minimumPointDistance (GPMMHelper.scala:75-87; the O(n^2) scans behind
  * AutomaticGaussian and automaticGPMMfromTemplate): largest pairwise distance, smallest distance to the nearest OTHER point. */
 int gingr_pointset_distance_extrema(gingr_ctx *ctx, const double *xyz, int64_t n, double *max_distance, double *min_distance);
